@@ -8,6 +8,7 @@ screening ladder -> merges -> exact fp32 re-score of 32 candidates per query, re
 (strong scaling: total work fixed), one process per GPU.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--batch B] [--k K] [--legs all|none|a,b,...]
+                  [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `value` is timed with nothing but the product path inside the bracket (no per-launch events); the dominant kernel's
@@ -1028,6 +1029,29 @@ def _denan(o):
     return o
 
 
+DUMP_BUDGET = 64 << 20      # bytes: --dump-outputs writes at most this much, .npy headers included
+NPY_HEADER = 128            # bytes: np.save's header for the 1-D / 2-D arrays written here
+
+
+def dump_outputs(out_dir: str, scores, ids, budget: int = DUMP_BUDGET) -> dict:
+    """--dump-outputs: the top-k a caller of the timed path received in its last step, as out_dir/scores.npy (float32) and
+    out_dir/ids.npy (float64; row ids are exact below 2^53).  Over `budget` bytes a fixed, seeded sample of query rows is written,
+    and out_dir/query_rows.npy (float64) names them.  Returns {name: shape}."""
+    s = torch.as_tensor(scores).detach().cpu().numpy().astype(np.float32)
+    r = torch.as_tensor(ids).detach().cpu().numpy().astype(np.float64)
+    arrays = {"scores": s, "ids": r}
+    row_bytes = s.shape[1] * 4 + r.shape[1] * 8
+    if s.shape[0] * row_bytes + 2 * NPY_HEADER > budget:
+        keep = (budget - 3 * NPY_HEADER) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(s.shape[0], size=keep, replace=False))
+        arrays = {"scores": s[rows], "ids": r[rows], "query_rows": rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+    assert sum(os.path.getsize(os.path.join(out_dir, f"{n}.npy")) for n in arrays) <= budget
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def _self_launch(n: int, argv: list, script: str | None = None) -> int:
     """`python bench.py --gpus N` started WITHOUT torch.distributed.run: re-exec as N ranks of one node (one process per GPU)
     and hand their output through -- rank 0 prints the JSON line."""
@@ -1064,7 +1088,11 @@ def main(argv=None, hooks=None):
     ap.add_argument("--no-kernel-timing", action="store_true", help="skip the hipEvent pass (no roofline block)")
     ap.add_argument("--exchange", default="native", choices=["native", "torch"],
                     help="N > 1: rmu_shard_allgather_topk (RCCL from librmu.so) or torch.distributed all_gather + rmu_topk_merge")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's top-k (scores.npy float32, ids.npy float64) under DIR (e.g. bench_outputs), at most 64 MB")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as a plain `python bench.py --gpus N` (the form of the driver's N = 1 command): launch the ranks ourselves
@@ -1186,6 +1214,7 @@ def main(argv=None, hooks=None):
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = dump_outputs(args.dump_outputs, out_s, out_r) if (args.dump_outputs and rank == 0) else None
 
     # ---- sanity on the timed outputs: planted neighbour is the top hit, scores sorted ---------------
     top1_ok = float((out_r[:, 0] == planted).float().mean().item())
@@ -1390,6 +1419,8 @@ def main(argv=None, hooks=None):
         "identical_check": f"{nchk} queries x full shard, ids and scores bit-equal; default path answered by {'screen' if path_chk != 0 else 'exact'}",
         "roofline": roofline, "cpu_baseline": cpu, "secondary": secondary, "host_cores": os.cpu_count(),
     }
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     full = _denan(line)
     try:
         with open(os.path.join(ROOT, FULL_RECORD), "w") as f:

@@ -1,12 +1,13 @@
-"""Stand-ins for the third-party modules the reference's server/RAGHelper.py imports (none is installable offline).
+"""Stand-ins for the LangChain modules the package's drop-in classes subclass when LangChain is importable (none is
+installable offline).
 
-NOT a LangChain re-implementation: just enough of its published 0.2.x surface for the reference's retrieval wiring
-(`_initialize_vector_store`, `_setup_retrievers`, `_initialize_reranker`, LCEL `|` / dict coercion) to execute, with
-the one property the boundary test is about kept strict -- every container is a pydantic model whose fields are
-validated by `isinstance` against the LangChain base types (`arbitrary_types_allowed`), exactly how the real
-`EnsembleRetriever`, `ContextualCompressionRetriever`, `VectorStoreRetriever` and the reference's
-`ScoredCrossEncoderReranker.model: BaseCrossEncoder` reject foreign objects.  `install()` registers the modules in
-`sys.modules`; run it before importing `ragmeup_amd` (the package resolves its base classes at import time).
+NOT a LangChain re-implementation: just enough of its published 0.2.x surface for the retrieval wiring a LangChain
+application builds around a vector store (store + `as_retriever`, BM25 + `EnsembleRetriever`, a cross-encoder compressor in
+`ContextualCompressionRetriever`, LCEL `|` / dict coercion) to execute, with the one property the boundary test is about
+kept strict -- every container is a pydantic model whose fields are validated by `isinstance` against the LangChain base
+types (`arbitrary_types_allowed`), exactly how the real `EnsembleRetriever`, `ContextualCompressionRetriever` and
+`VectorStoreRetriever` reject foreign objects.  `install()` registers the modules in `sys.modules`; run it before importing
+`ragmeup_amd` (the package resolves its base classes at import time).
 """
 from __future__ import annotations
 

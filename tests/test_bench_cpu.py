@@ -99,3 +99,41 @@ def test_stdout_guard_sends_stray_output_to_stderr():
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout == '{"ok": 1}\n', r.stdout
     assert "stray python print" in r.stderr and "stray fd write" in r.stderr and "stray C puts" in r.stderr
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the merged top-k of the last timed step as float32 scores / float64 ids; the same arguments give the
+    same inputs, so two runs dump the same arrays."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, DRIVER, *ARGS, "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        o = _line(r.stdout)
+        _check(o)
+        assert o["dumped_outputs"] == {"dir": str(d), "arrays": {"scores": [16, 10], "ids": [16, 10]}}
+        assert sorted(os.listdir(d)) == ["ids.npy", "scores.npy"]
+        s, i = np.load(d / "scores.npy"), np.load(d / "ids.npy")
+        assert s.dtype == np.float32 and i.dtype == np.float64 and s.shape == i.shape == (16, 10)
+        assert (s[:, :-1] >= s[:, 1:]).all() and (i >= 0).all() and (i < 6001).all() and (i == np.rint(i)).all()
+        dumps.append((s, i))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
+def test_dump_outputs_samples_above_the_budget(tmp_path):
+    sys.path.insert(0, os.path.dirname(HERE))
+    import numpy as np
+    import torch
+    import bench
+    s = torch.arange(1000 * 10, dtype=torch.float32).reshape(1000, 10)
+    r = torch.arange(1000 * 10, dtype=torch.int64).reshape(1000, 10)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), s, r, budget=100 * 128)
+    assert shapes == {"scores": [97, 10], "ids": [97, 10], "query_rows": [97]}
+    rows = np.load(tmp_path / "a" / "query_rows.npy")
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in shapes) <= 100 * 128     # headers included
+    assert np.array_equal(np.load(tmp_path / "a" / "ids.npy"), r.numpy()[rows.astype(np.int64)].astype(np.float64))
+    bench.dump_outputs(str(tmp_path / "b"), s, r, budget=100 * 128)    # the sample is fixed
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "query_rows.npy"))
+    assert bench.dump_outputs(str(tmp_path / "c"), s, r) == {"scores": [1000, 10], "ids": [1000, 10]}
