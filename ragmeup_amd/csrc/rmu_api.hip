@@ -1110,10 +1110,9 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
     for (int l = 0; l < nl; ++l)
         if (lv[(size_t)l].pace) pwords += (size_t)lv[(size_t)l].s_chunks * 4;
     const size_t gbytes = (gwords + pwords) * sizeof(u32);    // one memset zeroes thresholds and progress words
-    size_t gcand_bytes = 0;                              // K-split launches: global candidate slots (reused by every launch of the ladder)
+    size_t gcand_bytes = 0;                              // global candidate slots (reused by every launch of the ladder)
     for (int l = 0; l < nl; ++l)
-        if (lv[(size_t)l].kv >= 1)
-            gcand_bytes = std::max(gcand_bytes, (size_t)lv[(size_t)l].parts * (size_t)nb * (kp > RMU_KS_CAP - 8 ? RMU_KS_CAP_DEEP : RMU_KS_CAP) * sizeof(u64));
+        gcand_bytes = std::max(gcand_bytes, (size_t)lv[(size_t)l].parts * (size_t)nb * (kp > RMU_KS_CAP - 8 ? RMU_KS_CAP_DEEP : RMU_KS_CAP) * sizeof(u64));
     if (gcand_bytes && t.gcand.ensure(gcand_bytes)) return fail(RMU_E_OOM, "rmu_index_search: screening candidate slots");
     if (t.partial.ensure((size_t)slots * part_keys * sizeof(u64)) || t.qsplit.ensure((size_t)nb * RMU_IMG_ROW_BYTES) ||
         t.gthr.ensure(gbytes) || t.ckeys.ensure(part_keys * sizeof(u64)) || t.ensure_events(2 * nl))
@@ -1140,7 +1139,7 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
         static const int emit_raw = (rmu_env("RMU_EMIT_RAW") && atoi(rmu_env("RMU_EMIT_RAW")) == 0) ? 0 : 4;
         const int raw = l == 0 ? emit_raw : 0;
         S.gthr = (u32*)t.gthr.p; S.share_thr = sflags | raw; S.dbg = g_dbg; S.q = (const float*)t.qsplit.p;
-        S.gcand = S.kv >= 1 ? (u64*)t.gcand.p : nullptr;
+        S.gcand = (u64*)t.gcand.p;
         if (timed) HIP_TRY(hipEventRecord(t.lev[(size_t)(2 * l)], s));
         rc = rmu_screen_launch(&S, s);
         if (rc) return fail(rc, "rmu_index_search: screening launch");

@@ -179,15 +179,15 @@ struct ScanLaunch {
     u64* dbg;              // optional debug counters (nullptr in production): [0] slow tiles, [1] compactions, [2] appends, [3] tiles
     // filled by rmu_scan_plan
     int wq, kv, s_chunks, nqt, tiles_per_chunk, grid, lds_bytes;
-    int qg;                // screening scan only: 32-query groups per wave (rmu_screen_plan)
+    int qg;                // screening scan only: 32-query groups per wave, always 1 (rmu_screen_plan)
     int nt;                // 1 = stream the corpus with non-temporal loads (every byte is read by exactly one workgroup)
     RmuCond cond;          // exact scan only: device-side launch predicate (zero-initialised = always)
     // screening scan only: sibling pacing (scan_screen.hip).  prog = [s_chunks][4] progress words of the query-tile workgroups
     // of each row chunk (zeroed per launch; nullptr = off), pace = how many tiles a workgroup may run ahead of its slowest sibling
     u32* prog;
     int pace;
-    // screening scan, K-split form only (kv == 1; scan_screen.hip): candidate slots in global memory, [parts][nq][RMU_KS_CAP] keys.  Needs no
-    // initialisation (the slot counts live in registers); contents are dead once the launch has written its partials
+    // screening scan only (scan_screen.hip): candidate slots in global memory, [parts][nq][CAP] keys (RMU_KS_CAP, or RMU_KS_CAP_DEEP for
+    // deep K').  Needs no initialisation (the slot counts live in registers); contents are dead once the launch has written its partials
     u64* gcand;
     // screening scan of an RMU_METRIC_L2SQ index: -2048 |x|^2 per image row (indexed like the image: row0 is added); nullptr = inner product
     const float* nrm;
@@ -207,7 +207,6 @@ int rmu_merge_to_keys_launch(const u64* partial, int parts, int64_t nq, int k, u
 int rmu_split_launch(const float* src, void* dst, int64_t n_rows, hipStream_t s, int stride = 384,
                      float scale = 64.0f, u32* zero_a = nullptr, int n_zero_a = 0, u32* zero_b = nullptr, int n_zero_b = 0);                                             // fp32 [n, 384 of stride] -> fp16(scale x) image
 int rmu_screen_launch(const ScanLaunch* p, hipStream_t s);                             // x/q = split images, k = K'
-int rmu_screen_lds_bytes(int qg);
 int rmu_screen_plan(ScanLaunch* p);                      // geometry of one screening launch (k = K' <= 32)
 int rmu_img_err_launch(const float* x, int64_t n_rows, float* err2, hipStream_t s, int stride = 384);   // |x - image|^2 per row
 // stride = floats between rows of x AND of q; qn2_l2 (RMU_METRIC_L2SQ: |q|^2 per query; x and q in the L2 index's augmented form) or null

@@ -1041,9 +1041,9 @@ def test_deep_k_ladder_with_clustered_duplicates_tombstones_and_l2(rmu, corpus30
 def test_every_switchable_screening_kernel_returns_the_exact_answers(env):
     """Every form of the screening scan the PRODUCT library can be switched to (environment, read once per process) answers the same
     batches -- full query tiles, a ragged tile, one query tile, a lone wave -- and every answer must be the exact fp32 scan's, bit for
-    bit, through the screening path.  Round 5: the product library carries scan_screen_lean3_kernel only (tests/test_abi_cpu.py checks the
-    symbol table); round 3's kernel, the lean / lean2 steps, the K-split and 128-queries-per-wave forms exist in debug builds
-    (python -m ragmeup_amd.build --debug-kernels), where RMU_SCREEN_LEAN / _LEAN4 / _W8 / _KS / _G4 select them: profiles/r04_ab_screen_forms.txt."""
+    bit, through the screening path.  The library carries scan_screen_lean3_kernel only (tests/test_abi_cpu.py checks the symbol table);
+    round 3's kernel, the lean / lean2 steps, the K-split and 128-queries-per-wave forms are retired, their A/B numbers recorded in
+    profiles/r04_ab_screen_forms.txt and NOTES_r01_r05.md 4.5."""
     import json
     import os
     import subprocess

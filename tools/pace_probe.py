@@ -10,7 +10,7 @@ from ragmeup_amd import FlatIndex
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--pace", default="0,1,0,1")
-ap.add_argument("--env", default="RMU_SCREEN_PP", help="switch that is read per launch (RMU_SCREEN_PP while the ping-pong form is measured)")
+ap.add_argument("--env", default="RMU_SCREEN_PACE", help="switch the window values are written to")
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--rows", type=int, default=10_000_000)
 ap.add_argument("--batch", type=int, default=1024)
