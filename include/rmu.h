@@ -224,9 +224,12 @@ int rmu_bert_free(rmu_bert_t* m);
                                 * packed rows, sequence b at rows [sum(len[<b]), +len[b]), len = min(lens, max_len)
                                 *                                              -> out_dev fp32 [sum len, out_stride] */
 #define RMU_BERT_NO_NORMALIZE 0x100 /* OR-ed into POOL_MEAN / POOL_CLS: the checkpoint has no Normalize module */
-/* ids/type_ids: device int32 [batch, max_len] (row padded), lens: device int32 [batch].
- * Rounding and batch shape: activations are bf16, and which kernels serve a call depends on batch * max_len (<= 256 tokens: the
- * small-batch GEMMs; <= 16384: the GEMM pair; above: the fused FFN kernel) -- a sequence's result is bit-identical across
+/* ids/type_ids: device int32 [batch, max_len] (row padded), lens: device int32 [batch], clipped to [0, max_len].  A sequence of
+ * length 0 yields no TOKENS rows, a zero vector in POOL_MEAN / POOL_CLS (sentence-transformers' clamped mean of nothing) and the
+ * head applied to a zero hidden state in CE_LOGIT; the other sequences get what they get without it (bit for bit when both
+ * shapes take the same kernels, see below).
+ * Rounding and batch shape: activations are bf16, and which kernels serve a call depends on batch * max_len (<= 2560 tokens with
+ * max_len <= 256: the small-batch GEMMs; <= 16384: the GEMM pair; above: the fused FFN kernel) -- a sequence's result is bit-identical across
  * calls that take the same kernels and equal up to bf16 rounding noise (|d| < 2e-3 on unit vectors, cosine > 0.9999)
  * otherwise: a query embedded alone reproduces the vector its text got at indexing time to that noise, not bit for bit.
  * hip_stream != 0: the forward is left in flight on that stream (inputs and out_dev must stay valid until it has run); the model's next
