@@ -60,6 +60,9 @@ extern "C" {
                              * small-batch default for <= 128 queries).  Results are identical for every value. */
 #define RMU_OPT_LADDER_FIRST 4   /* tuning: rows of the ladder's smallest first range (0 = default).  Results identical for every value. */
 
+#define RMU_OPT_COMPACT_INPLACE 5 /* 0 (default): rmu_index_compact moves the rows into fresh, smaller allocations (in place when those do not
+                             * fit); 1: always in place, the capacity stays.  Results are identical either way (the tests force the path). */
+
 #define RMU_MAX_K 112       /* largest k the fused scan keeps in LDS */
 #define RMU_MAX_DIM 768
 
@@ -90,6 +93,8 @@ int rmu_index_set_option(rmu_index_t* idx, int option, int64_t value);
 #define RMU_STAT_GROW_COUNT 2
 #define RMU_STAT_GROW_MS 3
 #define RMU_STAT_LIVE_ROWS 4
+#define RMU_STAT_COMPACT_COUNT 5  /* rmu_index_compact calls that dropped rows, and their wall time */
+#define RMU_STAT_COMPACT_MS 6
 int rmu_index_stat(rmu_index_t* idx, int what, double* out);
 /* Make room for `rows` rows in all (grow-only; at most ONE re-allocation, none if the capacity is there).  A re-allocation waits for
  * everything in flight on the device before the old matrix is freed: a caller that knows how many rows are coming -- or that is about to
@@ -101,9 +106,23 @@ int rmu_index_reserve(rmu_index_t* idx, int64_t rows);
  * Serves: RAGHelper.py:431, :525 (db.add_documents -> add_texts -> insert). */
 int rmu_index_add(rmu_index_t* idx, const float* vecs, int64_t n, int is_device, int64_t* first_row);
 
-/* Tombstone rows (they stop appearing in results; storage is not compacted).  *n_removed counts rows
+/* Tombstone rows (they stop appearing in results; their storage stays until rmu_index_compact).  *n_removed counts rows
  * that were live.  Serves: server.py:373-377 (collection.delete('source == ...') -> delete_count). */
 int rmu_index_remove_rows(rmu_index_t* idx, const int64_t* rows, int64_t n, int64_t* n_removed);
+
+/* Drop every tombstoned row: live rows keep their relative order and are renumbered 0..n_live-1.  old_to_new (host, may be
+ * NULL) receives map_len >= n entries: the new id of old row r, or -1 if r was dead (entries [n, map_len) are set to -1; the map is
+ * valid when the call returns 0).  *n_after = rows after the call.  map_len < n -> RMU_E_INVALID and nothing changes: read n with
+ * rmu_index_size first, and expect an add from another thread to land in between.
+ * Storage: by default each array (fp32 rows, fp16 screening image, L2 norms) moves into a new allocation of
+ * max(4096, n_live + n_live / 8 + 1024) rows, one array at a time (the old one is freed before the next is allocated); in place, with the
+ * capacity kept, under RMU_OPT_COMPACT_INPLACE, when that capacity would not be smaller, or when an allocation fails (RMU_E_OOM, index
+ * unchanged, only when not even the in-place path's 64 MiB staging buffer fits; should that happen after the matrix has moved, the
+ * screening image is dropped instead, as after a growth without room for it).  No dead row: nothing moves.  Results of every search
+ * afterwards equal those before it with the row ids mapped.
+ * Searches of the index wait (exclusive lock) and scans still in flight on callers' streams are waited for first, as for growth.
+ * Serves: server.py:353-385 + RAGHelper.py:518-538 (delete / re-upload cycle). */
+int rmu_index_compact(rmu_index_t* idx, int64_t* old_to_new, int64_t map_len, int64_t* n_after);
 
 /* Gather stored rows to the host ([n, dim] fp32).  Serves: the MMR retriever's
  * `col.query(expr="pk in [...]", output_fields=[vector])` round trip (RAGHelper.py:497-499). */

@@ -18,7 +18,9 @@ F_Q_DEVICE, F_OUT_DEVICE, F_SMALLER_BETTER = 1, 2, 4
 OPT_SCREEN = 1
 OPT_SCREEN_MIN_NQ = 2
 OPT_LADDER_RATIO, OPT_LADDER_FIRST = 3, 4
+OPT_COMPACT_INPLACE = 5
 STAT_CAPACITY, STAT_GROW_COUNT, STAT_GROW_MS, STAT_LIVE_ROWS = 1, 2, 3, 4
+STAT_COMPACT_COUNT, STAT_COMPACT_MS = 5, 6
 COMM_ID_BYTES = 128
 MAX_K = 112
 MAX_DIM = 768
@@ -27,7 +29,7 @@ MAX_DIM = 768
 SYMBOLS = [
     "rmu_init", "rmu_last_error", "rmu_version",
     "rmu_index_create", "rmu_index_free", "rmu_index_size", "rmu_index_dim", "rmu_index_metric", "rmu_index_set_option", "rmu_index_stat", "rmu_index_reserve", "rmu_index_add",
-    "rmu_index_remove_rows", "rmu_index_get_rows", "rmu_index_save", "rmu_index_load", "rmu_index_mmr", "rmu_index_search_mmr", "rmu_index_search", "rmu_topk_merge",
+    "rmu_index_remove_rows", "rmu_index_compact", "rmu_index_get_rows", "rmu_index_save", "rmu_index_load", "rmu_index_mmr", "rmu_index_search_mmr", "rmu_index_search", "rmu_topk_merge",
     "rmu_last_scan_ms", "rmu_last_search_ms", "rmu_last_scan_geometry", "rmu_set_timing", "rmu_last_screened", "rmu_probe_mfma_rate",
     "rmu_comm_unique_id", "rmu_comm_init", "rmu_comm_free", "rmu_comm_world", "rmu_shard_allgather_topk", "rmu_index_screen_candidates",
     "rmu_bert_create", "rmu_bert_free", "rmu_bert_encode", "rmu_bert_encode_host", "rmu_bert_search_mmr",
@@ -67,6 +69,7 @@ def _declare(lib):
     lib.rmu_index_screen_candidates.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     lib.rmu_index_add.argtypes = [vp, vp, i64, i32, c.POINTER(i64)]
     lib.rmu_index_remove_rows.argtypes = [vp, vp, i64, c.POINTER(i64)]
+    lib.rmu_index_compact.argtypes = [vp, vp, i64, c.POINTER(i64)]
     lib.rmu_index_get_rows.argtypes = [vp, vp, i64, vp]
     lib.rmu_index_mmr.argtypes = [vp, vp, i64, vp, i32, i32, c.c_double, u32, vp]
     lib.rmu_index_search_mmr.argtypes = [vp, vp, i64, i32, i32, c.c_double, i64, vp, vp]

@@ -6,6 +6,7 @@
 //   rmu_index_search      RAGHelper.py:497-499   (dense retriever -> FLAT similarity search)
 //   rmu_index_get_rows    RAGHelper.py:497-499   (search_type="mmr": re-fetch the fetch_k vectors)
 //   rmu_index_remove_rows server.py:373-377      (collection.delete('source == ...'))
+//   rmu_index_compact     server.py:353-385 + RAGHelper.py:518-538 (delete / re-upload cycle; row moves in rmu_compact.hip)
 //   rmu_topk_merge        no counterpart (8-GPU shard merge)
 //
 // Data layout in HBM: one row-major [capacity, dpad] fp32 matrix, dpad = dim rounded up to 192/384/768
@@ -441,6 +442,9 @@ struct rmu_index {
     bool stat_pending = false;
     int64_t grow_count = 0;         // re-allocations of the corpus matrix (+ image) by rmu_index_add, and their wall time
     double grow_ms = 0.0;
+    int64_t compact_count = 0;      // rmu_index_compact calls that dropped rows, and their wall time
+    double compact_ms = 0.0;
+    bool compact_inplace = false;   // RMU_OPT_COMPACT_INPLACE: compaction never re-allocates
     bool screen_enabled = true;     // RMU_OPT_SCREEN: searches may take the screening path (when `split` exists)
     int ladder_ratio = 0, ladder_first = 0;   // RMU_OPT_LADDER_RATIO / _FIRST (0 = defaults; tools/ladder_sweep.py)
     int64_t screen_min_nq = 0;      // RMU_OPT_SCREEN_MIN_NQ: > 0 = screen every batch of at least this many queries, whatever the corpus size
@@ -578,6 +582,8 @@ extern "C" int rmu_index_stat(rmu_index_t* idx, int what, double* out) {
         case RMU_STAT_GROW_COUNT: *out = (double)idx->grow_count; break;
         case RMU_STAT_GROW_MS: *out = idx->grow_ms; break;
         case RMU_STAT_LIVE_ROWS: *out = (double)idx->n_live; break;
+        case RMU_STAT_COMPACT_COUNT: *out = (double)idx->compact_count; break;
+        case RMU_STAT_COMPACT_MS: *out = idx->compact_ms; break;
         default: return fail(RMU_E_INVALID, "rmu_index_stat: unknown statistic");
     }
     return RMU_OK;
@@ -775,6 +781,99 @@ extern "C" int rmu_index_remove_rows(rmu_index_t* idx, const int64_t* rows, int6
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     idx->n_live -= (int64_t)todo.size();
+    return RMU_OK;
+}
+
+// Drop the tombstoned rows (rmu.h).  The live rows from the first dead one on are gathered forward (rmu_compact.hip), array by array:
+// out of place into allocations of max(4096, n_live + n_live / 8 + 1024) rows (+ slack) -- one array's old and new allocation coexist at a
+// time, as in grow() -- or in place through a staging buffer (RMU_OPT_COMPACT_INPLACE, a new capacity that would not be smaller, or a failed
+// allocation).  Afterwards the index is what a fresh index of the live rows would hold: rows past n_live zero (x, image) / NaN (norms).
+extern "C" int rmu_index_compact(rmu_index_t* idx, int64_t* old_to_new, int64_t map_len, int64_t* n_after) {
+    RMU_ENTRY();
+    if (!idx || !n_after || (old_to_new && map_len < 0)) return fail(RMU_E_INVALID, "rmu_index_compact: bad argument");
+    int rc = g_tls.ensure_stream();
+    if (rc) return fail(rc, "rmu_index_compact: stream");
+    std::unique_lock<std::shared_mutex> lk(idx->mu);
+    const int64_t n = idx->n, n_live = idx->n_live;
+    if (old_to_new && map_len < n) return fail(RMU_E_INVALID, "rmu_index_compact: map_len is smaller than the index's row count");
+    const auto t0 = std::chrono::steady_clock::now();
+    // the map, and the source row of every new row from the first dead row on (branch-free: tombstones fall anywhere)
+    const uint8_t* alive = idx->alive.data();
+    const uint8_t* d0 = n ? (const uint8_t*)memchr(alive, 0, (size_t)n) : nullptr;
+    const int64_t first = d0 ? (int64_t)(d0 - alive) : n;
+    if (old_to_new) {
+        for (int64_t r = 0; r < first; ++r) old_to_new[r] = r;
+        for (int64_t r = first, j = first; r < n; ++r) {
+            old_to_new[r] = alive[r] ? j : -1;
+            j += alive[r];
+        }
+        for (int64_t r = n; r < map_len; ++r) old_to_new[r] = -1;
+    }
+    *n_after = n;
+    if (first == n) return RMU_OK;                         // nothing dead: nothing moves, nothing is re-allocated
+    std::vector<u32> src((size_t)(n_live - first) + 1);
+    for (int64_t r = first, i = 0; r < n; ++r) {
+        src[(size_t)i] = (u32)r;
+        i += alive[r];
+    }
+    src.pop_back();
+    struct Tick {
+        rmu_index* i; std::chrono::steady_clock::time_point t;
+        ~Tick() { i->compact_count++; i->compact_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+    } tick{idx, t0};
+    // scans still in flight on callers' streams read the rows about to move (and maybe the allocations about to be freed)
+    rc = wait_readers(idx);
+    if (rc) return rc;
+    hipStream_t s = g_tls.stream;
+    Buf& bs = g_tls.in_r;
+    if (!src.empty()) {
+        if (bs.ensure(src.size() * sizeof(u32))) return fail(RMU_E_OOM, "rmu_index_compact: source list workspace");
+        HIP_TRY(hipMemcpyAsync(bs.p, src.data(), src.size() * sizeof(u32), hipMemcpyHostToDevice, s));
+    }
+    const u32* d_src = (const u32*)bs.p;
+    const int64_t new_cap = std::max<int64_t>(4096, n_live + n_live / 8 + 1024);
+    const size_t kStagingBytes = (size_t)64 << 20;
+    void* staging = nullptr;
+    auto get_staging = [&]() -> bool {
+        if (!staging && hipMalloc(&staging, kStagingBytes) != hipSuccess) { (void)hipGetLastError(); staging = nullptr; }
+        return staging != nullptr;
+    };
+    struct Arr { void** base; int64_t row_bytes; int fill; };
+    Arr arrs[3] = {{(void**)&idx->x, (int64_t)idx->dpad * (int64_t)sizeof(float), 0},
+                   {(void**)&idx->split, RMU_IMG_ROW_BYTES, 0},
+                   {(void**)&idx->nrm, (int64_t)sizeof(float), 0xFF}};   // NaN norms: never a candidate
+    bool oop = !idx->compact_inplace && new_cap < idx->cap;
+    if (!oop && !get_staging()) return fail(RMU_E_OOM, "rmu_index_compact: staging buffer (the index is unchanged)");
+    hipError_t e = hipSuccess;
+    for (int a = 0; a < 3 && e == hipSuccess; ++a) {
+        if (!*arrs[a].base) continue;
+        const Arr& A = arrs[a];
+        if (oop) {
+            e = rmu_compact_array(A.base, A.row_bytes, A.fill, n, n_live, first, d_src, new_cap + kSlackRows, nullptr, 0, s);
+            if (e != hipErrorOutOfMemory) continue;
+            e = hipSuccess;
+            if (a == 0) {                                  // the matrix did not fit twice: the whole call goes in place
+                oop = false;
+                if (!get_staging()) return fail(RMU_E_OOM, "rmu_index_compact: staging buffer (the index is unchanged)");
+            } else if (!get_staging()) {                   // the matrix has moved; no room for the image either way: exact path only
+                (void)hipStreamSynchronize(s);             // (as grow() does when the image does not fit)
+                (void)rmu_free(idx->split);
+                if (idx->nrm) (void)rmu_free(idx->nrm);
+                idx->split = nullptr;
+                idx->nrm = nullptr;
+                break;
+            }
+        }
+        e = rmu_compact_array(A.base, A.row_bytes, A.fill, n, n_live, first, d_src, 0, staging, kStagingBytes, s);
+    }
+    const hipError_t es = hipStreamSynchronize(s);
+    if (staging) (void)rmu_free(staging);
+    if (e != hipSuccess || es != hipSuccess)
+        return fail(RMU_E_HIP, std::string("rmu_index_compact: ") + hipGetErrorString(e != hipSuccess ? e : es));
+    if (oop) idx->cap = new_cap;
+    idx->n = n_live;
+    idx->alive.assign((size_t)n_live, 1);
+    *n_after = n_live;
     return RMU_OK;
 }
 
@@ -1483,6 +1582,7 @@ extern "C" int rmu_index_set_option(rmu_index_t* idx, int option, int64_t value)
         case RMU_OPT_SCREEN_MIN_NQ: idx->screen_min_nq = value > 0 ? value : 0; return RMU_OK;
         case RMU_OPT_LADDER_RATIO: idx->ladder_ratio = value > 0 && value <= 4096 ? (int)value : 0; return RMU_OK;
         case RMU_OPT_LADDER_FIRST: idx->ladder_first = value > 0 && value <= (1 << 30) ? (int)value : 0; return RMU_OK;
+        case RMU_OPT_COMPACT_INPLACE: idx->compact_inplace = value != 0; return RMU_OK;
         default: return fail(RMU_E_INVALID, "rmu_index_set_option: unknown option");
     }
 }

@@ -217,3 +217,13 @@ int rmu_rescore_launch(const u64* cand, int kp, const float* x, const float* q, 
 // smaller_better: distances (RMU_METRIC_L2SQ) instead of similarities
 int rmu_merge_lists_launch(const float* scores, const int64_t* rows, int parts, int64_t stride_s, int64_t stride_r, int64_t nq, int k,
                            int smaller_better, float* out_scores, int64_t* out_rows, hipStream_t s);
+
+// row moves of rmu_index_compact (rmu_compact.hip), one array of the index at a time: rows of row_bytes (768 / 1536 / 3072, or 4 for the
+// L2 norms); new row j in [first, n_live) comes from old row src_rows[j - first] (device list, strictly increasing, src_rows[i] >= first + i);
+// rows [0, first) stay where they are.
+//   alloc_rows > 0: out of place -- a new allocation of alloc_rows rows (capacity + slack) receives the prefix and the gathered rows, its
+//     rows [n_live, alloc_rows) are set to the byte `fill`, the stream is drained and the old allocation freed (*base = the new one).  A
+//     failed allocation returns hipErrorOutOfMemory with nothing moved.
+//   alloc_rows == 0: in place, chunk by chunk through `staging`, then rows [n_live, n_old) are set to `fill`; enqueues only.
+hipError_t rmu_compact_array(void** base, int64_t row_bytes, int fill, int64_t n_old, int64_t n_live, int64_t first, const u32* src_rows,
+                             int64_t alloc_rows, void* staging, size_t staging_bytes, hipStream_t s);

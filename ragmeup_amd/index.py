@@ -78,6 +78,15 @@ class FlatIndex:
             out[name] = float(v.value) if name == "grow_ms" else int(v.value)
         return out
 
+    def compaction_stats(self) -> dict:
+        """rmu_index_stat: how many compact() calls dropped rows, and their wall time."""
+        out = {}
+        for name, what in (("compact_count", N.STAT_COMPACT_COUNT), ("compact_ms", N.STAT_COMPACT_MS)):
+            v = ctypes.c_double()
+            N.check(self._lib.rmu_index_stat(self._h, what, ctypes.byref(v)), "rmu_index_stat")
+            out[name] = float(v.value) if name == "compact_ms" else int(v.value)
+        return out
+
     def reserve(self, rows: int):
         """Make room for `rows` rows in all (grow-only; see rmu_index_reserve): a re-allocation waits for the device, so a caller that is
         about to leave work in flight does it first."""
@@ -107,6 +116,24 @@ class FlatIndex:
         N.check(self._lib.rmu_index_remove_rows(self._h, r.ctypes.data, r.shape[0], ctypes.byref(cnt)),
                 "rmu_index_remove_rows")
         return int(cnt.value)
+
+    def compact(self) -> np.ndarray:
+        """Drop the tombstoned rows (rmu_index_compact): live rows keep their order and become rows 0..n_live-1.  Returns the int64 map
+        old row -> new row (-1 = the row was dead), one entry per row the index held."""
+        after = ctypes.c_int64()
+        while True:
+            n = len(self)
+            m = np.empty(max(n, 1), dtype=np.int64)
+            rc = self._lib.rmu_index_compact(self._h, m.ctypes.data, n, ctypes.byref(after))
+            if rc != N.RMU_OK and len(self) > n:         # rows were added between the size and the call: a longer map
+                continue
+            N.check(rc, "rmu_index_compact")
+            return m[:n]
+
+    def set_compact_inplace(self, on: bool = True):
+        """RMU_OPT_COMPACT_INPLACE: compact() moves rows inside the current allocations (capacity kept) instead of into smaller ones;
+        results are identical either way."""
+        N.check(self._lib.rmu_index_set_option(self._h, N.OPT_COMPACT_INPLACE, 1 if on else 0), "rmu_index_set_option")
 
     def get_rows(self, rows) -> np.ndarray:
         r = np.ascontiguousarray(rows, dtype=np.int64)

@@ -135,7 +135,7 @@ class MI355XVectorStore(VectorStore):
                  use_jsonb: bool = True, *, embedding_function: Any = None, connection_args: dict | None = None,
                  drop_old: bool = False, score_mode: str | None = None, metric: str = "ip", dim: int | None = None,
                  device: int | None = None, auto_persist: bool | str = "atexit", pipeline_inserts: bool | str = "auto",
-                 pipeline_window: float = 0.25):
+                 pipeline_window: float = 0.25, compact_threshold: float | None = None):
         self._embeddings = embeddings if embeddings is not None else embedding_function
         if self._embeddings is None:
             raise ValueError("an Embeddings object is required")
@@ -163,6 +163,14 @@ class MI355XVectorStore(VectorStore):
         self._pks: list[str] = []
         self._alive: list[bool] = []
         self._pk_to_row: dict[str, int] = {}
+        # compact() renumbers the rows while searches run without self._lock: a seqlock.  _gen is odd while the index and the records
+        # are being renumbered; a read that started under another value (or an odd one) is repeated (see _consistent)
+        self._gen = 0
+        # None: rows of deleted / replaced records stay in the index (tombstones) until compact(); a fraction: compact() once dead rows
+        # exceed it of all rows -- checked at the end of delete() and of an insert (or flush()) that leaves no deferred half in flight
+        if compact_threshold is not None and not 0.0 <= float(compact_threshold) < 1.0:
+            raise ValueError("compact_threshold must be None or in [0, 1)")
+        self.compact_threshold = None if compact_threshold is None else float(compact_threshold)
         # Cross-call insert pipeline (see _add_pipelined).  "auto" (default): a call's GPU half is deferred only INSIDE an insert loop --
         # another add_texts ended less than `pipeline_window` seconds ago or halves are still pending -- so a single upload (the
         # reference's POST /add_document -> _add_to_vector_database, server/RAGHelper.py:518-538) is synchronous and a failure is raised
@@ -423,6 +431,8 @@ class MI355XVectorStore(VectorStore):
         """Wait until everything added so far is in the HBM-resident index (and raise what a pending add failed with)."""
         with self._lock:
             self._drain()
+            if self._maybe_compact() and self.auto_persist is True:
+                self.persist()
 
     def _can_pipeline(self) -> bool:
         """The GPU halves call the index from a worker thread: only the native index (and the stock factory methods) are known to allow it."""
@@ -781,6 +791,7 @@ class MI355XVectorStore(VectorStore):
             else:
                 old_rows.update(zip(sel_ids, range(n0, n0 + len(sel_ids))))
             self._dirty = True
+            self._maybe_compact()
             if self.auto_persist is True:
                 self.persist()
         return list(ids)
@@ -825,9 +836,71 @@ class MI355XVectorStore(VectorStore):
                 self._alive[r] = False
             if rows:
                 self._dirty = True
+                self._maybe_compact()
                 if self.auto_persist is True:
                     self.persist()
         return _DeleteResult(len(rows))
+
+    # ---- compaction (rmu_index_compact) ---------------------------------------------------------------------
+    def compact(self) -> int:
+        """Drop the rows of deleted and replaced records from the index (HBM and, at the next persist, disk); returns how many rows
+        were reclaimed (0: none were dead, nothing changed).  Records keep their pks; only row numbers change."""
+        with self._lock:
+            self._drain()
+            n = self._compact_locked()
+            if n and self.auto_persist is True:
+                self.persist()
+        return n
+
+    def _compact_locked(self) -> int:
+        """(under self._lock, nothing pending) renumber index rows and records together, as one seqlock write section"""
+        if self._index is None or all(self._alive):
+            return 0
+        before = len(self._alive)
+        if len(self._index) != before:
+            raise RuntimeError(f"index rows ({len(self._index)}) and host records ({before}) out of step: not compacting")
+        self._gen += 1                                   # odd: readers that overlap this section repeat their read
+        try:
+            m = np.asarray(self._index.compact())
+            keep = np.flatnonzero(m >= 0).tolist()
+            texts, metas, pks = self._texts, self._metas, self._pks
+            self._texts = [texts[r] for r in keep]
+            self._metas = [metas[r] for r in keep]
+            self._pks = [pks[r] for r in keep]
+            self._alive = [True] * len(keep)
+            self._pk_to_row = {pk: j for j, pk in enumerate(self._pks)}
+        finally:
+            self._gen += 1
+        self._dirty = True
+        return before - len(self._alive)
+
+    def _maybe_compact(self) -> bool:
+        """(under self._lock) compact when compact_threshold is set, no deferred insert half holds row numbers, and dead rows exceed
+        the threshold"""
+        if self.compact_threshold is None or self._pending or self._index is None or not self._alive:
+            return False
+        dead = len(self._alive) - sum(self._alive)
+        if dead <= self.compact_threshold * len(self._alive):
+            return False
+        return self._compact_locked() > 0
+
+    def _consistent(self, read):
+        """Run `read` (index call + row numbers -> Documents) until no compaction overlapped it: the seqlock's read side.  Searches
+        still run in parallel with each other; only a read that overlapped a compaction is repeated."""
+        while True:
+            g = self._gen
+            if g & 1:                                    # a compaction is in progress: it holds the writer lock until it is done
+                with self._lock:
+                    pass
+                continue
+            try:
+                out = read()
+            except Exception:
+                if self._gen != g:                       # e.g. a row number that no longer exists
+                    continue
+                raise
+            if self._gen == g:
+                return out
 
     # ---- search ---------------------------------------------------------------------------------------------
     def _search_vecs(self, qvecs: np.ndarray, k: int):
@@ -839,8 +912,12 @@ class MI355XVectorStore(VectorStore):
         return self._index.search(qvecs, kk)
 
     def similarity_search_with_score_by_vector(self, embedding, k: int = 4, **kw) -> list[tuple[Document, float]]:
-        s, r = self._search_vecs(np.asarray(embedding, dtype=np.float32)[None], k)
-        return [(self._doc(int(row)), self._convert(float(sc))) for sc, row in zip(s[0], r[0]) if row >= 0]
+        q = np.asarray(embedding, dtype=np.float32)[None]
+
+        def read():
+            s, r = self._search_vecs(q, k)
+            return [(self._doc(int(row)), self._convert(float(sc))) for sc, row in zip(s[0], r[0]) if row >= 0]
+        return self._consistent(read)
 
     def _fused_query(self, query: str, fetch_k: int, k: int, lambda_mult):
         """One query through `rmu_bert_search_mmr` (token ids in, rows out: forward, dense top-fetch_k and the selection in ONE library
@@ -858,27 +935,42 @@ class MI355XVectorStore(VectorStore):
         return rows[0], scores[0]
 
     def similarity_search_with_score(self, query: str, k: int = 4, **kw) -> list[tuple[Document, float]]:
-        hit = self._fused_query(query, int(k), int(k), None)
-        if hit is not None:
+        def read():
+            hit = self._fused_query(query, int(k), int(k), None)
+            if hit is None:
+                return None
             return [(self._doc(int(row)), self._convert(float(sc))) for row, sc in zip(*hit) if row >= 0]
+        out = self._consistent(read)
+        if out is not None:
+            return out
         return self.similarity_search_with_score_by_vector(self._embed_query(query), k, **kw)
 
     def similarity_search(self, query: str, k: int = 4, **kw) -> list[Document]:
         return [d for d, _ in self.similarity_search_with_score(query, k, **kw)]
 
     def similarity_search_with_relevance_scores(self, query: str, k: int = 4, **kw) -> list[tuple[Document, float]]:
-        s, r = self._search_vecs(self._embed_query(query)[None], k)
-        return [(self._doc(int(row)), float(sc)) for sc, row in zip(s[0], r[0]) if row >= 0]
+        q = self._embed_query(query)[None]
+
+        def read():
+            s, r = self._search_vecs(q, k)
+            return [(self._doc(int(row)), float(sc)) for sc, row in zip(s[0], r[0]) if row >= 0]
+        return self._consistent(read)
 
     def similarity_search_with_score_batch(self, queries: list[str], k: int = 4) -> list[list[tuple[Document, float]]]:
         qv = self._embed_docs(list(queries))
-        s, r = self._search_vecs(qv, k)
-        return [[(self._doc(int(row)), self._convert(float(sc))) for sc, row in zip(ss, rr) if row >= 0]
-                for ss, rr in zip(s, r)]
+
+        def read():
+            s, r = self._search_vecs(qv, k)
+            return [[(self._doc(int(row)), self._convert(float(sc))) for sc, row in zip(ss, rr) if row >= 0]
+                    for ss, rr in zip(s, r)]
+        return self._consistent(read)
 
     def max_marginal_relevance_search_by_vector(self, embedding, k: int = 4, fetch_k: int = 20,
                                                 lambda_mult: float = 0.5, **kw) -> list[Document]:
         q = np.asarray(embedding, dtype=np.float32)
+        return self._consistent(lambda: self._mmr_by_vector(q, k, fetch_k, lambda_mult))
+
+    def _mmr_by_vector(self, q: np.ndarray, k: int, fetch_k: int, lambda_mult: float) -> list[Document]:
         if self._pending:
             self.flush()
         if (self._index is not None and hasattr(self._index, "search_mmr") and len(self._index) > 0
@@ -902,9 +994,12 @@ class MI355XVectorStore(VectorStore):
 
     def max_marginal_relevance_search(self, query: str, k: int = 4, fetch_k: int = 20, lambda_mult: float = 0.5,
                                       **kw) -> list[Document]:
-        hit = self._fused_query(query, int(fetch_k), int(k), float(lambda_mult))     # the reference's per-request call (RAGHelper.py:497-499)
-        if hit is not None:
-            return [self._doc(int(x)) for x in hit[0] if x >= 0]
+        def read():
+            hit = self._fused_query(query, int(fetch_k), int(k), float(lambda_mult))     # the reference's per-request call (RAGHelper.py:497-499)
+            return None if hit is None else [self._doc(int(x)) for x in hit[0] if x >= 0]
+        out = self._consistent(read)
+        if out is not None:
+            return out
         return self.max_marginal_relevance_search_by_vector(self._embed_query(query), k, fetch_k, lambda_mult)
 
     def max_marginal_relevance_search_batch(self, queries: list[str], k: int = 4, fetch_k: int = 20,
@@ -912,6 +1007,9 @@ class MI355XVectorStore(VectorStore):
         """One dense search + ONE device-side MMR selection for the whole batch (`rmu_index_mmr`: fp64, same greedy rule and
         tie order as the single-query path; no per-query vector re-fetch).  fetch_k > 64 falls back to the host loop."""
         qv = self._embed_docs(list(queries))
+        return self._consistent(lambda: self._mmr_batch(qv, k, fetch_k, lambda_mult))
+
+    def _mmr_batch(self, qv: np.ndarray, k: int, fetch_k: int, lambda_mult: float) -> list[list[Document]]:
         s, r = self._search_vecs(qv, fetch_k)
         if r.shape[1] == 0:
             return [[] for _ in range(qv.shape[0])]
