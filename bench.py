@@ -7,13 +7,16 @@ screening ladder -> merges -> exact fp32 re-score of 32 candidates per query, re
 -> (N > 1: ONE RCCL all-gather of per-shard top-k, issued from librmu.so) -> merge.  N GPUs: the 10M rows are sharded N ways
 (strong scaling: total work fixed), one process per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--batch B] [--k K] [--legs all|none|a,b,...]
-                  [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--batch B] [--k K] [--dump-outputs DIR]
+                  [--full [--legs all|none|a,b,...] [--no-cpu-baseline] [--no-identity-check] [--no-kernel-timing]]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-`value` is timed with nothing but the product path inside the bracket (no per-launch events); the dominant kernel's
-launch durations (roofline) are measured afterwards, on the same inputs, with hipEvents on the stream the kernels run on.
-At N = 1 the same run also reports, under "secondary", every other BASELINE.json configuration (C1 on the GPU path, C2, C3, C5) with its own roofline and
+A plain run does only what the headline needs: it sets up the corpus and the queries, warms up, times the K steps, writes
+the last step's top-k if --dump-outputs is given, and prints the line.  Everything else runs only with --full.
+`value` is timed with nothing but the product path inside the bracket (no per-launch events).  With --full the run then
+checks the timed outputs (planted neighbour on top, sorted lists) and the default path against the exact fp32 scan, and
+measures the dominant kernel's launch durations (roofline) on the same inputs, with hipEvents on the stream the kernels run on.
+At N = 1 a --full run also reports, under "secondary", every other BASELINE.json configuration (C1 on the GPU path, C2, C3, C5) with its own roofline and
 CPU figure: the exact fp32 scan (API switch), the HBM-bound batch sizes 1 / 16 / 32 / 128 (the best of 16 / 32 above 10k queries/sec is
 repeated as `roofline.north_star`, on step and on kernel time), the EMULATED 8-way shard step (`emu8`, `roofline.emulated_shard_8`), config 2
 (1M rows; `l2`: the same rows and queries on the native squared-L2 index, screened since round 5), config 3 (chunk embedding) and config 5 (dense top-100 -> cross-encoder rerank -> top-10), config 1 on the GPU path with its
@@ -968,7 +971,7 @@ def _compact_roofline(r, top=False):
     return o
 
 
-def compact_line(full: dict, budget: int = LINE_BUDGET) -> dict:
+def compact_line(full: dict, budget: int = LINE_BUDGET, record: str | None = FULL_RECORD) -> dict:
     """The stdout line: the headline keys of the bench contract in full + a compact `secondary` (id, value, unit, ms_per_step,
     roofline numbers, cpu_baseline value per leg).  Prose, kernel descriptions and per-leg detail stay in FULL_RECORD.  Legs' detail is
     dropped in steps until the line fits the budget (it fits at the first step today; the ladder is the guarantee)."""
@@ -1005,7 +1008,7 @@ def compact_line(full: dict, budget: int = LINE_BUDGET) -> dict:
             out.append(o)
         return out
 
-    line["full_record"] = FULL_RECORD
+    line["full_record"] = record
     for level in (0, 1, 2):
         line["secondary"] = sec(level)
         if len(json.dumps(line, allow_nan=False)) <= budget:
@@ -1080,12 +1083,16 @@ def main(argv=None, hooks=None):
     ap.add_argument("--dim", type=int, default=384)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--k", type=int, default=10)
-    ap.add_argument("--legs", default="all", help="secondary legs at N=1: all | none | comma list of exact,b1,b16,b32,b128,emu8,c1,mmr,chat,c2,l2,embed,index,rerank")
-    ap.add_argument("--index-texts", type=int, default=1_000_000, help="texts pushed through add_documents by the `index` leg (BASELINE.json configs[2]: 1M chunks)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check the outputs against the planted neighbours and the exact fp32 scan, time the "
+                         "kernels (roofline, sustained MFMA rates), run the secondary legs and the CPU baselines, and write every leg to "
+                         f"{FULL_RECORD}; a plain run only sets up, warms up, times, dumps (--dump-outputs) and prints the line")
+    ap.add_argument("--legs", default="all", help="--full, secondary legs at N=1: all | none | comma list of exact,b1,b16,b32,b128,emu8,c1,mmr,chat,c2,l2,embed,index,rerank")
+    ap.add_argument("--index-texts", type=int, default=1_000_000, help="--full: texts pushed through add_documents by the `index` leg (BASELINE.json configs[2]: 1M chunks)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the recall check")
     ap.add_argument("--no-identity-check", action="store_true",
-                    help="skip the post-run comparison with the exact fp32 scan (keeps rocprofv3 per-kernel statistics to the timed launches)")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="skip the hipEvent pass (no roofline block)")
+                    help="--full: skip the post-run comparison with the exact fp32 scan (keeps rocprofv3 per-kernel statistics to the timed launches)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full: skip the hipEvent pass (no roofline block)")
     ap.add_argument("--exchange", default="native", choices=["native", "torch"],
                     help="N > 1: rmu_shard_allgather_topk (RCCL from librmu.so) or torch.distributed all_gather + rmu_topk_merge")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -1155,10 +1162,11 @@ def main(argv=None, hooks=None):
         planted = torch.empty((B,), dtype=torch.int64, device=device)
     if world > 1:
         dist.broadcast(q, 0)
-        dist.broadcast(planted, 0)
-    legs = set() if (args.legs == "none" or world > 1) else set("exact,b1,b16,b32,b128,emu8,c1,mmr,chat,c2,l2,embed,index,rerank".split(",") if args.legs == "all" else args.legs.split(","))
+        if args.full:
+            dist.broadcast(planted, 0)
+    legs = set() if (not args.full or args.legs == "none" or world > 1) else set("exact,b1,b16,b32,b128,emu8,c1,mmr,chat,c2,l2,embed,index,rerank".split(",") if args.legs == "all" else args.legs.split(","))
     sample_host = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sample_host = shard[:min(n_local, 2_000_000)].cpu().numpy()
     x1m = shard[:1_000_000].clone() if (legs & {"c2", "rerank"}) and n_local >= 1_000_000 else None
     n_emu = N // 8
@@ -1209,6 +1217,7 @@ def main(argv=None, hooks=None):
         dist.barrier()
     sync()
     elapsed = time.perf_counter() - t0
+    screened = index.last_screened() != 0          # the path the last timed step took (host state of this thread, no GPU work)
     out_s, out_r = torch.as_tensor(out_s), torch.as_tensor(out_r)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -1216,15 +1225,17 @@ def main(argv=None, hooks=None):
         elapsed = float(t.item())
     dumped = dump_outputs(args.dump_outputs, out_s, out_r) if (args.dump_outputs and rank == 0) else None
 
-    # ---- sanity on the timed outputs: planted neighbour is the top hit, scores sorted ---------------
-    top1_ok = float((out_r[:, 0] == planted).float().mean().item())
-    sorted_ok = bool((out_s[:, :-1] >= out_s[:, 1:]).all().item())
+    # ---- (--full) sanity on the timed outputs: planted neighbour is the top hit, scores sorted ---------
+    top1_ok = sorted_ok = None
+    if args.full:
+        top1_ok = float((out_r[:, 0] == planted).float().mean().item())
+        sorted_ok = bool((out_s[:, :-1] >= out_s[:, 1:]).all().item())
 
-    # ---- full-size parity property (outside the timed region): on this rank's whole shard the default path (fp16 screen
+    # ---- (--full) full-size parity property (outside the timed region): on this rank's whole shard the default path (fp16 screen
     # + fp32 re-score) must return the exact fp32 scan's ids AND scores bit for bit (RMU_OPT_SCREEN switches the path).
     nchk = min(B, 256)
     identical, path_chk = None, 0
-    if not args.no_identity_check:
+    if args.full and not args.no_identity_check:
         s_def, r_def = index.search(q[:nchk], K)
         path_chk = index.last_screened()
         index.set_screening(False)
@@ -1237,7 +1248,7 @@ def main(argv=None, hooks=None):
         identical = bool(t.item() > 0.5)
 
     roofline = None
-    if not args.no_kernel_timing:     # every rank runs it (same launches); rank 0 reports its own shard's kernel
+    if args.full and not args.no_kernel_timing:     # every rank runs it (same launches); rank 0 reports its own shard's kernel
         roofline = scan_roofline(index, lambda: index.search(q, K), n_local, D, B, K, steps=max(3, min(args.steps, 10)))
 
     if rank != 0:
@@ -1260,7 +1271,7 @@ def main(argv=None, hooks=None):
     ms_per_step = elapsed * 1e3 / args.steps
     qps = B * args.steps / elapsed
 
-    # ---- secondary legs (N = 1): the other BASELINE configurations, each with its own roofline -------
+    # ---- (--full) secondary legs (N = 1): the other BASELINE configurations, each with its own roofline -------
     secondary = []
     t_leg = [t_start]
 
@@ -1269,7 +1280,8 @@ def main(argv=None, hooks=None):
         print(f"[bench] {what}: {now - t_leg[0]:.1f} s", file=sys.stderr, flush=True)
         t_leg[0] = now
 
-    note("headline + identity check + kernel timing")
+    if args.full:
+        note("headline + identity check + kernel timing")
 
     def scan_leg(name, idx, qq, n_rows, steps, note=None):
         nq = qq.shape[0]
@@ -1392,7 +1404,8 @@ def main(argv=None, hooks=None):
     index.close()
     if on_gpu:
         torch.cuda.empty_cache()
-    note("c2 + cpu baselines")
+    if args.full:
+        note("c2 + cpu baselines")
     for name, fn in (("c1", leg_c1), ("mmr", leg_mmr), ("chat", leg_chat), ("embed", leg_embed), ("index", leg_index)):
         if name in legs:
             secondary.append(dict(fn(args), id=name))
@@ -1401,14 +1414,13 @@ def main(argv=None, hooks=None):
         secondary.append(dict(leg_rerank(args, x1m), id="rerank"))
         note("rerank")
 
-    path = roofline["path"] if roofline else "unknown"
     line = {
         "metric": "queries/sec, exact dense top-10 over an HBM-resident 10Mx384 fp32 corpus",
         "value": round(qps, 1), "unit": "queries/sec",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None,
-        "dtype": "f16 screen (fp32 accumulate) + f32 re-score" if path.startswith("screen") else "f32", "data": "synthetic",
+        "dtype": "f16 screen (fp32 accumulate) + f32 re-score" if screened else "f32", "data": "synthetic", "full": args.full,
         "config": {"workload": f"{N}x{D} fp32 unit-norm corpus, batch {B} queries, top-{K}, inner product",
                    "rows": N, "dim": D, "batch": B, "k": K, "n_ranks_seen": n_ranks_seen,
                    "rows_per_rank": n_local, "self_launched": bool(os.environ.get("RMU_BENCH_SELF_LAUNCHED")),
@@ -1422,13 +1434,14 @@ def main(argv=None, hooks=None):
     if dumped is not None:
         line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     full = _denan(line)
-    try:
-        with open(os.path.join(ROOT, FULL_RECORD), "w") as f:
-            json.dump(full, f, indent=1, allow_nan=False)
-    except OSError as e:
-        print(f"[bench] could not write {FULL_RECORD}: {e}", file=sys.stderr)
-    print("[bench] full record: " + json.dumps(full, allow_nan=False), file=sys.stderr, flush=True)
-    guard.emit(json.dumps(compact_line(full), allow_nan=False))
+    if args.full:
+        try:
+            with open(os.path.join(ROOT, FULL_RECORD), "w") as f:
+                json.dump(full, f, indent=1, allow_nan=False)
+        except OSError as e:
+            print(f"[bench] could not write {FULL_RECORD}: {e}", file=sys.stderr)
+        print("[bench] full record: " + json.dumps(full, allow_nan=False), file=sys.stderr, flush=True)
+    guard.emit(json.dumps(compact_line(full, record=FULL_RECORD if args.full else None), allow_nan=False))
     if world > 1:
         dist.destroy_process_group()
 

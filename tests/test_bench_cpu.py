@@ -1,5 +1,5 @@
 """CPU: bench.py's launch contract and its N > 1 branch, end to end to the JSON line (that branch had never run
-anywhere, and `python bench.py --gpus N` without torch.distributed.run printed nothing)."""
+anywhere, and `python bench.py --gpus N` without torch.distributed.run printed nothing), as a plain run and with --full."""
 import json
 import os
 import subprocess
@@ -23,16 +23,24 @@ def _line(out: str) -> dict:
     return _strict(lines[0])
 
 
-def _check(o):
+def _check(o, full=True):
+    assert o["full"] is full
     assert o["n_gpus"] == 2 and o["steps"] == 2 and o["warmup"] == 1 and o["scaling"] == "strong" and o["higher_is_better"] is True
     c = o["config"]
     assert c["n_ranks_seen"] == 2 and c["rows"] == 6001 and c["rows_per_rank"] == 3001 and c["parallelism"].startswith("row-shard x2")
     assert "all_gather_into_tensor" in c["exchange"]        # gloo: the torch.distributed exchange (the RCCL one needs GPUs)
-    # the merged answer is the global one: every planted neighbour (all in rank 0's shard) is the top hit, lists are sorted,
-    # and the default and exact paths agree on every rank (MIN over ranks)
-    assert o["planted_top1"] == 1.0 and o["sorted"] is True and o["identical_to_exact_f32_scan"] is True
     assert o["value"] > 0 and abs(o["value"] - 16 / (o["ms_per_step"] * 1e-3)) / o["value"] < 1e-3
     assert o["secondary"] == [] and o["cpu_baseline"] is None      # N > 1: the headline only
+    assert o["dtype"] == "f32"                                     # the oracle-backed index answers on the exact path
+    if full:
+        # the merged answer is the global one: every planted neighbour (all in rank 0's shard) is the top hit, lists are sorted,
+        # and the default and exact paths agree on every rank (MIN over ranks)
+        assert o["planted_top1"] == 1.0 and o["sorted"] is True and o["identical_to_exact_f32_scan"] is True
+        assert o["roofline"]["kernel_ms"] == 1.0 and o["full_record"] == "bench_secondary.json"
+    else:
+        # a plain run: set-up, warm-up, timed steps, the line -- no checks, no kernel timing, no full record
+        for k in ("planted_top1", "sorted", "identical_to_exact_f32_scan", "recall_at_10", "roofline", "full_record"):
+            assert o[k] is None, k
 
 
 def test_world2_under_torch_distributed_run():
@@ -41,14 +49,23 @@ def test_world2_under_torch_distributed_run():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), DRIVER, *ARGS], capture_output=True, text=True, timeout=600)
+                        "--master-port", str(port), DRIVER, *ARGS, "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     _check(_line(r.stdout))
+    assert "[bench] full record: " in r.stderr
+
+
+def test_plain_run_times_the_headline_only():
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, DRIVER, *ARGS], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    _check(_line(r.stdout), full=False)
+    assert "[bench] " not in r.stderr                             # no legs, no full record
 
 
 def test_plain_python_invocation_self_launches_its_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, DRIVER, *ARGS], capture_output=True, text=True, timeout=600, env=env)
+    r = subprocess.run([sys.executable, DRIVER, *ARGS, "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     o = _line(r.stdout)
     _check(o)
@@ -103,16 +120,17 @@ def test_stdout_guard_sends_stray_output_to_stderr():
 
 def test_dump_outputs_writes_the_last_timed_step(tmp_path):
     """--dump-outputs DIR: the merged top-k of the last timed step as float32 scores / float64 ids; the same arguments give the
-    same inputs, so two runs dump the same arrays."""
+    same inputs, so two runs dump the same arrays -- a plain run and a --full run alike (what --full adds runs after the dump)."""
     import numpy as np
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     dumps = []
-    for run in ("a", "b"):
+    for run, full in (("a", False), ("b", True)):
         d = tmp_path / run
-        r = subprocess.run([sys.executable, DRIVER, *ARGS, "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env)
+        r = subprocess.run([sys.executable, DRIVER, *ARGS, "--dump-outputs", str(d)] + (["--full"] if full else []),
+                           capture_output=True, text=True, timeout=600, env=env)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
         o = _line(r.stdout)
-        _check(o)
+        _check(o, full)
         assert o["dumped_outputs"] == {"dir": str(d), "arrays": {"scores": [16, 10], "ids": [16, 10]}}
         assert sorted(os.listdir(d)) == ["ids.npy", "scores.npy"]
         s, i = np.load(d / "scores.npy"), np.load(d / "ids.npy")

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 LEGS=${3:-b16,b32,c2,emu8}
 for rep in 1 2; do
 for L in "$1" "$2"; do
-  RMU_TUNING=1 RMU_LIB=$R/$L timeout 300 python $R/bench.py --legs $LEGS --no-cpu-baseline --no-identity-check > /tmp/ab.json 2> /tmp/ab.err
+  RMU_TUNING=1 RMU_LIB=$R/$L timeout 300 python $R/bench.py --full --legs $LEGS --no-cpu-baseline --no-identity-check > /tmp/ab.json 2> /tmp/ab.err
   python - "$L" <<'P'
 import json, sys
 d = json.load(open('/tmp/ab.json'))

@@ -12,7 +12,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 10 --warmup 2 --legs none --no-cpu-baseline --no-identity-check"
+B="python $R/bench.py --full --steps 10 --warmup 2 --legs none --no-cpu-baseline --no-identity-check"
 keep() {  # keep only our kernels' rows of a CSV
   f=$(find $OUT/$1 -name "*$2" | head -1)
   if [ -n "$f" ]; then (head -1 $f; grep -E "scan_topk|scan_screen|k_rescore|k_split_rows|k_seed_thr|k_img_err|k_mmr|merge_keys|merge_lists|merge_select|merge_wg|k_gather_flagged|k_ffn3|k_ffn2|k_ffn_fused|k_gemm3|k_gemm|k_attn3|k_qkv_attn_small|k_attention|k_layernorm|k_embed_ln|k_pool|k_cls_head|k_cu_seqlens" $f) | cut -c1-400 > $OUT/$1_$3.csv; fi
@@ -36,7 +36,7 @@ timeout 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OU
 keep exact_pmc_b counter_collection.csv counters
 unset RMU_SCREEN
 # 3) HBM-bound regime (B=1): default path (fp16 image, screening ladder) and the exact fp32 scan; kernel stats + FETCH_SIZE
-B1="python $R/bench.py --batch 1 --steps 10 --warmup 2 --legs none --no-cpu-baseline --no-identity-check"
+B1="python $R/bench.py --full --batch 1 --steps 10 --warmup 2 --legs none --no-cpu-baseline --no-identity-check"
 timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/scan_b1 -o scan -- $B1 > $OUT/scan_b1_bench.json 2>> $OUT/scan.err
 keep scan_b1 kernel_stats.csv stats
 timeout 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_b1 -o b -- $B1 > $OUT/pmc_b1_bench.json 2>> $OUT/scan.err
@@ -48,24 +48,24 @@ timeout 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OU
 keep exact_pmc_b1 counter_collection.csv counters
 unset RMU_SCREEN
 # 3b) the north-star regime (B=32, screened, nt stream): kernel stats + FETCH_SIZE
-B32="python $R/bench.py --batch 32 --steps 10 --warmup 2 --legs none --no-cpu-baseline --no-identity-check"
+B32="python $R/bench.py --full --batch 32 --steps 10 --warmup 2 --legs none --no-cpu-baseline --no-identity-check"
 timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/scan_b32 -o scan -- $B32 > $OUT/scan_b32_bench.json 2>> $OUT/scan.err
 keep scan_b32 kernel_stats.csv stats
 timeout 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_b32 -o b -- $B32 > $OUT/pmc_b32_bench.json 2>> $OUT/scan.err
 keep pmc_b32 counter_collection.csv counters
 # 3b') batch 16 -- the leg bench.py reports as roofline.north_star (>= 10k queries/sec at >= 0.70 of 8 TB/s): kernel stats + FETCH_SIZE (no b16 record existed)
-B16="python $R/bench.py --batch 16 --steps 10 --warmup 2 --legs none --no-cpu-baseline --no-identity-check"
+B16="python $R/bench.py --full --batch 16 --steps 10 --warmup 2 --legs none --no-cpu-baseline --no-identity-check"
 timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/scan_b16 -o scan -- $B16 > $OUT/scan_b16_bench.json 2>> $OUT/scan.err
 keep scan_b16 kernel_stats.csv stats
 timeout 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_b16 -o b -- $B16 > $OUT/pmc_b16_bench.json 2>> $OUT/scan.err
 keep pmc_b16 counter_collection.csv counters
 # 3c) BASELINE.json configs[1] (1M x 384, batch 1024) and the 8-way shard size (1.25M rows): kernel stats (round 5: VERDICT r4 asked for a c2_stats.csv)
 for cfg in "c2 1000000" "shard8 1250000"; do set -- $cfg
-  timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$1 -o scan -- python $R/bench.py --rows $2 --steps 10 --warmup 2 --legs none --no-cpu-baseline --no-identity-check > $OUT/$1_bench.json 2>> $OUT/scan.err
+  timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$1 -o scan -- python $R/bench.py --full --rows $2 --steps 10 --warmup 2 --legs none --no-cpu-baseline --no-identity-check > $OUT/$1_bench.json 2>> $OUT/scan.err
   keep $1 kernel_stats.csv stats
 done
 # 4) encoder (config 3) kernel stats (kernel-trace only: a PMC pass over the encoder hung rocprofv3 in round 1)
-timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/embed -o e -- python $R/bench.py --legs embed --rows 100000 --steps 2 --no-cpu-baseline --no-identity-check --no-kernel-timing > $OUT/embed_bench.json 2>> $OUT/scan.err
+timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/embed -o e -- python $R/bench.py --full --legs embed --rows 100000 --steps 2 --no-cpu-baseline --no-identity-check --no-kernel-timing > $OUT/embed_bench.json 2>> $OUT/scan.err
 keep embed kernel_stats.csv stats
 # 5) C5's dense part: 64 queries x 1M rows, top-100 (the deep-k threshold ladder): kernel stats
 timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/top100 -o t -- python $R/tools/topk_probe.py 1000000:64:100 > $OUT/top100_probe.txt 2>> $OUT/scan.err

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 for b in "$@"; do
   rm -rf /tmp/sb_$b
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/sb_$b -o s -- python $R/bench.py --batch $b --steps 20 --warmup 3 --legs none --no-cpu-baseline --no-identity-check > /tmp/sb_$b.json 2>/tmp/sb_$b.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/sb_$b -o s -- python $R/bench.py --full --batch $b --steps 20 --warmup 3 --legs none --no-cpu-baseline --no-identity-check > /tmp/sb_$b.json 2>/tmp/sb_$b.err
   python - <<PY
 import csv,glob,json
 d=json.loads(open("/tmp/sb_$b.json").read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ out=${1:-gpurun_out/sweep}; mkdir -p $out
 for b in 32 128; do
   for cfg in "0 256" "8 16384" "8 131072" "16 131072" "32 131072" "64 262144"; do
     set -- $cfg
-    RMU_SCREEN_RATIO=$1 RMU_SCREEN_MINLVL=$2 timeout 200 python bench.py --batch $b --steps 20 --warmup 3 --legs none --no-cpu-baseline --no-identity-check \
+    RMU_SCREEN_RATIO=$1 RMU_SCREEN_MINLVL=$2 timeout 200 python bench.py --full --batch $b --steps 20 --warmup 3 --legs none --no-cpu-baseline --no-identity-check \
       2> $out/b${b}_r$1_m$2.err | python -c "
 import sys,json
 for l in sys.stdin:
@@ -16,7 +16,7 @@ for l in sys.stdin:
 " | tee -a $out/summary.txt
   done
 done
-RMU_MERGE_SELECT=0 timeout 200 python bench.py --batch 32 --steps 20 --legs none --no-cpu-baseline --no-identity-check 2>/dev/null | python -c "
+RMU_MERGE_SELECT=0 timeout 200 python bench.py --full --batch 32 --steps 20 --legs none --no-cpu-baseline --no-identity-check 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
