@@ -164,6 +164,19 @@ int rmu_index_load(rmu_index_t** out, const char* path);
 int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, int k, unsigned flags,
                      int64_t row_base, float* out_scores, int64_t* out_rows, uint64_t hip_stream);
 
+/* Exact top-k of every query against the rows ONE list names (the same list for all nq queries), in time proportional to the list,
+ * not the corpus: a gathered form of the exact fp32 scan (no copy of the subset is made).  rows [n_sub] int64: strictly ascending
+ * index-local row ids.  A HOST list is checked before anything is enqueued (not ascending, negative or >= n -> RMU_E_INVALID, nothing
+ * launched) and copied; a DEVICE list (RMU_F_ROWS_DEVICE) is the caller's contract: ids outside [0, n) are ignored.  Tombstoned rows
+ * in the list never appear.  Everything else -- q, k, row_base, flags, output format and order (score, then lower row id), the stream
+ * contract -- is rmu_index_search's, and every returned score has the bits rmu_index_search returns for that row.  n_sub == 0, or fewer
+ * than k live rows in the list: the remaining slots hold (-inf | +inf for L2SQ, -1).
+ * Serves: VectorStore.similarity_search(**kwargs) with a filter -- Milvus col.search(expr='source == "a.pdf"') / PGVector
+ * filter={"source": "a.pdf"} behind the retriever's search_kwargs (RAGHelper.py:497-499). */
+#define RMU_F_ROWS_DEVICE 8u   /* rmu_index_search_subset: `rows` is a device address */
+int rmu_index_search_subset(rmu_index_t* idx, const float* q, int64_t nq, int k, unsigned flags, int64_t row_base,
+                            const int64_t* rows, int64_t n_sub, float* out_scores, int64_t* out_rows, uint64_t hip_stream);
+
 /* Merge `parts` per-shard top-k lists ([parts, nq, k] each, best first; larger score = better unless
  * RMU_F_SMALLER_BETTER) into one [nq, k].  Ties: lower part index first (give shards in ascending row order).
  * Serves: the 8-GPU shard merge after the RCCL all-gather; no reference counterpart. */

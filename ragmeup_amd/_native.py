@@ -15,6 +15,7 @@ if os.environ.get("RMU_TUNING") == "1" and os.environ.get("RMU_LIB"):
 RMU_OK = 0
 METRIC_IP, METRIC_COSINE, METRIC_L2SQ = 0, 1, 2
 F_Q_DEVICE, F_OUT_DEVICE, F_SMALLER_BETTER = 1, 2, 4
+F_ROWS_DEVICE = 8
 OPT_SCREEN = 1
 OPT_SCREEN_MIN_NQ = 2
 OPT_LADDER_RATIO, OPT_LADDER_FIRST = 3, 4
@@ -29,7 +30,7 @@ MAX_DIM = 768
 SYMBOLS = [
     "rmu_init", "rmu_last_error", "rmu_version",
     "rmu_index_create", "rmu_index_free", "rmu_index_size", "rmu_index_dim", "rmu_index_metric", "rmu_index_set_option", "rmu_index_stat", "rmu_index_reserve", "rmu_index_add",
-    "rmu_index_remove_rows", "rmu_index_compact", "rmu_index_get_rows", "rmu_index_save", "rmu_index_load", "rmu_index_mmr", "rmu_index_search_mmr", "rmu_index_search", "rmu_topk_merge",
+    "rmu_index_remove_rows", "rmu_index_compact", "rmu_index_get_rows", "rmu_index_save", "rmu_index_load", "rmu_index_mmr", "rmu_index_search_mmr", "rmu_index_search", "rmu_index_search_subset", "rmu_topk_merge",
     "rmu_last_scan_ms", "rmu_last_search_ms", "rmu_last_scan_geometry", "rmu_set_timing", "rmu_last_screened", "rmu_probe_mfma_rate",
     "rmu_comm_unique_id", "rmu_comm_init", "rmu_comm_free", "rmu_comm_world", "rmu_shard_allgather_topk", "rmu_index_screen_candidates",
     "rmu_bert_create", "rmu_bert_free", "rmu_bert_encode", "rmu_bert_encode_host", "rmu_bert_search_mmr",
@@ -76,6 +77,7 @@ def _declare(lib):
     lib.rmu_index_save.argtypes = [vp, c.c_char_p]
     lib.rmu_index_load.argtypes = [c.POINTER(vp), c.c_char_p]
     lib.rmu_index_search.argtypes = [vp, vp, i64, i32, u32, i64, vp, vp, u64]
+    lib.rmu_index_search_subset.argtypes = [vp, vp, i64, i32, u32, i64, vp, i64, vp, vp, u64]
     lib.rmu_topk_merge.argtypes = [vp, vp, i32, i64, i32, u32, vp, vp, u64]
     lib.rmu_last_scan_ms.restype = f32
     lib.rmu_last_search_ms.restype = f32

@@ -5,6 +5,7 @@
 //   rmu_index_add         RAGHelper.py:431, 525  (db.add_documents(documents, ids=ids))
 //   rmu_index_search      RAGHelper.py:497-499   (dense retriever -> FLAT similarity search)
 //   rmu_index_get_rows    RAGHelper.py:497-499   (search_type="mmr": re-fetch the fetch_k vectors)
+//   rmu_index_search_subset RAGHelper.py:497-499 (the same retriever with search_kwargs: Milvus col.search(expr=...) / PGVector filter=)
 //   rmu_index_remove_rows server.py:373-377      (collection.delete('source == ...'))
 //   rmu_index_compact     server.py:353-385 + RAGHelper.py:518-538 (delete / re-upload cycle; row moves in rmu_compact.hip)
 //   rmu_topk_merge        no counterpart (8-GPU shard merge)
@@ -83,7 +84,7 @@ struct Buf {
 struct Tls {
     hipStream_t stream = nullptr;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    Buf q, partial, out_s, out_r, in_s, in_r, qn, gthr, mscratch, qsplit, ckeys, flag, nrm, fbq, fb_s, fb_r, fb_i, mm_q, mm_s, mm_r, mm_p, gcand;
+    Buf q, partial, out_s, out_r, in_s, in_r, qn, gthr, mscratch, qsplit, ckeys, flag, nrm, fbq, fb_s, fb_r, fb_i, mm_q, mm_s, mm_r, mm_p, gcand, sub_ids, sub_rows;
     std::vector<hipEvent_t> lev;   // per-launch events of the screening ladder
     int ensure_events(int n) {
         while ((int)lev.size() < n) {
@@ -146,7 +147,7 @@ struct Tls {
         if (pend_ev) (void)hipEventDestroy(pend_ev);
         if (stream) (void)hipStreamSynchronize(stream);
         for (Buf* b : {&q, &partial, &out_s, &out_r, &in_s, &in_r, &qn, &gthr, &mscratch, &qsplit, &ckeys, &flag, &nrm, &fbq, &fb_s,
-                       &fb_r, &fb_i, &mm_q, &mm_s, &mm_r, &mm_p, &gcand})
+                       &fb_r, &fb_i, &mm_q, &mm_s, &mm_r, &mm_p, &gcand, &sub_ids, &sub_rows})
             b->release();
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -1519,6 +1520,119 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess) t.search_ms = ms;
         t.scan_ms = scan_total;
+    }
+    return RMU_OK;
+}
+
+// Exact top-k over the rows one ascending list names (include/rmu.h): the gathered scan of scan_subset.hip, whose keys carry list
+// positions, the ordinary final merge, then positions -> row ids.  The query preparation is rmu_index_search's (same padded, normalised,
+// augmented queries: the scores have the same bits).
+extern "C" int rmu_index_search_subset(rmu_index_t* idx, const float* q, int64_t nq, int k, unsigned flags, int64_t row_base,
+                                       const int64_t* rows, int64_t n_sub, float* out_scores, int64_t* out_rows, uint64_t hip_stream) {
+    RMU_ENTRY();
+    if (!idx || !q || !out_scores || !out_rows) return fail(RMU_E_INVALID, "rmu_index_search_subset: null pointer");
+    if (nq < 1) return fail(RMU_E_INVALID, "rmu_index_search_subset: nq must be >= 1");
+    if (k < 1 || k > RMU_MAX_K) return fail(RMU_E_INVALID, "rmu_index_search_subset: k must be in [1, 112]");
+    if (n_sub < 0 || (n_sub > 0 && !rows)) return fail(RMU_E_INVALID, "rmu_index_search_subset: rows / n_sub");
+    Tls& t = g_tls;
+    int rc = t.ensure_stream((hipStream_t)hip_stream);
+    if (rc) return fail(rc, "rmu_index_search_subset: stream");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : t.stream;
+    const bool q_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE, rows_dev = flags & RMU_F_ROWS_DEVICE;
+
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    const int dpad = idx->dpad, dim = idx->dim;
+    const bool l2 = idx->metric == RMU_METRIC_L2SQ;
+    if (!rows_dev) {            // a host list is checked before anything is enqueued; a device list is the caller's contract
+        int64_t prev = -1;
+        for (int64_t i = 0; i < n_sub; ++i) {
+            const int64_t r = rows[i];
+            if (r <= prev || r >= idx->n)
+                return fail(RMU_E_INVALID, "rmu_index_search_subset: rows must be strictly ascending ids in [0, n): entry " + std::to_string(i));
+            prev = r;
+        }
+    }
+    if (n_sub >= 0xFFFFFFFFll || idx->n >= 0xFFFFFFFFll) return fail(RMU_E_INVALID, "rmu_index_search_subset: row ids must fit 32 bits");
+    const int64_t n_eff = idx->n > 0 ? n_sub : 0;       // (an empty index: every id of a device list is absent)
+    t.scan_ms = -1.f; t.search_ms = -1.f; t.passes = 0; t.screened = 0;
+    if (n_eff > 0) {
+        if (t.sub_ids.ensure((size_t)rmu_subset_ids_len(n_eff) * sizeof(u32))) return fail(RMU_E_OOM, "rmu_index_search_subset: id workspace");
+        const int64_t* drows = rows;
+        if (!rows_dev) {
+            if (t.sub_rows.ensure((size_t)n_eff * sizeof(int64_t))) return fail(RMU_E_OOM, "rmu_index_search_subset: list workspace");
+            HIP_TRY(hipMemcpyAsync(t.sub_rows.p, rows, (size_t)n_eff * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            drows = (const int64_t*)t.sub_rows.p;
+        }
+        if ((rc = rmu_subset_narrow_launch(drows, n_eff, idx->n, (u32*)t.sub_ids.p, s))) return fail(rc, "rmu_index_search_subset: list conversion");
+    }
+
+    for (int64_t q0 = 0; q0 < nq; q0 += kMaxQueriesPerLaunch) {
+        const int64_t nb = (nq - q0) < kMaxQueriesPerLaunch ? (nq - q0) : kMaxQueriesPerLaunch;
+        // ---- queries -> device, padded to dpad, normalised for COSINE, augmented for L2SQ (as rmu_index_search) ---------------
+        const float* qsrc = q + q0 * dim;
+        const float* qdev = qsrc;
+        const bool need_copy = !q_dev || dpad != dim || idx->metric == RMU_METRIC_COSINE;
+        if (need_copy) {
+            if (t.q.ensure((size_t)nb * dpad * sizeof(float))) return fail(RMU_E_OOM, "rmu_index_search_subset: q workspace");
+            if (dpad != dim) HIP_TRY(hipMemsetAsync(t.q.p, 0, (size_t)nb * dpad * sizeof(float), s));
+            HIP_TRY(hipMemcpy2DAsync(t.q.p, (size_t)dpad * sizeof(float), qsrc, (size_t)dim * sizeof(float),
+                                     (size_t)dim * sizeof(float), (size_t)nb,
+                                     q_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+            if (idx->metric == RMU_METRIC_COSINE) {
+                hipLaunchKernelGGL(k_row_norm, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, dpad, nb, 1,
+                                   (float*)nullptr);
+                HIP_TRY(hipGetLastError());
+            }
+            if (l2) {
+                if (t.qn.ensure((size_t)nb * sizeof(float))) return fail(RMU_E_OOM, "rmu_index_search_subset: |q|^2 workspace");
+                hipLaunchKernelGGL(k_l2_aug_queries, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, dpad, dim, nb,
+                                   (float*)t.qn.p);
+                HIP_TRY(hipGetLastError());
+            }
+            qdev = (const float*)t.q.p;
+        }
+        float* d_s = out_scores + q0 * k;
+        int64_t* d_r = out_rows + q0 * k;
+        if (!out_dev) {
+            if (t.out_s.ensure((size_t)nb * k * sizeof(float)) || t.out_r.ensure((size_t)nb * k * sizeof(int64_t)))
+                return fail(RMU_E_OOM, "rmu_index_search_subset: output workspace");
+            d_s = (float*)t.out_s.p;
+            d_r = (int64_t*)t.out_r.p;
+        }
+        int parts = 1;
+        if (n_eff > 0) {
+            SubsetLaunch L{};
+            L.x = idx->x; L.n_rows = idx->n; L.dpad = dpad; L.ids = (const u32*)t.sub_ids.p; L.n_sub = n_eff; L.q = qdev; L.nq = (int)nb; L.k = k;
+            if ((rc = rmu_subset_plan(&L))) return fail(rc, "rmu_index_search_subset: no scan geometry for this (dim, k)");
+            const size_t gthr_bytes = (size_t)((nb + 127) / 128 * 128 + 64) * sizeof(u32);
+            if (t.partial.ensure((size_t)L.parts * nb * k * sizeof(u64)) || t.gthr.ensure(gthr_bytes))
+                return fail(RMU_E_OOM, "rmu_index_search_subset: partial workspace");
+            L.partial = (u64*)t.partial.p;
+            L.gthr = (u32*)t.gthr.p;
+            HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_bytes, s));
+            rc = rmu_subset_launch(&L, s);
+            if (rc) return fail(rc, std::string("rmu_index_search_subset: scan launch: ") + hipGetErrorString(hipGetLastError()));
+            t.grid = L.grid; t.block = 256; t.lds = L.lds_bytes; t.passes += 1;
+            parts = L.parts;
+        } else {               // nothing to scan: one all-empty partial, every slot comes out (-inf | +inf, -1)
+            if (t.partial.ensure((size_t)nb * k * sizeof(u64))) return fail(RMU_E_OOM, "rmu_index_search_subset: partial workspace");
+            HIP_TRY(hipMemsetAsync(t.partial.p, 0, (size_t)nb * k * sizeof(u64), s));
+        }
+        rc = rmu_merge_final_launch((const u64*)t.partial.p, parts, nb, k, 0, l2 ? 1 : 0, l2 ? (const float*)t.qn.p : nullptr, d_s, d_r, nullptr,
+                                    nullptr, s);
+        if (rc) return fail(rc, "rmu_index_search_subset: merge launch");
+        if (n_eff > 0 && (rc = rmu_subset_map_launch(d_r, (const u32*)t.sub_ids.p, nb * k, row_base, s)))
+            return fail(rc, "rmu_index_search_subset: row id launch");
+        if (!out_dev) {
+            HIP_TRY(hipMemcpyAsync(out_scores + q0 * k, d_s, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(out_rows + q0 * k, d_r, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        }
+        // as rmu_index_search: drain per block unless this is the only block of a caller stream with device outputs.  A host list was
+        // copied from pageable memory the caller may reuse: that call drains as well.
+        const bool drained = !hip_stream || q0 + nb < nq || !out_dev || !rows_dev;
+        if (drained) HIP_TRY(hipStreamSynchronize(s));
+        else mark_reader(idx, s);
+        t.finished(s, drained);
     }
     return RMU_OK;
 }

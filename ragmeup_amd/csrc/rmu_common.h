@@ -218,6 +218,27 @@ int rmu_rescore_launch(const u64* cand, int kp, const float* x, const float* q, 
 int rmu_merge_lists_launch(const float* scores, const int64_t* rows, int parts, int64_t stride_s, int64_t stride_r, int64_t nq, int k,
                            int smaller_better, float* out_scores, int64_t* out_rows, hipStream_t s);
 
+// gathered exact scan of rmu_index_search_subset (scan_subset.hip): the rows named by one ascending list, keys carry list positions
+struct SubsetLaunch {
+    const float* x;        // [n_rows, dpad] fp32 row-major: the index's matrix
+    int64_t n_rows;        // rows of the index: an id outside [0, n_rows) is absent
+    int dpad;
+    const u32* ids;        // [rmu_subset_ids_len(n_sub)] narrowed list (rmu_subset_narrow_launch), 0xFFFFFFFF = absent / padding
+    int64_t n_sub;
+    const float* q;        // [nq, dpad] fp32 device, prepared like rmu_index_search's
+    int nq;
+    int k;
+    u64* partial;          // [parts, nq, k] keys (score, list position)
+    u32* gthr;             // [nq padded to 128] shared thresholds: published, never read
+    // filled by rmu_subset_plan
+    int wq, kv, s_chunks, nqt, tiles_per_chunk, grid, parts, lds_bytes;
+};
+int64_t rmu_subset_ids_len(int64_t n_sub);               // u32 entries of the narrowed list (whole tiles + one tile of padding)
+int rmu_subset_plan(SubsetLaunch* p);
+int rmu_subset_launch(const SubsetLaunch* p, hipStream_t s);
+int rmu_subset_narrow_launch(const int64_t* rows, int64_t n_sub, int64_t n_rows, u32* ids, hipStream_t s);
+int rmu_subset_map_launch(int64_t* out_rows, const u32* ids, int64_t total, int64_t row_base, hipStream_t s);   // position -> row id + row_base
+
 // row moves of rmu_index_compact (rmu_compact.hip), one array of the index at a time: rows of row_bytes (768 / 1536 / 3072, or 4 for the
 // L2 norms); new row j in [first, n_live) comes from old row src_rows[j - first] (device list, strictly increasing, src_rows[i] >= first + i);
 // rows [0, first) stay where they are.

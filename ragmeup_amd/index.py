@@ -173,11 +173,17 @@ class FlatIndex:
         return rows, scores
 
     # -- search ------------------------------------------------------------------------------------
-    def search(self, q, k: int, row_base: int = 0, stream: int | None = None, out=None):
+    def search(self, q, k: int, row_base: int = 0, stream: int | None = None, out=None, rows=None):
         """Exact top-k.  numpy in -> numpy out; torch CUDA in -> torch CUDA out (same device).
         `stream` (torch CUDA input only): a non-zero hipStream_t handle (`torch.cuda.Stream.cuda_stream`) the search is ORDERED
         on -- the call returns without any host synchronisation (include/rmu.h stream contract) and the outputs are valid for
-        work queued behind it on that stream.  Default: complete on return."""
+        work queued behind it on that stream.  Default: complete on return.
+        `rows`: search these rows only (rmu_index_search_subset: a gathered scan, time proportional to the list) -- strictly ascending
+        index-local row ids, one list for all queries: a numpy int64 array (checked: RmuError RMU_E_INVALID when not ascending or out of
+        range) or, with torch CUDA queries, a torch CUDA int64 tensor (not checked: ids outside the index are ignored).  Scores and
+        order are those `search` without `rows` gives the same rows; fewer than k live rows in the list: (-inf | +inf, -1) padding."""
+        if rows is not None:
+            return self._search_subset(q, int(k), int(row_base), stream, out, rows)
         if _is_torch_cuda(q):
             import torch
             qq = q.detach().to(torch.float32).contiguous()
@@ -208,6 +214,53 @@ class FlatIndex:
         out_r = np.empty((nq, k), dtype=np.int64)
         N.check(self._lib.rmu_index_search(self._h, qq.ctypes.data, nq, int(k), 0, int(row_base),
                                            out_s.ctypes.data, out_r.ctypes.data, 0), "rmu_index_search")
+        return out_s, out_r
+
+    def _search_subset(self, q, k: int, row_base: int, stream, out, rows):
+        if _is_torch_cuda(q):
+            import torch
+            qq = q.detach().to(torch.float32).contiguous()
+            if qq.ndim == 1:
+                qq = qq[None]
+            if qq.shape[1] != self.dim:
+                raise ValueError(f"expected [nq, {self.dim}] got {tuple(qq.shape)}")
+            nq = qq.shape[0]
+            flags = N.F_Q_DEVICE | N.F_OUT_DEVICE
+            if _is_torch_cuda(rows):
+                if rows.dtype != torch.int64 or rows.ndim != 1 or rows.device != qq.device:
+                    raise ValueError("rows must be a 1-d int64 tensor on the queries' device")
+                rr = rows.contiguous()
+                rows_ptr, n_sub = rr.data_ptr(), int(rr.shape[0])
+                flags |= N.F_ROWS_DEVICE
+            else:
+                rr = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+                rows_ptr, n_sub = rr.ctypes.data, int(rr.shape[0])
+            if out is not None:
+                out_s, out_r = out
+                if (out_s.shape != (nq, k) or out_r.shape != (nq, k) or out_s.dtype != torch.float32 or out_r.dtype != torch.int64
+                        or not out_s.is_contiguous() or not out_r.is_contiguous() or out_s.device != qq.device or out_r.device != qq.device):
+                    raise ValueError("out must be (float32 [nq, k], int64 [nq, k]) contiguous tensors on the queries' device")
+            else:
+                out_s = torch.empty((nq, k), dtype=torch.float32, device=qq.device)
+                out_r = torch.empty((nq, k), dtype=torch.int64, device=qq.device)
+            if not stream:
+                torch.cuda.current_stream().synchronize()
+            N.check(self._lib.rmu_index_search_subset(self._h, qq.data_ptr(), nq, k, flags, row_base, rows_ptr, n_sub,
+                                                      out_s.data_ptr(), out_r.data_ptr(), int(stream or 0)), "rmu_index_search_subset")
+            return out_s, out_r
+        if _is_torch_cuda(rows):
+            raise ValueError("a device row list needs device queries")
+        qq = np.ascontiguousarray(q, dtype=np.float32)
+        if qq.ndim == 1:
+            qq = qq[None]
+        if qq.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] got {qq.shape}")
+        rr = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        nq = qq.shape[0]
+        out_s = np.empty((nq, k), dtype=np.float32)
+        out_r = np.empty((nq, k), dtype=np.int64)
+        N.check(self._lib.rmu_index_search_subset(self._h, qq.ctypes.data, nq, k, 0, row_base, rr.ctypes.data, int(rr.shape[0]),
+                                                  out_s.ctypes.data, out_r.ctypes.data, 0), "rmu_index_search_subset")
         return out_s, out_r
 
     def set_screening(self, on: bool = True):

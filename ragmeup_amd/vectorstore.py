@@ -106,7 +106,8 @@ class MI355XRetriever(VectorStoreRetriever):
         k = int(self.search_kwargs.get("k", 4))
         if self.search_type == "mmr":
             return self.vectorstore.max_marginal_relevance_search_batch(queries, **self.search_kwargs)
-        return [[d for d, _ in row] for row in self.vectorstore.similarity_search_with_score_batch(queries, k=k)]
+        flt = {name: self.search_kwargs[name] for name in ("filter", "expr") if name in self.search_kwargs}
+        return [[d for d, _ in row] for row in self.vectorstore.similarity_search_with_score_batch(queries, k=k, **flt)]
 
 
 _METRICS = {"ip": N.METRIC_IP, "cosine": N.METRIC_COSINE, "l2": N.METRIC_L2SQ}
@@ -163,6 +164,10 @@ class MI355XVectorStore(VectorStore):
         self._pks: list[str] = []
         self._alive: list[bool] = []
         self._pk_to_row: dict[str, int] = {}
+        # filtered search: field -> (value -> ascending int64 rows of the live records holding it), built on the first filtered query that
+        # names the field and dropped whenever records change (_records_changed); _field_map_builds counts the builds
+        self._field_maps: dict[str, tuple] = {}
+        self._field_map_builds = 0
         # compact() renumbers the rows while searches run without self._lock: a seqlock.  _gen is odd while the index and the records
         # are being renumbered; a read that started under another value (or an odd one) is repeated (see _consistent)
         self._gen = 0
@@ -309,6 +314,7 @@ class MI355XVectorStore(VectorStore):
             self.metric = m.get("metric", "ip")
             self.score_mode = m.get("score_mode", self.score_mode)
             self._pk_to_row = {pk: r for r, pk in enumerate(self._pks) if self._alive[r]}
+            self._records_changed()
             self._dirty = False
         return True
 
@@ -391,6 +397,7 @@ class MI355XVectorStore(VectorStore):
             _wait([self._pending[0][0]])
             exc = self._pending[0][0].exception()
             if exc is not None:
+                self._records_changed()
                 ents, self._pending = self._pending, []
                 _wait([ent[0] for ent in ents[1:]])      # queued behind the failure: skipped by the worker (their futures carry that)
                 self._pipe_failed = False
@@ -626,6 +633,7 @@ class MI355XVectorStore(VectorStore):
                 self._alive[r] = False
             old_rows.update(zip(sel_ids, range(n0, n0 + len(sel_ids))))
             self._dirty = True
+            self._records_changed()
             from concurrent.futures import Future, ThreadPoolExecutor
             if self._worker is None:
                 self._worker = ThreadPoolExecutor(max_workers=1, thread_name_prefix="rmu-add")
@@ -756,6 +764,7 @@ class MI355XVectorStore(VectorStore):
             self._drain()
             self._ensure_index(int(vecs.shape[1]))
             n0 = len(self._texts)
+            self._records_changed()
             # host records FIRST: a concurrent search may return a new row the moment index.add publishes it
             self._texts.extend(sel_texts)
             self._metas.extend(sel_metas)
@@ -808,27 +817,151 @@ class MI355XVectorStore(VectorStore):
         return self._add([d.page_content for d in documents], lambda: [d.metadata for d in documents], ids)
 
     # ---- delete (server.py:373-377) -----------------------------------------------------------------------
-    _EXPR = re.compile(r"""^\s*(\w+)\s*==\s*(['"])(.*)\2\s*$""")
+    # ---- conditions on records: one language for delete(expr=, filter=) and for every search entry point ------------------------
+    # expr (Milvus style): `field == "v"`, `field in ["a", 'b']`, joined by `and` / `&&`; values are quoted strings or plain numbers.
+    # filter (PGVector style): {field: value} or {field: [values]} = any of them.  Every condition must hold; "pk" names the primary key.
+    _EXPR = re.compile(r"""^\s*(\w+)\s*==\s*(['"])(.*)\2\s*$""")        # the whole expression as ONE equality: the value may hold anything
+    _TOKEN = re.compile(r"""\s*(?:(?P<str>"[^"]*"|'[^']*')|(?P<num>-?\d+(?:\.\d+)?(?![\w.]))|(?P<op>==|&&|\[|\]|,)|(?P<word>\w+))""")
+
+    @classmethod
+    def _parse_expr(cls, expr: str) -> list[tuple[str, list]]:
+        """-> [(field, [accepted values])]; ValueError for anything the grammar above does not cover (an expression is never ignored)"""
+        toks, pos = [], 0
+        text = expr.rstrip()
+        while pos < len(text):
+            m = cls._TOKEN.match(text, pos)
+            if not m:
+                toks = None
+                break
+            kind = m.lastgroup
+            raw = m.group(kind)
+            toks.append((kind, raw[1:-1] if kind == "str" else (float(raw) if "." in raw else int(raw)) if kind == "num" else raw))
+            pos = m.end()
+        conds: list[tuple[str, list]] = []
+
+        def value(i):
+            if i < len(toks) and toks[i][0] in ("str", "num"):
+                return toks[i][1], i + 1
+            raise ValueError
+
+        try:
+            if not toks:
+                raise ValueError
+            i = 0
+            while True:
+                if toks[i][0] != "word" or toks[i][1] in ("and", "in"):
+                    raise ValueError
+                field = toks[i][1]
+                if toks[i + 1] == ("op", "=="):
+                    v, i = value(i + 2)
+                    conds.append((field, [v]))
+                elif toks[i + 1] == ("word", "in") and toks[i + 2] == ("op", "["):
+                    vals, i = [], i + 3
+                    while True:
+                        v, i = value(i)
+                        vals.append(v)
+                        if toks[i] == ("op", "]"):
+                            i += 1
+                            break
+                        if toks[i] != ("op", ","):
+                            raise ValueError
+                        i += 1
+                    conds.append((field, vals))
+                else:
+                    raise ValueError
+                if i == len(toks):
+                    return conds
+                if toks[i] not in (("word", "and"), ("op", "&&")):
+                    raise ValueError
+                i += 1
+        except (ValueError, IndexError):
+            # what delete() always took: one equality whose value may itself hold quotes -- but not a second condition this grammar
+            # does not know (`or`, `>`...): that is an error, not a strange value
+            m = cls._EXPR.match(expr)
+            if m and not re.search(r"==|\bin\s*\[", m.group(3)):
+                return [(m.group(1), [m.group(3)])]
+            raise ValueError(f"unsupported filter expression: {expr!r}") from None
+
+    @classmethod
+    def _conditions(cls, expr, filter) -> list[tuple[str, list]] | None:
+        """The conditions `expr=` and `filter=` state together, or None when neither is given."""
+        if expr is None and filter is None:
+            return None
+        if filter is not None and not isinstance(filter, dict):
+            raise ValueError(f"filter must be a dict of field -> value or list of values, got {type(filter).__name__}")
+        if expr is not None and not isinstance(expr, str):
+            raise ValueError(f"expr must be a string, got {type(expr).__name__}")
+        conds = [(str(f), list(v) if isinstance(v, (list, tuple, set, frozenset)) else [v]) for f, v in (filter or {}).items()]
+        if expr is not None and expr.strip():
+            conds += cls._parse_expr(expr)
+        elif expr is not None and not conds:
+            raise ValueError("unsupported filter expression: ''")
+        return conds or None                             # (filter={} states nothing)
+
+    def _records_changed(self):
+        self._field_maps = {}
+
+    def _field_map(self, field: str):
+        """value -> ascending int64 rows of the live records whose `field` holds it (+ the few records with unhashable values), built once
+        per field until the records change.  Built under the writer lock: no insert or delete can slip between the walk and the store."""
+        fm = self._field_maps.get(field)
+        if fm is None:
+            with self._lock:
+                fm = self._field_maps.get(field)
+                if fm is None:
+                    buckets: dict = {}
+                    odd: list[tuple[int, Any]] = []
+                    alive, pks, metas = self._alive, self._pks, self._metas
+                    for r in range(len(alive)):
+                        if not alive[r]:
+                            continue
+                        if field == "pk":
+                            v = pks[r]
+                        else:
+                            v = metas[r].get(field)      # (a record without the field holds None, as delete always compared)
+                        try:
+                            buckets.setdefault(v, []).append(r)
+                        except TypeError:                # a list / dict as metadata value
+                            odd.append((r, v))
+                    fm = ({v: np.asarray(rs, dtype=np.int64) for v, rs in buckets.items()}, odd)
+                    self._field_maps[field] = fm
+                    self._field_map_builds += 1
+        return fm
+
+    def _filter_rows(self, conds: list[tuple[str, list]]) -> np.ndarray:
+        """Ascending int64 rows of the live records that satisfy every condition."""
+        rows = None
+        for field, vals in conds:
+            by_value, odd = self._field_map(field)
+            parts = []
+            for v in vals:
+                try:
+                    hit = by_value.get(v)
+                except TypeError:
+                    hit = None
+                if hit is not None:
+                    parts.append(hit)
+            if odd:
+                parts.append(np.asarray([r for r, v in odd if v in vals or v == vals], dtype=np.int64))
+            if not parts:
+                return np.zeros(0, np.int64)
+            cur = parts[0] if len(parts) == 1 else np.unique(np.concatenate(parts))
+            rows = cur if rows is None else np.intersect1d(rows, cur, assume_unique=True)
+            if rows.size == 0:
+                break
+        return rows if rows is not None else np.flatnonzero(np.asarray(self._alive, dtype=bool)).astype(np.int64)
 
     def delete(self, ids: Optional[list[str]] = None, expr: Optional[str] = None, filter: Optional[dict] = None, **kw):
-        """Delete by pk list, by a Milvus-style `field == "value"` expression, or by a metadata dict.
+        """Delete by pk list, by a Milvus-style expression (`field == "value"`, and the forms the searches take), or by a metadata dict.
         Returns an object with ``delete_count`` (what server.py:385 reads) that is also truthy/int-like."""
         with self._lock:
             self._drain()
             rows: list[int] = []
             if ids:
                 rows += [self._pk_to_row[i] for i in ids if i in self._pk_to_row]
-            cond = dict(filter or {})
-            if expr:
-                m = self._EXPR.match(expr)
-                if not m:
-                    raise ValueError(f"unsupported delete expression: {expr!r}")
-                cond[m.group(1)] = m.group(3)
-            if cond:
-                for r, md in enumerate(self._metas):
-                    if self._alive[r] and all(
-                            (self._pks[r] if k == "pk" else md.get(k)) == v for k, v in cond.items()):
-                        rows.append(r)
+            conds = self._conditions(expr or None, filter or None)
+            if conds:
+                rows += self._filter_rows(conds).tolist()
             rows = sorted({r for r in rows if self._alive[r]})
             if rows and self._index is not None:
                 self._index.remove_rows(rows)
@@ -836,6 +969,7 @@ class MI355XVectorStore(VectorStore):
                 self._alive[r] = False
             if rows:
                 self._dirty = True
+                self._records_changed()
                 self._maybe_compact()
                 if self.auto_persist is True:
                     self.persist()
@@ -870,6 +1004,7 @@ class MI355XVectorStore(VectorStore):
             self._alive = [True] * len(keep)
             self._pk_to_row = {pk: j for j, pk in enumerate(self._pks)}
         finally:
+            self._records_changed()                      # compaction renumbers the rows
             self._gen += 1
         self._dirty = True
         return before - len(self._alive)
@@ -903,19 +1038,29 @@ class MI355XVectorStore(VectorStore):
                 return out
 
     # ---- search ---------------------------------------------------------------------------------------------
-    def _search_vecs(self, qvecs: np.ndarray, k: int):
+    def _search_vecs(self, qvecs: np.ndarray, k: int, conds=None):
+        """conds (a filtered query): the conditions are resolved to rows HERE, inside the caller's _consistent read, and the index searches
+        those rows only (FlatIndex.search(rows=...): the gathered scan); without conditions the index is called as it always was."""
         if self._pending:
             self.flush()
+        none = np.full((qvecs.shape[0], 0), -np.inf, np.float32), np.full((qvecs.shape[0], 0), -1, np.int64)
         if self._index is None or len(self._index) == 0:
-            return np.full((qvecs.shape[0], 0), -np.inf, np.float32), np.full((qvecs.shape[0], 0), -1, np.int64)
+            return none
         kk = max(1, min(int(k), N.MAX_K))
-        return self._index.search(qvecs, kk)
+        if conds is None:
+            return self._index.search(qvecs, kk)
+        rows = self._filter_rows(conds)
+        if rows.size == 0:
+            return none
+        return self._index.search(qvecs, kk, rows=rows)
 
-    def similarity_search_with_score_by_vector(self, embedding, k: int = 4, **kw) -> list[tuple[Document, float]]:
+    def similarity_search_with_score_by_vector(self, embedding, k: int = 4, filter: Optional[dict] = None, expr: Optional[str] = None,
+                                               **kw) -> list[tuple[Document, float]]:
         q = np.asarray(embedding, dtype=np.float32)[None]
+        conds = self._conditions(expr, filter)
 
         def read():
-            s, r = self._search_vecs(q, k)
+            s, r = self._search_vecs(q, k, conds)
             return [(self._doc(int(row)), self._convert(float(sc))) for sc, row in zip(s[0], r[0]) if row >= 0]
         return self._consistent(read)
 
@@ -934,52 +1079,60 @@ class MI355XVectorStore(VectorStore):
         rows, scores = emb.encoder.search_host(idx, q[0], q[1], emb._mode, fetch_k, k, lambda_mult)
         return rows[0], scores[0]
 
-    def similarity_search_with_score(self, query: str, k: int = 4, **kw) -> list[tuple[Document, float]]:
+    def similarity_search_with_score(self, query: str, k: int = 4, filter: Optional[dict] = None, expr: Optional[str] = None,
+                                     **kw) -> list[tuple[Document, float]]:
         def read():
             hit = self._fused_query(query, int(k), int(k), None)
             if hit is None:
                 return None
             return [(self._doc(int(row)), self._convert(float(sc))) for row, sc in zip(*hit) if row >= 0]
-        out = self._consistent(read)
+        # a filtered query does not take the fused call (rmu_bert_search_mmr has no subset form): embed, subset search
+        out = self._consistent(read) if self._conditions(expr, filter) is None else None
         if out is not None:
             return out
-        return self.similarity_search_with_score_by_vector(self._embed_query(query), k, **kw)
+        return self.similarity_search_with_score_by_vector(self._embed_query(query), k, filter=filter, expr=expr, **kw)
 
     def similarity_search(self, query: str, k: int = 4, **kw) -> list[Document]:
         return [d for d, _ in self.similarity_search_with_score(query, k, **kw)]
 
-    def similarity_search_with_relevance_scores(self, query: str, k: int = 4, **kw) -> list[tuple[Document, float]]:
+    def similarity_search_with_relevance_scores(self, query: str, k: int = 4, filter: Optional[dict] = None, expr: Optional[str] = None,
+                                                **kw) -> list[tuple[Document, float]]:
+        conds = self._conditions(expr, filter)
         q = self._embed_query(query)[None]
 
         def read():
-            s, r = self._search_vecs(q, k)
+            s, r = self._search_vecs(q, k, conds)
             return [(self._doc(int(row)), float(sc)) for sc, row in zip(s[0], r[0]) if row >= 0]
         return self._consistent(read)
 
-    def similarity_search_with_score_batch(self, queries: list[str], k: int = 4) -> list[list[tuple[Document, float]]]:
+    def similarity_search_with_score_batch(self, queries: list[str], k: int = 4, filter: Optional[dict] = None,
+                                           expr: Optional[str] = None, **kw) -> list[list[tuple[Document, float]]]:
+        conds = self._conditions(expr, filter)
         qv = self._embed_docs(list(queries))
 
         def read():
-            s, r = self._search_vecs(qv, k)
+            s, r = self._search_vecs(qv, k, conds)
             return [[(self._doc(int(row)), self._convert(float(sc))) for sc, row in zip(ss, rr) if row >= 0]
                     for ss, rr in zip(s, r)]
         return self._consistent(read)
 
     def max_marginal_relevance_search_by_vector(self, embedding, k: int = 4, fetch_k: int = 20,
-                                                lambda_mult: float = 0.5, **kw) -> list[Document]:
+                                                lambda_mult: float = 0.5, filter: Optional[dict] = None, expr: Optional[str] = None,
+                                                **kw) -> list[Document]:
         q = np.asarray(embedding, dtype=np.float32)
-        return self._consistent(lambda: self._mmr_by_vector(q, k, fetch_k, lambda_mult))
+        conds = self._conditions(expr, filter)
+        return self._consistent(lambda: self._mmr_by_vector(q, k, fetch_k, lambda_mult, conds))
 
-    def _mmr_by_vector(self, q: np.ndarray, k: int, fetch_k: int, lambda_mult: float) -> list[Document]:
+    def _mmr_by_vector(self, q: np.ndarray, k: int, fetch_k: int, lambda_mult: float, conds=None) -> list[Document]:
         if self._pending:
             self.flush()
-        if (self._index is not None and hasattr(self._index, "search_mmr") and len(self._index) > 0
+        if (conds is None and self._index is not None and hasattr(self._index, "search_mmr") and len(self._index) > 0
                 and 1 <= k <= int(fetch_k) <= 64):
             # dense top-fetch_k and the greedy selection in one library call (rmu_index_search_mmr, fetch_k <= 64): one host
             # round trip.  A larger pool takes the search + selection below with the FULL fetch_k candidates.
             rows, _ = self._index.search_mmr(q[None], int(fetch_k), k, lambda_mult)
             return [self._doc(int(x)) for x in rows[0] if x >= 0]
-        s, r = self._search_vecs(q[None], fetch_k)
+        s, r = self._search_vecs(q[None], fetch_k, conds)    # (a filtered query: subset search, then the selection below)
         rows = [int(x) for x in r[0] if x >= 0]
         if not rows:
             return []
@@ -993,24 +1146,26 @@ class MI355XVectorStore(VectorStore):
         return [self._doc(rows[i]) for i in picked]
 
     def max_marginal_relevance_search(self, query: str, k: int = 4, fetch_k: int = 20, lambda_mult: float = 0.5,
-                                      **kw) -> list[Document]:
+                                      filter: Optional[dict] = None, expr: Optional[str] = None, **kw) -> list[Document]:
         def read():
             hit = self._fused_query(query, int(fetch_k), int(k), float(lambda_mult))     # the reference's per-request call (RAGHelper.py:497-499)
             return None if hit is None else [self._doc(int(x)) for x in hit[0] if x >= 0]
-        out = self._consistent(read)
+        out = self._consistent(read) if self._conditions(expr, filter) is None else None     # filtered: embed, subset search, device MMR
         if out is not None:
             return out
-        return self.max_marginal_relevance_search_by_vector(self._embed_query(query), k, fetch_k, lambda_mult)
+        return self.max_marginal_relevance_search_by_vector(self._embed_query(query), k, fetch_k, lambda_mult, filter=filter, expr=expr)
 
     def max_marginal_relevance_search_batch(self, queries: list[str], k: int = 4, fetch_k: int = 20,
-                                            lambda_mult: float = 0.5, **kw) -> list[list[Document]]:
+                                            lambda_mult: float = 0.5, filter: Optional[dict] = None, expr: Optional[str] = None,
+                                            **kw) -> list[list[Document]]:
         """One dense search + ONE device-side MMR selection for the whole batch (`rmu_index_mmr`: fp64, same greedy rule and
         tie order as the single-query path; no per-query vector re-fetch).  fetch_k > 64 falls back to the host loop."""
+        conds = self._conditions(expr, filter)
         qv = self._embed_docs(list(queries))
-        return self._consistent(lambda: self._mmr_batch(qv, k, fetch_k, lambda_mult))
+        return self._consistent(lambda: self._mmr_batch(qv, k, fetch_k, lambda_mult, conds))
 
-    def _mmr_batch(self, qv: np.ndarray, k: int, fetch_k: int, lambda_mult: float) -> list[list[Document]]:
-        s, r = self._search_vecs(qv, fetch_k)
+    def _mmr_batch(self, qv: np.ndarray, k: int, fetch_k: int, lambda_mult: float, conds=None) -> list[list[Document]]:
+        s, r = self._search_vecs(qv, fetch_k, conds)
         if r.shape[1] == 0:
             return [[] for _ in range(qv.shape[0])]
         if r.shape[1] <= 64 and hasattr(self._index, "mmr"):
