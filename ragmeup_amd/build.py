@@ -40,8 +40,8 @@ SAN_FLAGS = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-g", "-
 
 
 def build(force: bool = False, verbose: bool = False, debug_kernels: bool = False, asan: bool = False) -> str:
-    """debug_kernels: also compile the cycle-counter / ablation instantiations (-DRMU_DEBUG_KERNELS: RMU_FFN_DBG, RMU_G3_DBG,
-    RMU_GEMM_DBG); the product library carries none of them.  Switching the flag needs force=True.
+    """debug_kernels: also compile the cycle-counter / ablation instantiations (-DRMU_DEBUG_KERNELS: RMU_FFN3_DBG, RMU_G3_DBG,
+    RMU_QA_CLK, RMU_GEMM_DBG); the product library carries none of them.  Switching the flag needs force=True.
     asan: a SEPARATE library, lib/librmu_asan.so (objects under lib/obj_asan), whose HOST code -- the C-ABI, the WordPiece tokenizer and
     its thread pool, the index's locking and bookkeeping -- is compiled with AddressSanitizer + UBSan (`make asan-test` runs the CPU
     tests that call into the library against it; device code is not instrumented: GPU sanitizers are not available on this pool)."""

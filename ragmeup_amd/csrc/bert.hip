@@ -86,7 +86,7 @@ __device__ __forceinline__ float gelu_poly(float v) {
 
 // the same on four values at once, written with vector operations so that every polynomial step is emitted for all four
 // elements before the next step (four independent dependency chains in flight instead of one).  hipcc turns this into
-// v_pk_fma_f32 / v_pk_mul_f32; the same polynomial as 28 scalar inline-asm v_fma_f32 measured 5 % slower in k_ffn_fused.
+// v_pk_fma_f32 / v_pk_mul_f32; the same polynomial as 28 scalar inline-asm v_fma_f32 measured 5 % slower in the round-2 fused FFN kernel.
 __device__ __forceinline__ f32x4 gelu_poly4(f32x4 v) {
     auto sp = [](float c) { return f32x4{c, c, c, c}; };
     const f32x4 t = v * 0.70710678118654752f;
@@ -121,8 +121,10 @@ __global__ void k_scale_copy(const float* __restrict__ src, float* __restrict__ 
     if (i < n) dst[i] = src[i] * scale;
 }
 
-// W2 copy for k_ffn_fused: inside every block of 16 columns, slot 8 h + e holds column (e < 4 ? 4 h + e : 8 + 4 h + e - 4)
-// -- the order in which a lane half h of GEMM1's 32x32 accumulator layout holds 8 of the block's 16 features (see k_ffn_fused)
+// W2 copy for the fused FFN kernels (k_ffn2, k_ffn3): inside every block of 16 columns, slot 8 h + e holds column
+// (e < 4 ? 4 h + e : 8 + 4 h + e - 4) -- the order in which a lane half h of FFN1's 32x32 accumulator layout holds 8 of the block's 16
+// features.  With swapped operands (A = weights) that D layout -- lane = token, registers 8 s .. 8 s + 7 = features {4 h + e, 8 + 4 h + e}
+// of the 16-block s -- is a k-permuted B fragment of k-step s: the activated intermediate feeds FFN2 without leaving the registers.
 __global__ void k_permute_w2(const bf16* __restrict__ src, bf16* __restrict__ dst, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -130,31 +132,6 @@ __global__ void k_permute_w2(const bf16* __restrict__ src, bf16* __restrict__ ds
     const int s16 = (int)(i & 15), h = s16 >> 3, e = s16 & 7;
     dst[i] = src[blk + (e < 4 ? 4 * h + e : 8 + 4 * h + (e - 4))];
 }
-
-// Weight streams for k_ffn3: the very slab images its LDS slots hold, in stream order, so that a DMA wave instruction reads 1 KiB of
-// contiguous bytes and the 2-3 instructions a wave issues per slab differ only by the instruction's immediate offset.
-//   W1 stream: [chunk c][slab i] 16 KiB = [64 rows][16 units]; physical unit pu of row r holds logical lu = pu ^ (r & 15);
-//              lu < 8: k [64 i + 8 lu, +8), lu >= 8: k [192 + 64 i + 8 (lu - 8), +8) of W1 row 64 c + r
-//   W2 stream: [chunk c][tile t] 24 KiB = [384 rows][4 units]; pu of row r holds lu = pu ^ ((r >> 2) & 3): k [64 c + 32 t + 8 lu, +8) of
-//              the k_permute_w2 copy's row r
-#ifdef RMU_DEBUG_KERNELS
-__global__ void k_pack_ffn3(const bf16* __restrict__ w1, const bf16* __restrict__ w2p, bf16* __restrict__ w1s, bf16* __restrict__ w2s) {
-    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t n1 = (int64_t)FF * H / 8;
-    if (d < n1) {
-        const int slab = (int)(d >> 10), within = (int)(d & 1023), c = slab / 3, i = slab % 3;
-        const int r = within >> 4, pu = within & 15, lu = pu ^ (r & 15);
-        const int k0 = lu < 8 ? 64 * i + 8 * lu : 192 + 64 * i + 8 * (lu - 8);
-        *(bf16x8*)(w1s + d * 8) = *(const bf16x8*)(w1 + (int64_t)(64 * c + r) * H + k0);
-    } else if (d < 2 * n1) {
-        const int64_t e = d - n1;
-        const int slab = (int)(e / 1536), within = (int)(e % 1536), c = slab >> 1, t = slab & 1;
-        const int r = within >> 2, pu = within & 3, lu = pu ^ ((r >> 2) & 3);
-        *(bf16x8*)(w2s + e * 8) = *(const bf16x8*)(w2p + (int64_t)r * FF + 64 * c + 32 * t + 8 * lu);
-    }
-}
-
-#endif
 
 // Weight copy for k_gemm3's LDS-DMA: block (nb, kb) = rows [16 nb, +16) x k [32 kb, +32) stored as the very 1 KiB its ring
 // slot holds (row r of the block at byte 64 r, logical 16-byte unit u at physical unit u ^ tswz(r)), blocks in [nb][kb]
@@ -751,142 +728,6 @@ __global__ __launch_bounds__(64 * NWV) void k_gemm_small(const bf16* __restrict_
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// k_gemm_mid -- the same GEMM (and the same LayerNorm folds) for a few HUNDRED to a few THOUSAND tokens: the reference's rerank call
-// (<= 14 (query, passage) pairs, ~1.5k tokens, twice per /chat request).  k_gemm_small's K split costs four barriers and an LDS round
-// trip per 32-token tile -- ~2 us a tile whatever is prefetched (8-20 us per launch at 1.5k tokens), and the tiled kernels run 6-36
-// workgroups of 6-24 latency-bound stages there (11-15 us).  Here NOTHING is shared: a wave owns one 32-feature x 32-token output tile
-// for the whole K -- both operands straight from global memory / L2 as MFMA fragments, in k chunks of CK with the next chunk's
-// fragments requested before the current chunk's MFMAs (the weight rows are re-read per token tile: 56 MB of L2 reads for FFN2 at
-// 1.5k tokens, microseconds) -- no LDS, no barrier, the LayerNorm statistics of a token are this lane's and lane ^ 32's.  grid =
-// (N / 32) x ceil(tokens / 128); the four waves of a workgroup take four consecutive token tiles of one feature block.
-// ------------------------------------------------------------------------------------------------------------
-template <int EPI, int K, bool LNA = false, bool LNR = false>
-__global__ __launch_bounds__(256) void k_gemm_mid(const bf16* __restrict__ A, const bf16* __restrict__ W, const float* __restrict__ bias,
-                                                  const bf16* __restrict__ resid, bf16* __restrict__ out, const int* __restrict__ cu,
-                                                  int batch, int N, const float* __restrict__ lng, const float* __restrict__ lnb, float eps,
-                                                  float2* __restrict__ stats_out, const float* __restrict__ rg, const float* __restrict__ rb,
-                                                  const float2* __restrict__ rstats) {
-    static_assert(!LNA || K == H, "the normalised operand is a hidden-state row");
-    constexpr int CK = LNA ? K : 192;                  // k per chunk (LNA: the whole row at once -- its statistics come first)
-    constexpr int NC = K / CK, NF = CK / 16;
-    const int M = cu[batch];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int r31 = lane & 31, hh = lane >> 5;
-    __shared__ float sgb[LNA ? 2 * H : 2];             // LNA: gamma | beta (read per fragment from LDS: hoisted global loads of all 192 pairs
-    if constexpr (LNA) {                                // per lane cost 384 registers and spilled)
-        for (int i = threadIdx.x; i < H; i += 256) { sgb[i] = lng[i]; sgb[H + i] = lnb[i]; }
-        __syncthreads();
-    }
-    const int t0 = (blockIdx.y * 4 + w) * 32;
-    if (t0 >= M) return;
-    const int n0 = blockIdx.x * 32;
-    const int tok = min(t0 + r31, M - 1);
-    const bf16* wr = W + (int64_t)(n0 + r31) * K + hh * 8;       // A operand: feature n0 + r31, k = 16 f + 8 hh ..
-    const bf16* xr = A + (int64_t)tok * K + hh * 8;              // B operand: token, same k
-    bf16x8 wf[2][NF], xf[2][NF];
-    auto request = [&](int c, int buf) {
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-            wf[buf][f] = *(const bf16x8*)(wr + c * CK + f * 16);
-            xf[buf][f] = *(const bf16x8*)(xr + c * CK + f * 16);
-        }
-    };
-    request(0, 0);
-    // epilogue operands, requested now: acc[4 q + e] = feature n0 + 8 q + 4 hh + e of token t0 + r31
-    const bool live = t0 + r31 < M;
-    f32x4 bq[4];
-    bf16x4 rv[4];
-    float2 st = {0.f, 1.f};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        bq[q] = *(const f32x4*)(bias + n0 + 8 * q + 4 * hh);
-        rv[q] = bf16x4{};
-        if (EPI == EPI_RESID && live) rv[q] = *(const bf16x4*)(resid + (int64_t)(t0 + r31) * N + n0 + 8 * q + 4 * hh);
-    }
-    if constexpr (LNR) { if (live) st = rstats[t0 + r31]; }
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        if (c + 1 < NC) request(c + 1, (c + 1) & 1);
-        if constexpr (LNA) {
-            // LN(y) of this token on the way in: two-pass fp32 statistics over the 384 values = this lane's 192 and lane ^ 32's.  The
-            // fragments are handled as packed 32-bit PAIRS (a shift / a mask widens a bf16, one v_cvt_pk_bf16_f32 packs two results):
-            // element-wise bf16 arithmetic made hipcc keep every element in a register of its own (512 registers + 752 bytes of scratch)
-            typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-            auto lo_f = [](u32 u) { return __builtin_bit_cast(float, u << 16); };
-            auto hi_f = [](u32 u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
-            float sm = 0.f;
-#pragma unroll
-            for (int f = 0; f < NF; ++f) {
-                const u32x4 u = __builtin_bit_cast(u32x4, xf[0][f]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) sm += lo_f(u[j]) + hi_f(u[j]);
-            }
-            sm += __shfl_xor(sm, 32);
-            const float mu = sm * (1.0f / H);
-            float qv = 0.f;
-#pragma unroll
-            for (int f = 0; f < NF; ++f) {
-                const u32x4 u = __builtin_bit_cast(u32x4, xf[0][f]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { const float d0 = lo_f(u[j]) - mu, d1 = hi_f(u[j]) - mu; qv = fmaf(d0, d0, qv); qv = fmaf(d1, d1, qv); }
-            }
-            qv += __shfl_xor(qv, 32);
-            const float rs = rsqrtf(qv * (1.0f / H) + eps);
-#pragma unroll
-            for (int f = 0; f < NF; ++f) {
-                const int k0 = f * 16 + hh * 8;
-                const u32x4 u = __builtin_bit_cast(u32x4, xf[0][f]);
-                u32x4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float a = (lo_f(u[j]) - mu) * rs * sgb[k0 + 2 * j] + sgb[H + k0 + 2 * j];
-                    const float b = (hi_f(u[j]) - mu) * rs * sgb[k0 + 2 * j + 1] + sgb[H + k0 + 2 * j + 1];
-                    u32 pk;
-                    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk) : "v"(a), "v"(b));
-                    o[j] = pk;
-                }
-                xf[0][f] = __builtin_bit_cast(bf16x8, o);
-                if (f % 4 == 3) asm volatile("" ::: "memory");     // at most four fragments' parameters in registers at a time
-            }
-            if (stats_out && blockIdx.x == 0 && hh == 0 && live) stats_out[t0 + r31] = float2{mu, rs};
-        }
-#pragma unroll
-        for (int f = 0; f < NF; ++f) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[c & 1][f], xf[c & 1][f], acc, 0, 0, 0);
-    }
-    if (!live) return;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        f32x4 v = {acc[4 * q] + bq[q][0], acc[4 * q + 1] + bq[q][1], acc[4 * q + 2] + bq[q][2], acc[4 * q + 3] + bq[q][3]};
-        if (EPI == EPI_GELU) v = gelu_poly4(v);
-        bf16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (bf16)v[e];
-        if (EPI == EPI_RESID) {
-            bf16x4 r4 = rv[q];
-            if constexpr (LNR) {
-                const f32x4 gq = *(const f32x4*)(rg + n0 + 8 * q + 4 * hh), bb = *(const f32x4*)(rb + n0 + 8 * q + 4 * hh);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) r4[e] = (bf16)((bf2f(r4[e]) - st.x) * st.y * gq[e] + bb[e]);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (bf16)(bf2f(o[e]) + bf2f(r4[e]));
-        }
-        *(bf16x4*)(out + (int64_t)(t0 + r31) * N + n0 + 8 * q + 4 * hh) = o;
-    }
-}
-
-template <int EPI, int K, bool LNA = false, bool LNR = false>
-static void launch_mid(hipStream_t s, int64_t m_cap, const bf16* A, const bf16* W, const float* bias, const bf16* resid, bf16* out, const int* cu,
-                       int batch, int N, const float* lng = nullptr, const float* lnb = nullptr, float eps = 0.f, float2* stats_out = nullptr,
-                       const float* rg = nullptr, const float* rb = nullptr, const float2* rstats = nullptr) {
-    const dim3 grid((unsigned)(N / 32), (unsigned)((m_cap + 127) / 128));
-    hipLaunchKernelGGL((k_gemm_mid<EPI, K, LNA, LNR>), grid, dim3(256), 0, s, A, W, bias, resid, out, cu, batch, N, lng, lnb, eps, stats_out, rg, rb, rstats);
-}
-
 // one k_gemm_small launch: grid = N / 32 feature blocks x token blocks of `tb`
 template <int EPI, int K, bool LNA = false, bool LNR = false>
 static void launch_small(hipStream_t s, int64_t m_cap, int tb, const bf16* A, const bf16* W, const float* bias, const bf16* resid, bf16* out, const int* cu,
@@ -898,45 +739,9 @@ static void launch_small(hipStream_t s, int64_t m_cap, int tb, const bf16* A, co
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Fused FFN block: out = LayerNorm( GELU(h1 . W1^T + b1) . W2^T + b2 + h1 ) for a tile of 128 tokens.
-//
-// Unfused, the 1536-wide intermediate makes two HBM round trips per layer (3.2 GB written by FFN1, read again by FFN2),
-// the pre-LN sum a third and the LayerNorm a fourth; here the intermediate never leaves the registers:
-//   * 4 waves (one per SIMD, 512-register budget), wave w owns tokens [32w, 32w+32) of the tile for the WHOLE kernel:
-//     its h1 rows are v_mfma_f32_32x32x16_bf16 B-fragments held in registers (96), the FFN2 accumulators for all 384
-//     outputs too (192);
-//   * the 1536 intermediate features are walked in 24 chunks of 64 (two MFMA tiles; with 128 the accumulators would fill
-//     all 256 AGPRs and hipcc then spills the token fragments to scratch, whose reloads wait vmcnt(0) and drain the
-//     LDS-DMA ring at every k-step): GEMM1 (K = 384) into 32 accumulator registers
-//     (initialised with the bias), GELU(erf) + bf16 rounding (the same rounding point as the unfused `mid` tensor), and the
-//     result is used DIRECTLY as the B operand of GEMM2: with swapped operands (A = weights) the D layout -- lane = token,
-//     registers 8s .. 8s+7 = features {4h+e, 8+4h+e} of the 16-block s -- is a k-permuted B fragment of k-step s, and the
-//     W2 copy this kernel reads has the columns of every 16-block permuted the same way (k_permute_w2);
-//   * only the weights stream: W1 in [64 x 128] slabs, W2 in [384 x 32] slabs through a 4-slot LDS-DMA ring with
-//     counted vmcnt (XOR swizzles on the source address as in k_gemm); 5 slabs = 5 barriers per chunk;
-//   * a lone wave per SIMD hides only ~5 single-issue instructions behind a 32-cycle MFMA (MI355X_MICROARCH.md), so the
-//     inner loops are ONE fragment read (address = per-k-step base register + literal offset), ONE counted wait and ONE
-//     MFMA per step, four reads in flight; the activation of the next 32 features is slotted between GEMM2's MFMAs;
-//   * epilogue as k_gemm_ln: bf16(acc + b2) parked in LDS, residual added, LayerNorm per token row.
-// Weight traffic L2->LDS: 2.36 MB per 128 tokens (the layer's FFN weights stay L2-resident).
+// Inline-asm helpers shared by the LDS-DMA kernels (k_ffn2, k_ffn3, k_gemm3, k_qa)
 // ------------------------------------------------------------------------------------------------------------
-namespace ffn {
-constexpr int TOK = 128, CH = 64, NCH = FF / CH;      // tokens per tile, intermediate features per chunk, chunks
-constexpr int SLOT = 24 * 1024, NSLOT = 4;            // ring slot (holds the larger slab type), slots (a power of two)
-constexpr int W1_SLABS = 3, W2_SLABS = 2, PERIOD = W1_SLABS + W2_SLABS;
-constexpr int W1_NI = 4, W2_NI = 6;                    // LDS-DMA wave-instructions per wave per slab
-constexpr int TSTR = H * 2 + 16;                       // pre-LN tile row stride (epilogue, reuses the ring)
-constexpr int B1_OFF = NSLOT * SLOT > TOK * TSTR ? NSLOT * SLOT : ((TOK * TSTR + 255) / 256) * 256;   // b1 (1536 fp32) behind ring / tile
-constexpr int LDS_BYTES = B1_OFF + FF * 4;
-constexpr int PRE = 4;                                 // fragment reads in flight (8 measured the same: 3.35 ms)
-static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-__host__ __device__ constexpr int slab_ni(int t) { return (t % PERIOD) < W1_SLABS ? W1_NI : W2_NI; }
-// DMA instructions that may still be in flight when slab t must have landed: those of slabs t+1 .. t+NSLOT-2
-__host__ __device__ constexpr int wait_n(int t) {
-    int n = 0;
-    for (int u = 1; u <= NSLOT - 2; ++u) n += slab_ni(t + u);
-    return n;
-}
+namespace isa {
 // compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N-1>{}) -- the index is a
 // constant expression inside f, which inline-asm immediates (ds_read offset:, s_waitcnt) require
 template <class F, int... I>
@@ -957,296 +762,27 @@ __device__ __forceinline__ const char* sgpr_ptr(const char* p) {
     const u32 lo = (u32)__builtin_amdgcn_readfirstlane((int)(u32)v), hi = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(v >> 32));
     return (const char*)(((unsigned long long)hi << 32) | lo);
 }
-}  // namespace ffn
-
-template <bool DBG>      // DBG: cycle counters into `dbg` (RMU_FFN_DBG diagnostics); the product instantiation carries none of it
-__global__ __launch_bounds__(256) void k_ffn_fused(const bf16* __restrict__ h1, const bf16* __restrict__ W1,
-                                                   const float* __restrict__ b1, const bf16* __restrict__ W2,
-                                                   const float* __restrict__ b2, const float* __restrict__ g,
-                                                   const float* __restrict__ bta, float eps, bf16* __restrict__ out,
-                                                   const int* __restrict__ cu, int batch,
-                                                   unsigned long long* __restrict__ dbg /* RMU_FFN_DBG: cycle counters, else null */) {
-    using namespace ffn;
-    const unsigned long long t_begin = DBG ? clock64() : 0;
-    const int dflags = DBG ? (int)dbg[7] : 0;   // timing ablations (wrong results): 1 no DMA in the loop, 2 no fragment reads, 4 no GELU
-    unsigned long long t_wait = 0, t_g1 = 0, t_g2 = 0;
-    const int M = cu[batch];
-    const int m0 = blockIdx.x * TOK;
-    if (m0 >= M) return;
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r31 = lane & 31, hh = lane >> 5;       // MFMA 32x32x16: row / column of the operand tile, k-half
-    char* ring = gsm;
-    float* b1s = (float*)(gsm + B1_OFF);
-
-    // ---- h1 rows of this wave as B fragments (k-step ks covers k [16 ks, +16); lane half hh owns 8 of them), and b1 into
-    // LDS: all ordinary loads are issued and waited for BEFORE the first LDS-DMA (an ordinary load beside an in-flight DMA
-    // makes hipcc drain the ring) ------------------------------------------------------------------------------------------
-    bf16x8 hf[24];
-    {
-        const int tok = min(m0 + 32 * w + r31, M - 1);
-        const bf16* row = h1 + (int64_t)tok * H + hh * 8;
-#pragma unroll
-        for (int ks = 0; ks < 24; ++ks) hf[ks] = *(const bf16x8*)(row + ks * 16);
-    }
-    for (int i = threadIdx.x; i < FF; i += 256) b1s[i] = b1[i];
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    // ---- slab stream: slab (c, i), i < 3: W1 rows [64 c, +64) x k [128 i, +128);  i >= 3: W2 rows [0, 384) x
-    // k [64 c + 32 (i - 3), +32).  Slabs past the last chunk re-load the last chunk (keeps the vmcnt bookkeeping uniform).
-    // Per-lane byte offsets are fixed for the whole kernel; a DMA issue is scalar base + 32-bit lane offset (no VALU).
-    // (LDS unit f = (it * 4 + w) * 64 + lane of a slab: W1 row f >> 4, W2 row f >> 2; the swizzle term of a lane does not
-    // depend on `it`, so instruction `it` is the lane's offset for it = 0 plus a SCALAR stride: 16 W1 rows / 64 W2 rows)
-    u32 w1off0, w2off0;
-    {
-        const int f = w * 64 + lane;
-        const int row1 = f >> 4, p1 = f & 15;
-        w1off0 = (u32)((row1 * H + ((p1 ^ (row1 & 15)) * 8)) * 2);
-        const int row2 = f >> 2, p2 = f & 3;
-        w2off0 = (u32)((row2 * FF + ((p2 ^ ((row2 >> 2) & 3)) * 8)) * 2);
-    }
-    // DMA instruction `it` of slab number i of the period (compile time) for chunk cc (run time, clamped), into ring slot
-    // `slotn`.  One at a time: an LDS-DMA issue costs the wave 60-180 cycles (MI355X_MICROARCH.md), so the instructions of a
-    // slab are handed out BETWEEN the MFMAs of the slab being computed, not as a burst behind the barrier.
-    auto issue_part = [&](int cc, int i, int slotn, int it) {
-        if (cc >= NCH) cc = NCH - 1;
-        char* slot = ring + slotn * SLOT;
-        if (i < W1_SLABS) {
-            const char* sbase = (const char*)W1 + ((size_t)cc * CH * H + (size_t)i * 128) * 2;
-            u32 o = w1off0;
-            asm volatile("" : "+v"(o));      // opaque: keeps hipcc from hoisting base + offset into loop-invariant 64-bit VGPR pairs
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sgpr_ptr(sbase + (size_t)it * (16 * H * 2)) + o),
-                                             (__attribute__((address_space(3))) void*)(slot + (it * 4 + w) * 1024), 16, 0, 0);
-        } else {
-            const char* sbase = (const char*)W2 + ((size_t)cc * CH + (size_t)(i - W1_SLABS) * 32) * 2;
-            u32 o = w2off0;
-            asm volatile("" : "+v"(o));
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sgpr_ptr(sbase + (size_t)it * (64 * FF * 2)) + o),
-                                             (__attribute__((address_space(3))) void*)(slot + (it * 4 + w) * 1024), 16, 0, 0);
-        }
-    };
-    auto issue = [&](int cc, int i, int slotn) {
-        const int ni = i < W1_SLABS ? W1_NI : W2_NI;
-#pragma unroll
-        for (int it = 0; it < W2_NI; ++it)
-            if (it < ni) issue_part(cc, i, slotn, it);
-    };
-
-    f32x16 acc2[12];                                // [output feature tile of 32]: rows = output features, columns = tokens
-#pragma unroll
-    for (int o = 0; o < 12; ++o)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc2[o][r] = 0.f;
-
-    // Fragment addressing.  W1 slab image: [128 rows][16 units of 16 B], unit u of row r at physical unit u ^ (r & 15);
-    // fragment (feature tile ft, k-step ks) of lane (row r31, half hh) = unit 2 ks + hh of row 32 ft + r31: one base register
-    // per k-step, the feature tile is the literal offset ft * 8192.  W2 slab image: [384 rows][4 units], physical unit
-    // u ^ ((r >> 2) & 3); fragment (output tile ot, k-step s) = unit 2 s + hh of row 32 ot + r31: base per s, offset ot * 2048.
-    const u32 ring_addr = (u32)(uintptr_t)(__attribute__((address_space(3))) char*)ring;
-    u32 a1rel[8], a2rel[2];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) a1rel[ks] = (u32)(r31 * 256 + (((2 * ks + hh) ^ (r31 & 15)) * 16));
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) a2rel[s2] = (u32)(r31 * 64 + (((2 * s2 + hh) ^ ((r31 >> 2) & 3)) * 16));
-    bf16x8 fq[PRE];
-#pragma unroll
-    for (int m = 0; m < PRE; ++m) fq[m] = bf16x8{};
-
-    static_assert(NSLOT - 1 <= PERIOD, "prologue stays inside chunk 0");
-#pragma unroll
-    for (int t = 0; t < NSLOT - 1; ++t) issue(0, t, t);
-    int slot_cur = 0;                               // ring slot of the slab being consumed (run time: 84 slabs over 4 slots)
-    typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 pfu[2][2];                                // [tile parity][k-step]: B fragments of GEMM2 (current / next tile), as dwords
-    for (int c = 0; c < NCH; ++c) {
-        // GEMM1 accumulators start from the bias: register 4q + e of lane half hh <-> feature 32 ft + 8 q + 4 hh + e
-        f32x16 acc1[2];                             // [intermediate feature tile of 32]
-#pragma unroll
-        for (int ft = 0; ft < 2; ++ft)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 bv = *(const f32x4*)(b1s + c * CH + ft * 32 + q * 8 + hh * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc1[ft][4 * q + e] = bv[e];
-            }
-        // activation of register group q (4 values) of feature tile t -> two dwords of the B fragment of k-step q / 2
-        auto gelu_group = [&](int t, int q) {
-            f32x4 v = {acc1[t][4 * q], acc1[t][4 * q + 1], acc1[t][4 * q + 2], acc1[t][4 * q + 3]};
-            asm volatile("" : "+v"(v));              // program-order anchor: the work below cannot be hoisted above this point
-            const f32x4 r = gelu_poly4(v);
-            typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-            bf16x2 lo, hi;
-            lo[0] = (bf16)r[0]; lo[1] = (bf16)r[1]; hi[0] = (bf16)r[2]; hi[1] = (bf16)r[3];
-            u32 d0 = __builtin_bit_cast(u32, lo), d1 = __builtin_bit_cast(u32, hi);
-            asm volatile("" : "+v"(d0), "+v"(d1));   // ... nor sunk below this one: the group stays in the MFMA shadow it was given
-            pfu[t & 1][q >> 1][(q & 1) * 2] = d0;
-            pfu[t & 1][q >> 1][(q & 1) * 2 + 1] = d1;
-        };
-        static_for<PERIOD>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            // slab i of the chunk has landed (own DMA) once only the younger slabs' instructions are outstanding; own LDS reads
-            // returned; after the barrier every wave is done with the slot that the new issue refills
-            const unsigned long long tw0 = DBG ? clock64() : 0;
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(wait_n(i)) : "memory");
-            __builtin_amdgcn_s_barrier();
-            if (DBG) t_wait += clock64() - tw0;
-            // the slab prefetched now (NSLOT - 1 ahead) goes into the slot everyone finished reading before this barrier
-            constexpr int pi = (i + NSLOT - 1) % PERIOD, pni = pi < W1_SLABS ? W1_NI : W2_NI;
-            const int pc = c + (i + NSLOT - 1) / PERIOD, pslot = (slot_cur + NSLOT - 1) & (NSLOT - 1);
-            const u32 sa = ring_addr + (u32)slot_cur * SLOT;
-            slot_cur = (slot_cur + 1) & (NSLOT - 1);
-            const unsigned long long tc0 = DBG ? clock64() : 0;
-            if constexpr (i < W1_SLABS) {
-                // GEMM1: 8 k-steps x 2 feature tiles = 16 fragments, n = ks * 2 + ft; A = W1 rows (32 intermediate features
-                // x 16 k), B = the token fragments in registers
-                // The LAST k-slab runs feature tile 0 first (n = ft * 8 + ks): tile 0 is complete after 8 steps and the first half
-                // of its activation (k-step 0 of GEMM2) is computed in the shadow of tile 1's MFMAs.
-                constexpr bool last = i == W1_SLABS - 1;
-                static_for<PRE>([&](auto nc) {
-                    constexpr int n = decltype(nc)::value;
-                    constexpr int ks = last ? (n & 7) : (n >> 1), ft = last ? (n >> 3) : (n & 1);
-                    ds_read16<ft * 8192>(fq[n], sa + a1rel[ks]);
-                });
-                static_for<16>([&](auto nc) {
-                    constexpr int n = decltype(nc)::value;
-                    constexpr int ks = last ? (n & 7) : (n >> 1), ft = last ? (n >> 3) : (n & 1);
-                    // reads n+1 .. min(n+PRE-1, 15) may still be in flight.  NO read is issued past the slab: a fragment register
-                    // with a read in flight looks dead to hipcc, which would hand it out (as an address register!) under the data
-                    frag_wait<(16 - 1 - n < PRE - 1 ? 16 - 1 - n : PRE - 1)>(fq[n % PRE]);
-                    acc1[ft] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fq[n % PRE], hf[i * 8 + ks], acc1[ft], 0, 0, 0);
-                    if constexpr (n + PRE < 16) {
-                        constexpr int nn = n + PRE;
-                        constexpr int ks2 = last ? (nn & 7) : (nn >> 1), ft2 = last ? (nn >> 3) : (nn & 1);
-                        if (!DBG || !(dflags & 2)) ds_read16<ft2 * 8192>(fq[n % PRE], sa + a1rel[ks2]);
-                    }
-                    if constexpr (n % 2 == 1 && n / 2 < pni) { if (!DBG || !(dflags & 1)) issue_part(pc, pi, pslot, n / 2); }     // steps 1, 3, 5, ...
-                    if (!DBG || !(dflags & 4)) {
-                        if constexpr (last && n == 10) gelu_group(0, 0);
-                        if constexpr (last && n == 13) gelu_group(0, 1);
-                    }
-                });
-            } else {
-                // GEMM2 over feature tile t = i - 3 of the chunk: 2 k-steps x 12 output tiles = 24 fragments, n = s * 12 + ot.
-                // The activations are slotted between MFMAs (schedule below), so their VALU work sits in the MFMA shadow.
-                constexpr int t = i - W1_SLABS;
-                u32 ab[2];
-                ab[0] = sa + a2rel[0];
-                ab[1] = sa + a2rel[1];
-                static_for<PRE>([&](auto nc) {
-                    constexpr int n = decltype(nc)::value;
-                    ds_read16<(n % 12) * 2048>(fq[n], ab[n / 12]);
-                });
-                static_for<24>([&](auto nc) {
-                    constexpr int n = decltype(nc)::value;
-                    constexpr int s2 = n / 12, ot = n % 12;
-                    frag_wait<(24 - 1 - n < PRE - 1 ? 24 - 1 - n : PRE - 1)>(fq[n % PRE]);
-                    acc2[ot] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fq[n % PRE], __builtin_bit_cast(bf16x8, pfu[t & 1][s2]), acc2[ot], 0, 0, 0);
-                    if constexpr (n + PRE < 24) {
-                        constexpr int nn = n + PRE;
-                        if (!DBG || !(dflags & 2)) ds_read16<(nn % 12) * 2048>(fq[n % PRE], ab[nn / 12]);
-                    }
-                    // activation schedule: every 12-MFMA half-slab carries two register groups, each the half-slab before the
-                    // k-step that consumes it: tile 0 k-step 1 | tile 1 k-step 0 | tile 1 k-step 1 | (none)
-                    if (!DBG || !(dflags & 4)) {
-                        if constexpr (t == 0 && n == 2) gelu_group(0, 2);
-                        if constexpr (t == 0 && n == 7) gelu_group(0, 3);
-                        if constexpr (t == 0 && n == 14) gelu_group(1, 0);
-                        if constexpr (t == 0 && n == 19) gelu_group(1, 1);
-                        if constexpr (t == 1 && n == 2) gelu_group(1, 2);
-                        if constexpr (t == 1 && n == 7) gelu_group(1, 3);
-                    }
-                    if constexpr (n % 4 == 0 && n / 4 < pni) { if (!DBG || !(dflags & 1)) issue_part(pc, pi, pslot, n / 4); }     // steps 0, 4, 8, ...
-                });
-            }
-            if (DBG) { if (i < W1_SLABS) t_g1 += clock64() - tc0; else t_g2 += clock64() - tc0; }
-        });
-    }
-    if (DBG && lane == 0) {     // [0] cycles waiting for slabs + barrier, [1] main-loop cycles, [2] wave count
-        atomicAdd(dbg + 0, t_wait);
-        atomicAdd(dbg + 1, (unsigned long long)(clock64() - t_begin));
-        atomicAdd(dbg + 2, 1ull);
-        atomicAdd(dbg + 3, t_g1);
-        atomicAdd(dbg + 4, t_g2);
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // drain the tail reloads: the ring becomes the pre-LN tile
-    __syncthreads();
-    char* tile = gsm;
-    {
-        // acc2[ot][4 q + e] = output feature n = 32 ot + 8 q + 4 hh + e of token 32 w + r31.  The residual h1[token][n] is
-        // already on chip: hf[ks], ks = 2 ot + (q >> 1), holds features 16 ks + 8 h' .. + 7 in lane half h' -- the lane needs
-        // element 8 (q & 1) + 4 hh + e of that block, which is its own register when (q & 1) == hh and the other half-lane's
-        // (lane ^ 32) otherwise: one 2-dword exchange per k-step instead of 48 scattered 8-byte global loads.
-        // y = bf16(bf16(acc + b2) + resid): the rounding points of the unfused path.
-        const int tr = 32 * w + r31;
-        typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-        for (int ot = 0; ot < 12; ++ot)
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                const u32x4 hv = __builtin_bit_cast(u32x4, hf[2 * ot + qq]);
-                const u32x2 own = hh ? u32x2{hv[2], hv[3]} : u32x2{hv[0], hv[1]};      // elements 4 hh .. 4 hh + 3 of this half's 8
-                const u32x2 oth = hh ? u32x2{hv[0], hv[1]} : u32x2{hv[2], hv[3]};      // what the partner half-lane needs
-                u32x2 rcv;
-                rcv[0] = (u32)__shfl_xor((int)oth[0], 32);
-                rcv[1] = (u32)__shfl_xor((int)oth[1], 32);
-#pragma unroll
-                for (int qb = 0; qb < 2; ++qb) {
-                    const int q = 2 * qq + qb;
-                    const u32x2 rs2 = (qb == hh) ? own : rcv;
-                    const bf16x4 res = __builtin_bit_cast(bf16x4, rs2);
-                    const int n = ot * 32 + q * 8 + hh * 4;
-                    const f32x4 bv = *(const f32x4*)(b2 + n);
-                    bf16x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = (bf16)(bf2f((bf16)(acc2[ot][4 * q + e] + bv[e])) + bf2f(res[e]));
-                    *(bf16x4*)(tile + tr * TSTR + n * 2) = v;
-                }
-            }
-    }
-    __syncthreads();
-    // LayerNorm: each wave normalises its own 32 token rows; lanes 0..47 own 8 consecutive columns (16-byte accesses)
-    {
-        const bool act = lane < 48;
-        const int c0 = (act ? lane : 0) * 8;
-        float gg[8], bb[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { gg[i] = g[c0 + i]; bb[i] = bta[c0 + i]; }
-        for (int r = 0; r < 32; ++r) {
-            const int tr = w * 32 + r;
-            const int m = m0 + tr;
-            if (m >= M) break;                         // uniform per wave
-            const bf16x8 yv = *(const bf16x8*)(tile + tr * TSTR + c0 * 2);
-            float v[8];
-            float sm = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { v[i] = act ? bf2f(yv[i]) : 0.f; sm += v[i]; }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o);
-            const float mu = sm * (1.0f / H);
-            float q = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { const float d = act ? v[i] - mu : 0.f; q = fmaf(d, d, q); }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-            const float rs = rsqrtf(q * (1.0f / H) + eps);
-            bf16x8 ov;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) ov[i] = (bf16)((v[i] - mu) * rs * gg[i] + bb[i]);
-            if (act) *(bf16x8*)(out + (int64_t)m * H + c0) = ov;
-        }
-    }
-}
+}  // namespace isa
 
 // ------------------------------------------------------------------------------------------------------------
-// k_ffn2 -- the fused FFN block, second form (round 3): out = LN2( GELU(h1 . W1^T + b1) . W2^T + b2 + h1 ), optionally with
-// h1 = LN1(y) computed in the prologue (the out-proj GEMM's pre-LN sum comes in, no k_layernorm launch and no h1 round trip).
+// k_ffn2 -- the fused FFN block for a tile of 128 tokens (round 3; RMU_FFN_V=2): out = LN2( GELU(h1 . W1^T + b1) . W2^T + b2 + h1 ),
+// optionally with h1 = LN1(y) computed in the prologue (the out-proj GEMM's pre-LN sum comes in, no k_layernorm launch and no h1
+// round trip).
 //
-// Same ownership as k_ffn_fused (4 waves = 4 SIMDs, wave w keeps tokens [32w, +32) as B fragments and all 384 FFN2 accumulators
-// for the whole kernel, only weights stream through LDS), rebuilt around what bounded that kernel: a lone wave per SIMD issues at
-// most ~one instruction per 4 cycles, i.e. <= ~5 besides the MFMA in each 32-cycle MFMA slot (MI355X_MICROARCH.md), and the old
-// loop carried 7.9 (ISA count per 96-MFMA chunk: 369 VALU + 32 accvgpr reads, 104 ds_read, 102 s_waitcnt, ~100 SALU, 26 s_nop,
-// 24 DMA) with the activation lumped in 40-instruction blocks between two MFMAs.  Here:
+// Unfused, the 1536-wide intermediate makes two HBM round trips per layer (3.2 GB written by FFN1, read again by FFN2), the pre-LN
+// sum a third and the LayerNorm a fourth; here the intermediate never leaves the registers:
+//   * 4 waves = 4 SIMDs (512-register budget); wave w keeps tokens [32w, +32) of the tile as v_mfma_f32_32x32x16_bf16 B fragments (96
+//     registers) and all 384 FFN2 accumulators (192) for the WHOLE kernel; only the weights stream through LDS: 2.36 MB per 128
+//     tokens, L2-resident;
+//   * the 1536 intermediate features are walked in 24 chunks of 64 (two MFMA tiles; with 128 the accumulators would fill all 256
+//     AGPRs and hipcc then spills the token fragments to scratch, whose reloads wait vmcnt(0) and drain the LDS-DMA ring at every
+//     k-step): GEMM1 (K = 384) into 32 accumulator registers initialised with the bias, GELU + bf16 rounding (the same rounding
+//     point as the unfused `mid` tensor), and the result is used DIRECTLY as the B operand of GEMM2 (see k_permute_w2);
+//   * epilogue: bf16(acc + b2) parked in LDS, residual added, LayerNorm per token row.
+// The round-2 kernel with this ownership (retired; NOTES_r01_r05.md 4.3) was bound by issue slots: a lone wave per SIMD issues at
+// most ~one instruction per 4 cycles, i.e. <= ~5 besides the MFMA in each 32-cycle MFMA slot (MI355X_MICROARCH.md), and its loop
+// carried 7.9 (ISA count per 96-MFMA chunk: 369 VALU + 32 accvgpr reads, 104 ds_read, 102 s_waitcnt, ~100 SALU, 26 s_nop, 24 DMA)
+// with the activation lumped in 40-instruction blocks between two MFMAs.  Here:
 //   * GEMM2 runs ONE CHUNK BEHIND GEMM1: iteration c does GEMM1 of chunk c (48 MFMAs) and GEMM2 of chunk c-1 (48 MFMAs); the
 //     activation of chunk c-1 (8 groups of 4 values per lane) is cut into 7 stages of 2-4 instructions, one stage behind each
 //     MFMA of GEMM1(c) (and of the first GEMM2 slab for the last two groups): no MFMA ever waits for an activation, and no
@@ -1290,7 +826,7 @@ __global__ __launch_bounds__(256) void k_ffn2(const bf16* __restrict__ x, const 
                                               const int* __restrict__ cu, int batch, const float* __restrict__ g1,
                                               const float* __restrict__ bta1) {
     using namespace ffn2;
-    using ffn::static_for; using ffn::ds_read16; using ffn::sgpr_ptr;
+    using isa::static_for; using isa::ds_read16; using isa::sgpr_ptr;
     typedef u32 u32x4 __attribute__((ext_vector_type(4)));
     typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
     const int M = cu[batch];
@@ -1550,7 +1086,8 @@ __global__ __launch_bounds__(256) void k_ffn2(const bf16* __restrict__ x, const 
     char* tile = gsm;
     {
         // acc2[ot][4 q + e] = output feature n = 32 ot + 8 q + 4 hh + e of token 32 w + r31; the residual h1[token][n] sits in
-        // hf[2 ot + (q >> 1)] of this lane ((q & 1) == hh) or of lane ^ 32 (see k_ffn_fused).  y = bf16(bf16(acc + b2) + resid).
+        // hf[2 ot + (q >> 1)] of this lane ((q & 1) == hh) or of lane ^ 32 -- one 2-dword exchange per k-step
+        // instead of 48 scattered 8-byte global loads.  y = bf16(bf16(acc + b2) + resid): the rounding points of the unfused path.
         const int tr = 32 * w + r31;
         typedef u32 u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
@@ -1643,27 +1180,16 @@ static_assert(LDS_BYTES <= 160 * 1024 && TOK * TSTR <= LDS_BYTES, "LDS");
 // DMA instructions per wave that may still be in flight when slab i must have landed (W1 slab = 2 per wave, W2 slab = 3; issue
 // order per iteration as in k_ffn2: S4 during slab 0; S0', S1', S2' during slab 3; S3' during slab 4)
 __host__ __device__ constexpr int wait_n(int i) { return i == 0 ? 7 : i == 1 ? 8 : i == 2 ? 6 : i == 3 ? 3 : 6; }
-// VAR bit 2, LOOK-AHEAD (round 4): at the barrier that opens slab i, slab i + 1 has landed as well, so the first PF fragments of slab
-// i + 1 are read during the last PF steps of slab i and the MFMAs behind a barrier start at once -- without it all eight waves of a
-// workgroup (both waves of every SIMD) sit out an LDS round trip behind each of the five barriers of a chunk at the same time.  The
-// ring stays one chunk deep (5 slots = 5 slabs); the price is paid in DMA lead instead: the refill of slot j is issued during slab
-// j + 1 (everybody has passed barrier j + 1, i.e. is done reading slot j) and must have landed by barrier j - 1 of the next round:
-// three slab times for every slab (issue order R4, R0', R1', R2', R3', one refill per slab).  In flight at barrier i: the refills
-// issued during slabs i - 1 and i - 2, i.e. of slots i - 2 and i - 3 (2 instructions per wave for a W1 slot, 3 for a W2 slot).
-__host__ __device__ constexpr int slot_ni(int j) { return ((j % 5) + 5) % 5 < 3 ? 2 : 3; }
-__host__ __device__ constexpr int wait_la(int i) { return slot_ni(i - 2) + slot_ni(i - 3); }
-static_assert(wait_la(0) == 5 && wait_la(1) == 6 && wait_la(2) == 5 && wait_la(3) == 4 && wait_la(4) == 4, "look-ahead wait counts");
 }  // namespace ffn3
 
-template <bool LN_IN, int PF, bool DBG, int VAR, bool OP = false>   // OP: x is the attention output ctx -- the out-proj GEMM + bias + residual runs in the prologue (see below); VAR bit 0: activation as packed-f32 instructions (else hipcc's vector code), bit 1: k_pack_ffn3 weight streams (else W1 / W2p rows); DBG: ablation flags (RMU_FFN3_DBG, debug build): 1 no activation, 2 no fragment reads, 4 no DMA, 8 no exchange, 16 no barriers
+template <bool LN_IN, int PF, bool DBG>   // LN_IN: x is the pre-LayerNorm sum y, h1 = LN1(y) is formed here; PF: weight fragments read ahead; DBG: ablation flags (RMU_FFN3_DBG, debug build): 1 no activation, 2 no fragment reads, 4 no DMA, 8 no exchange, 16 no barriers
 __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const bf16* __restrict__ W1, const float* __restrict__ b1,
                                               const bf16* __restrict__ W2, const float* __restrict__ b2, const float* __restrict__ g,
                                               const float* __restrict__ bta, float eps, bf16* __restrict__ out,
                                               const int* __restrict__ cu, int batch, const float* __restrict__ g1,
-                                              const float* __restrict__ bta1, int dflags, const bf16* __restrict__ wo = nullptr,
-                                              const float* __restrict__ bo = nullptr, const bf16* __restrict__ resid = nullptr) {
+                                              const float* __restrict__ bta1, int dflags) {
     using namespace ffn3;
-    using ffn::static_for; using ffn::ds_read16;
+    using isa::static_for; using isa::ds_read16;
     typedef u32 u32x4 __attribute__((ext_vector_type(4)));
     typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
     // (round 5, measured and not kept: issuing the token / parameter loads BEFORE M = cu[batch] is known, to share one round trip -- the half
@@ -1677,15 +1203,15 @@ __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const 
     const int r31 = lane & 31, hh = lane >> 5;
     char* ring = gsm;
     float* b1s = (float*)(gsm + B1_OFF);
+    const u32 lane16 = (u32)lane * 16;              // this lane's 16-byte piece of an exchange buffer (xp_* / px_* below); formed HERE, ahead of
+                                                    // the slab offsets: moved down to its users hipcc schedules the prologue differently
 
-    // ---- slab stream: W1 / W2 are the k_pack_ffn3 streams (slab images, contiguous); wave w moves bytes [2048 w, +2048) of a W1 slab and
-    // [3072 w, +3072) of a W2 slab, 1 KiB per instruction: one LDS base (M0) and one address per slab, the pieces are immediate offsets
-    // (applied to the global and the LDS address alike) -------------------------------------------------------------------------
-    const u32 v1 = (u32)lane * 16 + (u32)w * 2048, v2 = (u32)lane * 16 + (u32)w * 3072;
-    // (VAR bit 1 clear: W1 / W2 are the row-major matrices; DMA instruction q = it * 8 + w of a slab covers LDS units [64 q, +64), the
-    // swizzle lives in the per-lane source offset -- 4 rows x 256 B resp. 16 rows x 64 B per instruction, one address + M0 per instruction)
-    u32 w1off0 = 0, w2off0 = 0;
-    if constexpr (!(VAR & 2)) {
+    // ---- slab stream: W1 / W2 are the row-major matrices (W1, the k_permute_w2 copy of W2); DMA instruction q = it * 8 + w of a slab
+    // covers LDS units [64 q, +64), the swizzle lives in the per-lane source offset -- 4 rows x 256 B resp. 16 rows x 64 B per
+    // instruction, one address + M0 per instruction.  (Pre-packed slab images read as contiguous KiB measured the same: 3245 vs 3227 us
+    // per launch, profiles/r03_ffn3_experiments.md.) ------------------------------------------------------------------------------------------
+    u32 w1off0, w2off0;
+    {
         const int row1 = w * 4 + (lane >> 4), lu = (lane & 15) ^ (row1 & 15);
         w1off0 = (u32)((row1 * H + (lu & 7) * 8 + (lu >> 3) * 192) * 2);
         const int row2 = w * 16 + (lane >> 2), p2 = lane & 3;
@@ -1697,176 +1223,41 @@ __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const 
         if (DBG && (dflags & 4)) return;
         if constexpr (i < 3) {
             const u32 cc = (u32)(ci < NCH ? ci : NCH - 1);
-            if constexpr (VAR & 2) {
-                const u32 o = v1 + (cc * (u32)(3 * S1) + (u32)(i * S1));
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)W1 + o),
-                                                 (__attribute__((address_space(3))) void*)(ring + i * S1 + w * 2048), 16, it * 1024, 0);
-            } else {
-                const u32 o = w1off0 + (cc * (u32)(CH * H * 2) + (u32)(i * 128 + it * (32 * H * 2)));
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)W1 + o),
-                                                 (__attribute__((address_space(3))) void*)(ring + i * S1 + (it * 8 + w) * 1024), 16, 0, 0);
-            }
+            const u32 o = w1off0 + (cc * (u32)(CH * H * 2) + (u32)(i * 128 + it * (32 * H * 2)));
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)W1 + o),
+                                             (__attribute__((address_space(3))) void*)(ring + i * S1 + (it * 8 + w) * 1024), 16, 0, 0);
         } else {
             const u32 cc = (u32)(ci < 1 ? 0 : (ci > NCH ? NCH - 1 : ci - 1));
-            if constexpr (VAR & 2) {
-                const u32 o = v2 + (cc * (u32)(2 * S2) + (u32)((i - 3) * S2));
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)W2 + o),
-                                                 (__attribute__((address_space(3))) void*)(ring + W2_OFF + (i - 3) * S2 + w * 3072), 16, it * 1024, 0);
-            } else {
-                const u32 o = w2off0 + (cc * (u32)(CH * 2) + (u32)((i - 3) * 64 + it * (128 * FF * 2)));
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)W2 + o),
-                                                 (__attribute__((address_space(3))) void*)(ring + W2_OFF + (i - 3) * S2 + (it * 8 + w) * 1024), 16, 0, 0);
-            }
+            const u32 o = w2off0 + (cc * (u32)(CH * 2) + (u32)((i - 3) * 64 + it * (128 * FF * 2)));
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)W2 + o),
+                                             (__attribute__((address_space(3))) void*)(ring + W2_OFF + (i - 3) * S2 + (it * 8 + w) * 1024), 16, 0, 0);
         }
-    };
-
-    // (round 5) the stream's first four slabs are requested BEFORE the token rows: the ring is not touched by the LayerNorm prologue, and a
-    // workgroup is alone on its CU (150 KiB of LDS) -- nobody else covers the L2 round trip of slab 0 behind the prologue
-    auto issue_stream_prologue = [&]() {
-        static_for<4>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            issue_part(0, ic, std::integral_constant<int, 0>{});
-            issue_part(0, ic, std::integral_constant<int, 1>{});
-            if constexpr (i == 3) issue_part(0, ic, std::integral_constant<int, 2>{});
-        });
     };
 
     // ---- this half's k range of the token rows as B fragments; b1 into LDS ---------------------------------------------------
     bf16x8 hf[12];
-    if constexpr (!OP) {
+    {
         const int tok = min(m0 + 32 * p + r31, M - 1);
         const bf16* row = x + (int64_t)tok * H + s * 192 + hh * 8;
 #pragma unroll
         for (int j = 0; j < 12; ++j) hf[j] = *(const bf16x8*)(row + j * 16);   // (non-temporal here: +3.5 % -- the out-proj launch has just written these rows)
-        issue_stream_prologue();       // behind the token loads in the CU's in-order memory queue: LayerNorm 1 starts on the rows while the slabs land
     }
+    // (round 5) the stream's first four slabs (iteration 0) are requested BEFORE the LayerNorm prologue: it does not touch the ring, and a
+    // workgroup is alone on its CU (150 KiB of LDS) -- nobody else covers the L2 round trip of slab 0 behind the prologue.  They queue
+    // behind the token loads in the CU's in-order memory queue: LayerNorm 1 starts on the rows while the slabs land.
+    static_for<4>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        issue_part(0, ic, std::integral_constant<int, 0>{});
+        issue_part(0, ic, std::integral_constant<int, 1>{});
+        if constexpr (i == 3) issue_part(0, ic, std::integral_constant<int, 2>{});
+    });
     for (int i = threadIdx.x; i < FF; i += 512) b1s[i] = b1[i];
     float* lnp = (float*)(gsm + LN_OFF);
     if (threadIdx.x < H) {
         const int i = threadIdx.x;
         lnp[i] = g1 ? g1[i] : 1.f; lnp[H + i] = bta1 ? bta1[i] : 0.f; lnp[2 * H + i] = g[i]; lnp[3 * H + i] = bta[i]; lnp[4 * H + i] = b2[i];
     }
-    if constexpr (OP) {
-        // ---- the attention block's output projection, here instead of in a launch of its own: y = ctx . Wo^T + bo + h for this wave's
-        // 32 tokens x ITS 192 features (the half s it needs as token fragments), then LayerNorm 1 -- the pre-LN sum never exists in memory,
-        // the out-proj launch (0.56 ms per layer, 2.4 GB of traffic) and the statistics re-read are gone; the price is 144 MFMAs per wave in
-        // front of the 1200 of the FFN and 288 KiB of Wo through the ring.  Same operand roles as FFN2: A = Wo rows out of W2-shaped slabs
-        // ([384 rows][32 k], 12 of them through FOUR 24-KiB slots = the whole ring), B = the ctx rows of the tokens (all 24 k-steps in registers
-        // for the duration, 96; the FFN's accumulators are not live yet), D = features x tokens.  D's register layout (register 4 q + e of
-        // lane half hh = feature 8 q + 4 hh + e of the tile) IS a k-permuted B fragment -- as for FFN2's activations -- so LayerNorm's output goes
-        // straight into the token fragments and W1 is read from its k-permuted copy (k_permute_w2 on W1: L.w1p); the residual of FFN2's
-        // outputs is then the same register of the same lane (no lane exchange in the epilogue).
-        const int tok = min(m0 + 32 * p + r31, M - 1);
-        bf16x8 cf[24];
-        if (dflags & 512) {                      // tiled ctx (k_attn3's store): block (token / 16, head = k / 32), unit ^ ((r >> 2) & 3)
-            const int r = tok & 15, sw = tswz(r);
-            const bf16* blk = x + (int64_t)(tok >> 4) * (NH * 512) + r * 32;
-#pragma unroll
-            for (int ks = 0; ks < 24; ++ks) cf[ks] = *(const bf16x8*)(blk + (ks >> 1) * 512 + ((((ks & 1) * 2 + hh) ^ sw) * 8));
-        } else {
-            const bf16* row = x + (int64_t)tok * H + hh * 8;
-#pragma unroll
-            for (int ks = 0; ks < 24; ++ks) cf[ks] = *(const bf16x8*)(row + ks * 16);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // ordinary loads done before the first LDS-DMA (hipcc drains the DMA queue for them otherwise)
-        f32x16 co[6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) co[j][r] = 0.f;
-        u32 wooff0;
-        {
-            const int row2 = w * 16 + (lane >> 2), p2 = lane & 3;
-            wooff0 = (u32)((row2 * H + ((p2 ^ ((row2 >> 2) & 3)) * 8)) * 2);
-        }
-        auto issue_wo = [&](int kb) {            // slab kb (clamped: harmless re-loads keep the counted wait uniform) into slot kb & 3
-            const u32 kc = (u32)(kb < 12 ? kb : 11);
-#pragma unroll
-            for (int it = 0; it < 3; ++it) {
-                const u32 o = wooff0 + (kc * 64u + (u32)(it * (128 * H * 2)));
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)wo + o),
-                                                 (__attribute__((address_space(3))) void*)(ring + (kb & 3) * S2 + (it * 8 + w) * 1024), 16, 0, 0);
-            }
-        };
-        const u32 lds0p = (u32)(uintptr_t)(__attribute__((address_space(3))) char*)gsm;
-        u32 ao[2];
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) ao[k2] = lds0p + (u32)((192 * s + r31) * 64 + (((2 * k2 + hh) ^ ((r31 >> 2) & 3)) * 16));
-        issue_wo(0); issue_wo(1); issue_wo(2);
-        bf16x8 fo[4];
-#pragma unroll
-        for (int kb = 0; kb < 12; ++kb) {                     // (unrolled: the ctx fragments are indexed by kb)
-            asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");     // slab kb landed (own pieces); the two younger slabs may be in flight
-            __builtin_amdgcn_s_barrier();                                     // ... everybody's pieces; and slot (kb + 3) & 3 = slab kb - 1's is free
-            issue_wo(kb + 3);
-            const u32 base0 = ao[0] + (u32)((kb & 3) * S2), base1 = ao[1] + (u32)((kb & 3) * S2);
-            // 2 k-steps x 6 tiles, fragments four ahead, one counted wait per two MFMAs (as the FFN2 slabs below)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) asm volatile("ds_read_b128 %0, %1" : "=v"(fo[n]) : "v"(base0 + (u32)(n * 2048)));
-            const bf16x8 cf0 = cf[2 * kb], cf1 = cf[2 * kb + 1];
-            static_for<12>([&, base0, base1, cf0, cf1](auto nc) {
-                constexpr int n = decltype(nc)::value;
-                if constexpr (n % 2 == 0)
-                    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(fo[n % 4]), "+v"(fo[(n + 1) % 4]) : "n"(n + 4 <= 12 ? 2 : 12 - 2 - n));
-                co[n % 6] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fo[n % 4], n / 6 ? cf1 : cf0, co[n % 6], 0, 0, 0);
-                if constexpr (n + 4 < 12) asm volatile("ds_read_b128 %0, %1" : "=v"(fo[n % 4]) : "v"(((n + 4) / 6 ? base1 : base0) + (u32)(((n + 4) % 6) * 2048)));
-                else asm volatile("" : "+v"(fo[n % 4]));
-            });
-        }
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");           // tail re-loads drained before the residual's ordinary loads
-        // y = bf16(bf16(acc + bo) + h) (the out-proj kernel's rounding points), kept as fp32 of those bf16 values
-        float sm = 0.f;
-        {
-            const int r = tok & 15, sw = tswz(r);
-#pragma unroll
-            for (int j = 0; j < 6; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int f0 = s * 192 + j * 32 + q * 8 + hh * 4;
-                    const bf16* rp = (dflags & 1024) ? resid + ((int64_t)(tok >> 4) * (H / 32) + (f0 >> 5)) * 512 + r * 32 + ((((f0 >> 3) & 3) ^ sw) * 8) + (f0 & 7)
-                                                     : resid + (int64_t)tok * H + f0;
-                    const bf16x4 rv = *(const bf16x4*)rp;
-                    const f32x4 bv = *(const f32x4*)(bo + f0);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float yv = bf2f((bf16)(bf2f((bf16)(co[j][4 * q + e] + bv[e])) + bf2f(rv[e])));
-                        co[j][4 * q + e] = yv;
-                        sm += yv;
-                    }
-                }
-        }
-        float* sc = (float*)(gsm + XP_OFF);
-        sm += __shfl_xor(sm, 32);
-        if (hh == 0) sc[w * 32 + r31] = sm;
-        __syncthreads();
-        sm += sc[(w ^ 4) * 32 + r31];
-        const float mu = sm * (1.0f / H);
-        float qv = 0.f;
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { const float d = co[j][r] - mu; qv = fmaf(d, d, qv); }
-        qv += __shfl_xor(qv, 32);
-        if (hh == 0) sc[256 + w * 32 + r31] = qv;
-        __syncthreads();
-        qv += sc[256 + (w ^ 4) * 32 + r31];
-        const float rs = rsqrtf(qv * (1.0f / H) + eps);
-        // token fragment of k-step 2 j + qh = registers of tile j, q in {2 qh, 2 qh + 1}: elements [0, 4) <- q even, [4, 8) <- q odd
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-#pragma unroll
-            for (int qh = 0; qh < 2; ++qh) {
-                bf16x8 o;
-#pragma unroll
-                for (int qb = 0; qb < 2; ++qb) {
-                    const int q = 2 * qh + qb, f0 = s * 192 + j * 32 + q * 8 + hh * 4;
-                    const f32x4 ga = *(const f32x4*)(g1 + f0), ba = *(const f32x4*)(bta1 + f0);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[4 * qb + e] = (bf16)((co[j][4 * q + e] - mu) * rs * ga[e] + ba[e]);
-                }
-                hf[2 * j + qh] = o;
-            }
-    } else if (LN_IN) {
+    if (LN_IN) {
         // h1 = bf16(LN1(y)): statistics over all 384 values of the token = this lane's 96, lane ^ 32's, and the partner wave's
         // two lanes' (through LDS).  Same arithmetic as k_ffn2 (fp32, two passes) up to the order of the partial sums.
         float* sc = (float*)(gsm + XP_OFF);
@@ -1925,10 +1316,10 @@ __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const 
     }
 #pragma unroll
     for (int k2 = 0; k2 < 2; ++k2) a2[k2] = lds0 + (u32)W2_OFF + (u32)((192 * s + r31) * 64 + (((2 * k2 + hh) ^ ((r31 >> 2) & 3)) * 16));
-    const u32 xp_w = lds0 + (u32)XP_OFF + (u32)(w * 4096) + (u32)lane * 16;             // + j * 1024: registers 4 j .. 4 j + 3
-    const u32 xp_r = lds0 + (u32)XP_OFF + (u32)((w ^ 4) * 4096) + (u32)lane * 16;
-    const u32 px_w = lds0 + (u32)PX_OFF + (u32)((p * 2 + s) * 2048) + (u32)lane * 16;   // + k-step * 1024
-    const u32 px_r = lds0 + (u32)PX_OFF + (u32)(p * 2 * 2048) + (u32)lane * 16;         // + tile * 2048 + k-step * 1024
+    const u32 xp_w = lds0 + (u32)XP_OFF + (u32)(w * 4096) + lane16;                     // + j * 1024: registers 4 j .. 4 j + 3
+    const u32 xp_r = lds0 + (u32)XP_OFF + (u32)((w ^ 4) * 4096) + lane16;
+    const u32 px_w = lds0 + (u32)PX_OFF + (u32)((p * 2 + s) * 2048) + lane16;           // + k-step * 1024
+    const u32 px_r = lds0 + (u32)PX_OFF + (u32)(p * 2 * 2048) + lane16;                 // + tile * 2048 + k-step * 1024
     bf16x8 fq[PF];
 #pragma unroll
     for (int m = 0; m < PF; ++m) fq[m] = bf16x8{};
@@ -1948,18 +1339,13 @@ __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const 
             for (int e = 0; e < 4; ++e) accA[4 * q + e] = bv[e];
         }
     };
-    // The activation in PACKED fp32 (v_pk_*_f32, two values per instruction), written as instructions because hipcc scalarises most of
-    // the vector form once registers are tight (88 v_fma_f32 + 20 v_pk_fma_f32 per chunk).  gelu(v) = v (0.5 + Q0 vc P(u)), vc =
-    // clamp(v), u = vc^2, P = Q / Q0 MONIC (its first Horner step is an add, and every step takes ONE constant: an SGPR pair --
-    // gfx950 packed-f32 operands are 64-bit, one scalar source per instruction).  Same polynomial as k_ffn2's up to fp32 rounding.
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    auto c2 = [](float c) { return f32x2{c, c}; };
-    auto pk_fma_s = [](f32x2& d, f32x2 a, f32x2 k) { asm volatile("v_pk_fma_f32 %0, %0, %1, %2" : "+v"(d) : "v"(a), "s"(k)); };   // d = d a + k
-    f32x2 gcl = {}, gch = {}, gul = {}, guh = {}, gpl = {}, gph = {};
+    // The activation: k_ffn2's stages, left to hipcc.  (Written as packed-f32 instructions -- v_pk_*_f32, two values each -- it measured
+    // SLOWER, 3404 vs 3227 us per launch, although the loop shrank from 431 to 357 instructions: profiles/r03_ffn3_experiments.md.)
     // one stage (of six) of the activation of group q of the own tile: values prv[4 q ..] -> pf
     f32x4 gc = {}, gu = {}, gp = {};
     auto sp = [](float c) { return f32x4{c, c, c, c}; };
-    auto gelu_stage_vec = [&](int q, int st) {        // VAR bit 0 clear: k_ffn2's stages, left to hipcc
+    auto gelu_stage = [&](int q, int st) {
+        if (DBG && (dflags & 1)) return;
         switch (st) {
             case 0:
                 asm volatile("" : "+v"(gc));
@@ -1995,66 +1381,7 @@ __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const 
             }
         }
     };
-    auto gelu_stage = [&](int q, int st) {
-        if (DBG && (dflags & 1)) return;
-        if constexpr (!(VAR & 1)) { gelu_stage_vec(q, st); return; }
-        switch (st) {
-            case 0:
-                asm volatile("v_med3_f32 %0, %1, -%2, %2" : "=v"(gcl[0]) : "v"(prv[4 * q]), "s"(RMU_GCLAMP));   // one scalar source, negated in place
-                asm volatile("v_med3_f32 %0, %1, -%2, %2" : "=v"(gcl[1]) : "v"(prv[4 * q + 1]), "s"(RMU_GCLAMP));   // one scalar source, negated in place
-                asm volatile("v_med3_f32 %0, %1, -%2, %2" : "=v"(gch[0]) : "v"(prv[4 * q + 2]), "s"(RMU_GCLAMP));   // one scalar source, negated in place
-                asm volatile("v_med3_f32 %0, %1, -%2, %2" : "=v"(gch[1]) : "v"(prv[4 * q + 3]), "s"(RMU_GCLAMP));   // one scalar source, negated in place
-                break;
-            case 1:
-                asm volatile("v_pk_mul_f32 %0, %1, %1" : "=v"(gul) : "v"(gcl));
-                asm volatile("v_pk_mul_f32 %0, %1, %1" : "=v"(guh) : "v"(gch));
-                asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(gpl) : "v"(gul), "s"(c2(RMU_GQ1 / RMU_GQ0)));
-                asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(gph) : "v"(guh), "s"(c2(RMU_GQ1 / RMU_GQ0)));
-                break;
-            case 2:
-                pk_fma_s(gpl, gul, c2(RMU_GQ2 / RMU_GQ0)); pk_fma_s(gph, guh, c2(RMU_GQ2 / RMU_GQ0));
-                pk_fma_s(gpl, gul, c2(RMU_GQ3 / RMU_GQ0)); pk_fma_s(gph, guh, c2(RMU_GQ3 / RMU_GQ0));
-                break;
-            case 3:
-                pk_fma_s(gpl, gul, c2(RMU_GQ4 / RMU_GQ0)); pk_fma_s(gph, guh, c2(RMU_GQ4 / RMU_GQ0));
-                pk_fma_s(gpl, gul, c2(RMU_GQ5 / RMU_GQ0)); pk_fma_s(gph, guh, c2(RMU_GQ5 / RMU_GQ0));
-                break;
-            case 4:
-                pk_fma_s(gpl, gul, c2(RMU_GQ6 / RMU_GQ0)); pk_fma_s(gph, guh, c2(RMU_GQ6 / RMU_GQ0));
-                pk_fma_s(gpl, gul, c2(RMU_GQ7 / RMU_GQ0)); pk_fma_s(gph, guh, c2(RMU_GQ7 / RMU_GQ0));
-                break;
-            default: {
-                // gp = vc P;  gp = Q0 gp + 0.5;  gp = v gp;  -> bf16 pairs
-                f32x2 pvl = {prv[4 * q], prv[4 * q + 1]}, pvh = {prv[4 * q + 2], prv[4 * q + 3]};
-                asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(gpl) : "v"(gcl));
-                asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(gph) : "v"(gch));
-                asm volatile("v_pk_fma_f32 %0, %0, %1, 0.5 op_sel_hi:[1,1,0]" : "+v"(gpl) : "s"(c2(RMU_GQ0)));
-                asm volatile("v_pk_fma_f32 %0, %0, %1, 0.5 op_sel_hi:[1,1,0]" : "+v"(gph) : "s"(c2(RMU_GQ0)));
-                asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(gpl) : "v"(pvl));
-                asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(gph) : "v"(pvh));
-                u32 d0, d1;
-                asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(d0) : "v"(gpl[0]), "v"(gpl[1]));
-                asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(d1) : "v"(gph[0]), "v"(gph[1]));
-                pf[q >> 1][(q & 1) * 2] = d0;
-                pf[q >> 1][(q & 1) * 2 + 1] = d1;
-            }
-        }
-    };
-
-    // prologue of the stream: slabs 0 .. 3 of iteration 0 (OP: the ring carried Wo until here; else they were requested at the top)
-    if constexpr (OP) issue_stream_prologue();
     load_bias(0);
-    constexpr bool LA = (VAR & 4) != 0;
-    if constexpr (LA) {
-        // slab 0 of iteration 0 has no barrier in front of it that proves everybody's pieces landed: one extra wait + barrier, then
-        // its first fragments (in flight behind it: slabs 1, 2, 3 = 2 + 2 + 3 instructions)
-        asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        static_for<PF>([&](auto nc) {
-            constexpr int n = decltype(nc)::value;
-            ds_read16<0>(fq[n], (n & 1) ? a1B[n >> 1] : a1A[n >> 1]);
-        });
-    }
 
     // (measured and not kept, round 5: s_setprio 1 for the second-dispatched half of the workgroup -- waves 4-7 lose every contested issue
     // slot to their older partners -- 3424.8 vs 3429.4 us per launch, same box: nothing)
@@ -2063,33 +1390,24 @@ __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const 
     for (int c = 0; c <= NCH; ++c) {
         static_for<5>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(LA ? wait_la(i) : wait_n(i)) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(wait_n(i)) : "memory");
             if (!DBG || !(dflags & 16)) __builtin_amdgcn_s_barrier();
             if constexpr (i == 0) asm volatile("" : "+v"(accA));      // the bias reads have landed (the wait above)
             if constexpr (i < 3) {
                 // ---- FFN1 slab i: 4 k-steps x 2 tiles, n = 2 ks + (0: own tile, 1: partner's); behind MFMA n: activation stage 8 i + n
-                if constexpr (!LA) static_for<PF>([&](auto nc) {
+                static_for<PF>([&](auto nc) {
                     constexpr int n = decltype(nc)::value;
                     if (!DBG || !(dflags & 2)) ds_read16<i * S1>(fq[n], (n & 1) ? a1B[n >> 1] : a1A[n >> 1]);
                 });
                 static_for<8>([&](auto nc) {
                     constexpr int n = decltype(nc)::value;
                     if constexpr (n % 2 == 0)
-                        asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(fq[n % PF]), "+v"(fq[(n + 1) % PF]) : "n"((LA || n + PF <= 8) ? PF - 2 : 8 - 2 - n));
+                        asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(fq[n % PF]), "+v"(fq[(n + 1) % PF]) : "n"(n + PF <= 8 ? PF - 2 : 8 - 2 - n));
                     if constexpr (n & 1) accB = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fq[n % PF], hf[i * 4 + (n >> 1)], accB, 0, 0, 0);
                     else accA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fq[n % PF], hf[i * 4 + (n >> 1)], accA, 0, 0, 0);
                     if constexpr (n + PF < 8) { if (!DBG || !(dflags & 2)) ds_read16<i * S1>(fq[n % PF], ((n + PF) & 1) ? a1B[(n + PF) >> 1] : a1A[(n + PF) >> 1]); }
-                    else if constexpr (LA) {                   // fragment m of the NEXT slab (landed: look-ahead wait at this slab's barrier)
-                        constexpr int m = n + PF - 8;
-                        if constexpr (i < 2) ds_read16<(i + 1) * S1>(fq[n % PF], (m & 1) ? a1B[m >> 1] : a1A[m >> 1]);
-                        else ds_read16<(m % 6) * 2048>(fq[n % PF], a2[m / 6]);
-                    } else asm volatile("" : "+v"(fq[n % PF]));
-                    if constexpr (LA) {                        // one refill per slab: slot 4 during slab 0, W1 slot i - 1 of the next chunk during slabs 1, 2
-                        if constexpr (i == 0 && n % 2 == 1 && n / 2 < 3) issue_part(c, std::integral_constant<int, 4>{}, std::integral_constant<int, n / 2>{});
-                        if constexpr (i > 0 && n % 2 == 1 && n / 2 < 2) issue_part(c + 1, std::integral_constant<int, i - 1>{}, std::integral_constant<int, n / 2>{});
-                    } else {
-                        if constexpr (i == 0 && n % 2 == 1 && n / 2 < 3) issue_part(c, std::integral_constant<int, 4>{}, std::integral_constant<int, n / 2>{});
-                    }
+                    else asm volatile("" : "+v"(fq[n % PF]));
+                    if constexpr (i == 0 && n % 2 == 1 && n / 2 < 3) issue_part(c, std::integral_constant<int, 4>{}, std::integral_constant<int, n / 2>{});
                     gelu_stage((8 * i + n) / 6, (8 * i + n) % 6);
                 });
                 if constexpr (i == 2) if (!DBG || !(dflags & 8)) {
@@ -2123,30 +1441,20 @@ __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const 
                     asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(pp[2]) : "v"(xp_r));
                     asm volatile("ds_read_b128 %0, %1 offset:3072" : "=v"(pp[3]) : "v"(xp_r));
                 }
-                if constexpr (!LA) static_for<PF>([&](auto nc) {
+                static_for<PF>([&](auto nc) {
                     constexpr int n = decltype(nc)::value;
                     if (!DBG || !(dflags & 2)) ds_read16<t * S2 + (n % 6) * 2048>(fq[n], a2[n / 6]);
                 });
                 static_for<12>([&](auto nc) {
                     constexpr int n = decltype(nc)::value;
-                    // look-ahead: the slab's first PF fragments are OLDER than the exchange reads above (they were issued during the previous
-                    // slab); the first wait must reach past them to pf[0] (2, resp. 2 + 4 exchange reads, all but the first may stay in flight)
-                    if constexpr (LA && n == 0)
-                        asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(fq[0]), "+v"(fq[1]) : "n"(t == 0 ? 5 : 1));
-                    else if constexpr (n % 2 == 0)
-                        asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(fq[n % PF]), "+v"(fq[(n + 1) % PF]) : "n"((LA || n + PF <= 12) ? PF - 2 : 12 - 2 - n));
+                    if constexpr (n % 2 == 0)
+                        asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(fq[n % PF]), "+v"(fq[(n + 1) % PF]) : "n"(n + PF <= 12 ? PF - 2 : 12 - 2 - n));
                     if constexpr (n == 0) asm volatile("" : "+v"(pf[0]), "+v"(pf[1]));
                     acc2[n % 6] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fq[n % PF], __builtin_bit_cast(bf16x8, pf[n / 6]), acc2[n % 6], 0, 0, 0);
                     if constexpr (n + PF < 12) { if (!DBG || !(dflags & 2)) ds_read16<t * S2 + ((n + PF) % 6) * 2048>(fq[n % PF], a2[(n + PF) / 6]); }
-                    else if constexpr (LA) {                   // fragment m of the next slab: W2 tile 1, resp. W1 slab 0 of the next iteration
-                        constexpr int m = n + PF - 12;
-                        if constexpr (t == 0) ds_read16<S2 + (m % 6) * 2048>(fq[n % PF], a2[m / 6]);
-                        else ds_read16<0>(fq[n % PF], (m & 1) ? a1B[m >> 1] : a1A[m >> 1]);
-                    } else asm volatile("" : "+v"(fq[n % PF]));
+                    else asm volatile("" : "+v"(fq[n % PF]));
                     if constexpr (t == 0) {
-                        if constexpr (LA) {                  // refill of W1 slot 2 (chunk c + 1): 2 instructions
-                            if constexpr (n == 0 || n == 2) issue_part(c + 1, std::integral_constant<int, 2>{}, std::integral_constant<int, n / 2>{});
-                        } else if constexpr (n % 2 == 0) {          // S0', S1', S2' of iteration c + 1: 6 instructions over 12 steps
+                        if constexpr (n % 2 == 0) {          // S0', S1', S2' of iteration c + 1: 6 instructions over 12 steps
                             constexpr int k = n / 2;
                             issue_part(c + 1, std::integral_constant<int, k / 2>{}, std::integral_constant<int, k % 2>{});
                         }
@@ -2177,14 +1485,10 @@ __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const 
     // statistics are taken where the values are: a lane holds 96 of its token's 384 values, lane ^ 32 another 96, the partner wave
     // (w ^ 4) the other 192 -- the same two exchanges as LayerNorm 1 in the prologue (two-pass, fp32); the tile receives the FINISHED
     // bf16 rows and is copied out with 16-byte accesses, all reads in flight.  Measured (profiles/r05_ab_ffn3.txt, same box): 3193.4 -> 3056.2 us
-    // per launch.  The old form stays in debug builds (dflags bit 2048, RMU_FFN3_EPI=0); with both in one kernel hipcc spills two registers.
-#ifdef RMU_DEBUG_KERNELS
-    if (!(dflags & 2048)) {
-#else
+    // per launch.  (With both forms in one kernel hipcc spilled two registers: the old one is gone, not switched off.)
     {
-#endif
         // acc2[j][4 q + e] = output feature n = 192 s + 32 j + 8 q + 4 hh + e of token 32 p + r31; the residual h1[token][n] sits in
-        // hf[2 j + (q >> 1)] of this lane ((q & 1) == hh) or of lane ^ 32 (as k_ffn2); OP: in this lane's fragment in accumulator order
+        // hf[2 j + (q >> 1)] of this lane ((q & 1) == hh) or of lane ^ 32 (as k_ffn2)
         const int tr = 32 * p + r31;
         typedef u32 u32x2 __attribute__((ext_vector_type(2)));
         float sm = 0.f;
@@ -2195,15 +1499,13 @@ __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const 
                 const u32x4 hv = __builtin_bit_cast(u32x4, hf[2 * j + qq]);
                 const u32x2 own = hh ? u32x2{hv[2], hv[3]} : u32x2{hv[0], hv[1]};
                 const u32x2 oth = hh ? u32x2{hv[0], hv[1]} : u32x2{hv[2], hv[3]};
-                u32x2 rcv = {0u, 0u};
-                if constexpr (!OP) {
-                    rcv[0] = (u32)__shfl_xor((int)oth[0], 32);
-                    rcv[1] = (u32)__shfl_xor((int)oth[1], 32);
-                }
+                u32x2 rcv;
+                rcv[0] = (u32)__shfl_xor((int)oth[0], 32);
+                rcv[1] = (u32)__shfl_xor((int)oth[1], 32);
 #pragma unroll
                 for (int qb = 0; qb < 2; ++qb) {
                     const int q = 2 * qq + qb;
-                    const u32x2 rs2 = OP ? (qb ? u32x2{hv[2], hv[3]} : u32x2{hv[0], hv[1]}) : ((qb == hh) ? own : rcv);
+                    const u32x2 rs2 = (qb == hh) ? own : rcv;
                     const bf16x4 res = __builtin_bit_cast(bf16x4, rs2);
                     const int n = s * 192 + j * 32 + q * 8 + hh * 4;
                     const f32x4 bv = *(const f32x4*)(lnp + 4 * H + n);
@@ -2253,7 +1555,7 @@ __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const 
         for (int r = 0; r < 16; ++r) {
             const int m = m0 + w * 16 + r;
             if (act && m < M) {
-                // dflags bit 8: the TILED activation form -- 1-KiB blocks of 16 tokens x 32 features, [token block][feature block] order, unit u
+                // dflags bit 256: the TILED activation form -- 1-KiB blocks of 16 tokens x 32 features, [token block][feature block] order, unit u
                 // (8 features) of row r at u ^ tswz(r): exactly what a ring slot of the next layer's QKV GEMM / the out-proj's
                 // residual piece holds, so their DMA instructions read whole contiguous KiB
                 int64_t off = (int64_t)m * H + c0;
@@ -2261,86 +1563,13 @@ __global__ __launch_bounds__(512) void k_ffn3(const bf16* __restrict__ x, const 
                 *(bf16x8*)(out + off) = ov[r];                  // (non-temporal here measured +0.6 %: the next layer's GEMMs read h right away)
             }
         }
-        return;
     }
-#ifdef RMU_DEBUG_KERNELS
-    {
-        // acc2[j][4 q + e] = output feature n = 192 s + 32 j + 8 q + 4 hh + e of token 32 p + r31; the residual h1[token][n] sits in
-        // hf[2 j + (q >> 1)] of this lane ((q & 1) == hh) or of lane ^ 32 (as k_ffn2).  y = bf16(bf16(acc + b2) + resid).
-        const int tr = 32 * p + r31;
-        typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                const u32x4 hv = __builtin_bit_cast(u32x4, hf[2 * j + qq]);
-                const u32x2 own = hh ? u32x2{hv[2], hv[3]} : u32x2{hv[0], hv[1]};
-                const u32x2 oth = hh ? u32x2{hv[0], hv[1]} : u32x2{hv[2], hv[3]};
-                u32x2 rcv = {0u, 0u};
-                if constexpr (!OP) {
-                    rcv[0] = (u32)__shfl_xor((int)oth[0], 32);
-                    rcv[1] = (u32)__shfl_xor((int)oth[1], 32);
-                }
-#pragma unroll
-                for (int qb = 0; qb < 2; ++qb) {
-                    const int q = 2 * qq + qb;
-                    // OP: the fragments are in accumulator order -- elements [4 qb, +4) of this lane's k-step 2 j + qq ARE features 8 q + 4 hh + e
-                    const u32x2 rs2 = OP ? (qb ? u32x2{hv[2], hv[3]} : u32x2{hv[0], hv[1]}) : ((qb == hh) ? own : rcv);
-                    const bf16x4 res = __builtin_bit_cast(bf16x4, rs2);
-                    const int n = s * 192 + j * 32 + q * 8 + hh * 4;
-                    const f32x4 bv = *(const f32x4*)(b2 + n);
-                    bf16x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = (bf16)(bf2f((bf16)(acc2[j][4 * q + e] + bv[e])) + bf2f(res[e]));
-                    *(bf16x4*)(tile + tr * TSTR + n * 2) = v;
-                }
-            }
-    }
-    __syncthreads();
-    {
-        const bool act = lane < 48;
-        const int c0 = (act ? lane : 0) * 8;
-        float gg[8], bb[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { gg[i] = g[c0 + i]; bb[i] = bta[c0 + i]; }
-        for (int r = 0; r < 16; ++r) {
-            const int tr = w * 16 + r;
-            const int m = m0 + tr;
-            if (m >= M) break;
-            const bf16x8 yv = *(const bf16x8*)(tile + tr * TSTR + c0 * 2);
-            float v[8];
-            float sm = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { v[i] = act ? bf2f(yv[i]) : 0.f; sm += v[i]; }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o);
-            const float mu = sm * (1.0f / H);
-            float q = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { const float d = act ? v[i] - mu : 0.f; q = fmaf(d, d, q); }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-            const float rs = rsqrtf(q * (1.0f / H) + eps);
-            bf16x8 ov;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) ov[i] = (bf16)((v[i] - mu) * rs * gg[i] + bb[i]);
-            if (act) {
-                // dflags bit 8: the TILED activation form -- 1-KiB blocks of 16 tokens x 32 features, [token block][feature block] order, unit u
-                // (8 features) of row r at u ^ tswz(r): exactly what a ring slot of the next layer's QKV GEMM / the out-proj's
-                // residual piece holds, so their DMA instructions read whole contiguous KiB
-                int64_t off = (int64_t)m * H + c0;
-                if (dflags & 256) { const int r = m & 15; off = ((int64_t)(m >> 4) * (H / 32) + (c0 >> 5)) * 512 + r * 32 + ((((c0 >> 3) & 3) ^ tswz(r)) * 8); }
-                *(bf16x8*)(out + off) = ov;
-            }
-        }
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------
 // k_gemm3 -- persistent big-tile GEMM for the encoder's shapes: out[m, n] = epi( sum_k A[m, k] W[n, k] + bias[n] ).
 //
-// What the cycle counters of k_gemm / k_ffn_fused and tools/ubench/fill.hip say about a CU's memory pipeline (all 256 CUs busy,
+// What the cycle counters of k_gemm / the round-2 fused FFN kernel and tools/ubench/fill.hip say about a CU's memory pipeline (all 256 CUs busy,
 // L2-resident source): an LDS fill (global_load_lds, or global_load + ds_write alike) runs at ~146 GB/s per CU when a wave
 // instruction covers 1 KiB of contiguous bytes but ~75 GB/s as 16 rows x 64 B -- the address path is paid per cache line touched
 // (~0.55 lines per clock), whatever the number of waves (4..16) or loads in flight; stores leave at ~14 B/clk per CU (a 1-KiB
@@ -2381,7 +1610,7 @@ __global__ __launch_bounds__(512) void k_gemm3(const bf16* __restrict__ A, const
     // hm_stride > 0: the output is written HEAD-MAJOR -- [feature / 32][hm_stride token rows][32] -- the layout k_attn3 reads its (sequence,
     // head) blocks from as contiguous bytes (a store instruction's 16 rows x 64 B are then one contiguous KiB too)
     using namespace g3;
-    using ffn::static_for; using ffn::ds_read16; using ffn::frag_wait; using ffn::sgpr_ptr;
+    using isa::static_for; using isa::ds_read16; using isa::frag_wait; using isa::sgpr_ptr;
     const int M = cu[batch];
     const int ncb = N / BNF, nk = K / 32;
     const int mtiles = (M + BM - 1) / BM;
@@ -2663,152 +1892,10 @@ __global__ __launch_bounds__(512) void k_gemm3(const bf16* __restrict__ A, const
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// attention: one workgroup = (sequence, head); K rows and V^T of the whole sequence staged in LDS once; each wave
-// takes 16 queries per round (rounds of 64) and keeps its full score strip S^T[keys, 16] in registers
-// (<= 32 key tiles): exact softmax, no online rescaling.
-// ------------------------------------------------------------------------------------------------------------
-template <int MAXT>   // max key tiles of 16 (sequence length <= 16*MAXT)
-__global__ __launch_bounds__(256) void k_attention(const bf16* __restrict__ qkv, const int* __restrict__ cu,
-                                                   bf16* __restrict__ ctx) {
-    constexpr int KSTR = 80;                       // bytes per K row in LDS (64 + 16 pad: conflict-free b128 reads)
-    constexpr int LP = MAXT * 16;
-    constexpr int VSTR = LP * 2 + 8;               // bytes per V^T row
-    char* ks = gsm;                                // [LP][KSTR]
-    char* vt = gsm + LP * KSTR;                    // [DH][VSTR]
-    const int b = blockIdx.y, head = blockIdx.x;
-    const int t0 = cu[b], L = cu[b + 1] - t0;
-    if (L <= 0) return;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int fr = lane & 15, kg = lane >> 4;
-    const int nt = (L + 15) >> 4;                  // key tiles in use
-    const int npair = (nt + 1) >> 1;               // 32-key blocks for P.V
-    const int rows_fill = npair * 32;              // rows touched by the MFMAs (<= LP)
-    const int64_t rs = 3 * H;                      // qkv row stride (elements)
-
-    // Q fragment of the first query block: issued BEFORE the K/V staging so its latency overlaps it
-    // (B operand: query q0+fr, dims 8*kg..; 1/sqrt(32) is folded into Wq at load time)
-    bf16x8 qf = {};
-    if (w * 16 + fr < L) qf = *(const bf16x8*)(qkv + (int64_t)(t0 + w * 16 + fr) * rs + head * DH + kg * 8);
-
-    // ---- K rows (16-B pieces) and V transposed into LDS, once per (sequence, head); rows >= L are zero -------
-    for (int p0 = 0; p0 < rows_fill * 4; p0 += 512) {
-        uint4 kv[2], vv[2];
-#pragma unroll
-        for (int u2 = 0; u2 < 2; ++u2) {           // both loads in flight before either is used
-            const int p = p0 + u2 * 256 + tid;
-            const int r = p >> 2, u = p & 3;
-            kv[u2] = uint4{0u, 0u, 0u, 0u};
-            vv[u2] = uint4{0u, 0u, 0u, 0u};
-            if (p < rows_fill * 4 && r < L) {
-                const bf16* base = qkv + (int64_t)(t0 + r) * rs + head * DH + u * 8;
-                kv[u2] = *(const uint4*)(base + H);
-                vv[u2] = *(const uint4*)(base + 2 * H);
-            }
-        }
-#pragma unroll
-        for (int u2 = 0; u2 < 2; ++u2) {
-            const int p = p0 + u2 * 256 + tid;
-            if (p < rows_fill * 4) {
-                const int r = p >> 2, u = p & 3;
-                *(uint4*)(ks + r * KSTR + u * 16) = kv[u2];
-                const unsigned short* ve = (const unsigned short*)&vv[u2];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) *(unsigned short*)(vt + (u * 8 + e) * VSTR + r * 2) = ve[e];
-            }
-        }
-    }
-    __syncthreads();
-
-    for (int q0 = w * 16; q0 < L; q0 += 64) {      // each wave: 16 queries per round; no barriers below
-        // prefetch the next round's Q fragment while this round computes
-        bf16x8 qn = {};
-        if (q0 + 64 + fr < L) qn = *(const bf16x8*)(qkv + (int64_t)(t0 + q0 + 64 + fr) * rs + head * DH + kg * 8);
-
-        // ---- S^T tiles: lane holds query fr, keys 16*kt + 4*kg + i --------------------------------------------
-        f32x4 st[MAXT];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < MAXT; ++kt) {
-            st[kt] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            if (kt < nt) {
-                const bf16x8 kf = *(const bf16x8*)(ks + (kt * 16 + fr) * KSTR + kg * 16);
-                f32x4 sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {       // (a uniform branch that masks only the last key tile measured 6 % slower)
-                    if (kt * 16 + kg * 4 + i >= L) sc[i] = -INFINITY;
-                    mx = fmaxf(mx, sc[i]);
-                }
-                st[kt] = sc;
-            }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        float sum = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < MAXT; ++kt) {
-            if (kt < nt) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float p = __builtin_amdgcn_exp2f(st[kt][i] - mx);   // scores carry log2(e) (folded into Wq); 2^-inf = 0 for masked keys
-                    st[kt][i] = p;
-                    sum += p;
-                }
-            }
-        }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
-
-        // ---- O = P . V : k-slot (kg, i, half) of block pb <-> key 32*pb + 16*half + 4*kg + i on BOTH operands --
-        f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int pb = 0; pb < MAXT / 2; ++pb) {
-            if (pb < npair) {
-                bf16x8 pf;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    pf[i] = (bf16)st[2 * pb][i];
-                    pf[4 + i] = (2 * pb + 1 < nt) ? (bf16)st[2 * pb + 1][i] : (bf16)0.f;
-                }
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    const char* vrow = vt + (dt * 16 + fr) * VSTR + (32 * pb + 4 * kg) * 2;
-                    const bf16x4 v0 = *(const bf16x4*)(vrow);
-                    const bf16x4 v1 = *(const bf16x4*)(vrow + 32);
-                    bf16x8 vf;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { vf[i] = v0[i]; vf[4 + i] = v1[i]; }
-                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[dt], 0, 0, 0);   // O^T: V^T is the A operand
-                }
-            }
-        }
-        // D layout of O^T: row = dim 4*kg + i (+16*dt), col = query fr -- the lane's own query, whose row sum it already holds.
-        // Lanes kg and kg ^ 1 (lane ^ 16) trade one 8-byte half so that each stores 8 consecutive dims: ONE 16-byte store per
-        // lane and round (2-byte stores of the O layout made this kernel store-issue-bound).
-        {
-            const float rden = 1.0f / sum;
-            union { bf16x4 v; int i[2]; } a0, a1, snd, rcv;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { a0.v[i] = (bf16)(o[0][i] * rden); a1.v[i] = (bf16)(o[1][i] * rden); }
-            const bool odd = kg & 1;
-            snd.v = odd ? a0.v : a1.v;                 // even kg keeps dims 4kg.. and gets 4(kg+1)..; odd keeps 16+4kg.. and gets 16+4(kg-1)..
-            rcv.i[0] = __shfl_xor(snd.i[0], 16);
-            rcv.i[1] = __shfl_xor(snd.i[1], 16);
-            if (q0 + fr < L) {
-                bf16x8 ov;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { ov[i] = odd ? rcv.v[i] : a0.v[i]; ov[4 + i] = odd ? a1.v[i] : rcv.v[i]; }
-                *(bf16x8*)(ctx + (int64_t)(t0 + q0 + fr) * H + head * DH + (odd ? 16 + 4 * (kg - 1) : 4 * kg)) = ov;
-            }
-        }
-        qf = qn;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// k_attn3 -- attention, third form (round 3; default).  k_attention above is VALU-bound: 38 VALU per MFMA = ~19 wave
-// instructions per score (per-element masks, a v_sub and a v_add per score, 4-lane shuffles, a branch skeleton per key tile),
-// 0.073 of the bf16 roof.  Here the matrix pipe does everything that is linear and the VALU keeps only max, exp2 and the bf16
-// pack (~3 instructions per score):
+// k_attn3 -- attention, one workgroup per (sequence, head) (round 3).  The round-1 kernel (retired; NOTES_r01_r05.md 4.3) kept a wave's
+// whole score strip S^T[keys, 16 queries] in registers and was VALU-bound: 38 VALU per MFMA = ~19 wave instructions per score
+// (per-element masks, a v_sub and a v_add per score, 4-lane shuffles, a branch skeleton per key tile), 0.073 of the bf16 roof.  Here the
+// matrix pipe does everything that is linear and the VALU keeps only max, exp2 and the bf16 pack (~3 instructions per score):
 //   * S^T = K . Q^T with v_mfma_f32_32x32x16_bf16 (A = K rows from LDS, B = Q straight from global memory): lane (query =
 //     lane & 31, half h) holds ITS query's scores against 16 keys of every 32-key tile -- row max / sum are chains over the
 //     lane's own registers plus ONE exchange with lane ^ 32;
@@ -2820,7 +1907,7 @@ __global__ __launch_bounds__(256) void k_attention(const bf16* __restrict__ qkv,
 //     a k-permuted B fragment, so P never leaves the registers; V^T is staged with the same key permutation;
 //   * row sums with v_dot2_f32_bf16 on the PACKED bf16 pairs against (1, 1): half the adds, and the sum is taken over exactly
 //     the rounded probabilities the P.V product uses;
-//   * ~120 registers per wave: four waves per SIMD hide the LDS / exp latencies (k_attention holds the whole strip: one).
+//   * ~120 registers per wave: four waves per SIMD hide the LDS / exp latencies (the round-1 kernel held the whole strip: one).
 // Workgroup = (sequence, head), 4 waves; wave w takes the 32-query tiles w, w + 4, ...; the heads of a sequence share an XCD.
 // KT = key tiles of 32 (L <= 32 KT).  What bounds it (measured, 8192 sequences of ~128 tokens, 0.90 ms per layer at four waves
 // per SIMD, 1.13 at three): with the staging AND all but one key tile removed 0.45 ms remain -- 98k workgroups each paying a
@@ -3242,218 +2329,6 @@ __global__ __launch_bounds__(256) void k_qkv_attn_small(const bf16* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// k_attn4 -- k_attn3 made PERSISTENT (round 4).  k_attn3 starts one workgroup per (sequence, head): 98k of them for 8192 chunks, each
-// paying a cold global round trip for its K / V / Q pieces before the first MFMA -- by the round-3 ablation 0.45 of its 0.82 ms per
-// layer is that start-up, not arithmetic.  Here a workgroup walks a list of (sequence, head) items (item it -> XCD it & 7, as the
-// grid map of k_attn3: the heads of a sequence stay on one XCD) and the NEXT item's K / V pieces and Q fragments are requested
-// before the current item's MFMAs begin, landing in registers while it computes; they go into the (single) LDS image after the
-// barrier that ends the current item.  Same arithmetic, same LDS layouts, same output as k_attn3 bit for bit.
-// ------------------------------------------------------------------------------------------------------------
-template <int KT, int OCC>
-__global__ __launch_bounds__(256, OCC) void k_attn4(const bf16* __restrict__ qkv, const int* __restrict__ cu, int batch, bf16* __restrict__ ctx, int ctx_tiled, long hm_stride) {
-    constexpr int LP = KT * 32;
-    constexpr int VSTR = LP * 2 + 16;
-    constexpr int KBYTES = LP * 64;
-    constexpr int NR = KT / 4;                     // staging rounds of 512 sixteen-byte pieces (two per thread for K, two for V)
-    typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    char* ks = gsm;
-    char* vt = gsm + KBYTES;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c31 = lane & 31, hh = lane >> 5;
-    const int n_items = (batch + 7) / 8 * 8 * NH;
-    const int64_t rs = hm_stride > 0 ? DH : 3 * H;
-    const int64_t koff = hm_stride > 0 ? (int64_t)NH * hm_stride * DH : H, voff = 2 * koff;
-    struct Item { int t0, L, nkt, head; const bf16* base; bool ok; };
-    auto item = [&](int it) -> Item {
-        Item c{0, 0, 0, 0, qkv, false};
-        if (it >= n_items) return c;
-        const int xcd = it & 7, idx = it >> 3;
-        const int b = (idx / NH) * 8 + xcd;
-        c.head = idx % NH;
-        if (b >= batch) return c;
-        c.t0 = cu[b];
-        c.L = cu[b + 1] - c.t0;
-        if (c.L <= 0) return c;
-        c.nkt = (c.L + 31) >> 5;
-        c.base = hm_stride > 0 ? qkv + ((int64_t)c.head * hm_stride + c.t0) * DH : qkv + (int64_t)c.t0 * rs + c.head * DH;
-        c.ok = true;
-        return c;
-    };
-    uint4 kv[NR][2], vv[NR][2];
-    auto request = [&](const Item& c, bf16x8 (&qf)[2]) {       // global loads of an item's K / V pieces and this wave's first Q fragments
-        qf[0] = bf16x8{}; qf[1] = bf16x8{};
-        if (w < c.nkt) {
-            const int q = min(w * 32 + c31, c.L - 1);
-            qf[0] = *(const bf16x8*)(c.base + (int64_t)q * rs + hh * 8);
-            qf[1] = *(const bf16x8*)(c.base + (int64_t)q * rs + 16 + hh * 8);
-        }
-#pragma unroll
-        for (int rd = 0; rd < NR; ++rd)
-#pragma unroll
-            for (int u2 = 0; u2 < 2; ++u2) {
-                const int p = rd * 512 + u2 * 256 + tid, r = p >> 2, u = p & 3;
-                kv[rd][u2] = uint4{0u, 0u, 0u, 0u};
-                vv[rd][u2] = uint4{0u, 0u, 0u, 0u};
-                if (r < c.L) {
-                    kv[rd][u2] = *(const uint4*)(c.base + (int64_t)r * rs + koff + u * 8);
-                    vv[rd][u2] = *(const uint4*)(c.base + (int64_t)r * rs + voff + u * 8);
-                }
-            }
-    };
-    auto stage = [&](const Item& c) {                           // registers -> the LDS images (K row-major swizzled, V^T key-permuted)
-#pragma unroll
-        for (int rd = 0; rd < NR; ++rd)
-#pragma unroll
-            for (int u2 = 0; u2 < 2; ++u2) {
-                const int p = rd * 512 + u2 * 256 + tid, r = p >> 2, u = p & 3;
-                if (p < c.nkt * 128) {
-                    *(uint4*)(ks + r * 64 + ((u ^ ((r >> 2) & 3)) * 16)) = kv[rd][u2];
-                    const int r16 = r & 15, slot = (r & ~15) + ((r16 & 3) | ((r16 & 4) << 1) | ((r16 & 8) >> 1));
-                    const unsigned short* ve = (const unsigned short*)&vv[rd][u2];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) *(unsigned short*)(vt + (u * 8 + e) * VSTR + slot * 2) = ve[e];
-                }
-            }
-    };
-    const u32 kaddr = (u32)(uintptr_t)(__attribute__((address_space(3))) char*)ks + (u32)(c31 * 64);
-    const u32 ksw = (u32)((c31 >> 2) & 3);
-    auto kfrag = [&](int kt, int s2) -> bf16x8 {
-        return *(const bf16x8*)((const __attribute__((address_space(3))) char*)(uintptr_t)(kaddr + (u32)(kt * 2048) + (((u32)(2 * s2 + hh) ^ ksw) * 16)));
-    };
-    f32x16 zero16;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
-
-    // OCC == 4 (126 registers, k_attn3's occupancy): no room for the next item's pieces in registers -- they are pulled into this XCD's L2
-    // instead (one 128-byte line per lane, value discarded), and requested for real when the item starts
-    auto touch_l2 = [&](const Item& c) {
-        const int n_lines = c.L * 64 / 128;                       // (head-major planes: an item's Q, K and V are three contiguous blocks)
-        if (hm_stride > 0 && tid < 3 * n_lines) {
-            const int part = tid / n_lines, ln = tid - part * n_lines;
-            const char* p = (const char*)(c.base + (int64_t)part * koff) + ln * 128;
-            u32 sink;
-            asm volatile("global_load_dword %0, %1, off" : "=v"(sink) : "v"(p) : "memory");
-        }
-    };
-    int it = blockIdx.x;
-    Item cur = item(it);
-    bf16x8 qf[2], qnx[2];
-    request(cur, qf);
-    for (;;) {
-        if (cur.ok) stage(cur);
-        __syncthreads();
-        const int itn = it + (int)gridDim.x;
-        const Item nxt = item(itn);
-        qnx[0] = bf16x8{}; qnx[1] = bf16x8{};
-        if (OCC == 4) { if (nxt.ok) touch_l2(nxt); }
-        else if (nxt.ok) request(nxt, qnx);                      // in flight while this item computes
-        if (cur.ok) {
-            const int L = cur.L, nkt = cur.nkt, t0 = cur.t0, head = cur.head;
-            const bf16* base = cur.base;
-            f32x16 maskc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) maskc[r] = ((nkt - 1) * 32 + 8 * (r >> 2) + 4 * hh + (r & 3) < L) ? 0.f : -INFINITY;
-            for (int qt = w; qt < nkt; qt += 4) {
-                bf16x8 qn[2] = {qf[0], qf[1]};
-                if (qt + 4 < nkt) {
-                    const int q = min((qt + 4) * 32 + c31, L - 1);
-                    qn[0] = *(const bf16x8*)(base + (int64_t)q * rs + hh * 8);
-                    qn[1] = *(const bf16x8*)(base + (int64_t)q * rs + 16 + hh * 8);
-                }
-                float mx = -INFINITY;
-                auto pass1 = [&](int kt, const f32x16& c0) {
-                    f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag(kt, 0), qf[0], c0, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag(kt, 1), qf[1], acc, 0, 0, 0);
-                    float m3 = fmaxf(fmaxf(acc[0], acc[1]), acc[2]);
-#pragma unroll
-                    for (int r = 3; r + 1 < 16; r += 2) m3 = fmaxf(fmaxf(m3, acc[r]), acc[r + 1]);
-                    mx = fmaxf(mx, fmaxf(m3, acc[15]));
-                };
-#pragma unroll 1
-                for (int kt = 0; kt < nkt - 1; ++kt) pass1(kt, zero16);
-                pass1(nkt - 1, maskc);
-                mx = fmaxf(mx, __shfl_xor(mx, 32));
-                f32x16 negm, negmm;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { negm[r] = -mx; negmm[r] = maskc[r] - mx; }
-                f32x16 ot;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) ot[r] = 0.f;
-                float sum = 0.f;
-                const bf16x2 one2 = {(bf16)1.0f, (bf16)1.0f};
-                auto pass2 = [&](int kt, const f32x16& c0) {
-                    f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag(kt, 0), qf[0], c0, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag(kt, 1), qf[1], acc, 0, 0, 0);
-                    u32x4 pu[2];
-#pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        bf16x2 pb;
-                        pb[0] = (bf16)__builtin_amdgcn_exp2f(acc[r]);
-                        pb[1] = (bf16)__builtin_amdgcn_exp2f(acc[r + 1]);
-                        sum = __builtin_amdgcn_fdot2_f32_bf16(pb, one2, sum, false);
-                        pu[r >> 3][(r & 7) >> 1] = __builtin_bit_cast(u32, pb);
-                    }
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) {
-                        const bf16x8 vf = *(const bf16x8*)(vt + c31 * VSTR + (kt * 32 + s2 * 16 + hh * 8) * 2);
-                        ot = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, __builtin_bit_cast(bf16x8, pu[s2]), ot, 0, 0, 0);
-                    }
-                };
-#pragma unroll 1
-                for (int kt = 0; kt < nkt - 1; ++kt) pass2(kt, negm);
-                pass2(nkt - 1, negmm);
-                sum += __shfl_xor(sum, 32);
-                const float inv = __builtin_amdgcn_rcpf(sum);
-                {
-                    union { bf16x4 v; int i[2]; } pc[4], rcv[2];
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) pc[g4].v[e] = (bf16)(ot[4 * g4 + e] * inv);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const int snd0 = hh ? pc[j].i[0] : pc[2 + j].i[0], snd1 = hh ? pc[j].i[1] : pc[2 + j].i[1];
-                        rcv[j].i[0] = __shfl_xor(snd0, 32);
-                        rcv[j].i[1] = __shfl_xor(snd1, 32);
-                    }
-                    const int q = qt * 32 + c31;
-                    if (q < L) {
-                        bf16x8 o0, o1;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            o0[e] = hh ? rcv[0].v[e] : pc[0].v[e];
-                            o0[4 + e] = hh ? pc[2].v[e] : rcv[0].v[e];
-                            o1[e] = hh ? rcv[1].v[e] : pc[1].v[e];
-                            o1[4 + e] = hh ? pc[3].v[e] : rcv[1].v[e];
-                        }
-                        if (ctx_tiled) {
-                            const int64_t m = t0 + q;
-                            const int r = (int)(m & 15), sw = tswz(r);
-                            bf16* blk = ctx + ((m >> 4) * NH + head) * 512 + r * 32;
-                            *(bf16x8*)(blk + ((2 * hh) ^ sw) * 8) = o0;
-                            *(bf16x8*)(blk + ((2 * hh + 1) ^ sw) * 8) = o1;
-                        } else {
-                            bf16* dst = ctx + (int64_t)(t0 + q) * H + head * DH + hh * 16;
-                            *(bf16x8*)dst = o0;
-                            *(bf16x8*)(dst + 8) = o1;
-                        }
-                    }
-                }
-                qf[0] = qn[0];
-                qf[1] = qn[1];
-            }
-        }
-        if (itn >= n_items) break;
-        __syncthreads();                                         // everybody is done reading this item's LDS images
-        cur = nxt; it = itn;
-        if (OCC == 4) request(cur, qf);
-        else { qf[0] = qnx[0]; qf[1] = qnx[1]; }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------
 // k_qa -- the bulk path's QKV projection AND attention in ONE launch (round 6).  Per layer k_gemm3 wrote 2.4 GB of
 // Q | K | V that k_attn3 read back 1 ms later (14.4 GB written + 14.6 GB fetched per forward, 98k cold workgroups each waiting for its
 // 64-byte row pieces): here Q, K and V never leave the CU.
@@ -3537,7 +2412,7 @@ __global__ __launch_bounds__(512) void k_qa(const bf16* __restrict__ x, int x_ti
     // dflags (RMU_QA_DBG, timing ablations only -- results are wrong with any bit set): 1 no attention, 2 no projection MFMAs / fragment reads,
     // 4 no epilogue (bias, pack, image writes), 8 no weight DMA
     using namespace qa;
-    using ffn::static_for; using ffn::sgpr_ptr;
+    using isa::static_for; using isa::sgpr_ptr;
     typedef u32 u32x4 __attribute__((ext_vector_type(4)));
     typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
     if ((int)blockIdx.x >= *n_items) return;
@@ -3655,14 +2530,14 @@ __global__ __launch_bounds__(512) void k_qa(const bf16* __restrict__ x, int x_ti
                     u32 base = ring_addr + (u32)(j * SLAB) + lane16;
                     asm volatile("" : "+v"(base));          // ONE address register per slab: the 24 fragments are immediate offsets (hipcc otherwise keeps 24 addresses -- spilled)
                     bf16x8 fo[4];
-                    static_for<4>([&, base](auto nc) { (void)base; ffn::ds_read16<decltype(nc)::value * 1024>(fo[decltype(nc)::value], base); });
+                    static_for<4>([&, base](auto nc) { (void)base; isa::ds_read16<decltype(nc)::value * 1024>(fo[decltype(nc)::value], base); });
                     static_for<24>([&, base](auto nc) {
                         constexpr int n = decltype(nc)::value;
                         (void)base;
                         if constexpr (n % 2 == 0)
                             asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(fo[n % 4]), "+v"(fo[(n + 1) % 4]) : "n"(n + 4 <= 24 ? 2 : 24 - 2 - n));
                         acc[n % 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fo[n % 4], xf[8 * j + n / 3], acc[n % 3], 0, 0, 0);
-                        if constexpr (n + 4 < 24) ffn::ds_read16<(n + 4) * 1024>(fo[n % 4], base);
+                        if constexpr (n + 4 < 24) isa::ds_read16<(n + 4) * 1024>(fo[n % 4], base);
                         else asm volatile("" : "+v"(fo[n % 4]));
                     });
                 }
@@ -4004,11 +2879,9 @@ __global__ __launch_bounds__(512) void k_cls_head(const bf16* __restrict__ h, co
 // ------------------------------------------------------------------------------------------------------------
 struct BertLayer {
     bf16 *wqkv, *wo, *w1, *w2;
-    bf16* w2p;      // W2 with the columns of every 32-block permuted to the fused FFN kernel's k-slot order
-    bf16* w1p;      // (debug builds) W1 with the same permutation of ITS columns: k_ffn3's fused out-proj prologue builds the token fragments in accumulator order
+    bf16* w2p;      // W2 with the columns of every 16-block permuted to the fused FFN kernels' k-slot order (k_permute_w2)
     bf16 *wqkv_t, *wo_t, *w1_t, *w2_t;   // k_tile_w copies for k_gemm3
     bf16* wqkv_s;                        // k_pack_qa stream for k_qa (per head: 72 fragments of 1 KiB in consumption order)
-    bf16 *w1s, *w2s;                     // k_pack_ffn3 streams for k_ffn3's VAR bit 1 (debug builds only; nullptr otherwise)
     float *bqkv, *bo, *b1, *b2, *ln1g, *ln1b, *ln2g, *ln2b;
 };
 struct rmu_bert {
@@ -4178,10 +3051,6 @@ extern "C" int rmu_bert_create(rmu_bert_t** out, const rmu_bert_cfg* cfg, const 
         rc |= copy_f32(m, &L.ln1b, wptr[wi++], H, 1.f, s);
         rc |= dev_alloc(m, &L.w1, (size_t)FF * H);
         if (!rc) conv_bf16(L.w1, wptr[wi], (size_t)FF * H, 1.f, s);
-#ifdef RMU_DEBUG_KERNELS
-        rc |= dev_alloc(m, &L.w1p, (size_t)FF * H);
-        if (!rc) hipLaunchKernelGGL(k_permute_w2, dim3((unsigned)(((size_t)FF * H + 255) / 256)), dim3(256), 0, s, (const bf16*)L.w1, L.w1p, (int64_t)FF * H);
-#endif
         wi++;
         rc |= copy_f32(m, &L.b1, wptr[wi++], FF, 1.f, s);
         rc |= dev_alloc(m, &L.w2, (size_t)H * FF);
@@ -4190,11 +3059,6 @@ extern "C" int rmu_bert_create(rmu_bert_t** out, const rmu_bert_cfg* cfg, const 
             conv_bf16(L.w2, wptr[wi], (size_t)H * FF, 1.f, s);
             hipLaunchKernelGGL(k_permute_w2, dim3((unsigned)(((size_t)H * FF + 255) / 256)), dim3(256), 0, s, (const bf16*)L.w2, L.w2p, (int64_t)H * FF);
         }
-#ifdef RMU_DEBUG_KERNELS
-        rc |= dev_alloc(m, &L.w1s, (size_t)FF * H);
-        rc |= dev_alloc(m, &L.w2s, (size_t)H * FF);
-        if (!rc) hipLaunchKernelGGL(k_pack_ffn3, dim3((unsigned)((2 * (size_t)FF * H / 8 + 255) / 256)), dim3(256), 0, s, (const bf16*)L.w1, (const bf16*)L.w2p, L.w1s, L.w2s);
-#endif
         wi++;
         rc |= copy_f32(m, &L.b2, wptr[wi++], H, 1.f, s);
         rc |= copy_f32(m, &L.ln2g, wptr[wi++], H, 1.f, s);
@@ -4326,7 +3190,8 @@ static void launch_gemm_cfg(const bf16* A, const bf16* W, const float* bias, con
 // persistent k_gemm3.  Round 4 measured the rerank shape (14 pairs, ~1.5k tokens, tools/ce_probe.py) with k_gemm_small over token blocks
 // of 32 / 64 / 128 up to 4k-64k tokens and with deeper / smaller tiled configurations (128x128 x 3-4 stages, 64x128 x 4-6): nothing beat
 // the round-3 choice (0.48-0.50 ms per call either way; every launch there is 5-15 us of latency, not of work), so the thresholds stay.
-// Debug builds keep the switches: RMU_MID_TOKENS, RMU_SMALL_TB, RMU_GEMM_CFG (+ RMU_GEMM_CFG_MAX), RMU_G3_MIN.
+// (The deeper / smaller configurations were selectable once, RMU_GEMM_CFG, and are retired.)  Debug builds keep the threshold knobs:
+// RMU_MID_TOKENS, RMU_SMALL_TB, RMU_G3_MIN.
 static int64_t mid_tokens() {
 #ifdef RMU_DEBUG_KERNELS
     const int64_t v = rmu_env("RMU_MID_TOKENS") ? atoll(rmu_env("RMU_MID_TOKENS")) : SMALL_M;
@@ -4360,56 +3225,13 @@ static void launch_gemm(const bf16* A, const bf16* W, const float* bias, const b
     // few tiles (latency-bound: every workgroup walks K alone): 128 x 128 tiles in 64-k stages halve the stage count and double
     // the workgroups -- 4k tokens 0.70 -> 0.60 ms per forward, 16k tokens 1.12 -> 1.07; big batches keep 256 x 128 / 32-k stages
     // (best of the seven tile / stage / ring combinations measured in round 2)
-#ifdef RMU_DEBUG_KERNELS
-    {   // (A/B of the mid-size shapes, measured and not adopted: RMU_GEMM_CFG = 1: 128x128 / 3 stages, 2: 128x128 / 4, 3: 64x128 / 4, 4: 64x128 / 6)
-        const int cfgv = rmu_env("RMU_GEMM_CFG") ? atoi(rmu_env("RMU_GEMM_CFG")) : 0;
-        const int64_t lim = rmu_env("RMU_GEMM_CFG_MAX") ? atoll(rmu_env("RMU_GEMM_CFG_MAX")) : 8192;
-        if (cfgv && m_cap <= lim) {
-            if (cfgv == 1) return launch_gemm_cfg<EPI, 2, 64, 3>(A, W, bias, resid, out, cu, batch, m_cap, N, K, s);
-            if (cfgv == 2) return launch_gemm_cfg<EPI, 2, 64, 4>(A, W, bias, resid, out, cu, batch, m_cap, N, K, s);
-            if (cfgv == 3) return launch_gemm_cfg<EPI, 1, 64, 4>(A, W, bias, resid, out, cu, batch, m_cap, N, K, s);
-            if (cfgv == 4) return launch_gemm_cfg<EPI, 1, 64, 6>(A, W, bias, resid, out, cu, batch, m_cap, N, K, s);
-        }
-    }
-#endif
     if (m_cap <= 32768) return launch_gemm_cfg<EPI, 2, 64, 2>(A, W, bias, resid, out, cu, batch, m_cap, N, K, s);
     return launch_gemm_cfg<EPI, 4, 32, 2>(A, W, bias, resid, out, cu, batch, m_cap, N, K, s);
 }
 
-#ifdef RMU_DEBUG_KERNELS
-// The cycle-counter / ablation instantiations (k_ffn_fused<true>, k_gemm3<*, true>: RMU_FFN_DBG, RMU_G3_DBG) exist only in a
-// build with -DRMU_DEBUG_KERNELS (python -m ragmeup_amd.build --debug-kernels): the product library carries one instantiation
+// The cycle-counter / ablation instantiations (k_ffn3<*, *, true>, k_gemm3<*, true>, k_qa<true>: RMU_FFN3_DBG, RMU_G3_DBG, RMU_QA_CLK) exist
+// only in a build with -DRMU_DEBUG_KERNELS (python -m ragmeup_amd.build --debug-kernels): the product library carries one instantiation
 // of every kernel it can actually take.
-static void launch_ffn_fused(const bf16* h1, const BertLayer& L, float eps, bf16* out, const int* cu, int batch, int64_t m_cap, hipStream_t s) {
-    const dim3 grid((unsigned)((m_cap + ffn::TOK - 1) / ffn::TOK));
-#ifdef RMU_DEBUG_KERNELS
-    static const bool want_dbg = rmu_env("RMU_FFN_DBG") != nullptr;
-    if (want_dbg) {
-        static const hipError_t attr_dbg = hipFuncSetAttribute((const void*)k_ffn_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ffn::LDS_BYTES);
-        (void)attr_dbg;
-        static unsigned long long* dbg = nullptr;
-        if (!dbg) { (void)hipMalloc((void**)&dbg, 64); (void)hipMemset(dbg, 0, 64); }
-        static const unsigned long long fl = rmu_env("RMU_FFN_FLAGS") ? strtoull(rmu_env("RMU_FFN_FLAGS"), nullptr, 10) : 0ull;
-        (void)hipMemcpyAsync(dbg + 7, &fl, 8, hipMemcpyHostToDevice, s);
-        hipLaunchKernelGGL(k_ffn_fused<true>, grid, dim3(256), ffn::LDS_BYTES, s, h1, L.w1, L.b1, L.w2p, L.b2, L.ln2g, L.ln2b, eps, out, cu, batch, dbg);
-        unsigned long long h[5];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, dbg, 40, hipMemcpyDeviceToHost);
-        (void)hipMemset(dbg, 0, 64);
-        fprintf(stderr, "[ffn dbg] waves=%llu  cycles/wave: total=%.0f  wait(slab+barrier)=%.0f (%.1f%%)  gemm1=%.0f (per slab %.0f)  gemm2+gelu=%.0f (per slab %.0f)\n",
-                h[2], (double)h[1] / (double)h[2], (double)h[0] / (double)h[2], 100.0 * (double)h[0] / (double)h[1], (double)h[3] / (double)h[2],
-                (double)h[3] / (double)h[2] / 72.0, (double)h[4] / (double)h[2], (double)h[4] / (double)h[2] / 48.0);
-        return;
-    }
-#endif
-    static const hipError_t attr_rc = hipFuncSetAttribute((const void*)k_ffn_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ffn::LDS_BYTES);
-    (void)attr_rc;
-    hipLaunchKernelGGL(k_ffn_fused<false>, grid, dim3(256), ffn::LDS_BYTES, s, h1, L.w1, L.b1, L.w2p, L.b2, L.ln2g, L.ln2b, eps, out, cu, batch,
-                       (unsigned long long*)nullptr);
-}
-
-#endif
-
 template <bool LN_IN, int GV, int PF>
 static void launch_ffn2_t(const bf16* x, const BertLayer& L, float eps, bf16* out, const int* cu, int batch, int64_t m_cap, hipStream_t s) {
     static const hipError_t attr_rc = hipFuncSetAttribute((const void*)k_ffn2<LN_IN, GV, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, ffn2::LDS_BYTES);
@@ -4427,64 +3249,31 @@ static void launch_ffn2(const bf16* x, bool ln_in, const BertLayer& L, float eps
     else { if (gv) launch_ffn2_t<false, 1, 4>(x, L, eps, out, cu, batch, m_cap, s); else launch_ffn2_t<false, 0, 4>(x, L, eps, out, cu, batch, m_cap, s); }
 }
 
-template <bool LN_IN, int PF, int VAR>
+template <bool LN_IN, int PF>
 static void launch_ffn3_t(const bf16* x, const BertLayer& L, float eps, bf16* out, const int* cu, int batch, int64_t m_cap, hipStream_t s, bool out_tiled) {
     const dim3 grid((unsigned)((m_cap + ffn3::TOK - 1) / ffn3::TOK));
-    const bf16* w1 = (VAR & 2) ? L.w1s : L.w1;
-    const bf16* w2 = (VAR & 2) ? L.w2s : L.w2p;
 #ifdef RMU_DEBUG_KERNELS
     static const int dflags = rmu_env("RMU_FFN3_DBG") ? atoi(rmu_env("RMU_FFN3_DBG")) : 0;
     if (dflags) {
-        static const hipError_t attr_d = hipFuncSetAttribute((const void*)k_ffn3<LN_IN, PF, true, VAR>, hipFuncAttributeMaxDynamicSharedMemorySize, ffn3::LDS_BYTES);
+        static const hipError_t attr_d = hipFuncSetAttribute((const void*)k_ffn3<LN_IN, PF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ffn3::LDS_BYTES);
         (void)attr_d;
-        hipLaunchKernelGGL((k_ffn3<LN_IN, PF, true, VAR>), grid, dim3(512), ffn3::LDS_BYTES, s, x, w1, L.b1, w2, L.b2, L.ln2g, L.ln2b, eps, out, cu, batch,
+        hipLaunchKernelGGL((k_ffn3<LN_IN, PF, true>), grid, dim3(512), ffn3::LDS_BYTES, s, x, L.w1, L.b1, L.w2p, L.b2, L.ln2g, L.ln2b, eps, out, cu, batch,
                            L.ln1g, L.ln1b, dflags | (out_tiled ? 256 : 0));
         return;
     }
 #endif
-    static const hipError_t attr_rc = hipFuncSetAttribute((const void*)k_ffn3<LN_IN, PF, false, VAR>, hipFuncAttributeMaxDynamicSharedMemorySize, ffn3::LDS_BYTES);
+    static const hipError_t attr_rc = hipFuncSetAttribute((const void*)k_ffn3<LN_IN, PF, false>, hipFuncAttributeMaxDynamicSharedMemorySize, ffn3::LDS_BYTES);
     (void)attr_rc;
-    static const int epi_old = rmu_env("RMU_FFN3_EPI") && atoi(rmu_env("RMU_FFN3_EPI")) == 0 ? 2048 : 0;   // A/B: the round-3/4 epilogue (row-serial LayerNorm 2)
-    hipLaunchKernelGGL((k_ffn3<LN_IN, PF, false, VAR>), grid, dim3(512), ffn3::LDS_BYTES, s, x, w1, L.b1, w2, L.b2, L.ln2g, L.ln2b, eps, out, cu, batch,
-                       L.ln1g, L.ln1b, (out_tiled ? 256 : 0) | epi_old);
+    hipLaunchKernelGGL((k_ffn3<LN_IN, PF, false>), grid, dim3(512), ffn3::LDS_BYTES, s, x, L.w1, L.b1, L.w2p, L.b2, L.ln2g, L.ln2b, eps, out, cu, batch,
+                       L.ln1g, L.ln1b, out_tiled ? 256 : 0);
 }
-#ifdef RMU_DEBUG_KERNELS
-// the attention output in, the layer output out: out-proj + residual + LayerNorm 1 + FFN + LayerNorm 2 in one launch.  MEASURED (8192
-// chunks, same box): 3830 us per launch against 3314 (k_ffn3) + 569 (out-proj k_gemm) = 3883 -- the prologue's 12 barrier-separated slabs
-// of 12 MFMAs per wave run at a third of the main loop's rate and eat what the saved launch and the 2.4 GB of traffic gave: -1.4 % per
-// layer, not worth a second k_ffn3 instantiation, a third copy of W1 and 40 bytes of scratch.  Debug builds: RMU_FFN_OUTPROJ=1.
-static void launch_ffn3_outproj(const bf16* ctx, bool ctx_tiled, const bf16* resid, bool resid_tiled, const BertLayer& L, float eps, bf16* out,
-                                const int* cu, int batch, int64_t m_cap, hipStream_t s, bool out_tiled) {
-    static const hipError_t attr_rc = hipFuncSetAttribute((const void*)k_ffn3<true, 4, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ffn3::LDS_BYTES);
-    (void)attr_rc;
-    const dim3 grid((unsigned)((m_cap + ffn3::TOK - 1) / ffn3::TOK));
-    hipLaunchKernelGGL((k_ffn3<true, 4, false, 0, true>), grid, dim3(512), ffn3::LDS_BYTES, s, ctx, L.w1p, L.b1, L.w2p, L.b2, L.ln2g, L.ln2b, eps, out, cu, batch,
-                       L.ln1g, L.ln1b, (out_tiled ? 256 : 0) | (ctx_tiled ? 512 : 0) | (resid_tiled ? 1024 : 0), L.wo, L.bo, resid);
-}
-#endif
+// x = h1 (ln_in false) or the pre-LN out-proj sum y (ln_in true: LN1 happens in the kernel's prologue).  MEASURED and retired (8192 chunks,
+// same box; NOTES_r01_r05.md 4.5, profiles/r04_ab_encoder.txt, profiles/r03_ffn3_experiments.md): the look-ahead form of the slab loop, bit-identical and equal (3346.7 vs 3351.7 us per
+// launch, embed leg 34.49-34.76 vs 34.58-34.70 ms); the out-proj GEMM inside this kernel's prologue, 3830 us against 3314 + 569 for the two
+// launches (-1.4 % per layer, for a second instantiation, a third copy of W1 and 40 bytes of scratch).
 static void launch_ffn3(const bf16* x, bool ln_in, const BertLayer& L, float eps, bf16* out, const int* cu, int batch, int64_t m_cap, hipStream_t s, bool out_tiled = false) {
-#ifdef RMU_DEBUG_KERNELS
-    // A/B forms (measured, 8192 chunks, per launch: VAR 0 3227 us, 1 3404, 2 3245, 3 3370 -- the packed-f32 activation is SLOWER than
-    // hipcc's mostly scalar one although the loop shrinks from 431 to 357 instructions, and the stream form of the weights changes nothing)
-    static const int var = rmu_env("RMU_FFN3_VAR") ? atoi(rmu_env("RMU_FFN3_VAR")) : 0;
-#define RMU_FFN3_CASE(V) case V: if (ln_in) launch_ffn3_t<true, 4, V>(x, L, eps, out, cu, batch, m_cap, s, out_tiled); else launch_ffn3_t<false, 4, V>(x, L, eps, out, cu, batch, m_cap, s, out_tiled); return;
-    switch (var & 3) { RMU_FFN3_CASE(1) RMU_FFN3_CASE(2) RMU_FFN3_CASE(3) default: break; }
-#undef RMU_FFN3_CASE
-#endif
-#ifdef RMU_DEBUG_KERNELS
-    // VAR bit 2, the LOOK-AHEAD form (round 4; ffn3::wait_la): bit-identical output, and MEASURED EQUAL -- bench.py's embed leg 34.49-34.76 ms
-    // per 8192-chunk forward without it, 34.58-34.70 with it (three interleaved runs each, one box), k_ffn3 3346.7 vs 3351.7 us per launch
-    // under rocprofv3, MFMA busy 0.393 vs 0.378: the LDS round trip behind each of a chunk's five barriers is NOT what the kernel waits
-    // for (the second wave of the SIMD and the 3-slab DMA lead already cover it).  Debug builds: RMU_FFN3_LA=1.
-    static const int la = rmu_env("RMU_FFN3_LA") ? atoi(rmu_env("RMU_FFN3_LA")) : 0;
-    if (la) {
-        if (ln_in) launch_ffn3_t<true, 4, 4>(x, L, eps, out, cu, batch, m_cap, s, out_tiled);
-        else launch_ffn3_t<false, 4, 4>(x, L, eps, out, cu, batch, m_cap, s, out_tiled);
-        return;
-    }
-#endif
-    if (ln_in) launch_ffn3_t<true, 4, 0>(x, L, eps, out, cu, batch, m_cap, s, out_tiled);
-    else launch_ffn3_t<false, 4, 0>(x, L, eps, out, cu, batch, m_cap, s, out_tiled);
+    if (ln_in) launch_ffn3_t<true, 4>(x, L, eps, out, cu, batch, m_cap, s, out_tiled);
+    else launch_ffn3_t<false, 4>(x, L, eps, out, cu, batch, m_cap, s, out_tiled);
 }
 
 template <int EPI>
@@ -4564,26 +3353,6 @@ static void launch_qkv_attn_small(hipStream_t s, int batch, const bf16* A, const
     hipLaunchKernelGGL((k_qkv_attn_small<KT, LNA>), dim3((unsigned)(batch * NH)), dim3(256), C::LDS_BYTES, s, A, W, bias, cu, batch, lng, lnb, eps, stats_out, ctx);
 }
 
-#ifdef RMU_DEBUG_KERNELS
-template <int KT, int OCC>
-static void launch_attn4(int batch, const bf16* qkv, const int* cu, bf16* ctx, bool ctx_tiled, int64_t hm_stride, hipStream_t s) {
-    constexpr int lds = KT * 32 * 64 + 32 * (KT * 32 * 2 + 16);
-    static const hipError_t attr_rc = hipFuncSetAttribute((const void*)k_attn4<KT, OCC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)attr_rc;
-    static const int n_cu = [] { int dev = 0, cus = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); return cus; }();
-    const int items = (batch + 7) / 8 * 8 * NH;
-    const int grid = std::min(items, std::max(8, n_cu * OCC / 8 * 8));
-    hipLaunchKernelGGL((k_attn4<KT, OCC>), dim3((unsigned)grid), dim3(256), lds, s, qkv, cu, batch, ctx, ctx_tiled ? 1 : 0, (long)hm_stride);
-}
-template <int MAXT>
-static void launch_attn(dim3 grid, const bf16* qkv, const int* cu, bf16* ctx, hipStream_t s) {
-    constexpr int lds = MAXT * 16 * 80 + DH * (MAXT * 16 * 2 + 8);
-    static const hipError_t attr_rc = hipFuncSetAttribute((const void*)k_attention<MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)attr_rc;
-    hipLaunchKernelGGL(k_attention<MAXT>, grid, dim3(256), lds, s, qkv, cu, ctx);
-}
-#endif
-
 static int check_encode_args(rmu_bert_t* m, const void* ids, const void* lens, const void* out, int batch, int max_len, int mode, int64_t out_stride) {
     if (!m || !ids || !lens || !out) return bfail(RMU_E_INVALID, "rmu_bert_encode: null argument");
     if (batch < 1 || batch > 65535 || max_len < 1 || max_len > m->cfg.max_pos)
@@ -4625,7 +3394,6 @@ static void enqueue_forward(rmu_bert* m, const int32_t* ids, const int32_t* type
                            m->cfg.type_vocab, m->h);
     }
     const dim3 ln_grid((unsigned)((cap + 4 * LN_ROWS - 1) / (4 * LN_ROWS)));
-    const dim3 at_grid(NH, (unsigned)batch);   // k_attention: one workgroup per (head, sequence); k_attn3: one per sequence
     size_t li = 0;
     bool h_in_tiled = false;                   // m->h as this layer reads it: row-major from k_embed_ln, tiled from a k_ffn3 that was told so
     // ---- the interactive sizes (one query; the <= 14 pairs of a rerank call, ~1.5k tokens; anything up to FOLD_TOKENS): five launches per
@@ -4649,28 +3417,10 @@ static void enqueue_forward(rmu_bert* m, const int32_t* ids, const int32_t* type
         const int* cu = m->cu;
         bf16 *y1 = m->y, *y2 = m->h1;
         const BertLayer* prev = nullptr;
-        // k_gemm_mid (a wave per output tile, both operands as MFMA fragments straight from global memory, nothing shared): measured and NOT
-        // adopted -- 14 pairs / 1548 tokens: 0.58 ms per forward against 0.42 with k_gemm_small and 0.47 with the tiled kernels; per launch
-        // 8-28 us: a fragment-shaped load touches 32 cache lines for 1 KiB and the CU's address path is paid per line (debug builds: RMU_GEMM_MID=1)
-#ifdef RMU_DEBUG_KERNELS
-        static const bool mid_env = rmu_env("RMU_GEMM_MID") && atoi(rmu_env("RMU_GEMM_MID")) != 0;
-        const bool mid = cap > SMALL_M && mid_env;
-#endif
+        // MEASURED and retired (NOTES_r01_r05.md 4.5, profiles/r04_ab_interactive.txt): a GEMM with a wave per output tile, both operands as MFMA fragments straight
+        // from global memory, nothing shared -- 14 pairs / 1548 tokens: 0.58 ms per forward against 0.42 with k_gemm_small and 0.47 with the tiled
+        // kernels; per launch 8-28 us: a fragment-shaped load touches 32 cache lines for 1 KiB and the CU's address path is paid per line
         for (const BertLayer& L : m->layers) {
-#ifdef RMU_DEBUG_KERNELS
-            if (mid) {
-                if (!prev) launch_mid<EPI_BIAS, H>(s, cap, m->h, L.wqkv, L.bqkv, nullptr, m->qkv, cu, batch, 3 * H);
-                else launch_mid<EPI_BIAS, H, true>(s, cap, y2, L.wqkv, L.bqkv, nullptr, m->qkv, cu, batch, 3 * H, prev->ln2g, prev->ln2b, eps, m->st2);
-                if (max_len <= 128) launch_attn3<4>(batch, m->qkv, m->cu, m->ctx, false, 0, s);
-                else launch_attn3<8>(batch, m->qkv, m->cu, m->ctx, false, 0, s);
-                if (!prev) launch_mid<EPI_RESID, H>(s, cap, m->ctx, L.wo, L.bo, m->h, y1, cu, batch, H);
-                else launch_mid<EPI_RESID, H, false, true>(s, cap, m->ctx, L.wo, L.bo, y2, y1, cu, batch, H, nullptr, nullptr, eps, nullptr, prev->ln2g, prev->ln2b, m->st2);
-                launch_mid<EPI_GELU, H, true>(s, cap, y1, L.w1, L.b1, nullptr, m->mid, cu, batch, FF, L.ln1g, L.ln1b, eps, m->st1);
-                launch_mid<EPI_RESID, FF, false, true>(s, cap, m->mid, L.w2, L.b2, y1, y2, cu, batch, H, nullptr, nullptr, eps, nullptr, L.ln1g, L.ln1b, m->st1);
-                prev = &L;
-                continue;
-            }
-#endif
             // (round 5) up to QKV_ATTN_TOKENS tokens the QKV projection and the attention are ONE launch
             // (k_qkv_attn_small: a workgroup per (head, sequence); bit-identical to the pair below); RMU_QKV_ATTN_TOKENS=0 keeps them apart
             static const int64_t qa_tokens = rmu_env("RMU_QKV_ATTN_TOKENS") ? atoll(rmu_env("RMU_QKV_ATTN_TOKENS")) : QKV_ATTN_TOKENS;
@@ -4713,14 +3463,11 @@ static void enqueue_forward(rmu_bert* m, const int32_t* ids, const int32_t* type
         hipLaunchKernelGGL(k_qa_items, dim3(1), dim3(1024), 0, s, (const int*)m->cu, batch, m->qa_items, (int*)(m->qa_items + m->ws_batch));
     for (const BertLayer& L : m->layers) {
         ++li;
-        static const int g3_mask = rmu_env("RMU_GEMM3") ? atoi(rmu_env("RMU_GEMM3")) : 1;   // k_gemm3 for: bit 0 QKV (default: 1.22 vs 1.38 ms), bit 1 out-proj (0.67 vs 0.61), bit 2 FFN1 + FFN2 instead of k_ffn_fused (3.6 vs 3.35)
-        // The round-1/2 kernels k_attention and k_ffn_fused are instantiated in debug builds only (RMU_ATTN_V=1, RMU_FFN_V=1: the A/B
-        // numbers of DESIGN.md); the product library carries the kernels it takes by default plus k_ffn2 (RMU_FFN_V=2).
-#ifdef RMU_DEBUG_KERNELS
-        static const int attn_v = rmu_env("RMU_ATTN_V") ? atoi(rmu_env("RMU_ATTN_V")) : 3;
-#else
+        static const int g3_mask = rmu_env("RMU_GEMM3") ? atoi(rmu_env("RMU_GEMM3")) : 1;   // k_gemm3 for: bit 0 QKV (default: 1.22 vs 1.38 ms), bit 1 out-proj (0.67 vs 0.61), bit 2 FFN1 + FFN2 instead of a fused FFN kernel (3.6 vs 3.35)
+        // The round-1/2 kernels (RMU_ATTN_V=1, RMU_FFN_V=1) are retired, their A/B numbers are in NOTES_r01_r05.md 4.3; the library carries the kernels
+        // it takes by default plus k_ffn2 (RMU_FFN_V=2).  attn_v names the one attention form left (k_attn3 / k_qa);
+        // the `attn_v == 3` terms below stay spelled out because tests/test_encoder_regimes_cpu.py reads these lines.
         constexpr int attn_v = 3;
-#endif
         // QKV head-major when k_gemm3 writes it and k_attn3 reads it (RMU_QKV_HM=0: row-major); the stride between (part, head) planes is the
         // workspace's token capacity
         static const bool hm_env = !(rmu_env("RMU_QKV_HM") && atoi(rmu_env("RMU_QKV_HM")) == 0);
@@ -4731,23 +3478,11 @@ static void enqueue_forward(rmu_bert* m, const int32_t* ids, const int32_t* type
         // big batches: k_attn3 writes ctx as the 1-KiB operand blocks the out-proj GEMM's LDS-DMA reads whole (RMU_CTX_TILED=0: row-major)
         static const bool tiled_env = !(rmu_env("RMU_CTX_TILED") && atoi(rmu_env("RMU_CTX_TILED")) == 0);
         const bool ctx_tiled = tiled_env && attn_v == 3 && !(g3_mask & 2) && cap > 32768;
-#ifdef RMU_DEBUG_KERNELS
-        // k_attn4, the PERSISTENT form (round 4): measured SLOWER in every variant -- 8192 chunks, per layer under rocprofv3: k_attn3 837-851 us;
-        // k_attn4 with the next item's pieces prefetched into registers 1372-1384 us (2 workgroups per CU), with an L2 touch of the next item
-        // and k_attn3's occupancy 1244 us; bench.py's embed leg 33.8-34.0 ms vs 35.7-36.2.  The hardware dispatcher already overlaps one
-        // workgroup's cold start with three others' arithmetic AND balances the 16..256-token items dynamically; a static item list
-        // loses both.  Debug builds: RMU_ATTN4=1, RMU_ATTN4_OCC=2|3|4.
-        static const int attn4 = rmu_env("RMU_ATTN4") ? atoi(rmu_env("RMU_ATTN4")) : 0;
-        if (attn_v == 3 && attn4 && batch * NH > 4096 && max_len <= 256) {
-            static const int occ = rmu_env("RMU_ATTN4_OCC") ? atoi(rmu_env("RMU_ATTN4_OCC")) : 3;
-            if (max_len <= 128) {
-                if (occ == 2) launch_attn4<4, 2>(batch, m->qkv, m->cu, m->ctx, ctx_tiled, hm_stride, s);
-                else if (occ == 4) launch_attn4<4, 4>(batch, m->qkv, m->cu, m->ctx, ctx_tiled, hm_stride, s);
-                else launch_attn4<4, 3>(batch, m->qkv, m->cu, m->ctx, ctx_tiled, hm_stride, s);
-            } else if (occ == 4) launch_attn4<8, 4>(batch, m->qkv, m->cu, m->ctx, ctx_tiled, hm_stride, s);
-            else launch_attn4<8, 2>(batch, m->qkv, m->cu, m->ctx, ctx_tiled, hm_stride, s);
-        } else
-#endif
+        // MEASURED and retired (NOTES_r01_r05.md 4.5, profiles/r04_ab_encoder.txt): k_attn3 made PERSISTENT, a workgroup walking a static list of (sequence, head)
+        // items with the next item's pieces prefetched -- SLOWER in every variant: 8192 chunks, per layer under rocprofv3 k_attn3 837-851 us,
+        // the persistent form 1372-1384 us (2 workgroups per CU), 1244 us with an L2 touch of the next item and k_attn3's occupancy; bench.py's
+        // embed leg 33.8-34.0 ms vs 35.7-36.2.  The hardware dispatcher already overlaps one workgroup's cold start with three others'
+        // arithmetic AND balances the 16..256-token items dynamically; a static item list loses both.
         if (qa_on && attn_v == 3) {
             launch_qa(batch, m->h, h_in_tiled, L.wqkv_s, L.bqkv, m->cu, m->qa_items, m->ws_batch, m->ctx, ctx_tiled, s);
         } else if (attn_v == 3) {
@@ -4755,26 +3490,6 @@ static void enqueue_forward(rmu_bert* m, const int32_t* ids, const int32_t* type
             else if (max_len <= 256) launch_attn3<8>(batch, m->qkv, m->cu, m->ctx, ctx_tiled, hm_stride, s);
             else launch_attn3<16>(batch, m->qkv, m->cu, m->ctx, ctx_tiled, hm_stride, s);
         }
-#ifdef RMU_DEBUG_KERNELS
-        else if (max_len <= 128) launch_attn<8>(at_grid, m->qkv, m->cu, m->ctx, s);
-        else if (max_len <= 256) launch_attn<16>(at_grid, m->qkv, m->cu, m->ctx, s);
-        else launch_attn<32>(at_grid, m->qkv, m->cu, m->ctx, s);
-#endif
-#ifdef RMU_DEBUG_KERNELS
-        // RMU_FFN_OUTPROJ=1: the out-proj GEMM runs inside k_ffn3's prologue (no launch, no pre-LN sum in memory)
-        static const bool op_env = rmu_env("RMU_FFN_OUTPROJ") && atoi(rmu_env("RMU_FFN_OUTPROJ")) != 0;
-        static const int fused_env0 = rmu_env("RMU_FUSED_FFN") ? atoi(rmu_env("RMU_FUSED_FFN")) : -1;
-        static const bool lnin0 = !(rmu_env("RMU_FFN_LNIN") && atoi(rmu_env("RMU_FFN_LNIN")) == 0);
-        static const bool v3 = !(rmu_env("RMU_FFN_V") && atoi(rmu_env("RMU_FFN_V")) != 3);
-        if (op_env && v3 && lnin0 && !(g3_mask & 6) && attn_v == 3 && (fused_env0 < 0 ? cap > 16384 : fused_env0 != 0)) {
-            static const bool h_env0 = !(rmu_env("RMU_H_TILED") && atoi(rmu_env("RMU_H_TILED")) == 0);
-            const bool h_out_tiled = h_env0 && ctx_tiled && (g3_mask & 1) && li < m->layers.size();
-            launch_ffn3_outproj(m->ctx, ctx_tiled, m->h, h_in_tiled, L, eps, m->h1, m->cu, batch, cap, s, h_out_tiled);
-            std::swap(m->h, m->h1);                // the kernel reads the residual h while other workgroups write the layer output: two buffers
-            h_in_tiled = h_out_tiled;
-            continue;
-        }
-#endif
         if (g3_mask & 2) launch_gemm3<EPI_RESID>(m->ctx, L.wo_t, L.bo, m->h, m->y, m->cu, batch, H, H, s);
         else if (ctx_tiled) launch_gemm_cfg<EPI_RESID, 4, 32, 2, true>(m->ctx, L.wo_t, L.bo, m->h, m->y, m->cu, batch, cap, H, H, s, h_in_tiled);
         else launch_gemm<EPI_RESID>(m->ctx, L.wo, L.bo, m->h, m->y, m->cu, batch, cap, H, H, s);
@@ -4785,13 +3500,8 @@ static void enqueue_forward(rmu_bert* m, const int32_t* ids, const int32_t* type
         static const int fused_env = rmu_env("RMU_FUSED_FFN") ? atoi(rmu_env("RMU_FUSED_FFN")) : -1;
         const bool fused_ffn = !(g3_mask & 4) && (fused_env < 0 ? cap > 16384 : fused_env != 0);
         // k_ffn3 (default; two waves per SIMD) and k_ffn2 (RMU_FFN_V=2; one) also take LayerNorm 1 into their prologue: the out-proj sum y
-        // goes straight in (RMU_FFN_LNIN=0: separate k_layernorm launch; RMU_FFN_V=1: the round-2 kernel k_ffn_fused -- both kept
-        // this round for the A/B numbers in DESIGN.md)
-#ifdef RMU_DEBUG_KERNELS
-        static const int ffn_v = rmu_env("RMU_FFN_V") ? atoi(rmu_env("RMU_FFN_V")) : 3;
-#else
+        // goes straight in (RMU_FFN_LNIN=0: separate k_layernorm launch)
         static const int ffn_v = rmu_env("RMU_FFN_V") && atoi(rmu_env("RMU_FFN_V")) == 2 ? 2 : 3;
-#endif
         static const bool ln_in = !(rmu_env("RMU_FFN_LNIN") && atoi(rmu_env("RMU_FFN_LNIN")) == 0);
         if (fused_ffn && ffn_v >= 2 && ln_in) {
             // Between layers h travels TILED (1-KiB blocks of 16 tokens x 32 features: the next QKV GEMM's A pieces and the next out-proj's
@@ -4814,9 +3524,6 @@ static void enqueue_forward(rmu_bert* m, const int32_t* ids, const int32_t* type
         if (fused_ffn) {          // FFN1 + GELU + FFN2 + residual + LayerNorm in one kernel: the 1536-wide intermediate stays on chip
             if (ffn_v == 3) launch_ffn3(m->h1, false, L, eps, m->h, m->cu, batch, cap, s);
             else if (ffn_v == 2) launch_ffn2(m->h1, false, L, eps, m->h, m->cu, batch, cap, s);
-#ifdef RMU_DEBUG_KERNELS
-            else launch_ffn_fused(m->h1, L, eps, m->h, m->cu, batch, cap, s);
-#endif
             continue;
         }
         launch_gemm<EPI_GELU>(m->h1, L.w1, L.b1, nullptr, m->mid, m->cu, batch, cap, FF, H, s);

@@ -98,7 +98,7 @@ def test_the_library_reads_tuning_switches_only_behind_the_master_switch():
 def test_the_product_library_carries_only_the_kernels_it_takes():
     """the superseded forms of the screening kernel (scan_screen_kernel, scan_screen_lean_kernel,
     scan_screen_lean2_kernel, the K-split / 128-queries-per-wave experiments) are retired (profiles/r04_ab_screen_forms.txt, NOTES_r01_r05.md 4.5)
-    and the round-1/2 encoder kernels are instantiated in debug builds only; the product library's symbol table names scan_screen_lean3_kernel (three geometries, each in its inner-product and its
+    and the round-1/2 encoder kernels are retired; the product library's symbol table names scan_screen_lean3_kernel (three geometries, each in its inner-product and its
     L2 form -- round 5 -- and, round 6, each of those with the 128-key candidate slots of 32 < k <= 104) and nothing else of that family."""
     import re
     import shutil

@@ -352,7 +352,7 @@ def test_cross_encoder_100_pairs_tolerance_1e2(cross):
 def test_every_switchable_kernel_variant_keeps_parity(env):
     """Every kernel the PRODUCT library can be switched to is held to the same bar as the default path (the default itself --
     k_ffn3, k_attn3, k_gemm3 for QKV, tiled activations -- is what every other test of this file runs).  The round-1/2 kernels
-    k_ffn_fused / k_attention exist in debug builds only (RMU_FFN_V=1, RMU_ATTN_V=1)."""
+    k_ffn_fused / k_attention are retired (RMU_FFN_V=1, RMU_ATTN_V=1 select nothing)."""
     import json
     import os
     import subprocess

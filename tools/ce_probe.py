@@ -16,14 +16,13 @@ for n in pairs:
     ids, tt, lens = synth_tokens(n, seed=9, lmin=60, lmax=160, mean=110, std=20, pair=True)
     a = [torch.as_tensor(t).cuda() for t in (ids, lens, tt)]
     for mid in mids:
-        # "FOLD[:TB[:CFG[:G3MIN]]]": FOLD = RMU_FOLD_TOKENS (tokens up to which the LN-folded k_gemm_small forward runs; 0 = the tiled kernels);
-        # the other three are debug-build switches
+        # "FOLD[:TB[:G3MIN]]": FOLD = RMU_FOLD_TOKENS (tokens up to which the LN-folded k_gemm_small forward runs; 0 = the tiled kernels);
+        # the other two are debug-build switches
         f = mid.split(":")
         os.environ["RMU_FOLD_TOKENS"] = f[0]
         os.environ["RMU_MID_TOKENS"] = "256"
         os.environ["RMU_SMALL_TB"] = f[1] if len(f) > 1 else "128"   # (debug builds only)
-        os.environ["RMU_GEMM_CFG"] = f[2] if len(f) > 2 else "0"
-        os.environ["RMU_G3_MIN"] = f[3] if len(f) > 3 else "0"
+        os.environ["RMU_G3_MIN"] = f[2] if len(f) > 2 else "0"
         out = ce.encode_ids(a[0], a[1], a[2], mode=1)
         ms = timed(lambda: ce.encode_ids(a[0], a[1], a[2], mode=1), 100, 10)
         o = out.cpu().numpy()
