@@ -1285,6 +1285,56 @@ static std::vector<int64_t> deep_bounds(int64_t n) {
     return b;
 }
 
+// ---- what rmu_index_search and rmu_index_search_subset do alike for a block of nb queries (`who` opens the error text).  The subset
+// search promises the unfiltered search's bits: both are given the SAME prepared queries by the one function below. -----------------
+// bytes of the shared per-query thresholds of n queries: padded to whole 128-query tiles, zero = no bound yet
+static size_t gthr_bytes(int64_t n) { return (size_t)((n + 127) / 128 * 128 + 64) * sizeof(u32); }
+
+// queries -> device, padded to dpad, normalised for COSINE, augmented for L2SQ (t.qn = |q|^2 per query; dpad > dim by construction there:
+// such queries are always copied).  *qdev = the prepared queries: t.q, or qsrc itself where nothing has to change
+static int prepare_queries(const rmu_index* idx, Tls& t, const float* qsrc, int64_t nb, bool q_dev, hipStream_t s, const float** qdev, const char* who) {
+    const int dpad = idx->dpad, dim = idx->dim;
+    *qdev = qsrc;
+    const bool need_copy = !q_dev || dpad != dim || idx->metric == RMU_METRIC_COSINE;
+    if (!need_copy) return RMU_OK;
+    if (t.q.ensure((size_t)nb * dpad * sizeof(float))) return fail(RMU_E_OOM, std::string(who) + ": q workspace");
+    if (dpad != dim) HIP_TRY(hipMemsetAsync(t.q.p, 0, (size_t)nb * dpad * sizeof(float), s));
+    HIP_TRY(hipMemcpy2DAsync(t.q.p, (size_t)dpad * sizeof(float), qsrc, (size_t)dim * sizeof(float),
+                             (size_t)dim * sizeof(float), (size_t)nb,
+                             q_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    if (idx->metric == RMU_METRIC_COSINE) {
+        hipLaunchKernelGGL(k_row_norm, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, dpad, nb, 1,
+                           (float*)nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    if (idx->metric == RMU_METRIC_L2SQ) {
+        if (t.qn.ensure((size_t)nb * sizeof(float))) return fail(RMU_E_OOM, std::string(who) + ": |q|^2 workspace");
+        hipLaunchKernelGGL(k_l2_aug_queries, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, dpad, dim, nb,
+                           (float*)t.qn.p);
+        HIP_TRY(hipGetLastError());
+    }
+    *qdev = (const float*)t.q.p;
+    return RMU_OK;
+}
+
+// host outputs: the block's results are staged in this thread's device buffers (*d_s, *d_r are redirected there) ...
+static int stage_outputs(Tls& t, int64_t nb, int k, bool out_dev, float** d_s, int64_t** d_r, const char* who) {
+    if (out_dev) return RMU_OK;
+    if (t.out_s.ensure((size_t)nb * k * sizeof(float)) || t.out_r.ensure((size_t)nb * k * sizeof(int64_t)))
+        return fail(RMU_E_OOM, std::string(who) + ": output workspace");
+    *d_s = (float*)t.out_s.p;
+    *d_r = (int64_t*)t.out_r.p;
+    return RMU_OK;
+}
+// ... and copied to the caller's arrays behind the block's work
+static int copy_outputs(float* out_scores, int64_t* out_rows, int64_t q0, int64_t nb, int k, bool out_dev, const float* d_s, const int64_t* d_r,
+                        hipStream_t s) {
+    if (out_dev) return RMU_OK;
+    HIP_TRY(hipMemcpyAsync(out_scores + q0 * k, d_s, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_rows + q0 * k, d_r, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    return RMU_OK;
+}
+
 extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, int k, unsigned flags, int64_t row_base,
                                 float* out_scores, int64_t* out_rows, uint64_t hip_stream) {
     RMU_ENTRY();
@@ -1315,37 +1365,10 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
 
     for (int64_t q0 = 0; q0 < nq; q0 += kMaxQueriesPerLaunch) {
         const int64_t nb = (nq - q0) < kMaxQueriesPerLaunch ? (nq - q0) : kMaxQueriesPerLaunch;
-        // ---- queries -> device, padded to dpad, normalised for COSINE, augmented for L2SQ -----------------------------
-        const float* qsrc = q + q0 * dim;
-        const float* qdev = qsrc;
-        const bool need_copy = !q_dev || dpad != dim || idx->metric == RMU_METRIC_COSINE;
-        if (need_copy) {
-            if (t.q.ensure((size_t)nb * dpad * sizeof(float))) return fail(RMU_E_OOM, "rmu_index_search: q workspace");
-            if (dpad != dim) HIP_TRY(hipMemsetAsync(t.q.p, 0, (size_t)nb * dpad * sizeof(float), s));
-            HIP_TRY(hipMemcpy2DAsync(t.q.p, (size_t)dpad * sizeof(float), qsrc, (size_t)dim * sizeof(float),
-                                     (size_t)dim * sizeof(float), (size_t)nb,
-                                     q_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-            if (idx->metric == RMU_METRIC_COSINE) {
-                hipLaunchKernelGGL(k_row_norm, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, dpad, nb, 1,
-                                   (float*)nullptr);
-                HIP_TRY(hipGetLastError());
-            }
-            if (l2) {
-                if (t.qn.ensure((size_t)nb * sizeof(float))) return fail(RMU_E_OOM, "rmu_index_search: |q|^2 workspace");
-                hipLaunchKernelGGL(k_l2_aug_queries, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, dpad, dim, nb,
-                                   (float*)t.qn.p);
-                HIP_TRY(hipGetLastError());
-            }
-            qdev = (const float*)t.q.p;
-        }
-        float* d_s = out_scores + q0 * k;
-        int64_t* d_r = out_rows + q0 * k;
-        if (!out_dev) {
-            if (t.out_s.ensure((size_t)nb * k * sizeof(float)) || t.out_r.ensure((size_t)nb * k * sizeof(int64_t)))
-                return fail(RMU_E_OOM, "rmu_index_search: output workspace");
-            d_s = (float*)t.out_s.p;
-            d_r = (int64_t*)t.out_r.p;
-        }
+        const float* qdev;
+        if ((rc = prepare_queries(idx, t, q + q0 * dim, nb, q_dev, s, &qdev, "rmu_index_search"))) return rc;
+        float* d_s = out_scores + q0 * k; int64_t* d_r = out_rows + q0 * k;
+        if ((rc = stage_outputs(t, nb, k, out_dev, &d_s, &d_r, "rmu_index_search"))) return rc;
         static const int share = rmu_env("RMU_NO_SHARED_THR") ? 0 : 1;
         bool exact_timed = false;
         // ---- the exact fp32 fused scan + merge of `nqq` device queries.  plan first (all workspace is sized before anything
@@ -1361,8 +1384,7 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
             const int rc2 = rmu_scan_plan(L);
             if (rc2) return fail(rc2, "rmu_index_search: no scan geometry for this (dim, k)");
             need_partial = std::max(need_partial, (size_t)L->parts * nqq * kk * sizeof(u64));
-            // shared per-query thresholds: padded to whole 128-query tiles, zero = no bound yet
-            need_gthr = std::max(need_gthr, (size_t)((nqq + 127) / 128 * 128 + 64) * sizeof(u32));
+            need_gthr = std::max(need_gthr, gthr_bytes(nqq));
             return RMU_OK;
         };
         // zero_gthr_bytes: bytes of the shared thresholds to zero in front of the launch (0: an earlier launch of a mutually exclusive
@@ -1452,7 +1474,7 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
             const int nl = (int)bounds.size();
             std::vector<ScanLaunch> lv((size_t)nl);
             int slots = nl - 1;
-            size_t gthr_need = 0;
+            const size_t gthr_need = gthr_bytes(nb);
             for (int l = 0; l < nl; ++l) {
                 ScanLaunch& S = lv[(size_t)l];
                 S = ScanLaunch{};
@@ -1460,7 +1482,6 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
                 S.x = idx->x + S.row0 * dpad; S.n_rows = bounds[(size_t)l] - S.row0; S.dpad = dpad; S.q = qdev; S.nq = (int)nb; S.k = k; S.dbg = g_dbg;
                 if ((rc = rmu_scan_plan(&S))) return fail(rc, "rmu_index_search: no scan geometry for this (dim, k)");
                 slots += S.parts;
-                gthr_need = std::max(gthr_need, (size_t)((nb + 127) / 128 * 128 + 64) * sizeof(u32));
             }
             const size_t part_keys = (size_t)nb * k;
             if (t.partial.ensure((size_t)slots * part_keys * sizeof(u64)) || t.gthr.ensure(gthr_need))
@@ -1493,10 +1514,7 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
             if (t.partial.ensure(need_partial) || t.gthr.ensure(need_gthr)) return fail(RMU_E_OOM, "rmu_index_search: partial workspace");
             if ((rc = run_exact(L, d_s, d_r, nullptr, timed, need_gthr))) return rc;
         }
-        if (!out_dev) {
-            HIP_TRY(hipMemcpyAsync(out_scores + q0 * k, d_s, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_rows + q0 * k, d_r, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        }
+        if ((rc = copy_outputs(out_scores, out_rows, q0, nb, k, out_dev, d_s, d_r, s))) return rc;
         // workspace is reused by the next query block (and host outputs must land): drain per block.  With a caller stream,
         // device outputs and a single block nothing here waits: the work is merely ordered on that stream.
         const bool drained = !hip_stream || q0 + nb < nq || !out_dev;
@@ -1568,48 +1586,20 @@ extern "C" int rmu_index_search_subset(rmu_index_t* idx, const float* q, int64_t
 
     for (int64_t q0 = 0; q0 < nq; q0 += kMaxQueriesPerLaunch) {
         const int64_t nb = (nq - q0) < kMaxQueriesPerLaunch ? (nq - q0) : kMaxQueriesPerLaunch;
-        // ---- queries -> device, padded to dpad, normalised for COSINE, augmented for L2SQ (as rmu_index_search) ---------------
-        const float* qsrc = q + q0 * dim;
-        const float* qdev = qsrc;
-        const bool need_copy = !q_dev || dpad != dim || idx->metric == RMU_METRIC_COSINE;
-        if (need_copy) {
-            if (t.q.ensure((size_t)nb * dpad * sizeof(float))) return fail(RMU_E_OOM, "rmu_index_search_subset: q workspace");
-            if (dpad != dim) HIP_TRY(hipMemsetAsync(t.q.p, 0, (size_t)nb * dpad * sizeof(float), s));
-            HIP_TRY(hipMemcpy2DAsync(t.q.p, (size_t)dpad * sizeof(float), qsrc, (size_t)dim * sizeof(float),
-                                     (size_t)dim * sizeof(float), (size_t)nb,
-                                     q_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-            if (idx->metric == RMU_METRIC_COSINE) {
-                hipLaunchKernelGGL(k_row_norm, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, dpad, nb, 1,
-                                   (float*)nullptr);
-                HIP_TRY(hipGetLastError());
-            }
-            if (l2) {
-                if (t.qn.ensure((size_t)nb * sizeof(float))) return fail(RMU_E_OOM, "rmu_index_search_subset: |q|^2 workspace");
-                hipLaunchKernelGGL(k_l2_aug_queries, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, dpad, dim, nb,
-                                   (float*)t.qn.p);
-                HIP_TRY(hipGetLastError());
-            }
-            qdev = (const float*)t.q.p;
-        }
-        float* d_s = out_scores + q0 * k;
-        int64_t* d_r = out_rows + q0 * k;
-        if (!out_dev) {
-            if (t.out_s.ensure((size_t)nb * k * sizeof(float)) || t.out_r.ensure((size_t)nb * k * sizeof(int64_t)))
-                return fail(RMU_E_OOM, "rmu_index_search_subset: output workspace");
-            d_s = (float*)t.out_s.p;
-            d_r = (int64_t*)t.out_r.p;
-        }
+        const float* qdev;
+        if ((rc = prepare_queries(idx, t, q + q0 * dim, nb, q_dev, s, &qdev, "rmu_index_search_subset"))) return rc;
+        float* d_s = out_scores + q0 * k; int64_t* d_r = out_rows + q0 * k;
+        if ((rc = stage_outputs(t, nb, k, out_dev, &d_s, &d_r, "rmu_index_search_subset"))) return rc;
         int parts = 1;
         if (n_eff > 0) {
             SubsetLaunch L{};
             L.x = idx->x; L.n_rows = idx->n; L.dpad = dpad; L.ids = (const u32*)t.sub_ids.p; L.n_sub = n_eff; L.q = qdev; L.nq = (int)nb; L.k = k;
             if ((rc = rmu_subset_plan(&L))) return fail(rc, "rmu_index_search_subset: no scan geometry for this (dim, k)");
-            const size_t gthr_bytes = (size_t)((nb + 127) / 128 * 128 + 64) * sizeof(u32);
-            if (t.partial.ensure((size_t)L.parts * nb * k * sizeof(u64)) || t.gthr.ensure(gthr_bytes))
+            if (t.partial.ensure((size_t)L.parts * nb * k * sizeof(u64)) || t.gthr.ensure(gthr_bytes(nb)))
                 return fail(RMU_E_OOM, "rmu_index_search_subset: partial workspace");
             L.partial = (u64*)t.partial.p;
             L.gthr = (u32*)t.gthr.p;
-            HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_bytes, s));
+            HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_bytes(nb), s));
             rc = rmu_subset_launch(&L, s);
             if (rc) return fail(rc, std::string("rmu_index_search_subset: scan launch: ") + hipGetErrorString(hipGetLastError()));
             t.grid = L.grid; t.block = 256; t.lds = L.lds_bytes; t.passes += 1;
@@ -1623,10 +1613,7 @@ extern "C" int rmu_index_search_subset(rmu_index_t* idx, const float* q, int64_t
         if (rc) return fail(rc, "rmu_index_search_subset: merge launch");
         if (n_eff > 0 && (rc = rmu_subset_map_launch(d_r, (const u32*)t.sub_ids.p, nb * k, row_base, s)))
             return fail(rc, "rmu_index_search_subset: row id launch");
-        if (!out_dev) {
-            HIP_TRY(hipMemcpyAsync(out_scores + q0 * k, d_s, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_rows + q0 * k, d_r, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        }
+        if ((rc = copy_outputs(out_scores, out_rows, q0, nb, k, out_dev, d_s, d_r, s))) return rc;
         // as rmu_index_search: drain per block unless this is the only block of a caller stream with device outputs.  A host list was
         // copied from pageable memory the caller may reuse: that call drains as well.
         const bool drained = !hip_stream || q0 + nb < nq || !out_dev || !rows_dev;

@@ -195,6 +195,27 @@ struct ScanLaunch {
 #define RMU_KS_CAP 48     /* K' <= 40 kept candidates + 8 free slots between compactions (one key per lane in the rank: <= 64) */
 #define RMU_KS_CAP_DEEP 128   /* (round 6) 32 < k <= 104: K' <= 120 kept candidates + 8 free slots, two keys per lane in the rank */
 
+// Row chunks of a scan launch of nqt query tiles over tiles_total row tiles (every planner's: rmu_scan_plan, rmu_subset_plan,
+// rmu_screen_plan): a multiple of 8 (XCD-aware block map) that makes grid = s_chunks * nqt fill 256 CUs evenly
+inline void rmu_plan_chunks(int nqt, int64_t tiles_total, int* s_chunks, int* tiles_per_chunk) {
+    int best_s = 8;
+    double best_eff = -1.0;
+    for (int s = 8; s <= 256; s += 8) {
+        const int64_t total = (int64_t)s * nqt;
+        const double eff = (double)total / (double)(((total + 255) / 256) * 256);
+        if (eff > best_eff + 1e-9) { best_eff = eff; best_s = s; }
+        if (total >= 256 && eff > 0.999) break;
+    }
+    int s = best_s;
+    if (tiles_total < s) s = tiles_total > 0 ? (int)tiles_total : 1;
+    *tiles_per_chunk = (int)((tiles_total + s - 1) / s);
+    if (*tiles_per_chunk < 1) *tiles_per_chunk = 1;
+    // drop empty trailing chunks (keeps the multiple-of-8 property only when nothing is dropped)
+    const int64_t used = (tiles_total + *tiles_per_chunk - 1) / *tiles_per_chunk;
+    if (used > 0 && used < s) s = (int)used;
+    *s_chunks = s;
+}
+
 int rmu_scan_plan(ScanLaunch* p);                        // chooses geometry; returns 0 or RMU_E_INVALID
 int rmu_scan_launch(const ScanLaunch* p, hipStream_t s); // launches the fused scan
 int rmu_merge_final_launch(const u64* partial, int parts, int64_t nq, int k, int64_t row_base, int l2_out, const float* qnorm2,

@@ -135,18 +135,8 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 5, j = lane & 31;
-    int s_idx, qt;
-    {
-        const int b = blockIdx.x;
-        if ((a.s_chunks & 7) == 0) {
-            const int xcd = b & 7, m = b >> 3;
-            qt = m % a.nqt;
-            s_idx = (m / a.nqt) * 8 + xcd;
-        } else {
-            qt = b % a.nqt;
-            s_idx = b / a.nqt;
-        }
-    }
+    int s_idx, qt;   // row chunk, query tile
+    block_map(a.s_chunks, a.nqt, s_idx, qt);
     const int64_t tiles_total = (a.n_rows + S_RT - 1) / S_RT;
     const int64_t t0 = (int64_t)s_idx * a.tiles_per_chunk;
     int64_t t1 = t0 + a.tiles_per_chunk;
@@ -772,24 +762,9 @@ int rmu_screen_plan(ScanLaunch* p) {
     p->kv = 4;
     const int qwg = 32 * p->wq;
     p->nqt = (p->nq + qwg - 1) / qwg;
-    const int64_t tiles_total = (p->n_rows + S_RT - 1) / S_RT;
-    int best_s = 8;
-    double best_eff = -1.0;
-    for (int s = 8; s <= 256; s += 8) {
-        const int64_t total = (int64_t)s * p->nqt;
-        const double eff = (double)total / (double)(((total + 255) / 256) * 256);
-        if (eff > best_eff + 1e-9) { best_eff = eff; best_s = s; }
-        if (total >= 256 && eff > 0.999) break;
-    }
-    int s = best_s;
-    if (tiles_total < s) s = tiles_total > 0 ? (int)tiles_total : 1;
-    p->tiles_per_chunk = (int)((tiles_total + s - 1) / s);
-    if (p->tiles_per_chunk < 1) p->tiles_per_chunk = 1;
-    const int64_t used = (tiles_total + p->tiles_per_chunk - 1) / p->tiles_per_chunk;
-    if (used > 0 && used < s) s = (int)used;
-    p->s_chunks = s;
-    p->grid = s * p->nqt;
-    p->parts = s;
+    rmu_plan_chunks(p->nqt, (p->n_rows + S_RT - 1) / S_RT, &p->s_chunks, &p->tiles_per_chunk);
+    p->grid = p->s_chunks * p->nqt;
+    p->parts = p->s_chunks;
     static const int nt_env = rmu_env("RMU_NT") ? atoi(rmu_env("RMU_NT")) : 1;
     p->nt = (nt_env && p->nqt == 1) ? 1 : 0;            // one query tile: each image byte is read by one workgroup
     p->lds_bytes = p->wq == 8 ? Lean3Cfg<8>::LDS_BYTES : Lean3Cfg<4>::LDS_BYTES;   // (the DEEP forms take the same LDS)
@@ -811,12 +786,7 @@ int rmu_screen_plan(ScanLaunch* p) {
 
 template <int EXP, int NWV, int NT, int L2N, bool DEEP = false>
 static int screen_launch_lean3(const ScanLaunch* p, hipStream_t s) {
-    static const hipError_t attr_rc = hipFuncSetAttribute((const void*)scan_screen_lean3_kernel<EXP, NWV, NT, L2N, DEEP>,
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (Lean3Cfg<NWV, DEEP>::LDS_BYTES));
-    if (attr_rc != hipSuccess) return RMU_E_HIP;
-    constexpr int lds = Lean3Cfg<NWV, DEEP>::LDS_BYTES;
-    hipLaunchKernelGGL((scan_screen_lean3_kernel<EXP, NWV, NT, L2N, DEEP>), dim3(p->grid), dim3(64 * NWV), lds, s, *p);
-    return hipGetLastError() == hipSuccess ? RMU_OK : RMU_E_HIP;
+    return launch_cfg<Lean3Cfg<NWV, DEEP>, scan_screen_lean3_kernel<EXP, NWV, NT, L2N, DEEP>, 64 * NWV>(p, s);
 }
 
 int rmu_screen_launch(const ScanLaunch* p, hipStream_t s) {

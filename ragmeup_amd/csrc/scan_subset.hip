@@ -3,10 +3,11 @@
 // Replaces: the FILTERED similarity search the reference reaches through VectorStore.similarity_search(**kwargs) --
 //   Milvus col.search(expr='source == "a.pdf"') / PGVector filter={"source": "a.pdf"} (server/RAGHelper.py:497-499 with search_kwargs).
 //
-// One ascending list of row ids per call, shared by all its queries.  The work is that of scan_topk_kernel -- query fragments in
-// registers, corpus rows HBM -> LDS through a ring of K-chunks filled by LDS-DMA, v_mfma_f32_32x32x2_f32 in the SAME k order (the
-// k-permutation and the swizzled LDS image are documented at the head of scan_topk.hip), per-(wave, query) candidate slots in LDS -- so
-// every score has the bits rmu_index_search gives the same row.  What differs:
+// One ascending list of row ids per call, shared by all its queries.  Every score has the bits rmu_index_search gives the same row
+// because both kernels are built from the SAME pieces of scan_common.h: the geometry (ScanGeom) and the swizzle of the LDS image, the
+// block map, the A-fragment reads (afrag_base, afrag_read), the per-(wave, query) candidate slots in LDS (carve_slots, compact_slot) and
+// the final emit (emit_slots).  The query fragments sit in registers and the MFMA chain below issues v_mfma_f32_32x32x2_f32 in the k order
+// documented at the head of scan_topk.hip.  What is this file's own -- the tile loop:
 //   * GATHER.  The global address of a global_load_lds is per lane (only the LDS side is lane-linear), so lane f of a DMA instruction
 //     reads its 16-byte unit from row ids[tile * RT + i] instead of row tile * RT + i.  A row is contiguous (dpad * 4 bytes), so the
 //     gather still moves whole 128-byte lines; nothing is copied anywhere first and the time follows the subset, not the corpus.
@@ -28,41 +29,17 @@
 
 namespace {
 
+// RING = 3: two chunks in flight
 template <int D_, int WQ_, int CKF_, int CAP_, int NCHECK_>
-struct SCfg {
-    static constexpr int D = D_;            // padded row length (floats)
-    static constexpr int WQ = WQ_;          // query groups per workgroup
-    static constexpr int RP = 4 / WQ_;      // row parts per tile
-    static constexpr int RT = 32 * RP;      // rows per tile
-    static constexpr int CKF = CKF_;        // floats per K-chunk
-    static constexpr int U16 = CKF_ / 4;    // 16-byte units per row-chunk
-    static constexpr int NCH = D_ / CKF_;   // chunks per tile
-    static constexpr int TS = CKF_ / 8;     // ds_read_b128 steps per chunk
-    static constexpr int RING = 3;          // two chunks in flight
-    static constexpr int SLOT_BYTES = RT * CKF_ * 4;
-    static constexpr int NI = RT * U16 / 256;  // DMA wave-instructions per wave per chunk
-    static constexpr int IDN = (RT + 63) / 64; // 4-byte DMA wave-instructions per wave per tile (row ids)
-    static constexpr int CAP = CAP_;
-    static constexpr int NPL = (CAP_ + 63) / 64;
-    static constexpr int NCHECK = NCHECK_;
-    static constexpr int A = 32 / NCHECK_;  // max appends per slot between overflow checks
-    static constexpr int SWB = (U16 % 16 == 8) ? 8 : 4;  // swizzle block (units)
-    static constexpr int RING_BYTES = RING * SLOT_BYTES;
-    static constexpr int CAND_BYTES = 4 * 32 * CAP_ * 8;
-    static constexpr int CNT_OFF = RING_BYTES + CAND_BYTES;
-    static constexpr int THR_OFF = CNT_OFF + 4 * 32 * 4;
-    static constexpr int TRASH_OFF = THR_OFF + 4 * 32 * 4;   // one private 8-B trash slot per lane
-    static constexpr int IDS_OFF = TRASH_OFF + 256 * 8;      // per-wave landing zone of a tile's row ids (128 u32)
+struct SCfg : ScanGeom<D_, WQ_, CKF_, 3, CAP_, NCHECK_> {
+    using G = ScanGeom<D_, WQ_, CKF_, 3, CAP_, NCHECK_>;
+    static constexpr int IDN = (G::RT + 63) / 64;            // 4-byte DMA wave-instructions per wave per tile (row ids)
+    static constexpr int IDS_OFF = G::TAIL_OFF;              // per-wave landing zone of a tile's row ids (128 u32)
     static constexpr int LDS_BYTES = IDS_OFF + 4 * 512;
-    static_assert(D_ % CKF_ == 0 && CKF_ % 8 == 0, "chunking");
-    static_assert((RT * U16) % 256 == 0, "DMA split");
-    static_assert(U16 % 16 == 8 || U16 % 16 == 4 || U16 % 16 == 12, "swizzle classes");
-    static_assert(NCH >= 3, "the row ids of a tile are requested three steps and read two steps before its first chunk is computed");
+    static_assert(G::NCH >= 3, "the row ids of a tile are requested three steps and read two steps before its first chunk is computed");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-    static_assert(NI + IDN <= 63, "vmcnt field");
+    static_assert(G::NI + IDN <= 63, "vmcnt field");
 };
-
-__device__ __forceinline__ int swz(int row, int swb) { return swb == 8 ? ((row >> 1) & 7) : ((row >> 2) & 3); }
 
 extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -75,19 +52,8 @@ __global__ __launch_bounds__(256) void scan_subset_kernel(const SubsetLaunch a) 
     const int h = lane >> 5;
     const int j = lane & 31;
 
-    // ---- block -> (list chunk, query tile), as scan_topk_kernel ------------------------------------
-    int s_idx, qt;
-    {
-        const int b = blockIdx.x;
-        if ((a.s_chunks & 7) == 0) {
-            const int xcd = b & 7, m = b >> 3;
-            qt = m % a.nqt;
-            s_idx = (m / a.nqt) * 8 + xcd;
-        } else {
-            qt = b % a.nqt;
-            s_idx = b / a.nqt;
-        }
-    }
+    int s_idx, qt;   // list chunk, query tile
+    block_map(a.s_chunks, a.nqt, s_idx, qt);
     const int64_t tiles_total = (a.n_sub + C::RT - 1) / C::RT;
     const int64_t t0 = (int64_t)s_idx * a.tiles_per_chunk;
     int64_t t1 = t0 + a.tiles_per_chunk;
@@ -95,21 +61,19 @@ __global__ __launch_bounds__(256) void scan_subset_kernel(const SubsetLaunch a) 
     const int ntiles = (int)(t1 > t0 ? t1 - t0 : 0);
 
     char* ring = smem;
-    u64* cand_w = (u64*)(smem + C::RING_BYTES) + (size_t)w * 32 * C::CAP;
-    u32* cnt_w = (u32*)(smem + C::CNT_OFF) + w * 32;
-    float* thr_w = (float*)(smem + C::THR_OFF) + w * 32;
     const u32* ids_w = (const u32*)(smem + C::IDS_OFF + w * 512);
 
-    const int q_idx = (qt * C::WQ + g) * 32 + j;
+    const int q_base = (qt * C::WQ + g) * 32, q_idx = q_base + j;
     const bool q_ok = q_idx < a.nq;
-    if (lane < 32) {
-        cnt_w[lane] = 0;
-        thr_w[lane] = q_ok ? -INFINITY : INFINITY;
-    }
+    u64* cand_w;
+    u32* cnt_w;
+    float* thr_w;
+    carve_slots<C>(smem, w, lane, q_ok, cand_w, cnt_w, thr_w);
     float thr = q_ok ? -INFINITY : INFINITY;
-    u32* gthr_w = a.gthr + (qt * C::WQ + g) * 32;
+    u32* gthr_w = a.gthr + q_base;
 
-    // ---- query fragments -> registers (padded query columns read row 0: their threshold is +inf) ---
+    // ---- query fragments -> registers, as scan_topk_kernel (padded query columns read row 0: their threshold is +inf).  One copy per
+    // kernel: see the head of scan_common.h -------------------------------------------------------------------------------------------
     f32x4 qf[C::D / 8];
     {
         const float* qrow = a.q + (size_t)(q_ok ? q_idx : 0) * C::D + 4 * h;
@@ -147,25 +111,18 @@ __global__ __launch_bounds__(256) void scan_subset_kernel(const SubsetLaunch a) 
                                              (__attribute__((address_space(3))) void*)(dst + (n * 4 + w) * 1024), 16, 0, 0);
     };
 
-    // A-fragment read offsets: row (32*rp + j), unit (2t+h) ^ swz
     const int rowi = 32 * rp + j;
     int abase[C::SWB / 2];
 #pragma unroll
-    for (int m = 0; m < C::SWB / 2; ++m)
-        abase[m] = (rowi * C::U16 + ((2 * m + h) ^ swz(rowi, C::SWB))) * 16;
-    auto read_frag = [&](int slot_off, int t) -> f32x4 {
-        const int off = abase[t % (C::SWB / 2)] + (t / (C::SWB / 2)) * (C::SWB * 16);
-        return *(const f32x4*)(ring + slot_off + off);
-    };
+    for (int m = 0; m < C::SWB / 2; ++m) abase[m] = afrag_base<C>(rowi, h, m);
+    auto read_frag = [&](int slot_off, int t) -> f32x4 { return afrag_read<C>(ring, abase, slot_off, t); };
 
     const u32 cnt_addr = lds_addr(cnt_w + j);
     const u32 cand_addr = lds_addr(cand_w + j * C::CAP);
     const u32 trash_addr = lds_addr(smem + C::TRASH_OFF) + threadIdx.x * 8u;
 
     auto check_compact = [&]() {
-        const u32 c = cnt_w[j];
-        const u64 bal = __ballot(c > (u32)(C::CAP - C::A));
-        u32 mask = (u32)bal | (u32)(bal >> 32);
+        u32 mask = full_slots<C>(cnt_w, j);
         if (mask) {
             while (mask) {
                 const int jj = __builtin_ctz(mask);
@@ -187,8 +144,7 @@ __global__ __launch_bounds__(256) void scan_subset_kernel(const SubsetLaunch a) 
             if (r < r0 || r >= r1) continue;
             const u64 key = rmu_make_key(acc[r] + 0.0f, pos0 + (u32)((r & 3) + 8 * (r >> 2)));
             const bool pass = (pmask >> r) & 1u;
-            lds_store_b64_nofence(pass ? wr_addr : trash_addr, key);   // every lane stores, the non-passing ones into their trash slot
-            wr_addr += pass ? 8u : 0u;
+            append_key(pass, wr_addr, trash_addr, key);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         check_compact();
@@ -262,31 +218,7 @@ __global__ __launch_bounds__(256) void scan_subset_kernel(const SubsetLaunch a) 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
 
-    // ---- final: sort every slot, emit k keys per (part, query) ---------------------------------------
-    const int part = s_idx * C::RP + rp;
-    for (int jj = 0; jj < 32; ++jj) {
-        const int qq = (qt * C::WQ + g) * 32 + jj;
-        if (qq >= a.nq) break;
-        const u32 n = cnt_w[jj];
-        u64 key[C::NPL];
-        u32 rank[C::NPL];
-#pragma unroll
-        for (int p = 0; p < C::NPL; ++p) {
-            const u32 e = lane + 64 * p;
-            key[p] = (e < n) ? cand_w[jj * C::CAP + e] : 0ull;
-        }
-        rank_keys<C::NPL>(key, n, rank);
-        u64* dst = a.partial + ((size_t)part * a.nq + qq) * a.k;
-#pragma unroll
-        for (int p = 0; p < C::NPL; ++p) {
-            const u32 e = lane + 64 * p;
-            if (e < n) {
-                if (rank[p] < (u32)a.k) dst[rank[p]] = key[p];
-            } else if (e < (u32)a.k) {
-                dst[e] = 0ull;   // fewer than k candidates: pad (e >= n are exactly the unfilled ranks)
-            }
-        }
-    }
+    emit_slots<C>(cand_w, cnt_w, a.partial, s_idx * C::RP + rp, q_base, a.nq, a.nq, a.k, lane);
 }
 
 // int64 list -> u32 ids, absent = 0xFFFFFFFF (outside [0, n_rows), or the padding past n_sub)
@@ -309,37 +241,20 @@ __global__ void k_subset_map(int64_t* __restrict__ out_rows, const u32* __restri
     out_rows[i] = p >= 0 ? (int64_t)ids[p] + row_base : -1;
 }
 
-template <class C>
-int launch_cfg(const SubsetLaunch* p, hipStream_t s) {
-    static const hipError_t attr_rc =
-        hipFuncSetAttribute((const void*)scan_subset_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    if (attr_rc != hipSuccess) return RMU_E_HIP;
-    hipLaunchKernelGGL(scan_subset_kernel<C>, dim3(p->grid), dim3(256), C::LDS_BYTES, s, *p);
-    return hipGetLastError() == hipSuccess ? RMU_OK : RMU_E_HIP;
-}
-
 // geometry table: (WQ) x (k class).  kv 0: k <= 32 (CAP 64, one check per tile); kv 1: k <= 112 (CAP 128, two).
 //                                     D   WQ  CKF      CAP NCHECK
 template <int D> using S_w1_k0 = SCfg<D, 1, 48, 64, 1>;                   // 72 KiB ring (48 KiB in flight) + 64 KiB candidates
 template <int D> using S_w4_k0 = SCfg<D, 4, D == 192 ? 32 : 96, 64, 1>;   // 36 KiB ring (192-wide rows: 12 KiB, six chunks per tile)
 template <int D> using S_w4_k1 = SCfg<D, 4, 32, 128, 2>;                  // 12 KiB ring + 128 KiB candidates
 
-template <int D>
-int launch_d(const SubsetLaunch* p, hipStream_t s) {
-    switch (p->wq * 2 + p->kv) {
-        case 2: return launch_cfg<S_w1_k0<D>>(p, s);
-        case 8: return launch_cfg<S_w4_k0<D>>(p, s);
-        case 9: return launch_cfg<S_w4_k1<D>>(p, s);
-        default: return RMU_E_INVALID;
-    }
-}
-template <int D>
-int lds_d(int wq, int kv) {
+// (wq, kv) of width D -> f(configuration)
+template <int D, class F>
+int with_cfg(int wq, int kv, F&& f) {
     switch (wq * 2 + kv) {
-        case 2: return S_w1_k0<D>::LDS_BYTES;
-        case 8: return S_w4_k0<D>::LDS_BYTES;
-        case 9: return S_w4_k1<D>::LDS_BYTES;
-        default: return -1;
+        case 2: return f(S_w1_k0<D>{});
+        case 8: return f(S_w4_k0<D>{});
+        case 9: return f(S_w4_k1<D>{});
+        default: return RMU_E_INVALID;
     }
 }
 
@@ -355,36 +270,18 @@ int rmu_subset_plan(SubsetLaunch* p) {
     p->wq = (p->nq <= 32 && p->kv == 0) ? 1 : 4;
     const int rt = 32 * (4 / p->wq);
     p->nqt = (p->nq + 32 * p->wq - 1) / (32 * p->wq);
-    const int64_t tiles_total = (p->n_sub + rt - 1) / rt;
-    // list chunks: a multiple of 8 (XCD-aware block map) that makes grid = S*nqt fill 256 CUs evenly (as rmu_scan_plan)
-    int best_s = 8;
-    double best_eff = -1.0;
-    for (int s = 8; s <= 256; s += 8) {
-        const int64_t total = (int64_t)s * p->nqt;
-        const double eff = (double)total / (double)(((total + 255) / 256) * 256);
-        if (eff > best_eff + 1e-9) { best_eff = eff; best_s = s; }
-        if (total >= 256 && eff > 0.999) break;
-    }
-    int s = best_s;
-    if (tiles_total < s) s = tiles_total > 0 ? (int)tiles_total : 1;
-    p->tiles_per_chunk = (int)((tiles_total + s - 1) / s);
-    if (p->tiles_per_chunk < 1) p->tiles_per_chunk = 1;
-    const int64_t used = (tiles_total + p->tiles_per_chunk - 1) / p->tiles_per_chunk;
-    if (used > 0 && used < s) s = (int)used;
-    p->s_chunks = s;
-    p->grid = s * p->nqt;
-    p->parts = s * (4 / p->wq);
-    p->lds_bytes = p->dpad == 384 ? lds_d<384>(p->wq, p->kv) : p->dpad == 768 ? lds_d<768>(p->wq, p->kv) : lds_d<192>(p->wq, p->kv);
+    // list chunks as the corpus chunks of rmu_scan_plan
+    rmu_plan_chunks(p->nqt, (p->n_sub + rt - 1) / rt, &p->s_chunks, &p->tiles_per_chunk);
+    p->grid = p->s_chunks * p->nqt;
+    p->parts = p->s_chunks * (4 / p->wq);
+    p->lds_bytes = for_dpad(p->dpad, [&](auto d) { return with_cfg<decltype(d)::value>(p->wq, p->kv, [](auto c) { return (int)decltype(c)::LDS_BYTES; }); });
     return p->lds_bytes > 0 ? RMU_OK : RMU_E_INVALID;
 }
 
 int rmu_subset_launch(const SubsetLaunch* p, hipStream_t s) {
-    switch (p->dpad) {
-        case 384: return launch_d<384>(p, s);
-        case 768: return launch_d<768>(p, s);
-        case 192: return launch_d<192>(p, s);
-        default: return RMU_E_INVALID;
-    }
+    return for_dpad(p->dpad, [&](auto d) {
+        return with_cfg<decltype(d)::value>(p->wq, p->kv, [&](auto c) { return launch_cfg<decltype(c), scan_subset_kernel<decltype(c)>>(p, s); });
+    });
 }
 
 int rmu_subset_narrow_launch(const int64_t* rows, int64_t n_sub, int64_t n_rows, u32* ids, hipStream_t s) {

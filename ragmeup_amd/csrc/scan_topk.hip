@@ -35,39 +35,16 @@
 namespace {
 
 template <int D_, int WQ_, int CKF_, int RING_, int CAP_, int NCHECK_, int EXP_ = 0, int LA_ = 1, int NT_ = 0>
-struct Cfg {
+struct Cfg : ScanGeom<D_, WQ_, CKF_, RING_, CAP_, NCHECK_> {
+    using G = ScanGeom<D_, WQ_, CKF_, RING_, CAP_, NCHECK_>;
     static constexpr bool NT = NT_ != 0;       // LDS-DMA cache policy of the corpus stream: nt (aux = 2) for read-once data
     static constexpr bool LA_ON = LA_ != 0;    // one-chunk look-ahead (costs one ring slot of in-flight data)
     static constexpr int EXP = EXP_;        // 0 = product; 1..3 = timing ablations (wrong results)
-    static constexpr int D = D_;            // padded row length (floats)
-    static constexpr int WQ = WQ_;          // query groups per workgroup
-    static constexpr int RP = 4 / WQ_;      // row parts per tile
-    static constexpr int RT = 32 * RP;      // rows per tile
-    static constexpr int CKF = CKF_;        // floats per K-chunk
-    static constexpr int U16 = CKF_ / 4;    // 16-byte units per row-chunk
-    static constexpr int NCH = D_ / CKF_;   // chunks per tile
-    static constexpr int TS = CKF_ / 8;     // ds_read_b128 steps per chunk
-    static constexpr int RING = RING_;
-    static constexpr int SLOT_BYTES = RT * CKF_ * 4;
-    static constexpr int NI = RT * U16 / 256;  // DMA wave-instructions per wave per chunk
-    static constexpr int CAP = CAP_;
-    static constexpr int NPL = (CAP_ + 63) / 64;
-    static constexpr int NCHECK = NCHECK_;
-    static constexpr int A = 32 / NCHECK_;  // max appends per slot between overflow checks
-    static constexpr int SWB = (U16 % 16 == 8) ? 8 : 4;  // swizzle block (units)
-    static constexpr int RING_BYTES = RING_ * SLOT_BYTES;
-    static constexpr int CAND_BYTES = 4 * 32 * CAP_ * 8;
-    static constexpr int TRASH_OFF = RING_BYTES + CAND_BYTES + 4 * 32 * 4 + 4 * 32 * 4;
-    static constexpr int GT_OFF = TRASH_OFF + 256 * 8;       // + one private 8-B trash slot per lane
-    static constexpr int LDS_BYTES = GT_OFF + 4 * 256;       // + per-wave landing zone of the shared thresholds
-    static_assert(D_ % CKF_ == 0 && CKF_ % 8 == 0, "chunking");
-    static_assert((RT * U16) % 256 == 0, "DMA split");
-    static_assert(U16 % 16 == 8 || U16 % 16 == 4 || U16 % 16 == 12, "swizzle classes");
+    static constexpr int GT_OFF = G::TAIL_OFF;               // per-wave landing zone of the shared thresholds
+    static constexpr int LDS_BYTES = GT_OFF + 4 * 256;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-    static_assert(NI * (RING_ - 2) <= 63 && RING_ >= 2, "vmcnt field");
+    static_assert(G::NI * (RING_ - 2) <= 63 && RING_ >= 2, "vmcnt field");
 };
-
-__device__ __forceinline__ int swz(int row, int swb) { return swb == 8 ? ((row >> 1) & 7) : ((row >> 2) & 3); }
 
 extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -87,45 +64,29 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const ScanLaunch a) {
     const int h = lane >> 5;
     const int j = lane & 31;
 
-    // ---- block -> (corpus chunk, query tile); query tiles of one chunk share an XCD's L2 ----------
-    int s_idx, qt;
-    {
-        const int b = blockIdx.x;
-        if ((a.s_chunks & 7) == 0) {
-            const int xcd = b & 7, m = b >> 3;
-            qt = m % a.nqt;
-            s_idx = (m / a.nqt) * 8 + xcd;
-        } else {
-            qt = b % a.nqt;
-            s_idx = b / a.nqt;
-        }
-    }
+    int s_idx, qt;   // corpus chunk, query tile
+    block_map(a.s_chunks, a.nqt, s_idx, qt);
     const int64_t tiles_total = (a.n_rows + C::RT - 1) / C::RT;
     const int64_t t0 = (int64_t)s_idx * a.tiles_per_chunk;
     int64_t t1 = t0 + a.tiles_per_chunk;
     if (t1 > tiles_total) t1 = tiles_total;
     const int ntiles = (int)(t1 > t0 ? t1 - t0 : 0);
 
-    // ---- LDS carve (one object: see guide "three .s-level traps" (a)) -----------------------------
     char* ring = smem;
-    u64* cand_w = (u64*)(smem + C::RING_BYTES) + (size_t)w * 32 * C::CAP;
-    u32* cnt_w = (u32*)(smem + C::RING_BYTES + C::CAND_BYTES) + w * 32;
-    float* thr_w = (float*)(smem + C::RING_BYTES + C::CAND_BYTES + 4 * 32 * 4) + w * 32;
-
-    const int q_idx = (qt * C::WQ + g) * 32 + j;
+    const int q_base = (qt * C::WQ + g) * 32, q_idx = q_base + j;
     const bool q_ok = q_idx < nq_eff;
     ((u32*)(smem + C::GT_OFF))[w * 64 + lane] = 0u;   // landing zone of the shared thresholds: 0 = no bound
-    if (lane < 32) {
-        cnt_w[lane] = 0;
-        thr_w[lane] = q_ok ? -INFINITY : INFINITY;
-    }
+    u64* cand_w;
+    u32* cnt_w;
+    float* thr_w;
+    carve_slots<C>(smem, w, lane, q_ok, cand_w, cnt_w, thr_w);
     float thr = q_ok ? -INFINITY : INFINITY;       // effective filter = max(local k-th best, shared bound)
     float thr_loc = thr, thr_g = -INFINITY;
     // shared thresholds of this wave's 32 queries (global) and their LDS landing zone
-    u32* gthr_w = a.gthr + (qt * C::WQ + g) * 32;
+    u32* gthr_w = a.gthr + q_base;
     const u32* gt_lds = (const u32*)(smem + C::GT_OFF) + w * 64;
 
-    // ---- query fragments -> registers --------------------------------------------------------------
+    // ---- query fragments -> registers (scan_subset_kernel holds the same lines: see the head of scan_common.h) ------
     f32x4 qf[C::D / 8];
     {
         // padded query columns read row 0 (valid memory): their threshold is +inf and nothing is emitted.
@@ -169,16 +130,13 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const ScanLaunch a) {
     const int rowi = 32 * rp + j;
     int abase[C::SWB / 2];
 #pragma unroll
-    for (int m = 0; m < C::SWB / 2; ++m)
-        abase[m] = (rowi * C::U16 + ((2 * m + h) ^ swz(rowi, C::SWB))) * 16;
+    for (int m = 0; m < C::SWB / 2; ++m) abase[m] = afrag_base<C>(rowi, h, m);
 
-    const u32 cnt_addr = (u32)(uintptr_t)(__attribute__((address_space(3))) char*)(char*)(cnt_w + j);
-    const u32 cand_addr = (u32)(uintptr_t)(__attribute__((address_space(3))) char*)(char*)(cand_w + j * C::CAP);
+    const u32 cnt_addr = lds_addr(cnt_w + j);
+    const u32 cand_addr = lds_addr(cand_w + j * C::CAP);
 
     auto check_compact = [&]() {
-        const u32 c = cnt_w[j];
-        const u64 bal = __ballot(c > (u32)(C::CAP - C::A));
-        u32 mask = (u32)bal | (u32)(bal >> 32);
+        u32 mask = full_slots<C>(cnt_w, j);
         if (mask) {
             const long long tc0 = (C::EXP == 7) ? clock64() : 0;
             while (mask) {
@@ -193,11 +151,7 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const ScanLaunch a) {
         }
     };
 
-    // A-fragment of step t of the chunk living in ring slot `slot_off` (bytes)
-    auto read_frag = [&](int slot_off, int t) -> f32x4 {
-        const int off = abase[t % (C::SWB / 2)] + (t / (C::SWB / 2)) * (C::SWB * 16);
-        return *(const f32x4*)(ring + slot_off + off);
-    };
+    auto read_frag = [&](int slot_off, int t) -> f32x4 { return afrag_read<C>(ring, abase, slot_off, t); };
     // LA (look-ahead): chunk cc+1 has landed when barrier cc is passed, so the first fragment of the
     // next chunk is read BEFORE its barrier and the MFMA pipe never waits on an LDS round trip.
     constexpr bool LA = C::RING >= 3 && C::LA_ON;
@@ -227,15 +181,12 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const ScanLaunch a) {
         wr_addr = cand_addr + res_pos * 8u;
     };
     auto slow_begin = [&](u32 bits) { slow_issue(bits); slow_wait(); };
-    // store prev[r]'s key at wr_addr (and advance it) in the lanes whose pass bit r is set.  No branch and
-    // no EXEC games (32 EXEC rewrites per tile stalled the MFMA stream for thousands of cycles): every
-    // lane stores, the non-passing ones into their private trash slot.
+    // store prev[r]'s key at wr_addr (and advance it) in the lanes whose pass bit r is set (append_key: every lane stores)
     const u32 trash_addr = lds_addr(smem + C::TRASH_OFF) + threadIdx.x * 8u;
     auto slow_slot_r = [&](const f32x16& prev, int r, int64_t rbase) {
         const u64 key = rmu_make_key(prev[r] + 0.0f, (u32)(a.row0 + rbase + (r & 3) + 8 * (r >> 2)));
         const bool pass = (pmask >> r) & 1u;   // r is a compile-time constant after unrolling
-        lds_store_b64_nofence(pass ? wr_addr : trash_addr, key);
-        wr_addr += pass ? 8u : 0u;
+        append_key(pass, wr_addr, trash_addr, key);
     };
     auto slow_end = [&]() {
         const long long te0 = (C::EXP == 7) ? clock64() : 0;
@@ -394,41 +345,7 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const ScanLaunch a) {
         }
     }
 
-    // ---- final: sort every slot, emit k keys per (part, query) ---------------------------------------
-    const int part = s_idx * C::RP + rp;
-    for (int jj = 0; jj < 32; ++jj) {
-        const int qq = (qt * C::WQ + g) * 32 + jj;
-        if (qq >= nq_eff) break;
-        const u32 n = cnt_w[jj];
-        u64 key[C::NPL];
-        u32 rank[C::NPL];
-#pragma unroll
-        for (int p = 0; p < C::NPL; ++p) {
-            const u32 e = lane + 64 * p;
-            key[p] = (e < n) ? cand_w[jj * C::CAP + e] : 0ull;
-        }
-        rank_keys<C::NPL>(key, n, rank);
-        u64* dst = a.partial + ((size_t)part * a.nq + qq) * a.k;
-#pragma unroll
-        for (int p = 0; p < C::NPL; ++p) {
-            const u32 e = lane + 64 * p;
-            if (e < n) {
-                if (rank[p] < (u32)a.k) dst[rank[p]] = key[p];
-            } else if (e < (u32)a.k) {
-                dst[e] = 0ull;   // fewer than k candidates: pad (e >= n are exactly the unfilled ranks)
-            }
-        }
-    }
-}
-
-template <class C>
-int launch_cfg(const ScanLaunch* p, hipStream_t s) {
-    // function-local static: initialised exactly once, thread-safe (C++11)
-    static const hipError_t attr_rc =
-        hipFuncSetAttribute((const void*)scan_topk_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    if (attr_rc != hipSuccess) return RMU_E_HIP;
-    hipLaunchKernelGGL(scan_topk_kernel<C>, dim3(p->grid), dim3(256), C::LDS_BYTES, s, *p);
-    return hipGetLastError() == hipSuccess ? RMU_OK : RMU_E_HIP;
+    emit_slots<C>(cand_w, cnt_w, a.partial, s_idx * C::RP + rp, q_base, nq_eff, a.nq, a.k, lane);
 }
 
 // geometry table: (WQ) x (k class).  kv 0: k <= 32 (CAP 64, one check per tile); kv 1: k <= 112.
@@ -442,39 +359,28 @@ template <int D> using C_w1_k0 = Cfg<D, 1, 48, 3, 64, 1, 0, 0>;   // 72 KiB ring
 template <int D> using C_w2_k0_nt = Cfg<D, 2, 96, 3, 64, 1, 0, 0, 1>;
 template <int D> using C_w1_k0_nt = Cfg<D, 1, 48, 3, 64, 1, 0, 0, 1>;
 
-template <int D>
-int launch_d(const ScanLaunch* p, hipStream_t s) {
-    switch (p->wq * 2 + p->kv) {
+// (wq, kv, nt) of width D -> f(configuration)
+template <int D, class F>
+int with_cfg(int wq, int kv, int nt, F&& f) {
+    switch (wq * 2 + kv) {
         case 8: {
 #ifdef RMU_DEBUG_KERNELS      // timing ablations / cycle counters (wrong results by design): python -m ragmeup_amd.build --debug-kernels
             static const int exp = rmu_env("RMU_SCAN_EXP") ? atoi(rmu_env("RMU_SCAN_EXP")) : 0;
-            if (D == 384 && exp == 1) return launch_cfg<Cfg<384, 4, 96, 4, 64, 1, 1>>(p, s);
-            if (D == 384 && exp == 2) return launch_cfg<Cfg<384, 4, 96, 4, 64, 1, 2>>(p, s);
-            if (D == 384 && exp == 3) return launch_cfg<Cfg<384, 4, 96, 4, 64, 1, 3>>(p, s);
-            if (D == 384 && exp == 4) return launch_cfg<Cfg<384, 4, 96, 4, 64, 1, 4>>(p, s);
-            if (D == 384 && exp == 5) return launch_cfg<Cfg<384, 4, 96, 4, 64, 1, 5>>(p, s);
-            if (D == 384 && exp == 6) return launch_cfg<Cfg<384, 4, 96, 4, 64, 1, 6>>(p, s);
-            if (D == 384 && exp == 7) return launch_cfg<Cfg<384, 4, 96, 4, 64, 1, 7>>(p, s);
+            if (D == 384 && exp == 1) return f(Cfg<384, 4, 96, 4, 64, 1, 1>{});
+            if (D == 384 && exp == 2) return f(Cfg<384, 4, 96, 4, 64, 1, 2>{});
+            if (D == 384 && exp == 3) return f(Cfg<384, 4, 96, 4, 64, 1, 3>{});
+            if (D == 384 && exp == 4) return f(Cfg<384, 4, 96, 4, 64, 1, 4>{});
+            if (D == 384 && exp == 5) return f(Cfg<384, 4, 96, 4, 64, 1, 5>{});
+            if (D == 384 && exp == 6) return f(Cfg<384, 4, 96, 4, 64, 1, 6>{});
+            if (D == 384 && exp == 7) return f(Cfg<384, 4, 96, 4, 64, 1, 7>{});
 #endif
-            return launch_cfg<C_w4_k0<D>>(p, s);
+            return f(C_w4_k0<D>{});
         }
-        case 9: return launch_cfg<C_w4_k1<D>>(p, s);
-        case 4: return p->nt ? launch_cfg<C_w2_k0_nt<D>>(p, s) : launch_cfg<C_w2_k0<D>>(p, s);
-        case 5: return launch_cfg<C_w2_k1<D>>(p, s);
-        case 2: return p->nt ? launch_cfg<C_w1_k0_nt<D>>(p, s) : launch_cfg<C_w1_k0<D>>(p, s);
+        case 9: return f(C_w4_k1<D>{});
+        case 4: return nt ? f(C_w2_k0_nt<D>{}) : f(C_w2_k0<D>{});
+        case 5: return f(C_w2_k1<D>{});
+        case 2: return nt ? f(C_w1_k0_nt<D>{}) : f(C_w1_k0<D>{});
         default: return RMU_E_INVALID;
-    }
-}
-
-template <int D>
-int lds_d(int wq, int kv) {
-    switch (wq * 2 + kv) {
-        case 8: return C_w4_k0<D>::LDS_BYTES;
-        case 9: return C_w4_k1<D>::LDS_BYTES;
-        case 4: return C_w2_k0<D>::LDS_BYTES;
-        case 5: return C_w2_k1<D>::LDS_BYTES;
-        case 2: return C_w1_k0<D>::LDS_BYTES;
-        default: return -1;
     }
 }
 
@@ -488,38 +394,17 @@ int rmu_scan_plan(ScanLaunch* p) {
     if (p->kv == 1 && p->wq == 1) p->wq = 2;   // no LDS room for a 128-row tile next to 128-deep buffers
     const int rt = 32 * (4 / p->wq);
     p->nqt = (p->nq + 32 * p->wq - 1) / (32 * p->wq);
-    const int64_t tiles_total = (p->n_rows + rt - 1) / rt;
-    // corpus chunks: a multiple of 8 (XCD-aware block map) that makes grid = S*nqt fill 256 CUs evenly
-    int best_s = 8;
-    double best_eff = -1.0;
-    for (int s = 8; s <= 256; s += 8) {
-        const int64_t total = (int64_t)s * p->nqt;
-        const double eff = (double)total / (double)(((total + 255) / 256) * 256);
-        if (eff > best_eff + 1e-9) { best_eff = eff; best_s = s; }
-        if (total >= 256 && eff > 0.999) break;
-    }
-    int s = best_s;
-    if (tiles_total < s) s = tiles_total > 0 ? (int)tiles_total : 1;
-    p->tiles_per_chunk = (int)((tiles_total + s - 1) / s);
-    if (p->tiles_per_chunk < 1) p->tiles_per_chunk = 1;
-    // drop empty trailing chunks (keeps the multiple-of-8 property only when nothing is dropped)
-    const int64_t used = (tiles_total + p->tiles_per_chunk - 1) / p->tiles_per_chunk;
-    if (used > 0 && used < s) s = (int)used;
-    p->s_chunks = s;
-    p->grid = s * p->nqt;
-    p->parts = s * (4 / p->wq);
+    rmu_plan_chunks(p->nqt, (p->n_rows + rt - 1) / rt, &p->s_chunks, &p->tiles_per_chunk);
+    p->grid = p->s_chunks * p->nqt;
+    p->parts = p->s_chunks * (4 / p->wq);
     static const int nt_env = rmu_env("RMU_NT") ? atoi(rmu_env("RMU_NT")) : 1;
     p->nt = (nt_env && p->nqt == 1 && p->kv == 0 && p->wq <= 2) ? 1 : 0;
-    p->lds_bytes = p->dpad == 384 ? lds_d<384>(p->wq, p->kv)
-                 : p->dpad == 768 ? lds_d<768>(p->wq, p->kv) : lds_d<192>(p->wq, p->kv);
+    p->lds_bytes = for_dpad(p->dpad, [&](auto d) { return with_cfg<decltype(d)::value>(p->wq, p->kv, 0, [](auto c) { return (int)decltype(c)::LDS_BYTES; }); });
     return p->lds_bytes > 0 ? RMU_OK : RMU_E_INVALID;
 }
 
 int rmu_scan_launch(const ScanLaunch* p, hipStream_t s) {
-    switch (p->dpad) {
-        case 384: return launch_d<384>(p, s);
-        case 768: return launch_d<768>(p, s);
-        case 192: return launch_d<192>(p, s);
-        default: return RMU_E_INVALID;
-    }
+    return for_dpad(p->dpad, [&](auto d) {
+        return with_cfg<decltype(d)::value>(p->wq, p->kv, p->nt, [&](auto c) { return launch_cfg<decltype(c), scan_topk_kernel<decltype(c)>>(p, s); });
+    });
 }

@@ -111,6 +111,18 @@ def test_the_product_library_carries_only_the_kernels_it_takes():
     assert screen == [f"scan_screen_lean3_kernel<0, {g}, {l2}, {deep}>" for g in ("4, 0", "4, 1", "8, 0") for l2 in (0, 1) for deep in ("false", "true")], screen
     for gone in ("k_ffn_fused", "k_attention<", "k_attn4", "k_gemm_mid"):
         assert gone not in out.stdout, gone
+    # the exact scan and its gathered form: the instantiations the library dispatches to, under the names tools/summarize_profiles.py and the
+    # committed profiles match on (Cfg<D, WQ, CKF, RING, CAP, NCHECK, EXP, LA, NT> / SCfg<D, WQ, CKF, CAP, NCHECK>)
+    topk = sorted(set(re.findall(r"scan_topk_kernel<[^>]*>", out.stdout)))
+    assert topk == [f"scan_topk_kernel<(anonymous namespace)::Cfg<{d}, {c}>" for d in (192, 384, 768) for c in TOPK_CFGS], topk
+    subset = sorted(set(re.findall(r"scan_subset_kernel<[^>]*>", out.stdout)))
+    assert subset == [f"scan_subset_kernel<(anonymous namespace)::SCfg<{d}>" for d in SUBSET_CFGS], subset
+
+
+TOPK_CFGS = ("1, 48, 3, 64, 1, 0, 0, 0", "1, 48, 3, 64, 1, 0, 0, 1", "2, 48, 2, 128, 2, 0, 1, 0", "2, 96, 3, 64, 1, 0, 0, 0",
+             "2, 96, 3, 64, 1, 0, 0, 1", "4, 96, 2, 128, 2, 0, 1, 0", "4, 96, 4, 64, 1, 0, 1, 0")      # x three widths = 21
+SUBSET_CFGS = ("192, 1, 48, 64, 1", "192, 4, 32, 128, 2", "192, 4, 32, 64, 1", "384, 1, 48, 64, 1", "384, 4, 32, 128, 2", "384, 4, 96, 64, 1",
+               "768, 1, 48, 64, 1", "768, 4, 32, 128, 2", "768, 4, 96, 64, 1")
 
 
 
