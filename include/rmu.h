@@ -41,7 +41,7 @@ extern "C" {
 #define RMU_METRIC_COSINE 1 /* rows are stored L2-normalised, queries normalised per call */
 #define RMU_METRIC_L2SQ 2   /* squared L2 distance on the stored (un-normalised) rows, smaller = better (Milvus "L2");
                              * dim <= 767 (rows carry -|x|^2 in one pad column: 384-d rows are stored 768 wide; at dim 384 the index also keeps the
-                             * fp16 screening image and one fp32 norm per row) */
+                             * fp16 screening image and one fp32 norm per row).  There is no wide (dim > 767) L2 index. */
 
 /* flags for rmu_index_search / rmu_topk_merge */
 #define RMU_F_Q_DEVICE 1u   /* query pointer is a device address */
@@ -63,8 +63,22 @@ extern "C" {
 #define RMU_OPT_COMPACT_INPLACE 5 /* 0 (default): rmu_index_compact moves the rows into fresh, smaller allocations (in place when those do not
                              * fit); 1: always in place, the capacity stays.  Results are identical either way (the tests force the path). */
 
+#define RMU_OPT_WIDE_SCAN 6 /* 0 (default) or 1.  1: an RMU_METRIC_IP / RMU_METRIC_COSINE index of ANY width sends its exact searches through
+                             * scan_wide_kernel (the kernel of rows wider than RMU_MAX_DIM, which streams the queries) instead of the
+                             * register-resident scan, and the screening path is off while it is set.  Results are identical either way, bit for
+                             * bit (the tests compare the two kernels through this switch; tools/wide_probe.py times them side by side at 768).
+                             * RMU_E_INVALID on an RMU_METRIC_L2SQ index. */
+
 #define RMU_MAX_K 112       /* largest k the fused scan keeps in LDS */
-#define RMU_MAX_DIM 768
+#define RMU_MAX_DIM 768     /* widest row of the register-resident scans */
+#define RMU_MAX_DIM_WIDE 3072 /* widest row of an index (RMU_METRIC_IP / RMU_METRIC_COSINE): rows of 769..3072 dimensions are padded to a multiple
+                             * of 64 floats and searched by the exact fp32 scan that streams its queries (scan_wide.hip).  Everything works on
+                             * such an index as on a narrow one -- add, reserve, remove_rows, compact, get_rows, mmr / search_mmr, save / load,
+                             * caller streams, RMU_OPT_* (the screening and ladder options are accepted and change nothing) -- except:
+                             *   - RMU_METRIC_L2SQ: dim <= 767 (rmu_index_create fails for a wide L2 index);
+                             *   - rmu_index_search_subset: rows of at most RMU_MAX_DIM dimensions (RMU_E_INVALID before anything is enqueued);
+                             *   - rmu_bert_search_mmr: 384-d rows (the encoder's width), as ever;
+                             *   - the fp16 screening path exists at dim 384 only. */
 
 typedef struct rmu_index rmu_index_t;
 typedef struct rmu_bert rmu_bert_t;
@@ -78,6 +92,8 @@ const char* rmu_last_error(void);
 const char* rmu_version(void);
 
 /* ---- HBM-resident flat index ------------------------------------------------------------------
+ * dim in [1, RMU_MAX_DIM_WIDE] for RMU_METRIC_IP / RMU_METRIC_COSINE, [1, 767] for RMU_METRIC_L2SQ.  Rows are stored zero-padded to 192 / 384 /
+ * 768 floats, wider ones to the next multiple of 64.
  * Serves: RAGHelper.py:385-404 (Milvus.from_documents / PGVector ctor -> an empty collection). */
 int rmu_index_create(rmu_index_t** out, int dim, int metric, int64_t capacity_hint);
 int rmu_index_free(rmu_index_t* idx);
@@ -171,6 +187,8 @@ int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, int k, unsign
  * in the list never appear.  Everything else -- q, k, row_base, flags, output format and order (score, then lower row id), the stream
  * contract -- is rmu_index_search's, and every returned score has the bits rmu_index_search returns for that row.  n_sub == 0, or fewer
  * than k live rows in the list: the remaining slots hold (-inf | +inf for L2SQ, -1).
+ * The index must hold rows of at most RMU_MAX_DIM dimensions: on a wider one the call returns RMU_E_INVALID before anything is enqueued (the
+ * gathered form of the wide scan does not exist yet).
  * Serves: VectorStore.similarity_search(**kwargs) with a filter -- Milvus col.search(expr='source == "a.pdf"') / PGVector
  * filter={"source": "a.pdf"} behind the retriever's search_kwargs (RAGHelper.py:497-499). */
 #define RMU_F_ROWS_DEVICE 8u   /* rmu_index_search_subset: `rows` is a device address */

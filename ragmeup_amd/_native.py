@@ -20,11 +20,13 @@ OPT_SCREEN = 1
 OPT_SCREEN_MIN_NQ = 2
 OPT_LADDER_RATIO, OPT_LADDER_FIRST = 3, 4
 OPT_COMPACT_INPLACE = 5
+OPT_WIDE_SCAN = 6
 STAT_CAPACITY, STAT_GROW_COUNT, STAT_GROW_MS, STAT_LIVE_ROWS = 1, 2, 3, 4
 STAT_COMPACT_COUNT, STAT_COMPACT_MS = 5, 6
 COMM_ID_BYTES = 128
 MAX_K = 112
-MAX_DIM = 768
+MAX_DIM = 768            # widest row of the register-resident scans
+MAX_DIM_WIDE = 3072      # widest row of an index (ip / cosine)
 
 # every symbol include/rmu.h declares (tests check the .so exports all of them)
 SYMBOLS = [

@@ -10,7 +10,7 @@
 //   rmu_index_compact     server.py:353-385 + RAGHelper.py:518-538 (delete / re-upload cycle; row moves in rmu_compact.hip)
 //   rmu_topk_merge        no counterpart (8-GPU shard merge)
 //
-// Data layout in HBM: one row-major [capacity, dpad] fp32 matrix, dpad = dim rounded up to 192/384/768
+// Data layout in HBM: one row-major [capacity, dpad] fp32 matrix, dpad = dim rounded up to 192/384/768, above 768 to the next multiple of 64
 // (zero padded), base 256-B aligned so every 1536-B row of the 384-d flagship is 12 full 128-B lines.
 // Tombstoned rows are NaN-poisoned in place: every score against them is NaN and fails the scan's
 // `score > threshold` compare, so deletion costs nothing in the hot loop.
@@ -447,6 +447,7 @@ struct rmu_index {
     double compact_ms = 0.0;
     bool compact_inplace = false;   // RMU_OPT_COMPACT_INPLACE: compaction never re-allocates
     bool screen_enabled = true;     // RMU_OPT_SCREEN: searches may take the screening path (when `split` exists)
+    bool wide_scan = false;         // RMU_OPT_WIDE_SCAN: exact searches run scan_wide_kernel whatever the width; no screening while set
     int ladder_ratio = 0, ladder_first = 0;   // RMU_OPT_LADDER_RATIO / _FIRST (0 = defaults; tools/ladder_sweep.py)
     int64_t screen_min_nq = 0;      // RMU_OPT_SCREEN_MIN_NQ: > 0 = screen every batch of at least this many queries, whatever the corpus size
     std::vector<uint8_t> alive;
@@ -497,18 +498,24 @@ static int wait_readers(rmu_index* idx, hipStream_t on = nullptr) {
 // past row n of the image.  Keep this many allocated (zero-filled) rows past the capacity of both matrices.
 static const int64_t kSlackRows = 256;
 static_assert(kSlackRows >= 160, "scan_screen_lean3_kernel's unclamped look-ahead");
-static int pad_dim(int d) { return d <= 192 ? 192 : (d <= 384 ? 384 : (d <= 768 ? 768 : -1)); }
-// L2SQ rows carry -|x|^2 in one extra column (see k_l2_aug_rows)
-static int pad_dim_metric(int d, int metric) { return pad_dim(metric == RMU_METRIC_L2SQ ? d + 1 : d); }
+// ... wide rows (scan_wide.hip streams them in 32- or 16-float chunks): the next multiple of 64 floats, i.e. of 256 bytes (rmu_compact.hip)
+static int pad_dim(int d) { return d <= 192 ? 192 : (d <= 384 ? 384 : (d <= RMU_MAX_DIM ? 768 : (d <= RMU_MAX_DIM_WIDE ? (d + 63) / 64 * 64 : -1))); }
+// L2SQ rows carry -|x|^2 in one extra column (see k_l2_aug_rows); there is no wide L2 index
+static int pad_dim_metric(int d, int metric) {
+    if (metric == RMU_METRIC_L2SQ) return d + 1 <= RMU_MAX_DIM ? pad_dim(d + 1) : -1;
+    return pad_dim(d);
+}
 
 extern "C" int rmu_index_create(rmu_index_t** out, int dim, int metric, int64_t capacity_hint) {
     RMU_ENTRY();
     if (!out) return fail(RMU_E_INVALID, "rmu_index_create: out is null");
-    if (dim < 1 || dim > RMU_MAX_DIM) return fail(RMU_E_INVALID, "rmu_index_create: dim must be in [1, 768]");
+    if (dim < 1 || dim > RMU_MAX_DIM_WIDE) return fail(RMU_E_INVALID, "rmu_index_create: dim must be in [1, 3072]");
     if (metric != RMU_METRIC_IP && metric != RMU_METRIC_COSINE && metric != RMU_METRIC_L2SQ)
         return fail(RMU_E_INVALID, "rmu_index_create: metric must be RMU_METRIC_IP, RMU_METRIC_COSINE or RMU_METRIC_L2SQ");
     if (pad_dim_metric(dim, metric) < 0)
-        return fail(RMU_E_INVALID, "rmu_index_create: RMU_METRIC_L2SQ needs one spare column: dim must be <= 767");
+        return fail(RMU_E_INVALID, dim <= RMU_MAX_DIM ? "rmu_index_create: RMU_METRIC_L2SQ needs one spare column: dim must be <= 767"
+                                                      : "rmu_index_create: a wide index (dim > 768) is RMU_METRIC_IP or RMU_METRIC_COSINE: RMU_METRIC_L2SQ (L2) "
+                                                        "rows are at most 767 dimensions");
     int rc = g_tls.ensure_stream();
     if (rc) return fail(rc, "rmu_index_create: stream");
     auto* idx = new (std::nothrow) rmu_index();
@@ -1015,7 +1022,7 @@ extern "C" int rmu_index_search_mmr_dev_(rmu_index_t* idx, const float* q_dev, i
     if (!idx || !q_dev || !out_rows || !hip_stream) return fail(RMU_E_INVALID, "rmu_bert_search_mmr: null pointer");
     if (nq < 1 || fetch_k < 1 || fetch_k > 64 || k < 1 || k > fetch_k)
         return fail(RMU_E_INVALID, "rmu_bert_search_mmr: nq >= 1, fetch_k in [1, 64], k in [1, fetch_k]");
-    if (idx->dim != 384) return fail(RMU_E_INVALID, "rmu_bert_search_mmr: the index must hold 384-d rows (the encoder's width)");
+    if (idx->dim != 384) return fail(RMU_E_INVALID, "rmu_bert_search_mmr: the index must hold 384-d rows (the encoder's width; a wide index never does)");
     Tls& t = g_tls;
     int rc = t.ensure_stream((hipStream_t)hip_stream);
     if (rc) return fail(rc, "rmu_bert_search_mmr: stream");
@@ -1069,7 +1076,7 @@ extern "C" int rmu_index_load(rmu_index_t** out, const char* path) {
     FILE* f = fopen(path, "rb");
     if (!f) return fail(RMU_E_INVALID, std::string("rmu_index_load: cannot open ") + path);
     RmuFileHeader h{};
-    if (fread(&h, sizeof(h), 1, f) != 1 || memcmp(h.magic, "RMUIDX01", 8) != 0 || h.n < 0 || h.dim < 1 ||
+    if (fread(&h, sizeof(h), 1, f) != 1 || memcmp(h.magic, "RMUIDX01", 8) != 0 || h.n < 0 || h.dim < 1 || h.dim > RMU_MAX_DIM_WIDE ||
         h.dpad != pad_dim_metric(h.dim, h.metric)) {
         fclose(f);
         return fail(RMU_E_INVALID, std::string("rmu_index_load: not an RMUIDX01 file: ") + path);
@@ -1267,6 +1274,7 @@ static bool screen_applies(const rmu_index* idx, int64_t nb, int k) {
     // (deep k: the alternative is the exact 128-deep ladder at ~0.3 of the HBM roof -- the screen pays from the size that ladder starts at)
     const bool screen_pays = nb >= 128 || idx->n >= 3000000 || (nb > 64 && idx->n >= 1000000) || min_nq_set || (k > 32 && idx->n >= 262144);
     const bool geom = idx->dim == 384 && (idx->metric == RMU_METRIC_L2SQ ? idx->nrm != nullptr : idx->dpad == 384);
+    if (idx->wide_scan) return false;   // RMU_OPT_WIDE_SCAN: every search is the exact scan, through scan_wide_kernel
     return idx->split && idx->screen_enabled && geom &&
            nb >= screen_min_nq && screen_pays && k <= kScreenMaxK && idx->n > 0 && idx->xnorm_max > 0.f &&
            idx->xnorm_max < 500.f;   // fp16(64*x) must not overflow
@@ -1380,6 +1388,7 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
             *L = ScanLaunch{};
             if (kk <= 0) kk = k;
             L->x = idx->x; L->n_rows = idx->n; L->dpad = dpad; L->q = qd; L->nq = (int)nqq; L->k = kk; L->dbg = g_dbg;
+            L->wide = idx->wide_scan ? 1 : 0;       // (a dpad above 768 is routed to the wide kernel by the planner itself)
             if (cond) L->cond = *cond;
             const int rc2 = rmu_scan_plan(L);
             if (rc2) return fail(rc2, "rmu_index_search: no scan geometry for this (dim, k)");
@@ -1480,6 +1489,7 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
                 S = ScanLaunch{};
                 S.row0 = l ? bounds[(size_t)l - 1] : 0;
                 S.x = idx->x + S.row0 * dpad; S.n_rows = bounds[(size_t)l] - S.row0; S.dpad = dpad; S.q = qdev; S.nq = (int)nb; S.k = k; S.dbg = g_dbg;
+                S.wide = idx->wide_scan ? 1 : 0;
                 if ((rc = rmu_scan_plan(&S))) return fail(rc, "rmu_index_search: no scan geometry for this (dim, k)");
                 slots += S.parts;
             }
@@ -1561,6 +1571,9 @@ extern "C" int rmu_index_search_subset(rmu_index_t* idx, const float* q, int64_t
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     const int dpad = idx->dpad, dim = idx->dim;
     const bool l2 = idx->metric == RMU_METRIC_L2SQ;
+    if (dpad > RMU_MAX_DIM)
+        return fail(RMU_E_INVALID, "rmu_index_search_subset: the index holds rows wider than 768 dimensions (RMU_MAX_DIM): the filtered search "
+                                   "does not serve a wide index yet");
     if (!rows_dev) {            // a host list is checked before anything is enqueued; a device list is the caller's contract
         int64_t prev = -1;
         for (int64_t i = 0; i < n_sub; ++i) {
@@ -1684,6 +1697,11 @@ extern "C" int rmu_index_set_option(rmu_index_t* idx, int option, int64_t value)
         case RMU_OPT_LADDER_RATIO: idx->ladder_ratio = value > 0 && value <= 4096 ? (int)value : 0; return RMU_OK;
         case RMU_OPT_LADDER_FIRST: idx->ladder_first = value > 0 && value <= (1 << 30) ? (int)value : 0; return RMU_OK;
         case RMU_OPT_COMPACT_INPLACE: idx->compact_inplace = value != 0; return RMU_OK;
+        case RMU_OPT_WIDE_SCAN:
+            if (idx->metric == RMU_METRIC_L2SQ) return fail(RMU_E_INVALID, "rmu_index_set_option: RMU_OPT_WIDE_SCAN serves RMU_METRIC_IP / RMU_METRIC_COSINE indexes only");
+            if (value != 0 && value != 1) return fail(RMU_E_INVALID, "rmu_index_set_option: RMU_OPT_WIDE_SCAN takes 0 or 1");
+            idx->wide_scan = value == 1;
+            return RMU_OK;
         default: return fail(RMU_E_INVALID, "rmu_index_set_option: unknown option");
     }
 }

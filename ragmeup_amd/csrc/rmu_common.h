@@ -167,7 +167,7 @@ struct ScanLaunch {
     int64_t n_rows;
     int64_t row0;          // first row of the scanned range: screening scan rows [row0, row0 + n_rows) of the image `x`; exact scan: `x`
                            // already points at row row0 and row0 is only added to the row ids of the keys
-    int dpad;              // row stride in floats (multiple of 96)
+    int dpad;              // row stride in floats (192 / 384 / 768; scan_wide_kernel: a multiple of 32)
     const float* q;        // [nq, dpad] fp32 device (padded like the rows)
     int nq;
     int k;
@@ -191,6 +191,9 @@ struct ScanLaunch {
     u64* gcand;
     // screening scan of an RMU_METRIC_L2SQ index: -2048 |x|^2 per image row (indexed like the image: row0 is added); nullptr = inner product
     const float* nrm;
+    // exact scan only: 1 = scan_wide_kernel (scan_wide.hip: queries streamed through the ring, any dpad that is a multiple of 32 up to 3072).  Set by
+    // rmu_scan_plan for dpad > 768, or by the caller in front of it (RMU_OPT_WIDE_SCAN) for a width scan_topk_kernel would take
+    int wide;
 };
 #define RMU_KS_CAP 48     /* K' <= 40 kept candidates + 8 free slots between compactions (one key per lane in the rank: <= 64) */
 #define RMU_KS_CAP_DEEP 128   /* (round 6) 32 < k <= 104: K' <= 120 kept candidates + 8 free slots, two keys per lane in the rank */
@@ -218,6 +221,8 @@ inline void rmu_plan_chunks(int nqt, int64_t tiles_total, int* s_chunks, int* ti
 
 int rmu_scan_plan(ScanLaunch* p);                        // chooses geometry; returns 0 or RMU_E_INVALID
 int rmu_scan_launch(const ScanLaunch* p, hipStream_t s); // launches the fused scan
+int rmu_wide_plan(ScanLaunch* p);                        // the same pair for scan_wide_kernel; rmu_scan_plan / rmu_scan_launch route to it
+int rmu_wide_launch(const ScanLaunch* p, hipStream_t s);
 int rmu_merge_final_launch(const u64* partial, int parts, int64_t nq, int k, int64_t row_base, int l2_out, const float* qnorm2,
                            float* out_scores, int64_t* out_rows, const int64_t* scatter /* or null */, const RmuCond* cond /* or null */,
                            hipStream_t s);
@@ -260,7 +265,7 @@ int rmu_subset_launch(const SubsetLaunch* p, hipStream_t s);
 int rmu_subset_narrow_launch(const int64_t* rows, int64_t n_sub, int64_t n_rows, u32* ids, hipStream_t s);
 int rmu_subset_map_launch(int64_t* out_rows, const u32* ids, int64_t total, int64_t row_base, hipStream_t s);   // position -> row id + row_base
 
-// row moves of rmu_index_compact (rmu_compact.hip), one array of the index at a time: rows of row_bytes (768 / 1536 / 3072, or 4 for the
+// row moves of rmu_index_compact (rmu_compact.hip), one array of the index at a time: rows of row_bytes (a multiple of 256, or 4 for the
 // L2 norms); new row j in [first, n_live) comes from old row src_rows[j - first] (device list, strictly increasing, src_rows[i] >= first + i);
 // rows [0, first) stay where they are.
 //   alloc_rows > 0: out of place -- a new allocation of alloc_rows rows (capacity + slack) receives the prefix and the gathered rows, its

@@ -38,6 +38,29 @@ __global__ __launch_bounds__(256) void k_compact_rows(const T* __restrict__ src,
     }
 }
 
+// the same for rows of any whole number of 16-byte pieces (per_row at run time): the wide rows of scan_wide.hip, 64 to 3072 floats
+template <int U>
+__global__ __launch_bounds__(256) void k_compact_rows_any(const u32x4* __restrict__ src, u32x4* __restrict__ dst, const u32* __restrict__ src_rows,
+                                                          int64_t rows, int per_row) {
+    const int64_t total = rows * per_row;
+    const int64_t i0 = (int64_t)blockIdx.x * (256 * U) + threadIdx.x;
+    u32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int64_t i = i0 + (int64_t)u * 256;
+        if (i < total) {
+            const int64_t r = i / per_row;
+            const int64_t p = i - r * per_row;
+            v[u] = __builtin_nontemporal_load(src + (int64_t)src_rows[r] * per_row + p);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int64_t i = i0 + (int64_t)u * 256;
+        if (i < total) dst[i] = v[u];
+    }
+}
+
 template <typename T, int PER_ROW>
 static hipError_t launch_rows(const void* src, void* dst, const u32* src_rows, int64_t rows, hipStream_t s) {
     constexpr int U = 4;
@@ -48,7 +71,8 @@ static hipError_t launch_rows(const void* src, void* dst, const u32* src_rows, i
     return hipGetLastError();
 }
 
-// rows of row_bytes: 768 / 1536 / 3072 (fp32 rows of dpad 192 / 384 / 768; 768 is also the fp16 screening image) or 4 (L2 norms)
+// rows of row_bytes: 768 / 1536 / 3072 (fp32 rows of dpad 192 / 384 / 768; 768 is also the fp16 screening image), 4 (L2 norms), or any
+// other multiple of 256 (the wide rows: dpad is a multiple of 64 floats)
 static hipError_t gather(const void* src, void* dst, int64_t row_bytes, const u32* src_rows, int64_t rows, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
     switch (row_bytes) {
@@ -56,8 +80,15 @@ static hipError_t gather(const void* src, void* dst, int64_t row_bytes, const u3
         case 1536: return launch_rows<u32x4, 96>(src, dst, src_rows, rows, s);
         case 3072: return launch_rows<u32x4, 192>(src, dst, src_rows, rows, s);
         case 4: return launch_rows<float, 1>(src, dst, src_rows, rows, s);
-        default: return hipErrorInvalidValue;
+        default: break;
     }
+    if (row_bytes % 256 != 0 || row_bytes > (int64_t)RMU_MAX_DIM_WIDE * 4) return hipErrorInvalidValue;
+    constexpr int U = 4;
+    const int per_row = (int)(row_bytes / 16);
+    const int64_t grid = (rows * per_row + 256 * U - 1) / (256 * U);
+    if (grid > 0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_compact_rows_any<U>, dim3((unsigned)grid), dim3(256), 0, s, (const u32x4*)src, (u32x4*)dst, src_rows, rows, per_row);
+    return hipGetLastError();
 }
 
 hipError_t rmu_compact_array(void** base, int64_t row_bytes, int fill, int64_t n_old, int64_t n_live, int64_t first, const u32* src_rows,

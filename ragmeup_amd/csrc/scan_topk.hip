@@ -387,6 +387,7 @@ int with_cfg(int wq, int kv, int nt, F&& f) {
 }  // namespace
 
 int rmu_scan_plan(ScanLaunch* p) {
+    if (p->wide || p->dpad > RMU_MAX_DIM) return rmu_wide_plan(p);   // rows the register-resident scan cannot hold, or RMU_OPT_WIDE_SCAN
     if (p->k < 1 || p->k > RMU_MAX_K || p->nq < 1 || p->n_rows < 0) return RMU_E_INVALID;
     if (p->dpad != 192 && p->dpad != 384 && p->dpad != 768) return RMU_E_INVALID;
     p->kv = p->k <= 32 ? 0 : 1;
@@ -404,6 +405,7 @@ int rmu_scan_plan(ScanLaunch* p) {
 }
 
 int rmu_scan_launch(const ScanLaunch* p, hipStream_t s) {
+    if (p->wide) return rmu_wide_launch(p, s);
     return for_dpad(p->dpad, [&](auto d) {
         return with_cfg<decltype(d)::value>(p->wq, p->kv, p->nt, [&](auto c) { return launch_cfg<decltype(c), scan_topk_kernel<decltype(c)>>(p, s); });
     });

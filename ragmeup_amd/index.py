@@ -20,6 +20,7 @@ def _is_torch_cuda(t) -> bool:
 
 class FlatIndex:
     def __init__(self, dim: int, metric: int = N.METRIC_IP, capacity_hint: int = 0, device: int | None = None):
+        """dim <= 3072 (N.MAX_DIM_WIDE) for METRIC_IP / METRIC_COSINE, <= 767 for METRIC_L2SQ; RmuError otherwise."""
         self._lib = N.lib()
         if device is not None:
             N.check(self._lib.rmu_init(int(device)), "rmu_init")
@@ -181,7 +182,8 @@ class FlatIndex:
         `rows`: search these rows only (rmu_index_search_subset: a gathered scan, time proportional to the list) -- strictly ascending
         index-local row ids, one list for all queries: a numpy int64 array (checked: RmuError RMU_E_INVALID when not ascending or out of
         range) or, with torch CUDA queries, a torch CUDA int64 tensor (not checked: ids outside the index are ignored).  Scores and
-        order are those `search` without `rows` gives the same rows; fewer than k live rows in the list: (-inf | +inf, -1) padding."""
+        order are those `search` without `rows` gives the same rows; fewer than k live rows in the list: (-inf | +inf, -1) padding.
+        ValueError on an index of more than 768 dimensions (N.MAX_DIM): the wide scan has no gathered form yet."""
         if rows is not None:
             return self._search_subset(q, int(k), int(row_base), stream, out, rows)
         if _is_torch_cuda(q):
@@ -217,6 +219,9 @@ class FlatIndex:
         return out_s, out_r
 
     def _search_subset(self, q, k: int, row_base: int, stream, out, rows):
+        if self.dim > N.MAX_DIM:
+            raise ValueError(f"search(rows=...) serves rows of at most {N.MAX_DIM} dimensions; this index holds {self.dim}-d rows "
+                             "(the filtered search of a wide index does not exist yet)")
         if _is_torch_cuda(q):
             import torch
             qq = q.detach().to(torch.float32).contiguous()
@@ -266,6 +271,11 @@ class FlatIndex:
     def set_screening(self, on: bool = True):
         """RMU_OPT_SCREEN: allow (default) or forbid the fp16 screening path; results are identical either way."""
         N.check(self._lib.rmu_index_set_option(self._h, N.OPT_SCREEN, 1 if on else 0), "rmu_index_set_option")
+
+    def set_wide_scan(self, on: bool = True):
+        """RMU_OPT_WIDE_SCAN (ip / cosine): exact searches run scan_wide_kernel -- the kernel of rows wider than 768 dimensions, which streams
+        its queries -- whatever the width, and the screening path is off; results are identical either way, bit for bit."""
+        N.check(self._lib.rmu_index_set_option(self._h, N.OPT_WIDE_SCAN, 1 if on else 0), "rmu_index_set_option")
 
     def set_screen_min_batch(self, n: int = 0):
         """RMU_OPT_SCREEN_MIN_NQ: n > 0 sends every batch of >= n queries through the screening path whatever the corpus size

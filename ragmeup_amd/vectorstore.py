@@ -1049,6 +1049,9 @@ class MI355XVectorStore(VectorStore):
         kk = max(1, min(int(k), N.MAX_K))
         if conds is None:
             return self._index.search(qvecs, kk)
+        if getattr(self._index, "dim", 0) > N.MAX_DIM:
+            raise ValueError(f"filtered search (expr= / filter=) serves embeddings of at most {N.MAX_DIM} dimensions; this store holds "
+                             f"{self._index.dim}-d vectors")
         rows = self._filter_rows(conds)
         if rows.size == 0:
             return none
