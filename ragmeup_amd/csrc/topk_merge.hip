@@ -317,7 +317,8 @@ __global__ __launch_bounds__(256) void merge_lists_kernel(const float* __restric
             } else {
                 const int64_t idx = rmu_key_row(key);
                 const int64_t part = idx / k, pos = idx % k;
-                out_scores[q * k + e] = smaller_better ? -rmu_key_score(key) : rmu_key_score(key);
+                // (0 - s, not -s: the key holds +0 for either zero, and an exact hit's squared distance is +0 as in the single-index search)
+                out_scores[q * k + e] = smaller_better ? 0.0f - rmu_key_score(key) : rmu_key_score(key);
                 out_rows[q * k + e] = rows[part * stride_r + q * k + pos];
             }
         }
