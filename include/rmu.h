@@ -60,6 +60,9 @@ extern "C" {
                              * small-batch default for <= 128 queries).  Results are identical for every value. */
 #define RMU_OPT_LADDER_FIRST 4   /* tuning: rows of the ladder's smallest first range (0 = default).  Results identical for every value. */
 
+#define RMU_OPT_SCREEN_BAND 7     /* tuning: 1 (default): the ladder's merges seed each launch's thresholds with max(K'-th best, k-th best - 2 EPS(q)),
+                             * the lower edge of the sufficiency test's band; 0: with the K'-th best alone.  Results are identical either way. */
+
 #define RMU_OPT_COMPACT_INPLACE 5 /* 0 (default): rmu_index_compact moves the rows into fresh, smaller allocations (in place when those do not
                              * fit); 1: always in place, the capacity stays.  Results are identical either way (the tests force the path). */
 

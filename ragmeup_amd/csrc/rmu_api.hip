@@ -84,7 +84,7 @@ struct Buf {
 struct Tls {
     hipStream_t stream = nullptr;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    Buf q, partial, out_s, out_r, in_s, in_r, qn, gthr, mscratch, qsplit, ckeys, flag, nrm, fbq, fb_s, fb_r, fb_i, mm_q, mm_s, mm_r, mm_p, gcand, sub_ids, sub_rows;
+    Buf q, partial, out_s, out_r, in_s, in_r, qn, gthr, mscratch, qsplit, ckeys, flag, nrm, fbq, fb_s, fb_r, fb_i, mm_q, mm_s, mm_r, mm_p, gcand, sub_ids, sub_rows, eps;
     std::vector<hipEvent_t> lev;   // per-launch events of the screening ladder
     int ensure_events(int n) {
         while ((int)lev.size() < n) {
@@ -449,6 +449,7 @@ struct rmu_index {
     bool screen_enabled = true;     // RMU_OPT_SCREEN: searches may take the screening path (when `split` exists)
     bool wide_scan = false;         // RMU_OPT_WIDE_SCAN: exact searches run scan_wide_kernel whatever the width; no screening while set
     int ladder_ratio = 0, ladder_first = 0;   // RMU_OPT_LADDER_RATIO / _FIRST (0 = defaults; tools/ladder_sweep.py)
+    bool screen_band = true;        // RMU_OPT_SCREEN_BAND: the ladder's merges also seed the lower edge of the sufficiency band (screen_enqueue)
     int64_t screen_min_nq = 0;      // RMU_OPT_SCREEN_MIN_NQ: > 0 = screen every batch of at least this many queries, whatever the corpus size
     std::vector<uint8_t> alive;
     std::shared_mutex mu;
@@ -1178,6 +1179,8 @@ static std::vector<int64_t> ladder_bounds(int64_t n, int64_t nb, int opt_ratio =
     // 1.25M x 1024 1.169 / 1.144 / 1.161, x 512 0.762 / 0.727 / 0.729, x 256 0.530 / 0.488 / 0.495; 2.5M x 1024 at 3 / 5: 1.97 / 1.92, x 256 0.699 / 0.670;
     // 4.5M x 1024 at 3 / 6: 3.30 / 3.25, x 256 1.092 / 1.022; but 10M x 1024 6.71 / 6.77 / 6.78 at 3 / 4 / 8 (ratio 6: 6.77): there the appends of a
     // wider level cost more than the level it saves, and the ratio stays 3.
+    // (These sweeps predate band seeding -- RMU_OPT_SCREEN_BAND: a seeded level appends about a third of what it did -- and have not been
+    // re-run with it; cheaper appends favour fewer levels, so the 10M figure is the one to re-measure first.)
     std::vector<int64_t> best = build(3);
     if (n < 6000000)
         for (int r : {4, 5, 6, 8}) {
@@ -1193,9 +1196,10 @@ static std::vector<int64_t> ladder_bounds(int64_t n, int64_t nb, int opt_ratio =
 // after each range its candidates are merged with the running top-K' and the K'-th best seeds the shared per-query
 // thresholds of the next launch.  A cold launch appends K' ln(rows/K') candidates per query and CHUNK, a seeded one only
 // K' (ratio - 1) per query in total, and every append stalls a whole workgroup for ~1-3k cycles: this cut
-// the filter overhead of the 10M x 1024 scan from 5.2 to ~1.5 ms.
+// the filter overhead of the 10M x 1024 scan from 5.2 to ~1.5 ms.  `k` (the caller's k) below `kp`: the merges also seed the lower edge of
+// the sufficiency band (see `band` below), about a third of those appends.
 static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb, hipStream_t s, bool timed, int* n_launches,
-                          ScanLaunch* last_geom, int kp = kScreenKp, u32* zero_word = nullptr /* one more word the query conversion zeroes (the re-run count) */) {
+                          ScanLaunch* last_geom, int k, int kp = kScreenKp, u32* zero_word = nullptr /* one more word the query conversion zeroes (the re-run count) */) {
     const int dpad = idx->dpad;
     static const int share = rmu_env("RMU_NO_SHARED_THR") ? 0 : 1;
     const std::vector<int64_t> bounds = ladder_bounds(idx->n, nb, idx->ladder_ratio, idx->ladder_first);
@@ -1222,14 +1226,21 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
         gcand_bytes = std::max(gcand_bytes, (size_t)lv[(size_t)l].parts * (size_t)nb * (kp > RMU_KS_CAP - 8 ? RMU_KS_CAP_DEEP : RMU_KS_CAP) * sizeof(u64));
     if (gcand_bytes && t.gcand.ensure(gcand_bytes)) return fail(RMU_E_OOM, "rmu_index_search: screening candidate slots");
     if (t.partial.ensure((size_t)slots * part_keys * sizeof(u64)) || t.qsplit.ensure((size_t)nb * RMU_IMG_ROW_BYTES) ||
-        t.gthr.ensure(gbytes) || t.ckeys.ensure(part_keys * sizeof(u64)) || t.ensure_events(2 * nl))
+        t.gthr.ensure(gbytes) || t.ckeys.ensure(part_keys * sizeof(u64)) || t.eps.ensure((size_t)nb * sizeof(float)) || t.ensure_events(2 * nl))
         return fail(RMU_E_OOM, "rmu_index_search: screening workspace");
     static const int nofilter = rmu_env("RMU_SCREEN_NOFILTER") != nullptr ? 2 : 0;
     const int sflags = share | nofilter;
     // (an L2 index holds its queries as (2q, 1): the image is fp16(64 q) all the same)
     // (round 6) the conversion's first workgroup also zeroes the ladder's thresholds + pacing words and the caller's word: was two memsets
-    int rc = rmu_split_launch(qdev, t.qsplit.p, nb, s, dpad, idx->metric == RMU_METRIC_L2SQ ? 32.0f : 64.0f, (u32*)t.gthr.p,
-                              (int)(gbytes / sizeof(u32)), zero_word, zero_word ? 1 : 0);
+    // Band seeding (scan_screen.hip header): a seeded launch needs only the rows that can reach the caller's top-k or decide its sufficiency
+    // test -- s~ above s~[k-1] - 2 EPS(q), about rank 11-12 of K' = 32 at k = 10 -- so the merges publish that edge beside the K'-th key, and a
+    // level appends about a third of the K' (ratio - 1) candidates per query.  EPS(q) is computed by the query conversion (no launch of its own).
+    // k = K' (rmu_index_screen_candidates) or RMU_OPT_SCREEN_BAND = 0: the K'-th key alone, as before.
+    const bool band = idx->screen_band && k < kp && nl > 1;
+    const bool l2q = idx->metric == RMU_METRIC_L2SQ;
+    int rc = rmu_split_launch(qdev, t.qsplit.p, nb, s, dpad, l2q ? 32.0f : 64.0f, (u32*)t.gthr.p,
+                              (int)(gbytes / sizeof(u32)), zero_word, zero_word ? 1 : 0, band ? (float*)t.eps.p : nullptr, idx->xnorm_max, idx->dx_max,
+                              l2q ? 1 : 0);
     if (rc) return fail(rc, "rmu_index_search: query conversion");
     u64* base = (u64*)t.partial.p;
     int cursor = 0;     // slot index: [merged keys of the ranges so far][this range's parts] ...
@@ -1254,8 +1265,9 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
         cursor += S.parts;
         if (g_dbg) dbg_dump("screen range", S.n_rows, s);
         u64* merged = l + 1 < nl ? base + (size_t)cursor * part_keys : (u64*)t.ckeys.p;
-        rc = rmu_merge_to_keys_launch(base + (size_t)first * part_keys, cursor - first, nb, kp, merged,
-                                      l + 1 < nl ? (u32*)t.gthr.p : nullptr /* merge + seed in one launch */, s, raw ? 1 : 0);
+        rc = rmu_merge_to_keys_band_launch(base + (size_t)first * part_keys, cursor - first, nb, kp, merged,
+                                           l + 1 < nl ? (u32*)t.gthr.p : nullptr /* merge + seed in one launch */, s, raw ? 1 : 0, k,
+                                           band ? (const float*)t.eps.p : nullptr);
         if (rc) return fail(rc, "rmu_index_search: screening merge / threshold seeding");
     }
     *n_launches = nl;
@@ -1447,7 +1459,7 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
             if (t.partial.ensure(need_partial) || t.gthr.ensure(need_gthr)) return fail(RMU_E_OOM, "rmu_index_search: re-run partials");
             int nl = 0;
             ScanLaunch lastg{};
-            rc = screen_enqueue(idx, t, qdev, nb, s, timed, &nl, &lastg, screen_kp(k), (u32*)t.flag.p);    // (flag[0] = 0 by the query conversion)
+            rc = screen_enqueue(idx, t, qdev, nb, s, timed, &nl, &lastg, k, screen_kp(k), (u32*)t.flag.p);    // (flag[0] = 0 by the query conversion)
             if (rc) return rc;
             // |s~ - s_fp32| <= EPS(q) from the measured image errors (derivation in scan_screen.hip); queries failing the
             // sufficiency test are appended to the list fb_i (count in flag[0])
@@ -1660,7 +1672,7 @@ extern "C" int rmu_index_screen_candidates(rmu_index_t* idx, const float* q_host
     if (idx->metric == RMU_METRIC_COSINE) hipLaunchKernelGGL(k_row_norm, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, 384, nq, 1, (float*)nullptr);
     HIP_TRY(hipMemsetAsync(t.flag.p, 0, sizeof(int), s));
     int nl = 0;
-    rc = screen_enqueue(idx, t, (const float*)t.q.p, nq, s, false, &nl, nullptr);
+    rc = screen_enqueue(idx, t, (const float*)t.q.p, nq, s, false, &nl, nullptr, kp /* k = K': no band -- the true approximate top-K' */);
     if (rc) return rc;
     // k = K': the re-score kernel writes the exact fp32 score of EVERY candidate (rank order) and EPS(q)
     rc = rmu_rescore_launch((const u64*)t.ckeys.p, kp, idx->x, (const float*)t.q.p, nq, kp, idx->xnorm_max, idx->dx_max, 0, (float*)t.out_s.p,
@@ -1696,6 +1708,7 @@ extern "C" int rmu_index_set_option(rmu_index_t* idx, int option, int64_t value)
         case RMU_OPT_SCREEN_MIN_NQ: idx->screen_min_nq = value > 0 ? value : 0; return RMU_OK;
         case RMU_OPT_LADDER_RATIO: idx->ladder_ratio = value > 0 && value <= 4096 ? (int)value : 0; return RMU_OK;
         case RMU_OPT_LADDER_FIRST: idx->ladder_first = value > 0 && value <= (1 << 30) ? (int)value : 0; return RMU_OK;
+        case RMU_OPT_SCREEN_BAND: idx->screen_band = value != 0; return RMU_OK;
         case RMU_OPT_COMPACT_INPLACE: idx->compact_inplace = value != 0; return RMU_OK;
         case RMU_OPT_WIDE_SCAN:
             if (idx->metric == RMU_METRIC_L2SQ) return fail(RMU_E_INVALID, "rmu_index_set_option: RMU_OPT_WIDE_SCAN serves RMU_METRIC_IP / RMU_METRIC_COSINE indexes only");

@@ -228,10 +228,15 @@ int rmu_merge_final_launch(const u64* partial, int parts, int64_t nq, int k, int
                            hipStream_t s);
 int rmu_merge_to_keys_launch(const u64* partial, int parts, int64_t nq, int k, u64* out_keys, u32* seed_thr /* or null */,
                              hipStream_t s, int unsorted = 0 /* the lists are compact but not sorted (ScanLaunch::share_thr bit 2) */);
+// the same merge; seed_thr also receives the lower edge of the sufficiency band of the caller's k = band_k < k (band_eps: EPS(q) per query, or null)
+int rmu_merge_to_keys_band_launch(const u64* partial, int parts, int64_t nq, int k, u64* out_keys, u32* seed_thr, hipStream_t s, int unsorted,
+                                  int band_k, const float* band_eps);
 // fp16 screening path (scan_screen.hip)
 #define RMU_IMG_ROW_BYTES 768                          /* fp16(64 x) image of a 384-d row */
 int rmu_split_launch(const float* src, void* dst, int64_t n_rows, hipStream_t s, int stride = 384,
-                     float scale = 64.0f, u32* zero_a = nullptr, int n_zero_a = 0, u32* zero_b = nullptr, int n_zero_b = 0);                                             // fp32 [n, 384 of stride] -> fp16(scale x) image
+                     float scale = 64.0f, u32* zero_a = nullptr, int n_zero_a = 0, u32* zero_b = nullptr, int n_zero_b = 0,
+                     float* eps_out = nullptr /* [n_rows]: EPS(q) of each row taken as a query (l2: rows are (2q, 1)) */, float xnorm_max = 0.f,
+                     float dx_max = 0.f, int l2 = 0);                                             // fp32 [n, 384 of stride] -> fp16(scale x) image
 int rmu_screen_launch(const ScanLaunch* p, hipStream_t s);                             // x/q = split images, k = K'
 int rmu_screen_plan(ScanLaunch* p);                      // geometry of one screening launch (k = K' <= 32)
 int rmu_img_err_launch(const float* x, int64_t n_rows, float* err2, hipStream_t s, int stride = 384);   // |x - image|^2 per row

@@ -19,6 +19,22 @@
 // Sufficiency (per query): with the approximate top-K' (K' = 32) sorted, tau = k-th best s~.  If fewer than K'
 // candidates exist, or s~[K'-1] < tau - 2*EPS, every row outside the candidate set has an exact score below k rows
 // of the set, so the exact top-k is inside it.  Otherwise the query is flagged and re-run on the exact scan.
+// Band seeding (the threshold ladder of rmu_api.hip: screen_enqueue): K' exists only so that the test above can pass, and a row that is
+// below the test's lower edge when it is seen can neither be in the exact top-k nor change the test's outcome.  So the merge that seeds a
+// launch (topk_merge.hip: seed_band) publishes, beside the K'-th key, the image of tau_now - 2 EPS (1 + 2^-10) rounded one key step down
+// (tau_now = the k-th best approximate score so far; EPS(q) is computed by the query conversion with the re-score kernel's own arithmetic:
+// screen_eps); the launch's threshold is the larger of the two.  Given: the filter is strict (p > thr), thresholds only rise, tau only rises,
+// so a dropped row had s~ <= thr_level <= max(final K'-th, tau_final - 2 EPS (1 + guard)).
+//   Dropped below the K'-th: the argument above, unchanged.
+//   Dropped below the band: its exact score is <= s~ + EPS < tau_final - EPS (strictly: the guard and the key step), and each of the k best
+//   approximate candidates has an exact score >= tau_final - EPS: k rows beat it outright, the row-id tie rule never gets to decide.
+//   Flagging: a query is flagged iff at least K' rows have s~ >= tau_final - 2 EPS.  fl(tau_now - 2 EPS (1 + 2^-10)) <= fl(tau_final - 2 EPS)
+//   (rounding is monotone; the guard also covers an EPS that differs from the re-score kernel's in its last bits), one key step below it is
+//   strictly less, so every such row passes every level's threshold and is kept: the same queries are flagged with the band and without.
+// The band is published only when the merged K'-th key exists ("fewer than K' candidates" must go on meaning that every live row is one),
+// when EPS is finite, and when k < K' (rmu_index_screen_candidates asks for k = K' and still gets the true approximate top-K').
+// RMU_OPT_SCREEN_BAND = 0 seeds the K'-th key alone.  On random unit rows the band's edge sits near rank 11-12 of K' = 32 at k = 10: a seeded
+// level appends about a third of the K' (ratio - 1) candidates per query it appended before (tests/test_screen_band_cpu.py: 0.34).
 // (An earlier hi/lo split variant, 3 MFMAs per 16 k with EPS = 1e-4, ran at 25 ms for the 10M x 1024 headline; its
 // ablations showed the LDS/L2 path, not the MFMA pipe, setting the time, which is what halving the bytes attacks.)
 #include <cstdlib>
@@ -43,12 +59,52 @@ constexpr int S_CS = S_TS / 2;          // ... 12 per chunk
 constexpr int S_SLOT = S_RT * S_CKB;    // 12 KiB ring slot
 extern __shared__ __attribute__((aligned(16))) char ssm[];
 
+// EPS(q) of the header, in the one order both of its users take: |q|^2 and |dq|^2 run over k as the re-score kernel's chain does (step t holds
+// k = 8t .. 8t+3 in qa and 8t+4 .. 8t+7 in qb, taken alternately), then the bound.  L2: the index stores 2q -- the query itself is half of it --
+// and the norm's roundings add 1.5e-5 |x|max^2 (see k_rescore).  k_rescore tests with it; the query conversion computes the same number in
+// front of the ladder for the band seeding of the merges (topk_merge.hip: seed_band).
+template <bool L2>
+__device__ __forceinline__ void screen_eps_step(const f32x4& qa, const f32x4& qb, float& qn2, float& dq2) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float ua = L2 ? 0.5f * qa[c] : qa[c], ub = L2 ? 0.5f * qb[c] : qb[c];      // the query itself (the L2 index stores 2q)
+        qn2 = fmaf(ua, ua, qn2);
+        qn2 = fmaf(ub, ub, qn2);
+        const float da = ua - (float)(_Float16)(ua * 64.0f) * (1.0f / 64.0f);
+        const float db = ub - (float)(_Float16)(ub * 64.0f) * (1.0f / 64.0f);
+        dq2 = fmaf(da, da, dq2);
+        dq2 = fmaf(db, db, dq2);
+    }
+}
+template <bool L2>
+__device__ __forceinline__ float screen_eps(float qn2, float dq2, float xnorm_max, float dx_max) {
+    const float qn = sqrtf(qn2) * 1.0001f, dq = sqrtf(dq2) * 1.0001f;
+    return dx_max * qn + xnorm_max * dq + dx_max * dq + 5.0e-5f * xnorm_max * qn +   // see the header
+           (L2 ? 1.5e-5f * xnorm_max * xnorm_max : 0.f);
+}
+
 // fp32 rows [n, 384 of `stride` floats] -> screening image [n, 768 B] = fp16(scale * x); one thread per group of 8 k.  scale = 64, or 32 for the
 // L2 index's queries, which are stored doubled (rmu_api.hip: k_l2_aug_queries)
 // (round 6, second session) zero_a / zero_b: words the FIRST workgroup zeroes on the way -- the query conversion opens every screened search, and
 // the ladder's shared thresholds and the re-run count used to be two memsets in front of it (~4.5 us of kernel boundary each)
+// eps_out (optional, [n_eps]): EPS(q) of each of the n_eps rows of src, by the blocks from conv_blocks on -- a launch of its own would cost the same 4.5 us
 __global__ void k_split_rows(const float* __restrict__ src, char* __restrict__ dst, int64_t n_groups, int stride, float scale,
-                             u32* __restrict__ zero_a, int n_zero_a, u32* __restrict__ zero_b, int n_zero_b) {
+                             u32* __restrict__ zero_a, int n_zero_a, u32* __restrict__ zero_b, int n_zero_b, int conv_blocks,
+                             float* __restrict__ eps_out, int64_t n_eps, float xnorm_max, float dx_max, int l2) {
+    if ((int)blockIdx.x >= conv_blocks) {       // the blocks behind the conversion: EPS(q) of the ladder's band seeding, one query per thread
+        const int64_t qi = (int64_t)(blockIdx.x - conv_blocks) * blockDim.x + threadIdx.x;
+        if (qi >= n_eps) return;
+        const float* qv = src + qi * stride;
+        float qn2 = 0.f, dq2 = 0.f;
+#pragma unroll 4
+        for (int t = 0; t < SD / 8; ++t) {
+            const f32x4 qa = *(const f32x4*)(qv + 8 * t), qb = *(const f32x4*)(qv + 8 * t + 4);
+            if (l2) screen_eps_step<true>(qa, qb, qn2, dq2);
+            else screen_eps_step<false>(qa, qb, qn2, dq2);
+        }
+        eps_out[qi] = l2 ? screen_eps<true>(qn2, dq2, xnorm_max, dx_max) : screen_eps<false>(qn2, dq2, xnorm_max, dx_max);
+        return;
+    }
     if (blockIdx.x == 0) {
         for (int i = threadIdx.x; i < n_zero_a; i += blockDim.x) zero_a[i] = 0u;
         for (int i = threadIdx.x; i < n_zero_b; i += blockDim.x) zero_b[i] = 0u;
@@ -680,16 +736,7 @@ __global__ __launch_bounds__(256) void k_rescore(const u64* __restrict__ cand, i
                     acc[p] = fmaf(xb[p][u][c], qb[c], acc[p]);
                 }
             }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float ua = L2 ? 0.5f * qa[c] : qa[c], ub = L2 ? 0.5f * qb[c] : qb[c];      // the query itself (the L2 index stores 2q)
-                qn2 = fmaf(ua, ua, qn2);
-                qn2 = fmaf(ub, ub, qn2);
-                const float da = ua - (float)(_Float16)(ua * 64.0f) * (1.0f / 64.0f);
-                const float db = ub - (float)(_Float16)(ub * 64.0f) * (1.0f / 64.0f);
-                dq2 = fmaf(da, da, dq2);
-                dq2 = fmaf(db, db, dq2);
-            }
+            screen_eps_step<L2>(qa, qb, qn2, dq2);
         }
     }
     if (L2) {
@@ -708,9 +755,7 @@ __global__ __launch_bounds__(256) void k_rescore(const u64* __restrict__ cand, i
     };
     const float tau = approx_at(k - 1);                         // k-th best approximate score (or -inf)
     const float smin = approx_at(kp - 1);                       // worst kept candidate
-    const float qn = sqrtf(qn2) * 1.0001f, dq = sqrtf(dq2) * 1.0001f;
-    const float eps = dx_max * qn + xnorm_max * dq + dx_max * dq + 5.0e-5f * xnorm_max * qn +   // see the header
-                      (L2 ? 1.5e-5f * xnorm_max * xnorm_max : 0.f);
+    const float eps = screen_eps<L2>(qn2, dq2, xnorm_max, dx_max);
     const bool complete = nvalid < kp;                           // every live row was a candidate
     // eps must be finite: a query with |q_i| >= ~1000 overflows fp16(64 q), its approximate scores are inf/NaN and rows
     // scoring NaN are never appended (so even `complete` proves nothing) -- such a query always goes to the exact scan
@@ -742,12 +787,15 @@ __global__ __launch_bounds__(256) void k_rescore(const u64* __restrict__ cand, i
 }  // namespace
 
 int rmu_split_launch(const float* src, void* dst, int64_t n_rows, hipStream_t s, int stride, float scale, u32* zero_a, int n_zero_a, u32* zero_b,
-                     int n_zero_b) {
+                     int n_zero_b, float* eps_out, float xnorm_max, float dx_max, int l2) {
     const int64_t groups = n_rows * (SD / 8);
-    if (groups <= 0) return (n_zero_a > 0 || n_zero_b > 0) ? RMU_E_INVALID : RMU_OK;      // (the zeroing rides on a launch that exists)
+    if (groups <= 0) return (n_zero_a > 0 || n_zero_b > 0 || eps_out) ? RMU_E_INVALID : RMU_OK;      // (the zeroing rides on a launch that exists)
     if (stride < SD) return RMU_E_INVALID;
-    hipLaunchKernelGGL(k_split_rows, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, src, (char*)dst, groups, stride, scale, zero_a,
-                       zero_a ? n_zero_a : 0, zero_b, zero_b ? n_zero_b : 0);
+    const int64_t conv_blocks = (groups + 255) / 256, eps_blocks = eps_out ? (n_rows + 255) / 256 : 0;
+    if (eps_out && conv_blocks + eps_blocks > 0x7fffffff) return RMU_E_INVALID;
+    hipLaunchKernelGGL(k_split_rows, dim3((unsigned)(conv_blocks + eps_blocks)), dim3(256), 0, s, src, (char*)dst, groups, stride, scale, zero_a,
+                       zero_a ? n_zero_a : 0, zero_b, zero_b ? n_zero_b : 0, (int)(eps_out ? conv_blocks : 0x7fffffff), eps_out, n_rows, xnorm_max, dx_max,
+                       l2);
     return hipGetLastError() == hipSuccess ? RMU_OK : RMU_E_HIP;
 }
 

@@ -110,7 +110,21 @@ struct MergeOut {
     const float* qnorm2;
     const int64_t* scatter;   // optional: query i writes output row scatter[i] (patching re-run queries into the batch)
     int unsorted;             // the part lists are compact (zeros last) but NOT sorted: the screening ladder's first launch (scan_screen.hip, share_thr bit 2)
+    int band_k;               // screening ladder (merge_select_kernel): the caller's k, below this merge's k = K' ...
+    const float* band_eps;    // ... and EPS(q) per query, or null: seed_thr also receives the lower edge of the sufficiency band (seed_band)
 };
+
+// Lower edge of the sufficiency band (scan_screen.hip header, "Band seeding"): the image of s~[k-1] - 2 EPS (1 + 2^-10), one key step down.
+// A row at or below it can neither be in the exact top-k nor decide the sufficiency test.  Only with a finite EPS (an overflowing query
+// has none and goes to the exact scan) and only when the merged K'-th key exists (`full`): "fewer than K' candidates" must go on
+// meaning that every live row is one.  seed_thr is an atomicMax: the launch's threshold is max(K'-th, band).
+__device__ __forceinline__ void seed_band(const MergeOut& o, int64_t qo, u64 kth_key, bool full) {
+    if (!full || !kth_key) return;
+    const float eps = o.band_eps[qo];
+    if (!__builtin_isfinite(eps)) return;
+    const u32 ord = rmu_f2ord(rmu_key_score(kth_key) - 2.0f * eps * (1.0f + 0x1p-10f) + 0.0f);
+    if (ord > 1u) atomicMax(o.seed_thr + qo, ord - 1u);
+}
 template <int NPL>
 __global__ __launch_bounds__(1024) void merge_wg_kernel(const u64* __restrict__ partial, int parts, int64_t nq, int k, int wpq,
                                                         MergeOut o, RmuCond cond) {
@@ -246,10 +260,13 @@ __global__ __launch_bounds__(BLOCK) void merge_select_kernel(const u64* __restri
     __syncthreads();
     const u32 m = count < (u32)CAPM ? count : (u32)CAPM;
     const int64_t qo = o.scatter ? o.scatter[q] : q;
+    const bool band = o.keys && o.seed_thr && o.band_eps && o.band_k >= 1 && o.band_k < k;      // (uniform)
+    const bool full = count >= (u32)k;          // the merged k-th key exists: every candidate is a distinct key > 0, ranks 0 .. count - 1 are all taken
     auto emit = [&](int e, u64 key) {
         if (o.keys) {
             o.keys[qo * k + e] = key;
             if (o.seed_thr && e == k - 1 && key) atomicMax(o.seed_thr + qo, (u32)(key >> 32));
+            if (band && e == o.band_k - 1) seed_band(o, qo, key, full);
         }
         if (o.scores) {
             float sc;
@@ -361,8 +378,14 @@ int rmu_merge_final_launch(const u64* partial, int parts, int64_t nq, int k, int
 
 // merge to keys (screening ladder): out_keys [nq, k]; seed_thr (optional) receives the merged k-th best per query
 int rmu_merge_to_keys_launch(const u64* partial, int parts, int64_t nq, int k, u64* out_keys, u32* seed_thr, hipStream_t s, int unsorted) {
+    return rmu_merge_to_keys_band_launch(partial, parts, nq, k, out_keys, seed_thr, s, unsorted, 0, nullptr);
+}
+// ... of the screening ladder: with band_eps (EPS(q) per query) and band_k (the caller's k, < k = K') seed_thr also receives the lower edge of
+// the sufficiency band (seed_band).  The merged keys are those of the plain form.
+int rmu_merge_to_keys_band_launch(const u64* partial, int parts, int64_t nq, int k, u64* out_keys, u32* seed_thr, hipStream_t s, int unsorted,
+                                  int band_k, const float* band_eps) {
     MergeOut o{};
-    o.keys = out_keys; o.seed_thr = seed_thr; o.unsorted = unsorted;
+    o.keys = out_keys; o.seed_thr = seed_thr; o.unsorted = unsorted; o.band_k = band_k; o.band_eps = band_eps;
     return merge_wg_launch(partial, parts, nq, k, o, RmuCond{}, s);
 }
 

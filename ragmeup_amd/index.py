@@ -288,6 +288,11 @@ class FlatIndex:
         N.check(self._lib.rmu_index_set_option(self._h, N.OPT_LADDER_RATIO, int(ratio)), "rmu_index_set_option")
         N.check(self._lib.rmu_index_set_option(self._h, N.OPT_LADDER_FIRST, int(first)), "rmu_index_set_option")
 
+    def set_screen_band(self, on: bool = True):
+        """Tuning (RMU_OPT_SCREEN_BAND): the ladder's merges seed each launch's thresholds with max(K'-th best, k-th best - 2 EPS(q)) (default)
+        or with the K'-th best alone.  Results and re-run counts are identical either way."""
+        N.check(self._lib.rmu_index_set_option(self._h, N.OPT_SCREEN_BAND, 1 if on else 0), "rmu_index_set_option")
+
     def screen_candidates(self, q):
         """Test hook (rmu_index_screen_candidates): per query the screening pass's 32 candidates ->
         (approx scores [nq,32], rows [nq,32], exact fp32 scores of the same rows [nq,32], EPS [nq])."""
