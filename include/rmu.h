@@ -331,6 +331,42 @@ int rmu_tok_encode(rmu_tok_t* tk, const char* const* texts_a, const char* const*
 int rmu_tok_encode_blob(rmu_tok_t* tk, const char* blob_a, int64_t bytes_a, const char* blob_b, int64_t bytes_b, int n, int max_len,
                         int32_t* ids, int32_t* type_ids, int32_t* lens);
 
+/* ---- BM25 retriever: inverted index in HBM, fused score + top-k (bm25.hip) -------------------------------------------
+ * Serves: the sparse member of the reference's ensemble, BM25Retriever.from_texts(...) under EnsembleRetriever([sparse, dense],
+ * weights=[0.5, 0.5]) (RAGHelper.py:436-443, :492-505; rebuilt after every upload, :529-531).  Okapi BM25 as rank_bm25.BM25Okapi computes it:
+ *   tokens = Python's str.split() (whitespace = str.isspace(); case-sensitive, nothing stripped; an empty document has length 0);
+ *   idf[t] = ln(N - df + 0.5) - ln(df + 0.5), every idf < 0 replaced by epsilon * mean(idf over the vocabulary, before replacement);
+ *   score  = sum over the query's tokens in order (duplicates count each time, unknown tokens add 0) of
+ *            idf[t] * tf * (k1 + 1) / (tf + k1 * (1 - b + b * dl / avgdl)).
+ * Every document is a candidate, zero and negative scores included.  Order: score descending, then LOWER document id -- rank_bm25's
+ * argsort()[::-1] puts the higher id first among equal scores and is not stable, so equal-scoring documents may come back in another order.
+ * Document ids are int64 numbers in insertion order.  The master postings live on the host (add_texts, stat and df never touch the GPU);
+ * the first search after an add packs them and uploads one image.  Not provided: deleting documents, persistence, the ParadeDB retriever. */
+typedef struct rmu_bm25 rmu_bm25_t;
+int rmu_bm25_create(rmu_bm25_t** out, double k1, double b, double epsilon);   /* rank_bm25's defaults: 1.5, 0.75, 0.25 */
+int rmu_bm25_free(rmu_bm25_t* h);
+/* Append n documents: blob holds n UTF-8 strings back to back, each terminated by '\0' (bytes = total size including the terminators, the
+ * convention of rmu_tok_encode_blob).  *first_doc (may be NULL) = id of the first one.  Host only. */
+int rmu_bm25_add_texts(rmu_bm25_t* h, const char* blob, int64_t bytes, int64_t n, int64_t* first_doc);
+#define RMU_BM25_STAT_DOCS 1    /* N */
+#define RMU_BM25_STAT_VOCAB 2   /* distinct terms */
+#define RMU_BM25_STAT_NNZ 3     /* postings = (term, document) pairs */
+#define RMU_BM25_STAT_AVGDL 4   /* mean tokens per document (0 for an empty index) */
+int rmu_bm25_stat(rmu_bm25_t* h, int what, double* out);
+/* Documents that contain the term (0 for an unknown one).  Host only. */
+int rmu_bm25_df(rmu_bm25_t* h, const char* term_utf8, int64_t* df);
+/* Testing switches: results are identical, bit for bit, for every value (the tests force many tiles, many workgroups and range boundaries on
+ * small corpora through them).  0 = default. */
+#define RMU_BM25_OPT_TILE_DOCS 1  /* documents per LDS tile: a power of two in [64, 8192] */
+#define RMU_BM25_OPT_MAX_WGS 2    /* workgroups per query (= part lists of the final merge), at most 1024 */
+int rmu_bm25_set_option(rmu_bm25_t* h, int option, int64_t value);
+/* Top-k of nq queries (a NUL-separated blob like add_texts'; at most 1024 tokens per query, 1 <= nq <= 65535, 1 <= k <= RMU_MAX_K; otherwise
+ * RMU_E_INVALID before anything is enqueued).  HOST outputs out_scores [nq, k] fp32 and out_docs [nq, k] int64 (+ doc_base), best first;
+ * slots beyond N hold (-inf, -1).  hip_stream: 0 = an internal per-thread stream, otherwise the work is ordered on that stream; either way the
+ * results are host arrays, so the stream has been drained when the call returns. */
+int rmu_bm25_search(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, float* out_scores,
+                    int64_t* out_docs, uint64_t hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,12 +7,13 @@ from .index import FlatIndex, topk_merge  # noqa: F401
 from .documents import Document  # noqa: F401
 from .reranker import ScoredCrossEncoderReranker  # noqa: F401
 from .vectorstore import MI355XVectorStore  # noqa: F401
+from .bm25 import BM25Index, MI355XBM25Retriever  # noqa: F401
 
 from .vectorstore import MI355XRetriever  # noqa: F401
 from . import factory  # noqa: F401
 
 __all__ = ["FlatIndex", "topk_merge", "Document", "ScoredCrossEncoderReranker", "MI355XVectorStore", "MI355XRetriever",
-           "BertEncoder", "MI355XEmbeddings", "MI355XCrossEncoder", "factory"]
+           "BM25Index", "MI355XBM25Retriever", "BertEncoder", "MI355XEmbeddings", "MI355XCrossEncoder", "factory"]
 
 
 def __getattr__(name):   # torch-dependent classes are imported lazily

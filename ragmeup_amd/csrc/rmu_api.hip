@@ -55,6 +55,7 @@ extern "C" int rmu_init(int device_ordinal) {
     g_device = device_ordinal;
     return RMU_OK;
 }
+int rmu_device_ordinal() { return g_device; }
 
 // ------------------------------------------------------------------------------------------------
 // per-thread context: stream, events, grow-only workspace

@@ -219,6 +219,7 @@ inline void rmu_plan_chunks(int nqt, int64_t tiles_total, int* s_chunks, int* ti
     *s_chunks = s;
 }
 
+int rmu_device_ordinal();                                // the device rmu_init chose, -1 before it (rmu_api.hip): per-thread contexts of other units follow it
 int rmu_scan_plan(ScanLaunch* p);                        // chooses geometry; returns 0 or RMU_E_INVALID
 int rmu_scan_launch(const ScanLaunch* p, hipStream_t s); // launches the fused scan
 int rmu_wide_plan(ScanLaunch* p);                        // the same pair for scan_wide_kernel; rmu_scan_plan / rmu_scan_launch route to it
