@@ -341,24 +341,35 @@ int rmu_tok_encode_blob(rmu_tok_t* tk, const char* blob_a, int64_t bytes_a, cons
  * Every document is a candidate, zero and negative scores included.  Order: score descending, then LOWER document id -- rank_bm25's
  * argsort()[::-1] puts the higher id first among equal scores and is not stable, so equal-scoring documents may come back in another order.
  * Document ids are int64 numbers in insertion order.  The master postings live on the host (add_texts, stat and df never touch the GPU);
- * the first search after an add packs them and uploads one image.  Not provided: deleting documents, persistence, the ParadeDB retriever. */
+ * the first search after an add packs them and uploads one image.
+ *
+ * Live documents.  A document is LIVE until rmu_bm25_remove_docs removes it; a removed document keeps its id until rmu_bm25_compact, and no id is
+ * reused before that.  Every search after a removal returns what rank_bm25.BM25Okapi built over the live documents in id order would return,
+ * with ids mapped back: N is the number of live documents; df[t] counts the live documents that contain t; the vocabulary is the set of terms
+ * with df > 0 (the mean idf of the epsilon replacement runs over those only, and a query token whose df has dropped to 0 contributes nothing,
+ * like an unknown one); avgdl is the live token total over the live count.  Removed documents are never candidates, not even with score 0;
+ * slots beyond the live count hold (-inf, -1); ties stay (score, then lower id).  An index whose documents are all removed answers like an
+ * empty one and does no device work.  Not provided: the ParadeDB retriever. */
 typedef struct rmu_bm25 rmu_bm25_t;
 int rmu_bm25_create(rmu_bm25_t** out, double k1, double b, double epsilon);   /* rank_bm25's defaults: 1.5, 0.75, 0.25 */
 int rmu_bm25_free(rmu_bm25_t* h);
 /* Append n documents: blob holds n UTF-8 strings back to back, each terminated by '\0' (bytes = total size including the terminators, the
  * convention of rmu_tok_encode_blob).  *first_doc (may be NULL) = id of the first one.  Host only. */
 int rmu_bm25_add_texts(rmu_bm25_t* h, const char* blob, int64_t bytes, int64_t n, int64_t* first_doc);
-#define RMU_BM25_STAT_DOCS 1    /* N */
-#define RMU_BM25_STAT_VOCAB 2   /* distinct terms */
-#define RMU_BM25_STAT_NNZ 3     /* postings = (term, document) pairs */
-#define RMU_BM25_STAT_AVGDL 4   /* mean tokens per document (0 for an empty index) */
+#define RMU_BM25_STAT_DOCS 1    /* ids handed out, removed documents included: what first_doc continues from */
+#define RMU_BM25_STAT_VOCAB 2   /* distinct terms of the live documents */
+#define RMU_BM25_STAT_NNZ 3     /* postings = (term, live document) pairs */
+#define RMU_BM25_STAT_AVGDL 4   /* mean tokens per live document (0 when there is none) */
+#define RMU_BM25_STAT_LIVE_DOCS 5 /* live documents */
 int rmu_bm25_stat(rmu_bm25_t* h, int what, double* out);
-/* Documents that contain the term (0 for an unknown one).  Host only. */
+/* Live documents that contain the term (0 for an unknown one).  Host only. */
 int rmu_bm25_df(rmu_bm25_t* h, const char* term_utf8, int64_t* df);
 /* Testing switches: results are identical, bit for bit, for every value (the tests force many tiles, many workgroups and range boundaries on
  * small corpora through them).  0 = default. */
 #define RMU_BM25_OPT_TILE_DOCS 1  /* documents per LDS tile: a power of two in [64, 8192] */
 #define RMU_BM25_OPT_MAX_WGS 2    /* workgroups per query (= part lists of the final merge), at most 1024 */
+#define RMU_BM25_OPT_REPACK_ON_REMOVE 4 /* 0 or 1.  1: a removal marks the image dirty (the next search repacks it without the removed documents'
+                                         * postings) instead of stale (the next search refreshes weights, doc_norm and the liveness bitmap only) */
 int rmu_bm25_set_option(rmu_bm25_t* h, int option, int64_t value);
 /* Top-k of nq queries (a NUL-separated blob like add_texts'; at most 1024 tokens per query, 1 <= nq <= 65535, 1 <= k <= RMU_MAX_K; otherwise
  * RMU_E_INVALID before anything is enqueued).  HOST outputs out_scores [nq, k] fp32 and out_docs [nq, k] int64 (+ doc_base), best first;
@@ -366,6 +377,34 @@ int rmu_bm25_set_option(rmu_bm25_t* h, int option, int64_t value);
  * results are host arrays, so the stream has been drained when the call returns. */
 int rmu_bm25_search(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, float* out_scores,
                     int64_t* out_docs, uint64_t hip_stream);
+/* Remove documents.  Host only, never touches the GPU.  An id outside [0, DOCS) gives RMU_E_INVALID and changes nothing; an id that is already
+ * removed, or given twice, counts once or not at all; *n_removed (may be NULL) = the documents that were live.  Recounts df in one pass over
+ * the master postings -- O(postings) per CALL, so batch the ids -- and marks the device image stale: the first search afterwards recomputes the
+ * weights and doc_norm from the live statistics and uploads them with a liveness bitmap (4 bytes + 1 bit per document); the postings image is
+ * not repacked, and the postings of removed documents stay in it until the next repack (an add, or a compact).  Results are the same, bit for
+ * bit, on either path. */
+int rmu_bm25_remove_docs(rmu_bm25_t* h, const int64_t* docs, int64_t n, int64_t* n_removed);
+/* rmu_bm25_search over a subset: the candidates are the LIVE documents of docs[0, n_sub), a HOST list of strictly ascending document ids
+ * (checked before anything is enqueued: not ascending, or outside [0, DOCS), gives RMU_E_INVALID); one list serves all queries.  The statistics
+ * stay the whole live corpus's, as a Milvus or ParadeDB filter leaves them: every returned score has the bits rmu_bm25_search returns for that
+ * document.  n_sub == 0, or fewer than k live documents in the list, fills the rest with (-inf, -1).  Everything else is rmu_bm25_search's
+ * contract.  The call ships a bitmap of N / 8 bytes with its descriptors; its time follows the postings of the query's terms, NOT the length
+ * of the list (every posting of a query term is still scored; only the selection is restricted). */
+int rmu_bm25_search_subset(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, const int64_t* docs,
+                           int64_t n_sub, float* out_scores, int64_t* out_docs, uint64_t hip_stream);
+/* Reclaim removed documents (the contract of rmu_index_compact): live documents keep their order and become 0 .. n_live-1.  old_to_new
+ * [map_len] receives the new id of every old one, -1 for removed ids and for the entries [DOCS, map_len); map_len < DOCS gives RMU_E_INVALID
+ * and changes nothing.  *n_after (may be NULL) = documents afterwards.  With no removed document nothing changes and the image stays clean.
+ * Host only: the next search repacks the image.  Term ids stay; a term left without postings is out of the statistics.  Results afterwards
+ * equal those before with ids mapped, bit for bit. */
+int rmu_bm25_compact(rmu_bm25_t* h, int64_t* old_to_new, int64_t map_len, int64_t* n_after);
+/* One flat little-endian file: "RMUBM25\0", u32 version (1), u32 0 | f64 k1, b, epsilon | u64 N, V, nnz | u32 dl[N] | u8 liveness[N] | the V
+ * terms in term-id order, each u32 length + bytes | u64 posting offsets[V + 1] | u32 posting documents[nnz] | u32 posting tfs[nnz].  Removed
+ * documents survive as removed (as in rmu_index_save); options do not.  Host only.  load checks every size against the file's length before
+ * it allocates, and that each term's postings ascend inside [0, N), tfs are >= 1 and dl equals the tf sums: a short, long or inconsistent
+ * file gives RMU_E_INVALID with a message.  A loaded index answers every search with the bits the saved one gave. */
+int rmu_bm25_save(rmu_bm25_t* h, const char* path);
+int rmu_bm25_load(rmu_bm25_t** out, const char* path);
 
 #ifdef __cplusplus
 }

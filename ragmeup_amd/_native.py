@@ -28,8 +28,8 @@ COMM_ID_BYTES = 128
 MAX_K = 112
 MAX_DIM = 768            # widest row of the register-resident scans
 MAX_DIM_WIDE = 3072      # widest row of an index (ip / cosine)
-BM25_STAT_DOCS, BM25_STAT_VOCAB, BM25_STAT_NNZ, BM25_STAT_AVGDL = 1, 2, 3, 4
-BM25_OPT_TILE_DOCS, BM25_OPT_MAX_WGS = 1, 2
+BM25_STAT_DOCS, BM25_STAT_VOCAB, BM25_STAT_NNZ, BM25_STAT_AVGDL, BM25_STAT_LIVE_DOCS = 1, 2, 3, 4, 5
+BM25_OPT_TILE_DOCS, BM25_OPT_MAX_WGS, BM25_OPT_REPACK_ON_REMOVE = 1, 2, 4
 
 # every symbol include/rmu.h declares (tests check the .so exports all of them)
 SYMBOLS = [
@@ -41,6 +41,7 @@ SYMBOLS = [
     "rmu_bert_create", "rmu_bert_free", "rmu_bert_encode", "rmu_bert_encode_host", "rmu_bert_search_mmr",
     "rmu_tok_create", "rmu_tok_free", "rmu_tok_vocab_size", "rmu_tok_encode", "rmu_tok_encode_blob",
     "rmu_bm25_create", "rmu_bm25_free", "rmu_bm25_add_texts", "rmu_bm25_stat", "rmu_bm25_df", "rmu_bm25_set_option", "rmu_bm25_search",
+    "rmu_bm25_remove_docs", "rmu_bm25_search_subset", "rmu_bm25_compact", "rmu_bm25_save", "rmu_bm25_load",
 ]
 
 
@@ -102,6 +103,11 @@ def _declare(lib):
     lib.rmu_bm25_df.argtypes = [vp, c.c_char_p, c.POINTER(i64)]
     lib.rmu_bm25_set_option.argtypes = [vp, i32, i64]
     lib.rmu_bm25_search.argtypes = [vp, c.c_char_p, i64, i64, i32, i64, vp, vp, u64]
+    lib.rmu_bm25_remove_docs.argtypes = [vp, vp, i64, c.POINTER(i64)]
+    lib.rmu_bm25_search_subset.argtypes = [vp, c.c_char_p, i64, i64, i32, i64, vp, i64, vp, vp, u64]
+    lib.rmu_bm25_compact.argtypes = [vp, vp, i64, c.POINTER(i64)]
+    lib.rmu_bm25_save.argtypes = [vp, c.c_char_p]
+    lib.rmu_bm25_load.argtypes = [c.POINTER(vp), c.c_char_p]
     if hasattr(lib, "rmu_bert_create"):
         lib.rmu_bert_create.argtypes = [c.POINTER(vp), vp, c.POINTER(vp), i32]
         lib.rmu_bert_free.argtypes = [vp]

@@ -12,7 +12,10 @@
 //   result   = every document is a candidate (zero and negative scores included); slots beyond N hold (-inf, -1) as in rmu_index_search.
 // ORDER OF TIES: the project's own -- score descending, then LOWER document id.  rank_bm25's get_top_n (argsort()[::-1]) puts the HIGHER id
 // first among equal scores and is not stable; documents with equal scores may therefore come back in another order than the reference's.
-// Out of scope: deleting documents, persistence (the reference pickles its chunks and rebuilds the retriever), the ParadeDB SQL retriever.
+// REMOVED DOCUMENTS (rmu.h, "Live documents"): every statistic (N, df, the vocabulary, avgdl) is the live corpus's.  A removal is host work
+// (liveness bytes + one recount of df) and marks the image stale; the next search refreshes the weights, doc_norm and a liveness bitmap and
+// leaves the postings where they are.  bm25_masked_kernel is bm25_topk_kernel with one more step: a document whose bit is clear selects with
+// key 0.  rmu_bm25_search_subset launches the same kernel with allow AND live.  Out of scope: the ParadeDB SQL retriever.
 //
 // Host (plain C++, no HIP: testable without a GPU): whitespace tokenizer over a NUL-separated blob, term -> id map, per-term master posting
 // vectors (ascending document id, tf) and dl.  Adding documents appends; document ids are insertion order.
@@ -32,6 +35,7 @@
 // the range; the workgroup writes one sorted, zero-padded list [part, q, k], and rmu_merge_final_launch (topk_merge.hip) finishes.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <shared_mutex>
@@ -73,6 +77,7 @@ struct Bm25Launch {
     const u32* term_ptr;     // [nq + 1]: query q's descriptors are terms[term_ptr[q] .. term_ptr[q + 1])
     const TermDesc* terms;
     u64* partial;            // [parts, nq, k]
+    const u32* mask;         // bm25_masked_kernel only: bit d set = document d is a candidate; ceil(n_docs / 32) + 1 words
     u32 n_docs;
     int nq, k, tile, tiles_per_wg;
 };
@@ -93,8 +98,10 @@ __device__ __forceinline__ u64 kth_of(const u64 (&top)[NPL], int k) {
     return __shfl(v, (k - 1) & 63);
 }
 
-template <int NPL>
-__global__ __launch_bounds__(kBlock) void bm25_topk_kernel(Bm25Launch p) {
+// The one body of both kernels.  MASKED: a document whose bit in p.mask is clear gets key 0, the padding key the final merge turns into
+// (-inf, -1); the score loop is the same, so a candidate's sum is the same ordered fp32 sum whatever is masked.
+template <int NPL, bool MASKED>
+__device__ __forceinline__ void bm25_score_select(const Bm25Launch& p) {
     __shared__ __attribute__((aligned(16))) float acc[kMaxTile];
     __shared__ u32 cur[kMaxTerms];
     __shared__ u32 wcnt[2][kWaves];
@@ -128,6 +135,17 @@ __global__ __launch_bounds__(kBlock) void bm25_topk_kernel(Bm25Launch p) {
     for (int64_t t0 = d_lo; t0 < d_hi; t0 += p.tile) {
         const int64_t t1 = t0 + p.tile < d_hi ? t0 + p.tile : d_hi;
         const int cnt = (int)(t1 - t0);
+        // MASKED: lane i holds the two bitmap words of the wave's i-th 64-document batch of this tile (batch w + 4 * i; a tile has at most
+        // 128 batches, 32 per wave), loaded here so that the term loop hides the latency.  t0 is a multiple of 64: the pair starts a word.
+        u32 m_lo = 0, m_hi = 0;
+        if constexpr (MASKED) {
+            const int jb = (w + kWaves * lane) * 64;
+            if (jb < cnt) {
+                const u32* __restrict__ mp = p.mask + ((t0 + jb) >> 5);
+                m_lo = mp[0];
+                m_hi = mp[1];
+            }
+        }
         __syncthreads();                       // the selection of the tile before has read acc
         for (int j = tid; j < cnt; j += kBlock) acc[j] = 0.f;
         __syncthreads();
@@ -167,8 +185,13 @@ __global__ __launch_bounds__(kBlock) void bm25_topk_kernel(Bm25Launch p) {
         // selection: wave w takes the 64-document batches w, w + 4, ... of the tile
         for (int j0 = w * 64; j0 < cnt; j0 += kBlock) {
             const int j = j0 + lane;
-            const u64 key = j < cnt ? rmu_make_key(acc[j], (u32)(t0 + j)) : 0ull;
-            if (!__any(key > kth)) continue;
+            u64 key = j < cnt ? rmu_make_key(acc[j], (u32)(t0 + j)) : 0ull;
+            if constexpr (MASKED) {
+                const int bi = j0 / kBlock;                                  // wave-uniform: the batch's words sit in lane bi
+                const u32 lo = __shfl(m_lo, bi), hi = __shfl(m_hi, bi);
+                if (!(((lane < 32 ? lo : hi) >> (lane & 31)) & 1u)) key = 0ull;
+            }
+            if (!__any(key > kth)) continue;                                 // (wave-uniform; a batch of masked documents never passes)
             fold64<NPL>(top, key, lane);
             kth = kth_of<NPL>(top, p.k);
         }
@@ -194,6 +217,13 @@ __global__ __launch_bounds__(kBlock) void bm25_topk_kernel(Bm25Launch p) {
         if (e < p.k) out[e] = top[i];
     }
 }
+
+// every document is a candidate: what an index without removed documents launches for an unfiltered search
+template <int NPL>
+__global__ __launch_bounds__(kBlock) void bm25_topk_kernel(Bm25Launch p) { bm25_score_select<NPL, false>(p); }
+// candidates = the set bits of p.mask (the handle's liveness bitmap, or a call's allow AND live)
+template <int NPL>
+__global__ __launch_bounds__(kBlock) void bm25_masked_kernel(Bm25Launch p) { bm25_score_select<NPL, true>(p); }
 
 // ---- host: tokenizer and index ---------------------------------------------------------------------------------------------------------
 // length in bytes of the str.isspace() character at p (n bytes left), 0 if there is none.  The multi-byte forms cannot occur inside another
@@ -299,65 +329,117 @@ struct rmu_bm25 {
     double k1 = 1.5, b = 0.75, epsilon = 0.25;
     std::unordered_map<std::string, u32> ids;      // term -> id, ids in order of first occurrence
     struct Postings { std::vector<u32> doc, tf; };
-    std::vector<Postings> terms;                   // master posting vectors, ascending document id
+    std::vector<Postings> terms;                   // master posting vectors, ascending document id (removed documents' postings stay until compact)
     std::vector<u32> dl;
-    uint64_t total_len = 0, nnz = 0;
+    uint64_t nnz = 0;                              // master postings
+    // the live corpus: what every statistic and every score is computed from
+    std::vector<uint8_t> live;                     // [N] 1 = live
+    std::vector<u32> df;                           // [V] live documents that hold the term
+    uint64_t n_live = 0, live_len = 0, live_nnz = 0, live_vocab = 0;
     bool broken = false;                           // an allocation failed half-way through an add
-    int64_t opt_tile = 0, opt_max_wgs = 0;
-    // device image + the host half of it (valid while !dirty)
-    bool dirty = true;
+    int64_t opt_tile = 0, opt_max_wgs = 0, opt_repack_on_remove = 0;
+    // device image + the host half of it (valid while !dirty).  stale: the postings are in place but documents were removed since the
+    // weights, doc_norm and the liveness bitmap were computed
+    bool dirty = true, stale = false;
     u32* post_doc = nullptr;
     u32* post_tf = nullptr;
     float* doc_norm = nullptr;
+    u32* live_bits = nullptr;                      // [ceil(N / 32) + 1], present while the image was built or refreshed with a removed document
     std::vector<u64> post_ptr;                     // [V + 1]
-    std::vector<float> weight;                     // [V] fp32(idf * (k1 + 1))
+    std::vector<float> weight;                     // [V] fp32(idf * (k1 + 1)), 0 for a term no live document holds
     std::shared_mutex mu;
 };
 
 static void drop_image(rmu_bm25* h) {
-    for (void* p : {(void*)h->post_doc, (void*)h->post_tf, (void*)h->doc_norm})
+    for (void* p : {(void*)h->post_doc, (void*)h->post_tf, (void*)h->doc_norm, (void*)h->live_bits})
         if (p) (void)rmu_free(p);
-    h->post_doc = h->post_tf = nullptr;
+    h->post_doc = h->post_tf = h->live_bits = nullptr;
     h->doc_norm = nullptr;
     h->dirty = true;
+    h->stale = false;
 }
 
-// (exclusive lock held) pack the master vectors and upload them; no search is in flight (see the header)
+// the one copy of the statistics -> (weights, doc_norm) step, over the live corpus: both the repack and the refresh path call it
+static void live_weights_and_norms(const rmu_bm25* h, std::vector<float>& weight, std::vector<float>& norm) {
+    const size_t V = h->terms.size(), N = h->dl.size();
+    const double n = (double)h->n_live;
+    std::vector<double> idf(V, 0.0);
+    double idf_sum = 0.0;
+    for (size_t t = 0; t < V; ++t) {
+        if (!h->df[t]) continue;                   // not in the vocabulary of the live corpus
+        const double df = (double)h->df[t];
+        idf[t] = std::log(n - df + 0.5) - std::log(df + 0.5);
+        idf_sum += idf[t];
+    }
+    const double repl = h->live_vocab ? h->epsilon * (idf_sum / (double)h->live_vocab) : 0.0;
+    weight.assign(V, 0.f);
+    for (size_t t = 0; t < V; ++t)
+        if (h->df[t]) weight[t] = (float)((idf[t] < 0.0 ? repl : idf[t]) * (h->k1 + 1.0));
+    const double avgdl = h->n_live ? (double)h->live_len / n : 0.0;
+    norm.resize(N);
+    for (size_t d = 0; d < N; ++d)
+        norm[d] = (float)(h->k1 * (1.0 - h->b + (avgdl > 0.0 ? h->b * (double)h->dl[d] / avgdl : 0.0)));
+}
+// liveness bitmap [ceil(N / 32) + 1] (the kernel reads word pairs); `allow`: an ascending id list to AND with, or null
+static void live_bitmap(const rmu_bm25* h, u32* words, const int64_t* allow, int64_t n_allow, int64_t* n_set) {
+    const size_t N = h->dl.size(), nw = (N + 31) / 32 + 1;
+    memset(words, 0, nw * sizeof(u32));
+    int64_t set = 0;
+    if (allow) {
+        for (int64_t i = 0; i < n_allow; ++i)
+            if (h->live[(size_t)allow[i]]) { words[allow[i] >> 5] |= 1u << (allow[i] & 31); ++set; }
+    } else {
+        for (size_t d = 0; d < N; ++d)
+            if (h->live[d]) { words[d >> 5] |= 1u << (d & 31); ++set; }
+    }
+    if (n_set) *n_set = set;
+}
+static int upload_norms_and_bitmap(rmu_bm25* h, const std::vector<float>& norm, hipStream_t s) {
+    const size_t N = h->dl.size(), nw = (N + 31) / 32 + 1;
+    std::vector<u32> bits;
+    if (N) BM25_TRY(hipMemcpyAsync(h->doc_norm, norm.data(), N * sizeof(float), hipMemcpyHostToDevice, s));
+    if (h->n_live != N) {
+        try { bits.resize(nw); } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory while packing the index"); }
+        live_bitmap(h, bits.data(), nullptr, 0, nullptr);
+        if (!h->live_bits) BM25_TRY(hipMalloc((void**)&h->live_bits, nw * sizeof(u32)));
+        BM25_TRY(hipMemcpyAsync(h->live_bits, bits.data(), nw * sizeof(u32), hipMemcpyHostToDevice, s));
+    }
+    BM25_TRY(hipStreamSynchronize(s));             // (the host vectors are pageable and go out of scope)
+    return RMU_OK;
+}
+
+// (exclusive lock held) pack the master vectors -- live documents' postings only -- and upload them; no search is in flight (see the header)
 static int build_image(rmu_bm25* h, hipStream_t s) {
     drop_image(h);
     const size_t V = h->terms.size(), N = h->dl.size();
+    const bool all_live = h->n_live == N;
     std::vector<u32> pk;          // post_doc | post_tf
     std::vector<float> norm;
     try {
         h->post_ptr.assign(V + 1, 0);
-        h->weight.assign(V, 0.f);
-        pk.resize(2 * (size_t)h->nnz);
-        norm.resize(N);
+        pk.resize(2 * (size_t)h->live_nnz);
+        live_weights_and_norms(h, h->weight, norm);
     } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory while packing the index"); }
     u32* pdoc = pk.data();
-    u32* ptf = pk.data() + h->nnz;
-    std::vector<double> idf(V);
-    double idf_sum = 0.0;
+    u32* ptf = pk.data() + h->live_nnz;
     u64 at = 0;
     for (size_t t = 0; t < V; ++t) {
         const auto& ps = h->terms[t];
-        const double df = (double)ps.doc.size();
-        idf[t] = std::log((double)N - df + 0.5) - std::log(df + 0.5);
-        idf_sum += idf[t];
         h->post_ptr[t] = at;
-        if (!ps.doc.empty()) {
-            memcpy(pdoc + at, ps.doc.data(), ps.doc.size() * sizeof(u32));
-            memcpy(ptf + at, ps.tf.data(), ps.tf.size() * sizeof(u32));
+        if (all_live) {
+            if (!ps.doc.empty()) {
+                memcpy(pdoc + at, ps.doc.data(), ps.doc.size() * sizeof(u32));
+                memcpy(ptf + at, ps.tf.data(), ps.tf.size() * sizeof(u32));
+            }
+            at += ps.doc.size();
+        } else {
+            for (size_t i = 0; i < ps.doc.size(); ++i)
+                if (h->live[ps.doc[i]]) { pdoc[at] = ps.doc[i]; ptf[at] = ps.tf[i]; ++at; }
         }
-        at += ps.doc.size();
     }
     h->post_ptr[V] = at;
-    const double repl = V ? h->epsilon * (idf_sum / (double)V) : 0.0;
-    for (size_t t = 0; t < V; ++t) h->weight[t] = (float)((idf[t] < 0.0 ? repl : idf[t]) * (h->k1 + 1.0));
-    const double avgdl = N ? (double)h->total_len / (double)N : 0.0;
-    for (size_t d = 0; d < N; ++d)
-        norm[d] = (float)(h->k1 * (1.0 - h->b + (avgdl > 0.0 ? h->b * (double)h->dl[d] / avgdl : 0.0)));
-    const size_t pbytes = (size_t)h->nnz * sizeof(u32);
+    if (at != h->live_nnz) return mfail(RMU_E_INVALID, "rmu_bm25_search: internal error, the live posting count is out of step");
+    const size_t pbytes = (size_t)h->live_nnz * sizeof(u32);
     BM25_TRY(hipMalloc((void**)&h->post_doc, pbytes ? pbytes : 4));
     BM25_TRY(hipMalloc((void**)&h->post_tf, pbytes ? pbytes : 4));
     BM25_TRY(hipMalloc((void**)&h->doc_norm, N ? N * sizeof(float) : 4));
@@ -365,9 +447,23 @@ static int build_image(rmu_bm25* h, hipStream_t s) {
         BM25_TRY(hipMemcpyAsync(h->post_doc, pdoc, pbytes, hipMemcpyHostToDevice, s));
         BM25_TRY(hipMemcpyAsync(h->post_tf, ptf, pbytes, hipMemcpyHostToDevice, s));
     }
-    if (N) BM25_TRY(hipMemcpyAsync(h->doc_norm, norm.data(), N * sizeof(float), hipMemcpyHostToDevice, s));
-    BM25_TRY(hipStreamSynchronize(s));
+    const int rc = upload_norms_and_bitmap(h, norm, s);
+    if (rc != RMU_OK) return rc;
     h->dirty = false;
+    h->stale = false;
+    return RMU_OK;
+}
+
+// (exclusive lock held, image clean but stale) the refresh path: documents were removed since the image was packed.  The postings stay as they
+// are -- those of removed documents only ever touch accumulators the bitmap masks -- and the weights, doc_norm and the bitmap are recomputed.
+static int refresh_image(rmu_bm25* h, hipStream_t s) {
+    std::vector<float> norm;
+    try {
+        live_weights_and_norms(h, h->weight, norm);
+    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory while refreshing the index"); }
+    const int rc = upload_norms_and_bitmap(h, norm, s);
+    if (rc != RMU_OK) return rc;
+    h->stale = false;
     return RMU_OK;
 }
 
@@ -421,6 +517,7 @@ extern "C" int rmu_bm25_add_texts(rmu_bm25_t* h, const char* blob, int64_t bytes
                 if (it == h->ids.end()) {
                     it = h->ids.emplace(key, (u32)h->terms.size()).first;
                     h->terms.emplace_back();
+                    h->df.push_back(0);
                 }
                 seen.push_back(it->second);
             });
@@ -432,10 +529,14 @@ extern "C" int rmu_bm25_add_texts(rmu_bm25_t* h, const char* blob, int64_t bytes
                 ps.doc.push_back(id);
                 ps.tf.push_back((u32)(j - i));
                 ++h->nnz;
+                ++h->live_nnz;
+                if (h->df[seen[i]]++ == 0) ++h->live_vocab;
                 i = j;
             }
             h->dl.push_back((u32)seen.size());
-            h->total_len += seen.size();
+            h->live.push_back(1);
+            ++h->n_live;
+            h->live_len += seen.size();
         }
         h->broken = false;
     } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_add_texts: out of memory, the index is unusable"); }
@@ -448,9 +549,10 @@ extern "C" int rmu_bm25_stat(rmu_bm25_t* h, int what, double* out) {
     std::shared_lock<std::shared_mutex> lk(h->mu);
     switch (what) {
         case RMU_BM25_STAT_DOCS: *out = (double)h->dl.size(); break;
-        case RMU_BM25_STAT_VOCAB: *out = (double)h->terms.size(); break;
-        case RMU_BM25_STAT_NNZ: *out = (double)h->nnz; break;
-        case RMU_BM25_STAT_AVGDL: *out = h->dl.empty() ? 0.0 : (double)h->total_len / (double)h->dl.size(); break;
+        case RMU_BM25_STAT_VOCAB: *out = (double)h->live_vocab; break;
+        case RMU_BM25_STAT_NNZ: *out = (double)h->live_nnz; break;
+        case RMU_BM25_STAT_AVGDL: *out = h->n_live ? (double)h->live_len / (double)h->n_live : 0.0; break;
+        case RMU_BM25_STAT_LIVE_DOCS: *out = (double)h->n_live; break;
         default: return mfail(RMU_E_INVALID, "rmu_bm25_stat: unknown statistic");
     }
     return RMU_OK;
@@ -462,7 +564,7 @@ extern "C" int rmu_bm25_df(rmu_bm25_t* h, const char* term_utf8, int64_t* df) {
     std::shared_lock<std::shared_mutex> lk(h->mu);
     try {
         const auto it = h->ids.find(term_utf8);
-        *df = it == h->ids.end() ? 0 : (int64_t)h->terms[it->second].doc.size();
+        *df = it == h->ids.end() ? 0 : (int64_t)h->df[it->second];
     } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_df: out of memory"); }
     return RMU_OK;
 }
@@ -481,14 +583,18 @@ extern "C" int rmu_bm25_set_option(rmu_bm25_t* h, int option, int64_t value) {
             if (value < 0 || value > kMaxParts) return mfail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_MAX_WGS takes 0 .. 1024");
             h->opt_max_wgs = value;
             break;
+        case RMU_BM25_OPT_REPACK_ON_REMOVE:
+            if (value != 0 && value != 1) return mfail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_REPACK_ON_REMOVE takes 0 or 1");
+            h->opt_repack_on_remove = value;
+            break;
         default: return mfail(RMU_E_INVALID, "rmu_bm25_set_option: unknown option");
     }
     return RMU_OK;
 }
 
-extern "C" int rmu_bm25_search(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, float* out_scores,
-                               int64_t* out_docs, uint64_t hip_stream) {
-    RMU_ENTRY();
+// rmu_bm25_search (subset = false) and rmu_bm25_search_subset (candidates = the live documents of docs[0, n_sub))
+static int search_impl(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, bool subset, const int64_t* docs,
+                       int64_t n_sub, float* out_scores, int64_t* out_docs, uint64_t hip_stream) {
     if (!h || !query_blob || !out_scores || !out_docs) return mfail(RMU_E_INVALID, "rmu_bm25_search: null argument");
     if (nq < 1 || nq > 65535 || bytes < nq) return mfail(RMU_E_INVALID, "rmu_bm25_search: 1 <= nq <= 65535 queries, each NUL-terminated");
     if (k < 1 || k > RMU_MAX_K) return mfail(RMU_E_INVALID, "rmu_bm25_search: 1 <= k <= RMU_MAX_K");
@@ -505,34 +611,45 @@ extern "C" int rmu_bm25_search(rmu_bm25_t* h, const char* query_blob, int64_t by
 
     Ctx& c = g_ctx;
     hipStream_t s = nullptr;
+    const auto nothing = [&]() {
+        for (int64_t i = 0; i < nq * k; ++i) { out_scores[i] = -INFINITY; out_docs[i] = -1; }
+        return RMU_OK;
+    };
     std::shared_lock<std::shared_mutex> lk(h->mu);
     for (;;) {
         if (h->broken) return mfail(RMU_E_OOM, "rmu_bm25_search: an earlier add ran out of memory, the index is unusable");
-        if (h->dl.empty()) {                     // nothing to search: no device work at all
-            for (int64_t i = 0; i < nq * k; ++i) { out_scores[i] = -INFINITY; out_docs[i] = -1; }
-            return RMU_OK;
+        if (subset) {                            // (again after the lock was given up: documents may have been added, never renumbered unseen)
+            const int64_t n_docs = (int64_t)h->dl.size();
+            for (int64_t i = 0; i < n_sub; ++i)
+                if (docs[i] < 0 || docs[i] >= n_docs || (i > 0 && docs[i] <= docs[i - 1]))
+                    return mfail(RMU_E_INVALID, "rmu_bm25_search_subset: docs must be strictly ascending document ids in [0, DOCS)");
         }
+        if (h->n_live == 0 || (subset && n_sub == 0)) return nothing();     // nothing to search: no device work at all
         if (!s) {
             if (c.ensure_stream() != RMU_OK) return mfail(RMU_E_HIP, "rmu_bm25_search: cannot create a stream");
             s = hip_stream ? (hipStream_t)hip_stream : c.stream;
         }
-        if (!h->dirty) break;
+        if (!h->dirty && !h->stale) break;
         lk.unlock();
         {
             std::unique_lock<std::shared_mutex> wl(h->mu);
-            if (h->dirty && !h->broken && !h->dl.empty()) {
-                const int rc = build_image(h, s);
+            if (!h->broken && h->n_live != 0 && (h->dirty || h->stale)) {
+                const int rc = h->dirty ? build_image(h, s) : refresh_image(h, s);
                 if (rc != RMU_OK) { drop_image(h); return rc; }
             }
         }
         lk.lock();
     }
+    const int64_t N = (int64_t)h->dl.size();
+    const bool masked = subset || h->n_live != (uint64_t)N;
 
     // descriptors: term_ptr [nq + 1] | TermDesc [...], one pinned staging buffer, one copy
     size_t n_terms = 0;
     for (const auto& t : toks) n_terms += t.size();
     const size_t ptr_bytes = ((size_t)(nq + 1) * sizeof(u32) + 15) & ~(size_t)15;
-    if (c.ensure_pin(ptr_bytes + (n_terms ? n_terms : 1) * sizeof(TermDesc)) != RMU_OK) return mfail(RMU_E_OOM, "rmu_bm25_search: pinned staging buffer");
+    const size_t mask_bytes = subset ? (((size_t)N + 31) / 32 + 1) * sizeof(u32) : 0;      // allow AND live, behind the descriptors
+    if (c.ensure_pin(ptr_bytes + (n_terms ? n_terms : 1) * sizeof(TermDesc) + mask_bytes) != RMU_OK)
+        return mfail(RMU_E_OOM, "rmu_bm25_search: pinned staging buffer");
     u32* tp = (u32*)c.pin;
     TermDesc* td = (TermDesc*)(c.pin + ptr_bytes);
     u32 nd = 0;
@@ -543,15 +660,21 @@ extern "C" int rmu_bm25_search(rmu_bm25_t* h, const char* query_blob, int64_t by
                 const auto it = h->ids.find(tok);
                 if (it == h->ids.end()) continue;                    // an unknown token contributes 0
                 const u32 id = it->second;
+                if (!h->df[id]) continue;                            // no live document holds it any more: like an unknown token
                 td[nd++] = TermDesc{h->post_ptr[id], (u32)(h->post_ptr[id + 1] - h->post_ptr[id]), h->weight[id]};
             }
         }
     } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory"); }
     tp[nq] = nd;
-    const size_t stage_bytes = ptr_bytes + (size_t)nd * sizeof(TermDesc);
+    const size_t desc_bytes = ptr_bytes + (size_t)nd * sizeof(TermDesc);       // (a multiple of 16: the bitmap's word pairs are aligned)
+    if (subset) {
+        int64_t n_cand = 0;
+        live_bitmap(h, (u32*)(c.pin + desc_bytes), docs, n_sub, &n_cand);
+        if (n_cand == 0) return nothing();
+    }
+    const size_t stage_bytes = desc_bytes + mask_bytes;
 
     // geometry.  Neither the tile nor the grid changes a bit of the result: both only spread the work
-    const int64_t N = (int64_t)h->dl.size();
     int tile = (int)h->opt_tile;
     if (!tile) {
         tile = kMaxTile;
@@ -575,9 +698,15 @@ extern "C" int rmu_bm25_search(rmu_bm25_t* h, const char* query_blob, int64_t by
     L.terms = (const TermDesc*)((const char*)c.stage.p + ptr_bytes);
     L.partial = (u64*)c.partial.p;
     L.n_docs = (u32)N; L.nq = (int)nq; L.k = k; L.tile = tile; L.tiles_per_wg = (int)tiles_per_wg;
+    L.mask = !masked ? nullptr : subset ? (const u32*)((const char*)c.stage.p + desc_bytes) : h->live_bits;
     const dim3 grid((unsigned)parts, (unsigned)nq), block(kBlock);
-    if (k <= 64) hipLaunchKernelGGL(bm25_topk_kernel<1>, grid, block, 0, s, L);
-    else hipLaunchKernelGGL(bm25_topk_kernel<2>, grid, block, 0, s, L);
+    if (!masked) {
+        if (k <= 64) hipLaunchKernelGGL(bm25_topk_kernel<1>, grid, block, 0, s, L);
+        else hipLaunchKernelGGL(bm25_topk_kernel<2>, grid, block, 0, s, L);
+    } else {
+        if (k <= 64) hipLaunchKernelGGL(bm25_masked_kernel<1>, grid, block, 0, s, L);
+        else hipLaunchKernelGGL(bm25_masked_kernel<2>, grid, block, 0, s, L);
+    }
     BM25_TRY(hipGetLastError());
     int64_t* d_docs = (int64_t*)c.out.p;
     float* d_scores = (float*)((char*)c.out.p + (size_t)nq * k * sizeof(int64_t));
@@ -586,5 +715,235 @@ extern "C" int rmu_bm25_search(rmu_bm25_t* h, const char* query_blob, int64_t by
     BM25_TRY(hipMemcpyAsync(out_docs, d_docs, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     BM25_TRY(hipMemcpyAsync(out_scores, d_scores, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s));
     BM25_TRY(hipStreamSynchronize(s));
+    return RMU_OK;
+}
+
+extern "C" int rmu_bm25_search(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, float* out_scores,
+                               int64_t* out_docs, uint64_t hip_stream) {
+    RMU_ENTRY();
+    return search_impl(h, query_blob, bytes, nq, k, doc_base, false, nullptr, 0, out_scores, out_docs, hip_stream);
+}
+
+extern "C" int rmu_bm25_search_subset(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, const int64_t* docs,
+                                      int64_t n_sub, float* out_scores, int64_t* out_docs, uint64_t hip_stream) {
+    RMU_ENTRY();
+    if (n_sub < 0 || (n_sub > 0 && !docs)) return mfail(RMU_E_INVALID, "rmu_bm25_search_subset: bad document list");
+    return search_impl(h, query_blob, bytes, nq, k, doc_base, true, docs, n_sub, out_scores, out_docs, hip_stream);
+}
+
+// ---- removal, compaction, persistence: host only -----------------------------------------------------------------------------------------
+// (exclusive lock held) df, the live posting count and the live vocabulary from the master postings and the liveness bytes: one pass
+static void recount_live(rmu_bm25* h) {
+    h->live_nnz = 0;
+    h->live_vocab = 0;
+    const bool all_live = h->n_live == h->dl.size();
+    for (size_t t = 0; t < h->terms.size(); ++t) {
+        const auto& pd = h->terms[t].doc;
+        u32 n = 0;
+        if (all_live) n = (u32)pd.size();
+        else
+            for (const u32 d : pd) n += h->live[d];
+        h->df[t] = n;
+        h->live_nnz += n;
+        h->live_vocab += n != 0;
+    }
+}
+
+extern "C" int rmu_bm25_remove_docs(rmu_bm25_t* h, const int64_t* docs, int64_t n, int64_t* n_removed) {
+    RMU_ENTRY();
+    if (!h || n < 0 || (n > 0 && !docs)) return mfail(RMU_E_INVALID, "rmu_bm25_remove_docs: bad argument");
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    if (h->broken) return mfail(RMU_E_OOM, "rmu_bm25_remove_docs: an earlier add ran out of memory, the index is unusable");
+    const int64_t N = (int64_t)h->dl.size();
+    for (int64_t i = 0; i < n; ++i)
+        if (docs[i] < 0 || docs[i] >= N) return mfail(RMU_E_INVALID, "rmu_bm25_remove_docs: a document id is outside [0, DOCS)");
+    int64_t removed = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t d = (size_t)docs[i];
+        if (!h->live[d]) continue;                 // already removed, or given twice
+        h->live[d] = 0;
+        --h->n_live;
+        h->live_len -= h->dl[d];
+        ++removed;
+    }
+    if (n_removed) *n_removed = removed;
+    if (!removed) return RMU_OK;
+    recount_live(h);
+    if (h->opt_repack_on_remove) h->dirty = true;
+    else h->stale = true;                          // (a dirty image stays dirty: the repack drops the postings anyway)
+    return RMU_OK;
+}
+
+extern "C" int rmu_bm25_compact(rmu_bm25_t* h, int64_t* old_to_new, int64_t map_len, int64_t* n_after) {
+    RMU_ENTRY();
+    if (!h || !old_to_new) return mfail(RMU_E_INVALID, "rmu_bm25_compact: null argument");
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    if (h->broken) return mfail(RMU_E_OOM, "rmu_bm25_compact: an earlier add ran out of memory, the index is unusable");
+    const size_t N = h->dl.size();
+    if (map_len < (int64_t)N) return mfail(RMU_E_INVALID, "rmu_bm25_compact: old_to_new holds fewer entries than the index has documents");
+    u32 next = 0;
+    for (size_t d = 0; d < N; ++d) old_to_new[d] = h->live[d] ? (int64_t)next++ : -1;
+    for (int64_t d = (int64_t)N; d < map_len; ++d) old_to_new[d] = -1;
+    if (n_after) *n_after = (int64_t)next;
+    if (next == N) return RMU_OK;                  // nothing to reclaim: the image stays as it is
+    for (auto& ps : h->terms) {                    // in place: an entry only ever moves towards the front
+        size_t out = 0;
+        for (size_t i = 0; i < ps.doc.size(); ++i)
+            if (h->live[ps.doc[i]]) { ps.doc[out] = (u32)old_to_new[ps.doc[i]]; ps.tf[out] = ps.tf[i]; ++out; }
+        ps.doc.resize(out);
+        ps.tf.resize(out);
+    }
+    for (size_t d = 0; d < N; ++d)
+        if (h->live[d]) h->dl[(size_t)old_to_new[d]] = h->dl[d];
+    h->dl.resize(next);
+    h->live.assign(next, 1);
+    h->nnz = h->live_nnz;
+    h->dirty = true;
+    h->stale = false;
+    return RMU_OK;
+}
+
+namespace {
+// the index file: one flat little-endian file, in this order
+//   "RMUBM25\0" | u32 version = 1 | u32 0 | f64 k1, b, epsilon | u64 N, V, nnz | u32 dl[N] | u8 live[N]
+//   | V x (u32 length, bytes) terms in term-id order | u64 offsets[V + 1] | u32 posting documents[nnz] | u32 posting tfs[nnz]
+constexpr char kMagic[8] = {'R', 'M', 'U', 'B', 'M', '2', '5', '\0'};
+constexpr u32 kFileVersion = 1;
+constexpr size_t kHeaderBytes = 8 + 8 + 3 * 8 + 3 * 8;
+struct File {
+    FILE* f = nullptr;
+    ~File() { if (f) fclose(f); }
+};
+}  // namespace
+
+extern "C" int rmu_bm25_save(rmu_bm25_t* h, const char* path) {
+    RMU_ENTRY();
+    if (!h || !path) return mfail(RMU_E_INVALID, "rmu_bm25_save: null argument");
+    std::shared_lock<std::shared_mutex> lk(h->mu);
+    if (h->broken) return mfail(RMU_E_OOM, "rmu_bm25_save: an earlier add ran out of memory, the index is unusable");
+    File fl;
+    fl.f = fopen(path, "wb");
+    if (!fl.f) return mfail(RMU_E_INVALID, std::string("rmu_bm25_save: cannot open ") + path + " for writing");
+    bool ok = true;
+    const auto put = [&](const void* p, size_t bytes) { if (bytes && fwrite(p, 1, bytes, fl.f) != bytes) ok = false; };
+    const uint64_t N = h->dl.size(), V = h->terms.size();
+    const u32 ver[2] = {kFileVersion, 0};
+    const double par[3] = {h->k1, h->b, h->epsilon};
+    const uint64_t cnt[3] = {N, V, h->nnz};
+    put(kMagic, 8); put(ver, 8); put(par, 24); put(cnt, 24);
+    put(h->dl.data(), N * sizeof(u32));
+    put(h->live.data(), N);
+    try {
+        std::vector<const std::string*> names(V, nullptr);
+        for (const auto& kv : h->ids) names[kv.second] = &kv.first;
+        for (uint64_t t = 0; t < V; ++t) {
+            const u32 len = (u32)names[t]->size();
+            put(&len, 4);
+            put(names[t]->data(), len);
+        }
+    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_save: out of memory"); }
+    uint64_t at = 0;
+    for (uint64_t t = 0; t < V; ++t) { put(&at, 8); at += h->terms[t].doc.size(); }
+    put(&at, 8);
+    for (const auto& ps : h->terms) put(ps.doc.data(), ps.doc.size() * sizeof(u32));
+    for (const auto& ps : h->terms) put(ps.tf.data(), ps.tf.size() * sizeof(u32));
+    if (fflush(fl.f) != 0) ok = false;
+    if (!ok) return mfail(RMU_E_INVALID, std::string("rmu_bm25_save: writing ") + path + " failed");
+    return RMU_OK;
+}
+
+extern "C" int rmu_bm25_load(rmu_bm25_t** out, const char* path) {
+    RMU_ENTRY();
+    if (!out || !path) return mfail(RMU_E_INVALID, "rmu_bm25_load: null argument");
+    const auto bad = [&](const char* what) { return mfail(RMU_E_INVALID, std::string("rmu_bm25_load: ") + path + ": " + what); };
+    File fl;
+    fl.f = fopen(path, "rb");
+    if (!fl.f) return bad("cannot open the file");
+    if (fseek(fl.f, 0, SEEK_END) != 0) return bad("cannot seek");
+    const long end = ftell(fl.f);
+    if (end < 0 || fseek(fl.f, 0, SEEK_SET) != 0) return bad("cannot seek");
+    const uint64_t size = (uint64_t)end;
+    if (size < kHeaderBytes) return bad("shorter than the header");
+    unsigned char head[kHeaderBytes];
+    if (fread(head, 1, kHeaderBytes, fl.f) != kHeaderBytes) return bad("cannot read the header");
+    u32 ver[2];
+    double par[3];
+    uint64_t cnt[3];
+    memcpy(ver, head + 8, 8); memcpy(par, head + 16, 24); memcpy(cnt, head + 40, 24);
+    if (memcmp(head, kMagic, 8) != 0 || ver[0] != kFileVersion) return bad("not a BM25 index file of this version");
+    const double k1 = par[0], b = par[1], eps = par[2];
+    if (!(k1 >= 0.0) || !std::isfinite(k1) || !(b >= 0.0 && b <= 1.0) || !std::isfinite(eps)) return bad("k1, b or epsilon out of range");
+    const uint64_t N = cnt[0], V = cnt[1], nnz = cnt[2];
+    // every size against the file's length BEFORE anything is allocated (each count first on its own: no product can overflow after that)
+    if (N > 0x7FFFFFFFull || N > size || V > size || nnz > size) return bad("a count in the header exceeds the file's length");
+    const uint64_t fixed = kHeaderBytes + 5 * N + 4 * V + 8 * (V + 1) + 8 * nnz;        // all but the terms' bytes
+    if (fixed > size) return bad("the file is shorter than its header says");
+    std::vector<char> buf;
+    rmu_bm25* h = nullptr;
+    try {
+        buf.resize((size_t)(size - kHeaderBytes));
+        if (fread(buf.data(), 1, buf.size(), fl.f) != buf.size()) return bad("cannot read the file");
+        h = new rmu_bm25();
+    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_load: out of memory"); }
+    struct Drop { rmu_bm25* h; ~Drop() { delete h; } } drop{h};
+    h->k1 = k1; h->b = b; h->epsilon = eps;
+    try {
+        const char* p = buf.data();
+        const char* e = p + buf.size();
+        h->dl.resize((size_t)N);
+        if (N) memcpy(h->dl.data(), p, (size_t)N * 4);
+        p += N * 4;
+        h->live.resize((size_t)N);
+        if (N) memcpy(h->live.data(), p, (size_t)N);
+        p += N;
+        for (uint64_t d = 0; d < N; ++d) {
+            if (h->live[d] > 1) return bad("a liveness byte is neither 0 nor 1");
+            h->n_live += h->live[d];
+            if (h->live[d]) h->live_len += h->dl[d];
+        }
+        h->terms.resize((size_t)V);
+        h->df.assign((size_t)V, 0);
+        const uint64_t tail = 8 * (V + 1) + 8 * nnz;
+        for (uint64_t t = 0; t < V; ++t) {
+            if ((uint64_t)(e - p) < 4 + tail) return bad("the terms run past the end of the file");
+            u32 len;
+            memcpy(&len, p, 4);
+            p += 4;
+            if (len == 0 || (uint64_t)len > (uint64_t)(e - p) || (uint64_t)(e - p) - len < tail) return bad("a term is empty or runs past the end of the file");
+            if (!h->ids.emplace(std::string(p, len), (u32)t).second) return bad("a term occurs twice");
+            p += len;
+        }
+        if ((uint64_t)(e - p) != tail) return bad("the file is longer or shorter than its header says");
+        std::vector<uint64_t> off((size_t)V + 1);
+        memcpy(off.data(), p, 8 * ((size_t)V + 1));
+        p += 8 * (V + 1);
+        if (off[0] != 0 || off[V] != nnz) return bad("the posting offsets do not cover the postings");
+        for (uint64_t t = 0; t < V; ++t)
+            if (off[t + 1] < off[t] || off[t + 1] > nnz) return bad("the posting offsets do not ascend");
+        const char* pdoc = p;
+        const char* ptf = p + 4 * nnz;
+        std::vector<uint64_t> sum((size_t)N, 0);
+        for (uint64_t t = 0; t < V; ++t) {
+            const size_t n = (size_t)(off[t + 1] - off[t]);
+            auto& ps = h->terms[t];
+            ps.doc.resize(n);
+            ps.tf.resize(n);
+            if (n) {
+                memcpy(ps.doc.data(), pdoc + 4 * off[t], 4 * n);
+                memcpy(ps.tf.data(), ptf + 4 * off[t], 4 * n);
+            }
+            for (size_t i = 0; i < n; ++i) {
+                if (ps.doc[i] >= N || (i > 0 && ps.doc[i] <= ps.doc[i - 1])) return bad("a term's postings do not ascend inside [0, N)");
+                if (ps.tf[i] < 1) return bad("a posting has term frequency 0");
+                sum[ps.doc[i]] += ps.tf[i];
+            }
+        }
+        for (uint64_t d = 0; d < N; ++d)
+            if (sum[d] != h->dl[d]) return bad("a document's length differs from the sum of its term frequencies");
+        h->nnz = nnz;
+        recount_live(h);
+    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_load: out of memory"); }
+    drop.h = nullptr;
+    *out = h;
     return RMU_OK;
 }

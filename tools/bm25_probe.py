@@ -10,7 +10,14 @@ Times are host wall-clock around calls that end in a stream synchronise inside t
 the query tokenisation, the descriptor copy, the scoring kernel, the merge and the copy back.  Every shape is warmed up first; the image
 upload of the first search is reported separately.  "postings_bytes" is what the kernel must read for the queries: 8 bytes (document id, tf)
 per posting of every query token plus the 4-byte doc_norm it gathers; bytes / time is the only rate given.
-The GPU step runs in a child process under its own time limit (`--step-timeout`)."""
+The GPU step runs in a child process under its own time limit (`--step-timeout`).
+
+  python tools/bm25_probe.py --lifecycle [--docs 1000000] [--out profiles/bm25_lifecycle.json]
+
+measures, on the same corpus and in one process, what removing documents costs: single-query and batch time with 0 % (bm25_topk_kernel: the
+baseline) and with 10 % of the documents removed (bm25_masked_kernel); rmu_bm25_remove_docs of 1 % of the documents in one call; the first
+search after that removal on the refresh path and, on a second handle with RMU_BM25_OPT_REPACK_ON_REMOVE, on the repack path; compact; save;
+load + first search against building the index from the texts.  No CPU leg."""
 import argparse
 import json
 import os
@@ -94,6 +101,71 @@ def gpu_step(a):
     print("BM25_PROBE_GPU " + json.dumps(res), flush=True)
 
 
+def lifecycle_step(a):
+    import tempfile
+    from ragmeup_amd.bm25 import BM25Index
+    texts = corpus(a.docs, a.vocab)
+    qs = queries(texts, a.singles + a.batch)
+    singles, batch = qs[:a.singles], qs[a.singles:]
+    rng = np.random.default_rng(7)
+    order = rng.permutation(a.docs)
+    one_pct, ten_pct = np.sort(order[:a.docs // 100]), np.sort(order[:a.docs // 10])
+
+    def ms(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    def build(repack):
+        ix = BM25Index()
+        ix.set_option(4, repack)
+        t, _ = ms(lambda: [ix.add_texts(texts[lo:lo + 100_000]) for lo in range(0, len(texts), 100_000)])
+        t2, _ = ms(lambda: ix.search(qs[:1], a.k))
+        return ix, t, t2
+
+    def timed_searches(ix):
+        for q in singles[:5]:
+            ix.search([q], a.k)
+        t_single = [ms(lambda: ix.search([q], a.k))[0] for q in singles]
+        for _ in range(3):
+            ix.search(batch, a.k)
+        t_batch = [ms(lambda: ix.search(batch, a.k))[0] for _ in range(a.reps)]
+        return {"single_query": summary(t_single), "batch": dict(summary(t_batch), queries=len(batch))}
+
+    ix, add_ms, first_ms = build(0)
+    res = {"stat": ix.stat(), "build_from_texts": {"add_texts_ms": round(add_ms, 1), "first_search_with_image_upload_ms": round(first_ms, 1)}}
+    res["removed_0pct_plain_kernel"] = timed_searches(ix)
+    t, n = ms(lambda: ix.remove(one_pct))
+    res["remove_1pct_one_call"] = {"ms": round(t, 2), "documents": n}
+    t, _ = ms(lambda: ix.search(qs[:1], a.k))
+    res["first_search_after_remove_refresh_path_ms"] = round(t, 2)
+    ix2, _, _ = build(1)
+    ix2.remove(one_pct)
+    t, _ = ms(lambda: ix2.search(qs[:1], a.k))
+    res["first_search_after_remove_repack_path_ms"] = round(t, 2)
+    same = all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) and np.array_equal(dx, dy)
+               for (x, dx), (y, dy) in [(ix.search(batch, a.k), ix2.search(batch, a.k))])
+    res["refresh_and_repack_results_identical"] = bool(same)
+    ix2.close()
+    ix.remove(ten_pct)
+    ix.search(qs[:1], a.k)
+    res["removed_10pct_masked_kernel"] = dict(timed_searches(ix), stat=ix.stat())
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "probe.bm25")
+        t, _ = ms(lambda: ix.save(path))
+        res["save"] = {"ms": round(t, 1), "bytes": os.path.getsize(path), "with_removed_documents": True}
+        t, back = ms(lambda: BM25Index.load(path))
+        t2, _ = ms(lambda: back.search(qs[:1], a.k))
+        res["load"] = {"load_ms": round(t, 1), "first_search_with_image_upload_ms": round(t2, 1)}
+        back.close()
+    t, m = ms(ix.compact)
+    res["compact"] = {"ms": round(t, 1), "documents_after": int((m >= 0).sum())}
+    t, _ = ms(lambda: ix.search(qs[:1], a.k))
+    res["first_search_after_compact_ms"] = round(t, 1)
+    ix.close()
+    print("BM25_PROBE_GPU " + json.dumps(res), flush=True)
+
+
 def cpu_sample(a):
     """rank_bm25's get_scores + get_top_n, restated: idf table, per-document tf dicts, per query token a list comprehension over all
     documents, argsort of all scores."""
@@ -141,15 +213,18 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=100_000)
     ap.add_argument("--cpu-queries", type=int, default=8)
     ap.add_argument("--step-timeout", type=int, default=420, help="seconds the GPU step may take")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bm25_probe.json"))
+    ap.add_argument("--lifecycle", action="store_true", help="measure remove / refresh / repack / compact / save / load instead")
+    ap.add_argument("--out", default=None, help="default: profiles/bm25_probe.json, or profiles/bm25_lifecycle.json with --lifecycle")
     ap.add_argument("--gpu-step", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "bm25_lifecycle.json" if a.lifecycle else "bm25_probe.json")
     if a.gpu_step:
         import torch
         if not torch.cuda.is_available():
             raise SystemExit("bm25_probe: no GPU: there is nothing to measure without one")
         print("BM25_PROBE_DEVICE " + torch.cuda.get_device_name(0), flush=True)
-        return gpu_step(a)
+        return lifecycle_step(a) if a.lifecycle else gpu_step(a)
     child = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpu-step"] + [x for x in sys.argv[1:] if x != "--gpu-step"],
                            capture_output=True, text=True, timeout=a.step_timeout)
     if child.returncode != 0:
@@ -161,8 +236,12 @@ def main():
             gpu = json.loads(ln[len("BM25_PROBE_GPU "):])
         if ln.startswith("BM25_PROBE_DEVICE "):
             device = ln[len("BM25_PROBE_DEVICE "):]
-    line = json.dumps({"probe": "bm25", "docs": a.docs, "vocab": a.vocab, "k": a.k, "query_tokens": [8, 16], "device": device,
-                       "timing": "host wall-clock around rmu_bm25_search (ends in a stream synchronise)", "gpu": gpu, "cpu": cpu_sample(a)})
+    if a.lifecycle:
+        line = json.dumps({"probe": "bm25_lifecycle", "docs": a.docs, "vocab": a.vocab, "k": a.k, "query_tokens": [8, 16], "device": device,
+                           "timing": "host wall-clock around each call (searches end in a stream synchronise)", "gpu": gpu})
+    else:
+        line = json.dumps({"probe": "bm25", "docs": a.docs, "vocab": a.vocab, "k": a.k, "query_tokens": [8, 16], "device": device,
+                           "timing": "host wall-clock around rmu_bm25_search (ends in a stream synchronise)", "gpu": gpu, "cpu": cpu_sample(a)})
     print(line, flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
