@@ -406,6 +406,60 @@ int rmu_bm25_compact(rmu_bm25_t* h, int64_t* old_to_new, int64_t map_len, int64_
 int rmu_bm25_save(rmu_bm25_t* h, const char* path);
 int rmu_bm25_load(rmu_bm25_t** out, const char* path);
 
+/* ---- hybrid retrieval: reciprocal-rank fusion on the device, and the ensemble's whole retrieval step as one call (rrf_fuse.hip) ----------
+ * Serves: EnsembleRetriever([bm25, dense_mmr], weights=[0.5, 0.5]).invoke, the only retrieval call of the reference's chains
+ * (RAGHelper.py:497-503, RAGHelper_local.py:251-259): langchain's weighted_reciprocal_rank with c = 60, documents identified by page_content.
+ *
+ * rmu_rrf_fuse: weighted reciprocal-rank fusion of `lists` ranked key lists per query.  keys [lists, nq, depth] int64, best first; a key is >= 0,
+ * -1 = absent (anywhere in a list).  Per query, with the entries taken in CHAIN order (list 0 first, positions ascending):
+ *   rank   = 1 + the present entries in front of the entry in its own list (an absent slot consumes no rank);
+ *   score  = the fp64 sum, in chain order from 0.0, of weights[l] / (rank + c) over every entry holding the key (duplicates inside a list count);
+ *   output = the distinct keys, score descending, equal scores in order of their first entries -- Python's stable sort over first-seen order, so
+ *            with equal weights rank r of list 0 comes before rank r of list 1.
+ * The quotients are computed on the host and only added on the device, in Python's order: out_scores has the bits of
+ * ragmeup_amd.ensemble.weighted_reciprocal_rank's sums.  out_scores [nq, k_out] fp64, out_keys [nq, k_out] int64, out_src [nq, k_out] int32 =
+ * list * depth + position of the key's first entry; slots beyond the distinct keys hold (-inf, -1, -1).
+ * weights [lists]: HOST fp64, finite and >= 0; c >= 0; 1 <= lists <= RMU_RRF_MAX_LISTS, 1 <= depth <= RMU_MAX_K, 1 <= k_out <= lists * depth,
+ * 1 <= nq; anything else is RMU_E_INVALID before any HIP call.  flags: RMU_F_Q_DEVICE (keys is a device address), RMU_F_OUT_DEVICE (the three
+ * outputs are).  hip_stream as rmu_topk_merge: drained on return unless a caller stream is given with device keys AND device outputs. */
+#define RMU_RRF_MAX_LISTS 4
+int rmu_rrf_fuse(const int64_t* keys, int lists, int64_t nq, int depth, const double* weights, int c, int k_out,
+                 unsigned flags, double* out_scores, int64_t* out_keys, int32_t* out_src, uint64_t hip_stream);
+
+/* The two members of the ensemble behind one handle.  The members are BORROWED: never freed here, and they must outlive the handle.  Either
+ * may be NULL (not both): an absent member contributes an empty list and its key table must stay empty. */
+typedef struct rmu_hybrid rmu_hybrid_t;
+int rmu_hybrid_create(rmu_hybrid_t** out, rmu_bm25_t* sparse, rmu_index_t* dense);
+int rmu_hybrid_free(rmu_hybrid_t* h);
+/* The identity of the members' records: keys[i] = key of document id / row id first + i of `member` (0 = sparse, 1 = dense); two records are
+ * the same document iff their keys are equal (the host numbers the classes of page_content).  Writes [first, first + n) of the member's table
+ * from a HOST array; first <= the table's current length, which becomes first + n: first = 0 replaces the table, first = length appends, n = 0
+ * truncates.  Every key >= 0.  Host only (the device copy follows at the next search); RMU_E_INVALID changes nothing. */
+int rmu_hybrid_set_keys(rmu_hybrid_t* h, int member, int64_t first, const int64_t* keys, int64_t n);
+/* The retrieval step in ONE call with ONE synchronisation.  HOST q [nq, dim of the dense member] fp32 and the NUL-separated query blob of
+ * rmu_bm25_search (the same nq queries as text).  On one stream (hip_stream, or the calling thread's own) it enqueues rmu_bm25_search's work for
+ * k_sparse, rmu_index_search_mmr's for (fetch_k, k_dense, lambda_mult; lambda_mult < 0: no selection, the top-k_dense in score order, as in
+ * rmu_bert_search_mmr), the fusion of the two lists read through the key tables -- the sparse list is list 0 -- and one copy of the results;
+ * then it drains the stream.  The two lists inside the call are, bit for bit, what those two calls return on their own, and the fusion is
+ * rmu_rrf_fuse's over their keys.
+ * HOST outputs, [nq, k_out] each: out_scores fp64; out_ids int64 and out_member int32 name each fused hit by the first entry that holds its key:
+ * the member (0 / 1) and that member's own id (document id / row id).  Slots beyond the distinct keys hold (-inf, -1, -1).
+ * weights [2] (sparse, dense) and c as rmu_rrf_fuse; 1 <= k_out <= k_sparse + k_dense.
+ * Checked before anything is enqueued, the members' records under their shared locks: every limit of rmu_bm25_search and rmu_index_search_mmr,
+ * and that each table is as long as its member (BM25 DOCS / index rows) -- otherwise RMU_E_INVALID with a message that contains "out of step":
+ * the caller refreshes the table and repeats the call.  Ids the tables do not cover can therefore not occur.  A member with nothing live
+ * contributes an empty list (BM25: no device work). */
+int rmu_hybrid_search(rmu_hybrid_t* h, const float* q, int64_t nq, const char* query_blob, int64_t bytes,
+                      int k_sparse, int fetch_k, int k_dense, double lambda_mult, const double* weights /* [2]: sparse, dense */, int c,
+                      int k_out, double* out_scores, int64_t* out_ids, int32_t* out_member, uint64_t hip_stream);
+/* The same call behind the encoder forward (the pattern of rmu_bert_search_mmr): HOST token ids of `batch` queries in (as rmu_bert_encode_host;
+ * a pooling mode), their texts in query_blob; the pooled vectors stay on the device, everything runs on the encoder's stream, one
+ * synchronisation.  The dense member must hold 384-d rows.  Results equal rmu_bert_search_mmr's rows and rmu_bm25_search's documents fused. */
+int rmu_bert_search_hybrid(rmu_bert_t* m, rmu_hybrid_t* h, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch,
+                           int max_len, int mode, const char* query_blob, int64_t bytes, int k_sparse, int fetch_k, int k_dense,
+                           double lambda_mult, const double* weights, int c, int k_out, double* out_scores, int64_t* out_ids,
+                           int32_t* out_member);
+
 #ifdef __cplusplus
 }
 #endif

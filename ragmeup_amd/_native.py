@@ -30,6 +30,7 @@ MAX_DIM = 768            # widest row of the register-resident scans
 MAX_DIM_WIDE = 3072      # widest row of an index (ip / cosine)
 BM25_STAT_DOCS, BM25_STAT_VOCAB, BM25_STAT_NNZ, BM25_STAT_AVGDL, BM25_STAT_LIVE_DOCS = 1, 2, 3, 4, 5
 BM25_OPT_TILE_DOCS, BM25_OPT_MAX_WGS, BM25_OPT_REPACK_ON_REMOVE = 1, 2, 4
+RRF_MAX_LISTS = 4
 
 # every symbol include/rmu.h declares (tests check the .so exports all of them)
 SYMBOLS = [
@@ -42,6 +43,7 @@ SYMBOLS = [
     "rmu_tok_create", "rmu_tok_free", "rmu_tok_vocab_size", "rmu_tok_encode", "rmu_tok_encode_blob",
     "rmu_bm25_create", "rmu_bm25_free", "rmu_bm25_add_texts", "rmu_bm25_stat", "rmu_bm25_df", "rmu_bm25_set_option", "rmu_bm25_search",
     "rmu_bm25_remove_docs", "rmu_bm25_search_subset", "rmu_bm25_compact", "rmu_bm25_save", "rmu_bm25_load",
+    "rmu_rrf_fuse", "rmu_hybrid_create", "rmu_hybrid_free", "rmu_hybrid_set_keys", "rmu_hybrid_search", "rmu_bert_search_hybrid",
 ]
 
 
@@ -108,12 +110,19 @@ def _declare(lib):
     lib.rmu_bm25_compact.argtypes = [vp, vp, i64, c.POINTER(i64)]
     lib.rmu_bm25_save.argtypes = [vp, c.c_char_p]
     lib.rmu_bm25_load.argtypes = [c.POINTER(vp), c.c_char_p]
+    f64p = c.POINTER(c.c_double)
+    lib.rmu_rrf_fuse.argtypes = [vp, i32, i64, i32, f64p, i32, i32, u32, vp, vp, vp, u64]
+    lib.rmu_hybrid_create.argtypes = [c.POINTER(vp), vp, vp]
+    lib.rmu_hybrid_free.argtypes = [vp]
+    lib.rmu_hybrid_set_keys.argtypes = [vp, i32, i64, vp, i64]
+    lib.rmu_hybrid_search.argtypes = [vp, vp, i64, c.c_char_p, i64, i32, i32, i32, c.c_double, f64p, i32, i32, vp, vp, vp, u64]
     if hasattr(lib, "rmu_bert_create"):
         lib.rmu_bert_create.argtypes = [c.POINTER(vp), vp, c.POINTER(vp), i32]
         lib.rmu_bert_free.argtypes = [vp]
         lib.rmu_bert_encode.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i64, u64]
         lib.rmu_bert_encode_host.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i64]
         lib.rmu_bert_search_mmr.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, c.c_double, i64, vp, vp, vp]
+        lib.rmu_bert_search_hybrid.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, c.c_char_p, i64, i32, i32, i32, c.c_double, f64p, i32, i32, vp, vp, vp]
 
 
 def lib():

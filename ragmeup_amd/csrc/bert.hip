@@ -3727,3 +3727,38 @@ extern "C" int rmu_bert_search_mmr(rmu_bert_t* m, rmu_index_t* idx, const int32_
     if (out_vecs) memcpy(out_vecs, m->h_out, (size_t)batch * H * sizeof(float));
     return RMU_OK;
 }
+
+// The reference's whole retrieval step behind the forward (EnsembleRetriever([bm25, dense_mmr]).invoke, server/RAGHelper.py:497-503): token ids and
+// the query texts in, fused hits out.  The pooled vectors stay on the device and feed rmu_hybrid_search's work (rrf_fuse.hip: BM25 search, dense
+// search + selection, fusion) enqueued behind the forward on the encoder's stream; one synchronisation.
+extern "C" int rmu_hybrid_check_(rmu_hybrid_t* h, rmu_index_t** dense, int64_t nq, const char* query_blob, int64_t bytes, int k_sparse, int fetch_k,
+                                 int k_dense, const double* weights, int c, int k_out, double* out_scores, int64_t* out_ids, int32_t* out_member);
+extern "C" int rmu_hybrid_search_dev_(rmu_hybrid_t* h, const float* q_dev, int64_t nq, const char* query_blob, int64_t bytes, int k_sparse, int fetch_k,
+                                      int k_dense, double lambda_mult, const double* weights, int c, int k_out, double* out_scores, int64_t* out_ids,
+                                      int32_t* out_member, void* hip_stream);
+extern "C" int rmu_bert_search_hybrid(rmu_bert_t* m, rmu_hybrid_t* h, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch,
+                                      int max_len, int mode, const char* query_blob, int64_t bytes, int k_sparse, int fetch_k, int k_dense,
+                                      double lambda_mult, const double* weights, int c, int k_out, double* out_scores, int64_t* out_ids,
+                                      int32_t* out_member) {
+    RMU_ENTRY();
+    if (!h || !out_scores) return bfail(RMU_E_INVALID, "rmu_bert_search_hybrid: null argument");
+    int rc = check_encode_args(m, ids, lens, out_scores, batch, max_len, mode, H);
+    if (rc) return rc;
+    const int kind = mode & 0xff;
+    if (kind != RMU_BERT_POOL_MEAN && kind != RMU_BERT_POOL_CLS) return bfail(RMU_E_INVALID, "rmu_bert_search_hybrid: mode must be a pooling mode");
+    rmu_index_t* idx = nullptr;
+    rc = rmu_hybrid_check_(h, &idx, batch, query_blob, bytes, k_sparse, fetch_k, k_dense, weights, c, k_out, out_scores, out_ids, out_member);
+    if (rc) return rc;
+    int dim = 0;
+    if (!idx || rmu_index_dim(idx, &dim) != RMU_OK || dim != 384)
+        return bfail(RMU_E_INVALID, "rmu_bert_search_hybrid: the dense member must be an index of 384-d rows (the encoder's width)");
+    std::unique_lock<std::mutex> lk;
+    m = acquire_ctx(m, lk);
+    rc = host_forward_locked(m, ids, type_ids, lens, batch, max_len, mode, "rmu_bert_search_hybrid");
+    if (rc) return rc;
+    // drains m->stream: forward, both members' searches, the fusion and the copy of the results
+    rc = rmu_hybrid_search_dev_(h, m->d_out, batch, query_blob, bytes, k_sparse, fetch_k, k_dense, lambda_mult, weights, c, k_out, out_scores, out_ids,
+                                out_member, (void*)m->stream);
+    if (rc) { (void)hipStreamSynchronize(m->stream); return rc; }
+    return RMU_OK;
+}

@@ -592,10 +592,16 @@ extern "C" int rmu_bm25_set_option(rmu_bm25_t* h, int option, int64_t value) {
     return RMU_OK;
 }
 
-// rmu_bm25_search (subset = false) and rmu_bm25_search_subset (candidates = the live documents of docs[0, n_sub))
-static int search_impl(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, bool subset, const int64_t* docs,
-                       int64_t n_sub, float* out_scores, int64_t* out_docs, uint64_t hip_stream) {
-    if (!h || !query_blob || !out_scores || !out_docs) return mfail(RMU_E_INVALID, "rmu_bm25_search: null argument");
+// The first half of a search: everything up to and including the final merge is enqueued on *s_out (hip_stream, or the calling thread's own
+// stream) and the results are left on the device, *d_docs [nq, k] int64 (+ doc_base) and *d_scores [nq, k] fp32, in the thread's workspace.  `lk`
+// comes back holding the handle's shared lock, which the caller keeps until it has drained the stream (see the header: no reader is ever left in
+// flight behind the lock).  *empty: there is nothing to search (every slot is (-inf, -1)) and nothing was enqueued.  expect_docs >= 0 (the hybrid
+// call, rrf_fuse.hip): DOCS must equal it, checked under the lock before anything is enqueued.
+static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, bool subset, const int64_t* docs,
+                          int64_t n_sub, int64_t expect_docs, uint64_t hip_stream, std::shared_lock<std::shared_mutex>& lk, hipStream_t* s_out,
+                          int64_t** d_docs_out, float** d_scores_out, bool* empty) {
+    *empty = false;
+    if (!h || !query_blob) return mfail(RMU_E_INVALID, "rmu_bm25_search: null argument");
     if (nq < 1 || nq > 65535 || bytes < nq) return mfail(RMU_E_INVALID, "rmu_bm25_search: 1 <= nq <= 65535 queries, each NUL-terminated");
     if (k < 1 || k > RMU_MAX_K) return mfail(RMU_E_INVALID, "rmu_bm25_search: 1 <= k <= RMU_MAX_K");
     std::vector<std::pair<const char*, size_t>> qs;
@@ -612,12 +618,15 @@ static int search_impl(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int
     Ctx& c = g_ctx;
     hipStream_t s = nullptr;
     const auto nothing = [&]() {
-        for (int64_t i = 0; i < nq * k; ++i) { out_scores[i] = -INFINITY; out_docs[i] = -1; }
+        *empty = true;
         return RMU_OK;
     };
-    std::shared_lock<std::shared_mutex> lk(h->mu);
+    lk = std::shared_lock<std::shared_mutex>(h->mu);
     for (;;) {
         if (h->broken) return mfail(RMU_E_OOM, "rmu_bm25_search: an earlier add ran out of memory, the index is unusable");
+        if (expect_docs >= 0 && (int64_t)h->dl.size() != expect_docs)
+            return mfail(RMU_E_INVALID, "rmu_hybrid_search: the sparse key table (" + std::to_string(expect_docs) + " keys) and the BM25 index (" +
+                                            std::to_string(h->dl.size()) + " documents) are out of step");
         if (subset) {                            // (again after the lock was given up: documents may have been added, never renumbered unseen)
             const int64_t n_docs = (int64_t)h->dl.size();
             for (int64_t i = 0; i < n_sub; ++i)
@@ -712,10 +721,43 @@ static int search_impl(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int
     float* d_scores = (float*)((char*)c.out.p + (size_t)nq * k * sizeof(int64_t));
     const int rc = rmu_merge_final_launch((const u64*)c.partial.p, parts, nq, k, doc_base, 0, nullptr, d_scores, d_docs, nullptr, nullptr, s);
     if (rc != RMU_OK) { (void)hipStreamSynchronize(s); return mfail(rc, "rmu_bm25_search: merge launch failed"); }
+    *s_out = s;
+    *d_docs_out = d_docs;
+    *d_scores_out = d_scores;
+    return RMU_OK;
+}
+
+// rmu_bm25_search (subset = false) and rmu_bm25_search_subset (candidates = the live documents of docs[0, n_sub)): the half above, then the
+// copies to the caller's arrays and the one synchronisation
+static int search_impl(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, bool subset, const int64_t* docs,
+                       int64_t n_sub, float* out_scores, int64_t* out_docs, uint64_t hip_stream) {
+    if (!h || !query_blob || !out_scores || !out_docs) return mfail(RMU_E_INVALID, "rmu_bm25_search: null argument");
+    std::shared_lock<std::shared_mutex> lk;
+    hipStream_t s = nullptr;
+    int64_t* d_docs = nullptr;
+    float* d_scores = nullptr;
+    bool empty = false;
+    const int rc = search_enqueue(h, query_blob, bytes, nq, k, doc_base, subset, docs, n_sub, -1, hip_stream, lk, &s, &d_docs, &d_scores, &empty);
+    if (rc != RMU_OK) return rc;
+    if (empty) {
+        for (int64_t i = 0; i < nq * k; ++i) { out_scores[i] = -INFINITY; out_docs[i] = -1; }
+        return RMU_OK;
+    }
     BM25_TRY(hipMemcpyAsync(out_docs, d_docs, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     BM25_TRY(hipMemcpyAsync(out_scores, d_scores, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s));
     BM25_TRY(hipStreamSynchronize(s));
     return RMU_OK;
+}
+
+// rrf_fuse.hip (rmu_hybrid_search): the sparse member's list, left on the device on the caller's stream (rmu_common.h)
+int rmu_bm25_search_enqueue_(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t expect_docs, hipStream_t stream,
+                             std::shared_lock<std::shared_mutex>& lk, const int64_t** d_docs, bool* empty) {
+    hipStream_t s = nullptr;
+    int64_t* docs = nullptr;
+    float* scores = nullptr;
+    const int rc = search_enqueue(h, query_blob, bytes, nq, k, 0, false, nullptr, 0, expect_docs, (uint64_t)(uintptr_t)stream, lk, &s, &docs, &scores, empty);
+    *d_docs = docs;
+    return rc;
 }
 
 extern "C" int rmu_bm25_search(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, float* out_scores,

@@ -960,10 +960,14 @@ extern "C" int rmu_index_mmr(rmu_index_t* idx, const float* q, int64_t nq, const
     return RMU_OK;
 }
 
-// dense top-fetch_k + greedy selection of `nq` queries (host or device fp32 [nq, dim]) on stream s; HOST results; drains s.
-// lambda_mult < 0: no selection -- the top-k (k <= fetch_k) in score order, as rmu_index_search returns them.
-static int search_mmr_on(rmu_index_t* idx, const float* q, bool q_dev, int64_t nq, int fetch_k, int k, double lambda_mult, int64_t row_base,
-                         int64_t* out_rows, float* out_scores, hipStream_t s, const char* who) {
+// dense top-fetch_k + greedy selection of `nq` queries (host or device fp32 [nq, dim]), first half: everything is enqueued on stream s and the
+// results are left on the device, *d_rows_out = rows [nq, k] int64 (+ row_base) with the scores [nq, k] fp32 right behind them (one contiguous
+// block of the thread's workspace).  `lk` comes back holding the index's shared lock: the selection kernel reads the corpus matrix behind the
+// search's reader mark, so the caller keeps the lock until it has drained s.  lambda_mult < 0: no selection -- the top-k (k <= fetch_k) in score
+// order, as rmu_index_search returns them.  expect_rows >= 0 (the hybrid call, rrf_fuse.hip): the index must hold exactly that many rows, checked
+// under the lock before anything is enqueued.
+static int search_mmr_enqueue(rmu_index_t* idx, const float* q, bool q_dev, int64_t nq, int fetch_k, int k, double lambda_mult, int64_t row_base,
+                              int64_t expect_rows, hipStream_t s, const char* who, std::shared_lock<std::shared_mutex>& lk, int64_t** d_rows_out) {
     Tls& t = g_tls;
     const size_t nf = (size_t)nq * fetch_k, nk = (size_t)nq * k;
     // candidate scores / rows, the raw queries (the search normalises its own copy for COSINE), picks, and the results (rows | scores)
@@ -973,16 +977,21 @@ static int search_mmr_on(rmu_index_t* idx, const float* q, bool q_dev, int64_t n
     int64_t* d_rows = (int64_t*)t.mm_p.p;
     float* d_sc = (float*)(d_rows + nk);
     int* d_pos = (int*)(d_sc + nk);
+    if (expect_rows >= 0) {
+        std::shared_lock<std::shared_mutex> chk(idx->mu);
+        if (idx->n != expect_rows)
+            return fail(RMU_E_INVALID, std::string(who) + ": the dense key table (" + std::to_string(expect_rows) + " keys) and the index (" +
+                                           std::to_string(idx->n) + " rows) are out of step");
+    }
     // (round 5: every stream operation of the one-query path is ~4.4 us of dependent-kernel boundary.)  No selection and fetch_k == k: the
-    // search writes the result rows (row_base applied) and scores where the copy below reads them -- no k_take_picks launch.
+    // search writes the result rows (row_base applied) and scores where the caller reads them -- no k_take_picks launch.
     const bool direct = lambda_mult < 0.0 && fetch_k == k;
-    if (t.ensure_hpin(nk * (sizeof(int64_t) + sizeof(float)))) return fail(RMU_E_OOM, std::string(who) + ": pinned result buffer");
     // the search on the given stream, results left on the device (no synchronisation inside)
     int rc = direct ? rmu_index_search(idx, q, nq, k, RMU_F_OUT_DEVICE | (q_dev ? RMU_F_Q_DEVICE : 0u), row_base, d_sc, d_rows, (uint64_t)(uintptr_t)s)
                     : rmu_index_search(idx, q, nq, fetch_k, RMU_F_OUT_DEVICE | (q_dev ? RMU_F_Q_DEVICE : 0u), 0, (float*)t.mm_s.p, (int64_t*)t.mm_r.p,
                                        (uint64_t)(uintptr_t)s);
     if (rc) return rc;
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    lk = std::shared_lock<std::shared_mutex>(idx->mu);
     if (!direct) {
         const float* dq = q;
         if (!q_dev && lambda_mult >= 0.0) {
@@ -994,6 +1003,20 @@ static int search_mmr_on(rmu_index_t* idx, const float* q, bool q_dev, int64_t n
                            (const int64_t*)t.mm_r.p, (const float*)t.mm_s.p, nq, fetch_k, k, row_base, d_rows, d_sc);
         HIP_TRY(hipGetLastError());
     }
+    *d_rows_out = d_rows;
+    return RMU_OK;
+}
+
+// ... and the second half: HOST results; drains s.
+static int search_mmr_on(rmu_index_t* idx, const float* q, bool q_dev, int64_t nq, int fetch_k, int k, double lambda_mult, int64_t row_base,
+                         int64_t* out_rows, float* out_scores, hipStream_t s, const char* who) {
+    Tls& t = g_tls;
+    const size_t nk = (size_t)nq * k;
+    if (t.ensure_hpin(nk * (sizeof(int64_t) + sizeof(float)))) return fail(RMU_E_OOM, std::string(who) + ": pinned result buffer");
+    std::shared_lock<std::shared_mutex> lk;
+    int64_t* d_rows = nullptr;
+    const int rc = search_mmr_enqueue(idx, q, q_dev, nq, fetch_k, k, lambda_mult, row_base, -1, s, who, lk, &d_rows);
+    if (rc) return rc;
     // rows | scores are contiguous on the device: ONE copy into pinned memory (a copy into the caller's pageable arrays is staged by the
     // runtime, one staging round per call), split on the host behind the synchronisation
     HIP_TRY(hipMemcpyAsync(t.hpin, d_rows, nk * (sizeof(int64_t) + sizeof(float)), hipMemcpyDeviceToHost, s));
@@ -1002,6 +1025,23 @@ static int search_mmr_on(rmu_index_t* idx, const float* q, bool q_dev, int64_t n
     if (out_scores) memcpy(out_scores, t.hpin + nk * sizeof(int64_t), nk * sizeof(float));
     t.finished(s, true);
     return RMU_OK;
+}
+
+// rrf_fuse.hip (rmu_hybrid_search; prototypes in rmu_common.h): the calling thread's stream, the dense member's list left on the device on it, and
+// the end-of-call bookkeeping of the thread's workspaces
+int rmu_thread_stream_(hipStream_t user, hipStream_t* s) {
+    const int rc = g_tls.ensure_stream(user);
+    if (rc) return fail(rc, "cannot create the calling thread's stream");
+    *s = user ? user : g_tls.stream;
+    return RMU_OK;
+}
+void rmu_thread_finished_(hipStream_t s, bool drained) { g_tls.finished(s, drained); }
+int rmu_index_search_mmr_enqueue_(rmu_index_t* idx, const float* q, bool q_dev, int64_t nq, int fetch_k, int k, double lambda_mult, int64_t expect_rows,
+                                  hipStream_t s, const char* who, std::shared_lock<std::shared_mutex>& lk, const int64_t** d_rows) {
+    int64_t* rows = nullptr;
+    const int rc = search_mmr_enqueue(idx, q, q_dev, nq, fetch_k, k, lambda_mult, 0, expect_rows, s, who, lk, &rows);
+    *d_rows = rows;
+    return rc;
 }
 
 extern "C" int rmu_index_search_mmr(rmu_index_t* idx, const float* q, int64_t nq, int fetch_k, int k, double lambda_mult, int64_t row_base,

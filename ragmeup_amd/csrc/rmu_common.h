@@ -1,6 +1,7 @@
 // rmu_common.h -- shared device/host helpers for librmu.so (gfx950 only).
 #pragma once
 #include <mutex>
+#include <shared_mutex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -218,6 +219,19 @@ inline void rmu_plan_chunks(int nqt, int64_t tiles_total, int* s_chunks, int* ti
     if (used > 0 && used < s) s = (int)used;
     *s_chunks = s;
 }
+
+// ---- the one-call hybrid (rrf_fuse.hip) borrows the first halves of the members' searches: everything enqueued on ONE stream, results left on
+// the device, the member's shared lock handed back held (the caller releases it once it has drained the stream) --------------------------------
+struct rmu_index;
+struct rmu_bm25;
+int rmu_thread_stream_(hipStream_t user, hipStream_t* s);         // rmu_api.hip: the stream a call of this thread runs on (user, or the thread's own)
+void rmu_thread_finished_(hipStream_t s, bool drained);           // rmu_api.hip: end of a call that used the thread's workspaces on s
+// *d_rows: [nq, k] int64 row ids in pick order (-1 = none); expect_rows >= 0: RMU_E_INVALID ("out of step") unless the index holds that many rows
+int rmu_index_search_mmr_enqueue_(rmu_index* idx, const float* q, bool q_dev, int64_t nq, int fetch_k, int k, double lambda_mult, int64_t expect_rows,
+                                  hipStream_t s, const char* who, std::shared_lock<std::shared_mutex>& lk, const int64_t** d_rows);
+// *d_docs: [nq, k] int64 document ids, best first (-1 = none); *empty: no live document, nothing enqueued; expect_docs as expect_rows
+int rmu_bm25_search_enqueue_(rmu_bm25* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t expect_docs, hipStream_t stream,
+                             std::shared_lock<std::shared_mutex>& lk, const int64_t** d_docs, bool* empty);
 
 int rmu_device_ordinal();                                // the device rmu_init chose, -1 before it (rmu_api.hip): per-thread contexts of other units follow it
 int rmu_scan_plan(ScanLaunch* p);                        // chooses geometry; returns 0 or RMU_E_INVALID
