@@ -341,7 +341,9 @@ int rmu_tok_encode_blob(rmu_tok_t* tk, const char* blob_a, int64_t bytes_a, cons
  * Every document is a candidate, zero and negative scores included.  Order: score descending, then LOWER document id -- rank_bm25's
  * argsort()[::-1] puts the higher id first among equal scores and is not stable, so equal-scoring documents may come back in another order.
  * Document ids are int64 numbers in insertion order.  The master postings live on the host (add_texts, stat and df never touch the GPU);
- * the first search after an add packs them and uploads one image.
+ * the first search packs them and uploads one image.  The first search after a later add packs and uploads only the added documents'
+ * postings and splices them into the image on the device (host work O(vocabulary + new postings) + the O(N) doc_norm pass; the old postings
+ * never cross the bus again) -- unless RMU_BM25_OPT_REPACK_ON_ADD is 1, or the image was not there: then it packs the whole image again.
  *
  * Live documents.  A document is LIVE until rmu_bm25_remove_docs removes it; a removed document keeps its id until rmu_bm25_compact, and no id is
  * reused before that.  Every search after a removal returns what rank_bm25.BM25Okapi built over the live documents in id order would return,
@@ -361,6 +363,10 @@ int rmu_bm25_add_texts(rmu_bm25_t* h, const char* blob, int64_t bytes, int64_t n
 #define RMU_BM25_STAT_NNZ 3     /* postings = (term, live document) pairs */
 #define RMU_BM25_STAT_AVGDL 4   /* mean tokens per live document (0 when there is none) */
 #define RMU_BM25_STAT_LIVE_DOCS 5 /* live documents */
+/* Counters of the device image, all 0 until the first search (host-only reads like the others): */
+#define RMU_BM25_STAT_IMAGE_PACKS 16        /* full packs: every master posting packed on the host and uploaded */
+#define RMU_BM25_STAT_IMAGE_SPLICES 17      /* splices: only the added documents' postings packed and uploaded, the image re-laid on the device */
+#define RMU_BM25_STAT_IMAGE_UPLOAD_BYTES 18 /* host-to-device bytes of postings and posting pointers so far, both paths (not: doc_norm, bitmap, descriptors) */
 int rmu_bm25_stat(rmu_bm25_t* h, int what, double* out);
 /* Live documents that contain the term (0 for an unknown one).  Host only. */
 int rmu_bm25_df(rmu_bm25_t* h, const char* term_utf8, int64_t* df);
@@ -370,6 +376,8 @@ int rmu_bm25_df(rmu_bm25_t* h, const char* term_utf8, int64_t* df);
 #define RMU_BM25_OPT_MAX_WGS 2    /* workgroups per query (= part lists of the final merge), at most 1024 */
 #define RMU_BM25_OPT_REPACK_ON_REMOVE 4 /* 0 or 1.  1: a removal marks the image dirty (the next search repacks it without the removed documents'
                                          * postings) instead of stale (the next search refreshes weights, doc_norm and the liveness bitmap only) */
+#define RMU_BM25_OPT_REPACK_ON_ADD 8    /* 0 or 1.  1: an add marks the image dirty (the next search packs and uploads every posting again)
+                                         * instead of grown (the next search uploads the added postings and splices them in on the device) */
 int rmu_bm25_set_option(rmu_bm25_t* h, int option, int64_t value);
 /* Top-k of nq queries (a NUL-separated blob like add_texts'; at most 1024 tokens per query, 1 <= nq <= 65535, 1 <= k <= RMU_MAX_K; otherwise
  * RMU_E_INVALID before anything is enqueued).  HOST outputs out_scores [nq, k] fp32 and out_docs [nq, k] int64 (+ doc_base), best first;
@@ -381,8 +389,8 @@ int rmu_bm25_search(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_
  * removed, or given twice, counts once or not at all; *n_removed (may be NULL) = the documents that were live.  Recounts df in one pass over
  * the master postings -- O(postings) per CALL, so batch the ids -- and marks the device image stale: the first search afterwards recomputes the
  * weights and doc_norm from the live statistics and uploads them with a liveness bitmap (4 bytes + 1 bit per document); the postings image is
- * not repacked, and the postings of removed documents stay in it until the next repack (an add, or a compact).  Results are the same, bit for
- * bit, on either path. */
+ * not repacked, and the postings of removed documents stay in it until the next repack (a compact; an add splices and keeps them, unless
+ * RMU_BM25_OPT_REPACK_ON_ADD is set).  Results are the same, bit for bit, on either path. */
 int rmu_bm25_remove_docs(rmu_bm25_t* h, const int64_t* docs, int64_t n, int64_t* n_removed);
 /* rmu_bm25_search over a subset: the candidates are the LIVE documents of docs[0, n_sub), a HOST list of strictly ascending document ids
  * (checked before anything is enqueued: not ascending, or outside [0, DOCS), gives RMU_E_INVALID); one list serves all queries.  The statistics
@@ -395,7 +403,7 @@ int rmu_bm25_search_subset(rmu_bm25_t* h, const char* query_blob, int64_t bytes,
 /* Reclaim removed documents (the contract of rmu_index_compact): live documents keep their order and become 0 .. n_live-1.  old_to_new
  * [map_len] receives the new id of every old one, -1 for removed ids and for the entries [DOCS, map_len); map_len < DOCS gives RMU_E_INVALID
  * and changes nothing.  *n_after (may be NULL) = documents afterwards.  With no removed document nothing changes and the image stays clean.
- * Host only: the next search repacks the image.  Term ids stay; a term left without postings is out of the statistics.  Results afterwards
+ * Host only: the next search repacks the whole image (adds after that are spliced in again).  Term ids stay; a term left without postings is out of the statistics.  Results afterwards
  * equal those before with ids mapped, bit for bit. */
 int rmu_bm25_compact(rmu_bm25_t* h, int64_t* old_to_new, int64_t map_len, int64_t* n_after);
 /* One flat little-endian file: "RMUBM25\0", u32 version (1), u32 0 | f64 k1, b, epsilon | u64 N, V, nnz | u32 dl[N] | u8 liveness[N] | the V

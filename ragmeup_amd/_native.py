@@ -30,6 +30,8 @@ MAX_DIM = 768            # widest row of the register-resident scans
 MAX_DIM_WIDE = 3072      # widest row of an index (ip / cosine)
 BM25_STAT_DOCS, BM25_STAT_VOCAB, BM25_STAT_NNZ, BM25_STAT_AVGDL, BM25_STAT_LIVE_DOCS = 1, 2, 3, 4, 5
 BM25_OPT_TILE_DOCS, BM25_OPT_MAX_WGS, BM25_OPT_REPACK_ON_REMOVE = 1, 2, 4
+BM25_OPT_REPACK_ON_ADD = 8
+BM25_STAT_IMAGE_PACKS, BM25_STAT_IMAGE_SPLICES, BM25_STAT_IMAGE_UPLOAD_BYTES = 16, 17, 18
 RRF_MAX_LISTS = 4
 
 # every symbol include/rmu.h declares (tests check the .so exports all of them)

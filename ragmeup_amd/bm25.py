@@ -71,7 +71,8 @@ class BM25Index:
             pass
 
     def add_texts(self, texts: Iterable[str]) -> int:
-        """Append documents (host only; the next search uploads the image); returns the id of the first one."""
+        """Append documents (host only; the next search uploads their postings and splices them into the image); returns the id of
+        the first one."""
         texts = list(texts)
         blob = _blob(texts)
         first = ctypes.c_int64()
@@ -90,6 +91,18 @@ class BM25Index:
             out[name] = float(v.value) if name == "avgdl" else int(v.value)
         if out["live"] == out["docs"]:
             del out["live"]
+        return out
+
+    def image_stat(self) -> dict:
+        """What the device image has cost so far: "packs" (whole image packed and uploaded), "splices" (only the added documents'
+        postings uploaded and spliced in on the device) and "upload_bytes" (postings and posting pointers sent, both paths); all 0
+        until the first search."""
+        out = {}
+        for name, what in (("packs", N.BM25_STAT_IMAGE_PACKS), ("splices", N.BM25_STAT_IMAGE_SPLICES),
+                           ("upload_bytes", N.BM25_STAT_IMAGE_UPLOAD_BYTES)):
+            v = ctypes.c_double()
+            N.check(self._lib.rmu_bm25_stat(self._h, what, ctypes.byref(v)), "rmu_bm25_stat")
+            out[name] = int(v.value)
         return out
 
     def __len__(self) -> int:

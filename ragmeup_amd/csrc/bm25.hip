@@ -19,9 +19,14 @@
 //
 // Host (plain C++, no HIP: testable without a GPU): whitespace tokenizer over a NUL-separated blob, term -> id map, per-term master posting
 // vectors (ascending document id, tf) and dl.  Adding documents appends; document ids are insertion order.
-// Device image, built lazily by the first search after an add (one packed copy per dirty search; the reference rebuilds its whole retriever per
-// upload): post_doc[nnz] u32, post_tf[nnz] u32, doc_norm[N] fp32 = k1 * (1 - b + b * dl / avgdl) computed in double.  post_ptr[V + 1] and the
-// fp32 term weights idf * (k1 + 1) stay on the host: a search resolves its terms there and ships (posting begin, length, weight) descriptors.
+// Device image, built lazily by the first search (one packed copy; the reference rebuilds its whole retriever per upload): post_doc[nnz] u32,
+// post_tf[nnz] u32, doc_norm[N] fp32 = k1 * (1 - b + b * dl / avgdl) computed in double.  post_ptr[V + 1] and the fp32 term weights
+// idf * (k1 + 1) stay on the host: a search resolves its terms there and ships (posting begin, length, weight) descriptors.
+// ADDED DOCUMENTS: an add to a handle with a clean or stale image marks it GROWN.  New documents have the highest ids, so a term's new
+// postings belong at the end of its list: the next search packs only those (the delta, O(V + new postings) on the host), uploads them with
+// the old and the new post_ptr, and bm25_splice_kernel lays the new image out in HBM from the old image and the delta -- one pass, 8 bytes
+// read and 8 written per posting; then the refresh step below recomputes weights, doc_norm and the bitmap, since N, df and avgdl moved for the
+// old documents too.  RMU_BM25_OPT_REPACK_ON_ADD = 1 marks the image dirty instead (a full pack); the results are the same bit for bit.
 // The image is swapped under the handle's exclusive lock.  Every search hands HOST results back, i.e. it drains its stream before it returns and
 // does so under the shared lock: a writer that holds the exclusive lock has no reader left in flight to wait for.
 //
@@ -33,6 +38,11 @@
 // without postings reads none of it).  Selection: each wave folds its 64-document batches into a running sorted top list (rmu_common.h's
 // bitonic helpers) and skips, with one ballot, every batch in which no key beats its current k-th; the waves combine through LDS at the end of
 // the range; the workgroup writes one sorted, zero-padded list [part, q, k], and rmu_merge_final_launch (topk_merge.hip) finishes.
+//
+// Kernel (bm25_splice_kernel): a workgroup owns kSpliceSpan consecutive positions of the new image.  One binary search over the new post_ptr
+// finds the term that holds its first position; from there every lane walks the terms forward as its positions (lane, lane + 256, ...) pass
+// their ends.  Position j of term t is element j - new_ptr[t] of the term's list: the old image's while that is below the old length,
+// the delta's after it.  The delta's pointer is not shipped: both arrays are prefix sums, so delta_ptr[t] = new_ptr[t] - old_ptr[t].
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -225,6 +235,54 @@ __global__ __launch_bounds__(kBlock) void bm25_topk_kernel(Bm25Launch p) { bm25_
 template <int NPL>
 __global__ __launch_bounds__(kBlock) void bm25_masked_kernel(Bm25Launch p) { bm25_score_select<NPL, true>(p); }
 
+// ---- splice: old image + delta -> new image --------------------------------------------------------------------------------------------
+constexpr int kSpliceItems = 8;                       // positions per lane
+constexpr int kSpliceSpan = kBlock * kSpliceItems;    // positions per workgroup
+
+struct SpliceLaunch {
+    const u32* old_doc;      // the image so far: term t at [old_ptr[t], old_ptr[t + 1])
+    const u32* old_tf;
+    const u32* delta_doc;    // the postings of the documents added since: term t at [new_ptr[t] - old_ptr[t], new_ptr[t + 1] - old_ptr[t + 1])
+    const u32* delta_tf;
+    u32* new_doc;            // [nnz_new]
+    u32* new_tf;
+    const u64* old_ptr;      // [n_terms + 1]; a term that is new to the vocabulary has old length 0
+    const u64* new_ptr;      // [n_terms + 1], new_ptr[n_terms] = nnz_new > 0
+    u64 nnz_new;
+    u32 n_terms;
+};
+
+__global__ __launch_bounds__(kBlock) void bm25_splice_kernel(SpliceLaunch p) {
+    const u64 j0 = (u64)blockIdx.x * kSpliceSpan;          // < nnz_new: the grid is ceil(nnz_new / kSpliceSpan)
+    // the only search: the last term t with new_ptr[t] <= j0, i.e. new_ptr[t] <= j0 < new_ptr[t + 1] (empty terms before it are passed over)
+    u32 t = 0, hi = p.n_terms;                             // new_ptr[t] <= j0 < new_ptr[hi]
+    while (hi - t > 1) {
+        const u32 mid = t + ((hi - t) >> 1);
+        if (p.new_ptr[mid] <= j0) t = mid;
+        else hi = mid;
+    }
+    u64 b_new = p.new_ptr[t], e_new = p.new_ptr[t + 1], b_old = p.old_ptr[t], n_old = p.old_ptr[t + 1] - b_old;
+#pragma unroll
+    for (int i = 0; i < kSpliceItems; ++i) {
+        const u64 j = j0 + (u64)(i * kBlock + (int)threadIdx.x);
+        if (j >= p.nnz_new) break;
+        if (e_new <= j) {                                  // j < nnz_new = new_ptr[n_terms]: the walk ends at a term below n_terms
+            do {
+                ++t;
+                b_new = e_new;
+                e_new = p.new_ptr[t + 1];
+            } while (e_new <= j);
+            b_old = p.old_ptr[t];
+            n_old = p.old_ptr[t + 1] - b_old;
+        }
+        const u64 o = j - b_new;
+        const bool from_old = o < n_old;
+        const u64 src = from_old ? b_old + o : (b_new - b_old) + (o - n_old);
+        p.new_doc[j] = (from_old ? p.old_doc : p.delta_doc)[src];
+        p.new_tf[j] = (from_old ? p.old_tf : p.delta_tf)[src];
+    }
+}
+
 // ---- host: tokenizer and index ---------------------------------------------------------------------------------------------------------
 // length in bytes of the str.isspace() character at p (n bytes left), 0 if there is none.  The multi-byte forms cannot occur inside another
 // character of valid UTF-8, so matching bytes is matching code points.
@@ -337,10 +395,14 @@ struct rmu_bm25 {
     std::vector<u32> df;                           // [V] live documents that hold the term
     uint64_t n_live = 0, live_len = 0, live_nnz = 0, live_vocab = 0;
     bool broken = false;                           // an allocation failed half-way through an add
-    int64_t opt_tile = 0, opt_max_wgs = 0, opt_repack_on_remove = 0;
+    int64_t opt_tile = 0, opt_max_wgs = 0, opt_repack_on_remove = 0, opt_repack_on_add = 0;
     // device image + the host half of it (valid while !dirty).  stale: the postings are in place but documents were removed since the
-    // weights, doc_norm and the liveness bitmap were computed
-    bool dirty = true, stale = false;
+    // weights, doc_norm and the liveness bitmap were computed.  grown: the image holds the first imaged[t] master postings of every term
+    // and documents were added since
+    bool dirty = true, stale = false, grown = false;
+    std::vector<u32> imaged;                       // [terms at the last pack or splice] master postings of the term the image has consumed
+    uint64_t imaged_nnz = 0;                       // their sum
+    uint64_t n_packs = 0, n_splices = 0, upload_bytes = 0;      // RMU_BM25_STAT_IMAGE_*
     u32* post_doc = nullptr;
     u32* post_tf = nullptr;
     float* doc_norm = nullptr;
@@ -356,7 +418,7 @@ static void drop_image(rmu_bm25* h) {
     h->post_doc = h->post_tf = h->live_bits = nullptr;
     h->doc_norm = nullptr;
     h->dirty = true;
-    h->stale = false;
+    h->stale = h->grown = false;
 }
 
 // the one copy of the statistics -> (weights, doc_norm) step, over the live corpus: both the repack and the refresh path call it
@@ -417,6 +479,7 @@ static int build_image(rmu_bm25* h, hipStream_t s) {
     std::vector<float> norm;
     try {
         h->post_ptr.assign(V + 1, 0);
+        h->imaged.resize(V);
         pk.resize(2 * (size_t)h->live_nnz);
         live_weights_and_norms(h, h->weight, norm);
     } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory while packing the index"); }
@@ -426,6 +489,7 @@ static int build_image(rmu_bm25* h, hipStream_t s) {
     for (size_t t = 0; t < V; ++t) {
         const auto& ps = h->terms[t];
         h->post_ptr[t] = at;
+        h->imaged[t] = (u32)ps.doc.size();
         if (all_live) {
             if (!ps.doc.empty()) {
                 memcpy(pdoc + at, ps.doc.data(), ps.doc.size() * sizeof(u32));
@@ -449,6 +513,9 @@ static int build_image(rmu_bm25* h, hipStream_t s) {
     }
     const int rc = upload_norms_and_bitmap(h, norm, s);
     if (rc != RMU_OK) return rc;
+    h->imaged_nnz = h->nnz;
+    ++h->n_packs;
+    h->upload_bytes += 2 * pbytes;
     h->dirty = false;
     h->stale = false;
     return RMU_OK;
@@ -465,6 +532,80 @@ static int refresh_image(rmu_bm25* h, hipStream_t s) {
     if (rc != RMU_OK) return rc;
     h->stale = false;
     return RMU_OK;
+}
+
+// (exclusive lock held, image grown, stale or not) the splice path.  The host touches only what is new: O(V) for the pointers and the master
+// postings past imaged[t] of every term -- those of the documents added since, removed ones among them (the bitmap masks them, as it does on
+// the refresh path).  Nothing of the handle changes before the new arrays are complete; any failure leaves it to the caller's drop_image.
+static int splice_image(rmu_bm25* h, hipStream_t s) {
+    const size_t V = h->terms.size(), V_old = h->imaged.size(), N = h->dl.size();
+    const u64 nnz_old = h->post_ptr[V_old], nnz_delta = h->nnz - h->imaged_nnz, nnz_new = nnz_old + nnz_delta;
+    std::vector<u64> old_ptr, new_ptr;
+    std::vector<u32> dk;          // delta: post_doc | post_tf
+    try {
+        old_ptr.resize(V + 1);
+        new_ptr.resize(V + 1);
+        dk.resize(2 * (size_t)nnz_delta);
+        h->imaged.resize(V, 0);
+    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory while packing the added documents"); }
+    u32* ddoc = dk.data();
+    u32* dtf = dk.data() + nnz_delta;
+    u64 at = 0;                   // in the delta
+    for (size_t t = 0; t < V; ++t) {
+        const auto& ps = h->terms[t];
+        old_ptr[t] = t < V_old ? h->post_ptr[t] : nnz_old;
+        new_ptr[t] = old_ptr[t] + at;
+        const size_t done = h->imaged[t], n = ps.doc.size() - done;
+        if (n) {
+            if (n > nnz_delta - at) return mfail(RMU_E_INVALID, "rmu_bm25_search: internal error, the added posting count is out of step");
+            memcpy(ddoc + at, ps.doc.data() + done, n * sizeof(u32));
+            memcpy(dtf + at, ps.tf.data() + done, n * sizeof(u32));
+            at += n;
+        }
+    }
+    old_ptr[V] = nnz_old;
+    new_ptr[V] = nnz_new;
+    if (at != nnz_delta) return mfail(RMU_E_INVALID, "rmu_bm25_search: internal error, the added posting count is out of step");
+
+    struct Held {                 // device arrays that are not the handle's yet
+        void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Held() { for (void* q : p) if (q) (void)rmu_free(q); }
+    } held;
+    void*& d_ptr = held.p[0]; void*& d_delta = held.p[1]; void*& d_doc = held.p[2]; void*& d_tf = held.p[3]; void*& d_norm = held.p[4];
+    const size_t ptr_bytes = (V + 1) * sizeof(u64), delta_bytes = (size_t)nnz_delta * sizeof(u32), new_bytes = (size_t)nnz_new * sizeof(u32);
+    BM25_TRY(hipMalloc(&d_ptr, 2 * ptr_bytes));
+    BM25_TRY(hipMalloc(&d_delta, delta_bytes ? 2 * delta_bytes : 4));
+    BM25_TRY(hipMalloc(&d_doc, new_bytes ? new_bytes : 4));
+    BM25_TRY(hipMalloc(&d_tf, new_bytes ? new_bytes : 4));
+    BM25_TRY(hipMalloc(&d_norm, N * sizeof(float)));
+    if (nnz_new) {
+        BM25_TRY(hipMemcpyAsync(d_ptr, old_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, s));
+        BM25_TRY(hipMemcpyAsync((char*)d_ptr + ptr_bytes, new_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, s));
+        if (delta_bytes) BM25_TRY(hipMemcpyAsync(d_delta, dk.data(), 2 * delta_bytes, hipMemcpyHostToDevice, s));
+        const u64 wgs = (nnz_new + kSpliceSpan - 1) / kSpliceSpan;
+        if (wgs > 0x7FFFFFFFull) return mfail(RMU_E_INVALID, "rmu_bm25_search: too many postings for one splice launch");
+        SpliceLaunch L{};
+        L.old_doc = h->post_doc; L.old_tf = h->post_tf;
+        L.delta_doc = (const u32*)d_delta; L.delta_tf = (const u32*)d_delta + nnz_delta;
+        L.new_doc = (u32*)d_doc; L.new_tf = (u32*)d_tf;
+        L.old_ptr = (const u64*)d_ptr; L.new_ptr = (const u64*)((const char*)d_ptr + ptr_bytes);
+        L.nnz_new = nnz_new; L.n_terms = (u32)V;
+        hipLaunchKernelGGL(bm25_splice_kernel, dim3((unsigned)wgs), dim3(kBlock), 0, s, L);
+        BM25_TRY(hipGetLastError());
+        BM25_TRY(hipStreamSynchronize(s));         // (the host vectors are pageable; the old arrays are free to go)
+        h->upload_bytes += 2 * ptr_bytes + 2 * delta_bytes;
+    }
+    for (void* q : {(void*)h->post_doc, (void*)h->post_tf, (void*)h->doc_norm, (void*)h->live_bits})
+        if (q) (void)rmu_free(q);
+    h->post_doc = (u32*)d_doc; h->post_tf = (u32*)d_tf; h->doc_norm = (float*)d_norm;
+    h->live_bits = nullptr;                        // (N grew: the refresh below allocates it again if a document is removed)
+    d_doc = d_tf = d_norm = nullptr;
+    h->post_ptr.swap(new_ptr);
+    for (size_t t = 0; t < V; ++t) h->imaged[t] = (u32)h->terms[t].doc.size();
+    h->imaged_nnz = h->nnz;
+    h->grown = false;
+    ++h->n_splices;
+    return refresh_image(h, s);
 }
 
 extern "C" int rmu_bm25_create(rmu_bm25_t** out, double k1, double b, double epsilon) {
@@ -504,7 +645,8 @@ extern "C" int rmu_bm25_add_texts(rmu_bm25_t* h, const char* blob, int64_t bytes
     try {
         std::vector<std::pair<const char*, size_t>> docs;
         if (!split_blob(blob, bytes, n, docs)) return mfail(RMU_E_INVALID, "rmu_bm25_add_texts: the blob does not hold exactly n NUL-terminated strings");
-        h->dirty = true;
+        if (h->dirty || h->opt_repack_on_add) h->dirty = true;
+        else h->grown = true;                   // (clean or stale: the next search splices the new postings in)
         h->broken = true;                       // until the add is complete
         std::vector<u32> seen;
         std::string key;
@@ -553,6 +695,9 @@ extern "C" int rmu_bm25_stat(rmu_bm25_t* h, int what, double* out) {
         case RMU_BM25_STAT_NNZ: *out = (double)h->live_nnz; break;
         case RMU_BM25_STAT_AVGDL: *out = h->n_live ? (double)h->live_len / (double)h->n_live : 0.0; break;
         case RMU_BM25_STAT_LIVE_DOCS: *out = (double)h->n_live; break;
+        case RMU_BM25_STAT_IMAGE_PACKS: *out = (double)h->n_packs; break;
+        case RMU_BM25_STAT_IMAGE_SPLICES: *out = (double)h->n_splices; break;
+        case RMU_BM25_STAT_IMAGE_UPLOAD_BYTES: *out = (double)h->upload_bytes; break;
         default: return mfail(RMU_E_INVALID, "rmu_bm25_stat: unknown statistic");
     }
     return RMU_OK;
@@ -586,6 +731,10 @@ extern "C" int rmu_bm25_set_option(rmu_bm25_t* h, int option, int64_t value) {
         case RMU_BM25_OPT_REPACK_ON_REMOVE:
             if (value != 0 && value != 1) return mfail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_REPACK_ON_REMOVE takes 0 or 1");
             h->opt_repack_on_remove = value;
+            break;
+        case RMU_BM25_OPT_REPACK_ON_ADD:
+            if (value != 0 && value != 1) return mfail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_REPACK_ON_ADD takes 0 or 1");
+            h->opt_repack_on_add = value;
             break;
         default: return mfail(RMU_E_INVALID, "rmu_bm25_set_option: unknown option");
     }
@@ -638,12 +787,12 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
             if (c.ensure_stream() != RMU_OK) return mfail(RMU_E_HIP, "rmu_bm25_search: cannot create a stream");
             s = hip_stream ? (hipStream_t)hip_stream : c.stream;
         }
-        if (!h->dirty && !h->stale) break;
+        if (!h->dirty && !h->stale && !h->grown) break;
         lk.unlock();
         {
             std::unique_lock<std::shared_mutex> wl(h->mu);
-            if (!h->broken && h->n_live != 0 && (h->dirty || h->stale)) {
-                const int rc = h->dirty ? build_image(h, s) : refresh_image(h, s);
+            if (!h->broken && h->n_live != 0 && (h->dirty || h->stale || h->grown)) {
+                const int rc = h->dirty ? build_image(h, s) : h->grown ? splice_image(h, s) : refresh_image(h, s);
                 if (rc != RMU_OK) { drop_image(h); return rc; }
             }
         }

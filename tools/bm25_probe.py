@@ -17,7 +17,11 @@ The GPU step runs in a child process under its own time limit (`--step-timeout`)
 measures, on the same corpus and in one process, what removing documents costs: single-query and batch time with 0 % (bm25_topk_kernel: the
 baseline) and with 10 % of the documents removed (bm25_masked_kernel); rmu_bm25_remove_docs of 1 % of the documents in one call; the first
 search after that removal on the refresh path and, on a second handle with RMU_BM25_OPT_REPACK_ON_REMOVE, on the repack path; compact; save;
-load + first search against building the index from the texts.  No CPU leg."""
+load + first search against building the index from the texts.  No CPU leg.
+It also measures the first search after appending 1, 1000 and 100 000 documents to the `--docs` corpus, `--append-reps` times on the splice
+path (RMU_BM25_OPT_REPACK_ON_ADD = 0) and as many on the repack path (= 1), alternating and starting with the repack; after every leg the
+appended documents are removed and compacted away and the image is packed again, so every leg meets the same index.  The repack legs are
+the yardstick: "splice_is_faster_by_more_than_the_repack_spread" is median(splice) < median(repack) - (max - min of the repack legs)."""
 import argparse
 import json
 import os
@@ -101,6 +105,50 @@ def gpu_step(a):
     print("BM25_PROBE_GPU " + json.dumps(res), flush=True)
 
 
+def append_legs(a, ix, qs, batch, ms):
+    """ix: every document live, image clean; it is left that way"""
+    extra = corpus(100_000, a.vocab, seed=99)
+    base = ix.stat()
+    out = {"measured": True, "docs_before_every_leg": base["docs"], "nnz_before_every_leg": base["nnz"], "reps_per_path": a.append_reps,
+           "rate": "device_bytes_moved = 16 bytes per posting of the new image (8 read from the old image or the delta, 8 written); "
+                   "gb_per_s_over_the_call divides it by the whole call's median time, host work included: not a kernel rate"}
+    for n in (1, 1000, 100_000):
+        legs = {0: [], 1: []}
+        add_ms, stats, results = [], [], []
+        for rep in range(2 * a.append_reps):
+            repack = 1 - rep % 2
+            ix.set_option(8, repack)
+            before = ix.image_stat()
+            t, first = ms(lambda: ix.add_texts(extra[:n]))
+            add_ms.append(t)
+            t, _ = ms(lambda: ix.search(qs[:1], a.k))
+            legs[repack].append(t)
+            after = ix.image_stat()
+            stats.append({k: after[k] - before[k] for k in after})
+            assert stats[-1]["packs"] == repack and stats[-1]["splices"] == 1 - repack, stats[-1]
+            results.append(ix.search(batch, a.k))
+            nnz_new = ix.stat()["nnz"]
+            ix.remove(np.arange(first, first + n))
+            ix.compact()
+            ix.search(qs[:1], a.k)                            # packs: the next leg starts from a clean image of the base corpus
+            assert ix.stat()["docs"] == base["docs"] and ix.stat()["nnz"] == base["nnz"]
+        same = all(np.array_equal(s.view(np.uint32), results[0][0].view(np.uint32)) and np.array_equal(d, results[0][1]) for s, d in results)
+        spread = max(legs[1]) - min(legs[1])
+        med0, med1 = statistics.median(legs[0]), statistics.median(legs[1])
+        moved = 16 * nnz_new
+        out[f"append_{n}"] = {
+            "add_texts": summary(add_ms), "repack_on_add_1": dict(summary(legs[1]), spread_ms=round(spread, 4), all_ms=[round(x, 3) for x in legs[1]]),
+            "repack_on_add_0_splice": dict(summary(legs[0]), all_ms=[round(x, 3) for x in legs[0]],
+                                           image_stat_delta_per_leg=stats[1], device_bytes_moved=moved,
+                                           gb_per_s_over_the_call=round(moved / (med0 * 1e-3) / 1e9, 2)),
+            "upload_bytes_per_repack_leg": stats[0]["upload_bytes"], "results_identical_on_every_leg": bool(same),
+            "splice_is_faster_by_more_than_the_repack_spread": bool(med0 < med1 - spread)}
+    ix.set_option(8, 0)
+    out["splice_default_holds_at_all_three_sizes"] = all(out[f"append_{n}"]["splice_is_faster_by_more_than_the_repack_spread"]
+                                                         for n in (1, 1000, 100_000))
+    return out
+
+
 def lifecycle_step(a):
     import tempfile
     from ragmeup_amd.bm25 import BM25Index
@@ -135,6 +183,7 @@ def lifecycle_step(a):
     ix, add_ms, first_ms = build(0)
     res = {"stat": ix.stat(), "build_from_texts": {"add_texts_ms": round(add_ms, 1), "first_search_with_image_upload_ms": round(first_ms, 1)}}
     res["removed_0pct_plain_kernel"] = timed_searches(ix)
+    res["first_search_after_append"] = append_legs(a, ix, qs, batch, ms)
     t, n = ms(lambda: ix.remove(one_pct))
     res["remove_1pct_one_call"] = {"ms": round(t, 2), "documents": n}
     t, _ = ms(lambda: ix.search(qs[:1], a.k))
@@ -210,6 +259,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--k", type=int, default=4)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--append-reps", type=int, default=5, help="--lifecycle: legs per path and append size")
     ap.add_argument("--cpu-sample", type=int, default=100_000)
     ap.add_argument("--cpu-queries", type=int, default=8)
     ap.add_argument("--step-timeout", type=int, default=420, help="seconds the GPU step may take")
