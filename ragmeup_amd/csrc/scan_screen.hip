@@ -8,12 +8,14 @@
 // Screening image (built at add time, HALF the bytes of the fp32 matrix: 768 B per 384-d row): h = fp16(64 * x) in
 // natural k order (the 2^6 scale keeps |x| >= 1e-6 out of the fp16 subnormal range; |x| must stay below ~1000).
 // Queries are converted the same way per call.
-//   4096 * s~ = sum h_x . h_q                    (ONE v_mfma_f32_32x32x16_f16 per 16 k, one fp32 accumulator)
+//   4096 * s~ = sum h_x . h_q                    (one fp32 accumulator per score: 24 accumulations of 16 k by v_mfma_f32_32x32x16_f16 in the
+//                                                 4-wave kernels, 12 of 32 k by v_mfma_f32_16x16x32_f16 in the 8-wave ones)
 // Error vs the exact kernel's fp32 score, with dx = x - h_x/64 (row), dq = q - h_q/64 (query), by Cauchy-Schwarz:
 //   |sum (x q - h_x h_q)/4096| <= |dx| |q| + |x| |dq| + |dx| |dq|.
 // |dx|max is MEASURED when rows are added (k_img_err; ~1.7e-4 |x| for real data, 4.9e-4 |x| worst case) and |dq| is
 // measured per query in the re-score kernel, so subnormal flushes and odd value ranges are covered by construction.
-// The fp32 accumulation of 384 exact fp16 products adds <= 408 * 2^-24 = 2.5e-5 |x||q| and the exact kernel is itself
+// The fp32 accumulation of 384 exact fp16 products adds <= 408 * 2^-24 = 2.5e-5 |x||q| (the 8-wave kernels round 12 partial sums of 32 k into
+// the accumulator where the 4-wave ones round 24 of 16 k: inside the same budget) and the exact kernel is itself
 // within 384 * 2^-24 = 2.3e-5 |x||q| of the true dot product:
 //   EPS(q) = |dx|max |q| + |x|max |dq| + |dx|max |dq| + 5e-5 |x|max |q|          (~4e-4 for unit vectors)
 // Sufficiency (per query): with the approximate top-K' (K' = 32) sorted, tau = k-th best s~.  If fewer than K'
@@ -135,8 +137,13 @@ __global__ __launch_bounds__(256) void k_img_err(const float* __restrict__ x, in
 }
 
 // ---- lean form, one barrier per TWO tiles (round 4): the screening kernel (the earlier forms are retired) ------------------------------
-// Workgroup = NWV waves x 32 queries; every wave multiplies the same 32-row tiles (one v_mfma_f32_32x32x16_f16 per 16 k, 24 per tile) by
-// its own queries, whose fragments stay in registers for the whole scan.
+// Workgroup = NWV waves x 32 queries; every wave multiplies the same 32-row tiles by its own queries, whose fragments stay in registers for
+// the whole scan: NWV = 4 with one v_mfma_f32_32x32x16_f16 per 16 k (24 per tile), NWV = 8 with v_mfma_f32_16x16x32_f16 -- a fragment is 16
+// rows x 32 k and feeds two MFMAs back to back, queries 0-15 and 16-31 of the wave (48 per tile, the same 24 fragment reads, four f32x4
+// accumulators).  Same cycles, same LDS bytes; the chip holds a higher clock on the smaller shape (tools/ubench/mfma_power.hip,
+// profiles/mfma_shape.txt: 1.56 against 1.40 PFLOP/s for fragment stream + fill on random f16; profiles/screen_mfma_shape.md for the kernel).
+// The 8-wave filter runs in the MFMA's own accumulator layout -- a lane holds 8 scores of each of two queries: a running maximum and one compare
+// per query group -- and the accumulators change owner (eight v_permlane32_swap: to_owner) only when something passes.
 // NWV = 8: full query tiles (256 queries per workgroup, batches over 128), TWO waves per SIMD.  A lone wave per SIMD issues roughly one
 // instruction per 6-7 cycles in a wait / MFMA / ds_read / VALU mix (tools/ubench/mfma_issue.hip: 46 cycles per MFMA bare, 65 with five
 // VALU fillers), which keeps the matrix pipe under half busy; two interleaved instruction streams hide each other's issue gaps.  (64
@@ -177,7 +184,8 @@ struct Lean3Cfg {
 // L2N = 1 (round 5): the index ranks by 2 q.x - |x|^2 (RMU_METRIC_L2SQ).  The image has no k-slot left for the norm (384 fp16 = the 24 MFMA
 // steps exactly), so it enters as the chain's C operand: a.nrm[row] = -2048 |x|^2 (fp32, built at add time from the exact scan's own
 // -|x|^2 column) initialises the accumulator of the tile's first MFMA -- acc = 4096 (q~.x~ - |x|^2 / 2), the approximate HALF score; filter,
-// thresholds, candidate keys and merges never know.  A lane's 16 accumulator rows (4h + 8i + c) are four 16-byte LDS reads, issued half a
+// thresholds, candidate keys and merges never know.  A lane's 16 accumulator rows (4h + 8i + c) are four 16-byte LDS reads (NWV = 8: its native
+// rows 16 t + 4 (lane >> 4) + c are two, one per row half, shared by both query groups; the L2 instantiations run the 16x16x32 body too), issued half a
 // tile ahead between two fragment reads (the lgkmcnt of the four steps behind them counts them in); the norms of a PAIR of tiles are one
 // 256-byte LDS-DMA by wave 0, issued two pairs ahead next to the threshold refresh (older than the pieces the pair barrier's vmcnt leaves
 // in flight, like the refresh).  +4 KiB-reads per 24 on the LDS return path; the fp16 image bytes are unchanged.
@@ -190,7 +198,16 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
     constexpr int NW = NWV, S_PRE = 4;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h = lane >> 5, j = lane & 31;
+    // Lane roles of the candidate path (filter slow path, appends, compaction, epilogue, emit): lane (h, j) owns query j of the wave and the
+    // tile rows 4h + 8i + c (i, c = 0..3); the query's other lane is lane ^ XL.  NWV = 4 (32x32x16): that is the MFMA's own D layout, h = lane
+    // bit 5.  NWV = 8 (16x16x32): the accumulators reach that ownership through to_owner() only when something passes; there h = lane bit 4
+    // and j = 16 (lane bit 5) + (lane & 15).  qlane(jj): the h = 0 lane of query jj; jl: this lane's own one; qidx: the query of an h = 0 lane.
+    constexpr bool M16 = NWV == 8;
+    constexpr int XL = M16 ? 16 : 32;
+    const int h = M16 ? (lane >> 4) & 1 : lane >> 5, j = M16 ? 16 * (lane >> 5) + (lane & 15) : lane & 31;
+    const int jl = M16 ? lane & 47 : j;
+    auto qlane = [](int jj) { return M16 ? 32 * (jj >> 4) + (jj & 15) : jj; };
+    auto qidx = [](int ll) { return M16 ? 16 * (ll >> 5) + (ll & 15) : ll; };
     int s_idx, qt;   // row chunk, query tile
     block_map(a.s_chunks, a.nqt, s_idx, qt);
     const int64_t tiles_total = (a.n_rows + S_RT - 1) / S_RT;
@@ -223,7 +240,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
     const bool pace_on = a.prog != nullptr;
     u32* prog_w = a.prog + (size_t)s_idx * 4;
     bool pace_live = pace_on;
-    const u32* gsrc = gthr_w + j;
+    const u32* gsrc = gthr_w + (lane & 31);              // (LDS word l comes from lane l: word jj is query jj's threshold in either lane mapping)
     if (pace_on && lane >= 32 && lane < 36) gsrc = prog_w + (lane - 32);
     auto refresh_gthr = [&]() {
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
@@ -248,11 +265,22 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
             if (spins >= 400) pace_live = false;
         }
     };
+    // NWV = 4: qh[T] = k-step T (16 k) of query j, k-half h.  NWV = 8: qh[12 g + s] = k-step s (32 k) of query 16 g + (lane & 15), k-group lane >> 4
     f16x8 qh[S_TS];
-    {
+    if constexpr (M16) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const int qi = q_base + 16 * g + (lane & 15);
+            const char* qrow = (const char*)a.q + (size_t)(qi < a.nq ? qi : 0) * IMGB + (lane >> 4) * 16;
+#pragma unroll
+            for (int sk = 0; sk < S_TS / 2; ++sk) qh[12 * g + sk] = *(const f16x8*)(qrow + sk * 64);
+        }
+    } else {
         const char* qrow = (const char*)a.q + (size_t)(q_ok ? q_base + j : 0) * IMGB + h * 16;
 #pragma unroll
         for (int T = 0; T < S_TS; ++T) qh[T] = *(const f16x8*)(qrow + T * 32);
+    }
+    {
 #pragma unroll
         for (int T = 0; T < S_TS; ++T) asm volatile("" : "+v"(qh[T]));
         // The loads must be COMPLETE, as far as the compiler's wait-count pass can tell, before the first LDS-DMA is issued: it cannot count
@@ -289,33 +317,39 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
     // hipcc sinks every ds_read to just before the MFMA that consumes it and waits lgkmcnt(0) there (a 32-cycle MFMA cannot hide an LDS round
     // trip).  The reads keep their program order (volatile), S_PRE of them are in flight, and frag_wait ties the counted wait to the register
     // the MFMA reads, so the MFMA cannot be scheduled above it.
-    u32 ab[4], ab_hi[4], ab_h2[4];                        // (the offset field is 16 bits: slots 4..7 and 8..11 go through their own bases)
+    // NWV = 8: a fragment is 16 rows x 32 k -- lane l reads row 16 t + (l & 15) (t = row half), logical unit 4 T' + (l >> 4) of the chunk
+    // (T' = 0..5): TWO per-lane bases (T' & 1) + immediates t * 6144 + (T' >> 1) * 128 (rows 16 apart share the XOR: (16 >> 1) & 7 = 0).
+    // Conflict free under the same swizzle (tests/test_screen_shape_cpu.py).  Read index i = 0..11 of a chunk is (T' = i >> 1, t = i & 1).
+    constexpr int NAB = M16 ? 2 : 4;
+    u32 ab[NAB], ab_hi[NAB], ab_h2[NAB];                  // (the offset field is 16 bits: slots 4..7 and 8..11 go through their own bases)
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        ab[m] = lds_addr(ring) + (u32)(j * S_CKB + (((2 * m + h) ^ ((j >> 1) & 7)) * 16));
+    for (int m = 0; m < NAB; ++m) {
+        if constexpr (M16) ab[m] = lds_addr(ring) + (u32)((lane & 15) * S_CKB + (((4 * m + (lane >> 4)) ^ (((lane & 15) >> 1) & 7)) * 16));
+        else ab[m] = lds_addr(ring) + (u32)(j * S_CKB + (((2 * m + h) ^ ((j >> 1) & 7)) * 16));
         ab_hi[m] = ab[m] + 4u * S_SLOT;
         ab_h2[m] = ab[m] + 8u * S_SLOT;
     }
     f16x8 fr[S_PRE];
 #pragma unroll
     for (int m = 0; m < S_PRE; ++m) fr[m] = f16x8{};
-    auto read_frag = [&](f16x8& dst, auto OFF, int t) {
+    auto read_frag = [&](f16x8& dst, auto OFF, int t) {   // t: which per-lane base
         if (EXP & 2) { asm volatile("" : "+v"(dst)); return; }
         constexpr int off = decltype(OFF)::value;
-        const u32 ad = off >= 8 * S_SLOT ? ab_h2[t & 3] : off >= 4 * S_SLOT ? ab_hi[t & 3] : ab[t & 3];
+        const u32 ad = off >= 8 * S_SLOT ? ab_h2[t & (NAB - 1)] : off >= 4 * S_SLOT ? ab_hi[t & (NAB - 1)] : ab[t & (NAB - 1)];
         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(ad), "n"(off % (4 * S_SLOT)));
     };
     auto frag_wait = [&](f16x8& f) {
         if (EXP & 2) return;
         asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f) : "n"(S_PRE - 1));
     };
-    auto frag_wait_nrm = [&](f16x8& f) {                   // the four norm reads sit between this fragment's read and the newest ones
+    auto frag_wait_nrm = [&](f16x8& f) {                   // the four (NWV = 8: two) norm reads sit between this fragment's read and the newest ones
         if (EXP & 2) return;
-        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f) : "n"(S_PRE - 1 + 4));
+        if constexpr (M16) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f) : "n"(S_PRE - 1 + 2));
+        else asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f) : "n"(S_PRE - 1 + 4));
     };
     // L2 form: row norms of the ring tiles
     const float* np = L2N ? a.nrm + a.row0 + t0 * S_RT + lane : nullptr;     // one float per lane = the 64 rows of a pair of tiles
-    const u32 nrm_ad = lds_addr(ssm + C::NRM_OFF) + (u32)h * 16u;
+    const u32 nrm_ad = lds_addr(ssm + C::NRM_OFF) + (u32)(M16 ? lane >> 4 : h) * 16u;
     f32x4 zq[4] = {};
     auto issue_nrm = [&](auto PI, const float* src) {      // PI = ring position of the pair's first tile
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -325,6 +359,10 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
         constexpr int o = decltype(PI)::value * S_RT * 4;
         f32x4 &z0 = zq[0], &z1 = zq[1], &z2 = zq[2], &z3 = zq[3];      // (asm operands alone do not capture in a generic lambda)
         const u32 ad = nrm_ad;
+        if constexpr (M16) {                               // native rows 16 t + 4 (lane >> 4) + c: one read per row half, the same for both query groups
+            asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4" : "=v"(z0), "=v"(z1) : "v"(ad), "n"(o), "n"(o + 64));
+            return;
+        }
         asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %4 offset:%8"
                      : "=v"(z0), "=v"(z1), "=v"(z2), "=v"(z3)
                      : "v"(ad), "n"(o), "n"(o + 32), "n"(o + 64), "n"(o + 96));
@@ -334,7 +372,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
     // keep the best K' of query lane jj's slot (sorted), raise its threshold, publish it.  Every VMEM operation of compact and slow_path is
     // inline asm: one the compiler can see puts an s_waitcnt vmcnt(0) in front of the tile loop's first MFMA -- the join of this path -- and
     // drains the DMA ring once per tile.
-    auto compact = [&](int jj) {
+    auto compact = [&](int jj) {                           // jj: the query's h = 0 lane
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const u32 n = (u32)__builtin_amdgcn_readlane((int)cnt, jj);
         u64* slot = (u64*)(((u64)(u32)__builtin_amdgcn_readlane((int)(u32)((u64)gslot >> 32), jj) << 32) |
@@ -356,14 +394,14 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
             const u64 kb = __ballot(keep && rank[pp] == (u32)(a.k - 1));
             if (kb) {
                 const u32 hi = (u32)__builtin_amdgcn_readlane((int)(u32)(key[pp] >> 32), __builtin_ctzll(kb));
-                if (j == jj) thr_s = fmaxf(thr_s, rmu_ord2f(hi) * 4096.0f);
-                if (lane == 0) asm volatile("global_atomic_umax %0, %1, off sc1" ::"v"(gthr_w + jj), "v"(hi) : "memory");
+                if (jl == jj) thr_s = fmaxf(thr_s, rmu_ord2f(hi) * 4096.0f);
+                if (lane == 0) asm volatile("global_atomic_umax %0, %1, off sc1" ::"v"(gthr_w + qidx(jj)), "v"(hi) : "memory");
             }
         }
-        if (j == jj) cnt = n < (u32)a.k ? n : (u32)a.k;
+        if (jl == jj) cnt = n < (u32)a.k ? n : (u32)a.k;
         if (DBG) ++d_comp;
     };
-    auto slow_path = [&](const f32x16& p, int64_t rbase, u32 inmask) {
+    auto slow_path = [&](const f32x16& p, int64_t rbase, u32 inmask) __attribute__((always_inline)) {   // (out of line it would put the kernel's state into scratch)
         unsigned long long c0 = 0;
         u32 todo = 0;
 #pragma unroll
@@ -376,12 +414,16 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
         for (int r = 0; r < 16; ++r) {
             if ((uni >> r) & 1u) {
                 bool has = ((todo >> r) & 1u) && p[r] > thr_s;
-                u32 other = (u32)__shfl_xor((int)has, 32);
+                u32 other = (u32)__shfl_xor((int)has, XL);
                 const u64 full = __ballot(cnt + (u32)has + other > (u32)C::CAP);
-                if (__builtin_expect(full != 0, 0)) {
-                    for (u32 fm = (u32)full | (u32)(full >> 32); fm; fm &= fm - 1) compact(__builtin_ctz(fm));
+                if (__builtin_expect(full != 0, 0)) {          // (both lanes of a query vote alike: its h = 0 lane stands for it)
+                    if constexpr (M16) {
+                        for (u64 fm = full & 0x0000ffff0000ffffull; fm; fm &= fm - 1) compact(__builtin_ctzll(fm));
+                    } else {
+                        for (u32 fm = (u32)full | (u32)(full >> 32); fm; fm &= fm - 1) compact(__builtin_ctz(fm));
+                    }
                     has = has && p[r] > thr_s;
-                    other = (u32)__shfl_xor((int)has, 32);
+                    other = (u32)__shfl_xor((int)has, XL);
                 }
                 const u32 pos = cnt + (h ? other : 0u);
                 if (has) {
@@ -392,6 +434,34 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
             }
         }
         if (DBG) d_clk_slow += clock64() - c0;
+    };
+    // NWV = 8: the 16x16x32 accumulators in the MFMA's own layout, element 8 g + 4 t + c of a tile's f32x16 = query 16 g + (lane & 15), row
+    // 16 t + 4 (lane >> 4) + c.  The fast filter works on it as it is: a running maximum per query group against that group's threshold (thr_g0 /
+    // thr_g1: the threshold of query (lane & 15) and of query 16 + (lane & 15), whichever lane half owns it).  to_owner: eight half-swaps -- lanes
+    // 32..63 of group 0's register against lanes 0..31 of group 1's -- leave lane 32 b5 + 16 b4 + n with query 16 b5 + n alone, rows 4 b4 + 8 i + c
+    // at element 4 i + c, i = 2 t + (the register's old lane bit 5): slow_path's layout.
+    float thr_g0 = thr_s, thr_g1 = thr_s;
+    auto share_thr16 = [&]() {
+        if constexpr (M16) {
+            const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(thr_s), __float_as_uint(thr_s), false, false);
+            thr_g0 = __uint_as_float(r[0]);
+            thr_g1 = __uint_as_float(r[1]);
+        }
+    };
+    share_thr16();
+    auto to_owner = [&](const f32x16& nat) -> f32x16 {
+        f32x16 p = nat;
+        if constexpr (M16)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float g0 = nat[4 * t + c], g1 = nat[8 + 4 * t + c];      // (scalars first: a bit cast applied to a vector element reads element 0)
+                const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(g0), __float_as_uint(g1), false, false);
+                p[8 * t + c] = __uint_as_float(r[0]);
+                p[8 * t + 4 + c] = __uint_as_float(r[1]);
+            }
+        return p;
     };
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
@@ -420,9 +490,16 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::NIW) : "memory");   // tiles 0, 1, 2 (and the thresholds)
         __builtin_amdgcn_s_barrier();
         if (L2N && (NWV == 8 || wave_live)) read_nrm(I0{});   // (in front of the fragment prefetch: step 0's counted wait covers it)
+        if constexpr (M16) {                               // reads 0..3 of tile 0's first chunk
+            read_frag(fr[0], std::integral_constant<int, 0>{}, 0);
+            read_frag(fr[1], std::integral_constant<int, 16 * S_CKB>{}, 0);
+            read_frag(fr[2], std::integral_constant<int, 0>{}, 1);
+            read_frag(fr[3], std::integral_constant<int, 16 * S_CKB>{}, 1);
+        } else {
 #pragma unroll
         for (int m = 0; m < S_PRE; ++m) {
             if (!(EXP & 2)) asm volatile("ds_read_b128 %0, %1" : "=v"(fr[m]) : "v"(ab[m]));
+        }
         }
         f32x16 accA, accB;
 #pragma unroll
@@ -441,13 +518,55 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
                 if (DBG) d_clk_bar += clock64() - cb;
                 const u32 go = gt_lds[j];
                 if (go && (a.share_thr & 1)) thr_s = fmaxf(thr_s, rmu_ord2f(go - 1u) * 4096.0f);
+                share_thr16();
                 if (w == PW && pace_live) pace_step(tl);
             }
             // (Measured per wave: waves 0-3 wait ~600 cycles per tile at the pair barrier, waves 4-7 ~75 -- issue arbitration between the two waves
             // of a SIMD is by age.  Giving the younger half s_setprio 1 for the first tile of every pair halves the total wait and changes
             // the kernel's time by nothing: the SIMD's throughput, not the rendezvous, sets it.)
-            float mx = -INFINITY;
+            float mx = -INFINITY, mx1 = -INFINITY;
+            // NWV = 8: one step = one counted wait, one ds_read_b128 and TWO v_mfma_f32_16x16x32_f16 -- the fragment (rows 16 t .., 32 k) times query
+            // group 0 and group 1; read i of chunk cch is k-step 6 cch + (i >> 1) of row half t = i & 1, so each of the four accumulators
+            // acc[g][t] is touched every fourth MFMA.  12 fp32 accumulations per score (inside the header's 408 * 2^-24).
+            auto step16 = [&](auto TI) {
+                constexpr int gs = decltype(TI)::value, i = gs % S_CS, cch = gs / S_CS;
+                constexpr int cur = 2 * P + cch, nxt = (cur + 1) % C::NR;
+                constexpr int tt = i & 1, sk = 6 * cch + (i >> 1), e0 = 4 * tt, e1 = 8 + 4 * tt;
+                if (gs == 18 && !(a.share_thr & 2) && !(EXP & 8) && __builtin_expect(__ballot(mx > thr_g0 || mx1 > thr_g1) != 0, 0)) {
+                    slow_path(to_owner(prev), lane_r0 + (int64_t)(tl - 1) * S_RT, 0xffffu);
+                    share_thr16();
+                }
+                if (L2N && gs >= 13 && gs <= 16) frag_wait_nrm(fr[gs % S_PRE]);
+                else frag_wait(fr[gs % S_PRE]);
+                f32x4 c0, c1;
+                if (sk == 0) {
+                    c0 = L2N ? zq[tt] : f32x4{0.f, 0.f, 0.f, 0.f};
+                    c1 = c0;
+                } else {
+                    c0 = f32x4{acc[e0], acc[e0 + 1], acc[e0 + 2], acc[e0 + 3]};
+                    c1 = f32x4{acc[e1], acc[e1 + 1], acc[e1 + 2], acc[e1 + 3]};
+                }
+                c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(fr[gs % S_PRE], qh[sk], c0, 0, 0, 0);
+                c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(fr[gs % S_PRE], qh[12 + sk], c1, 0, 0, 0);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) { acc[e0 + c] = c0[c]; acc[e1 + c] = c1[c]; }
+                if (gs >= 1 && gs <= 4 && !(EXP & 8)) asm("v_max3_f32 %0, %0, %1, %2" : "+v"(mx) : "v"(prev[2 * gs - 2]), "v"(prev[2 * gs - 1]));
+                if (gs >= 5 && gs <= 8 && !(EXP & 8)) asm("v_max3_f32 %0, %0, %1, %2" : "+v"(mx1) : "v"(prev[2 * gs - 2]), "v"(prev[2 * gs - 1]));
+                constexpr int ni = i + S_PRE < S_CS ? i + S_PRE : i + S_PRE - S_CS, ns = i + S_PRE < S_CS ? cur : nxt;
+                read_frag(fr[gs % S_PRE], std::integral_constant<int, ns * S_SLOT + (ni & 1) * 16 * S_CKB + (ni >> 2) * 128>{}, ni >> 1);
+                if (L2N && gs == 12) read_nrm(std::integral_constant<int, (P + 1) % 6>{});        // the NEXT tile's norms (landed: see the kernel's header)
+                if (gs % (S_TS / C::NIW) == 1) issue_part(std::integral_constant<int, (P + 4) % 6>{}, tp, gs / (S_TS / C::NIW));   // steps 1, 9, 17
+                if (gs == 4 && P % 2 == 0) refresh_gthr();
+                if (L2N && gs == 4 && P % 2 == 0) {       // norms of the pair two pairs ahead, into the slots of the pair that has just been left
+                    if (w == 0) issue_nrm(std::integral_constant<int, (P + 4) % 6>{}, np);
+                    np += 2 * S_RT;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            };
             auto step = [&](auto TI) {
+                if constexpr (M16) {
+                    step16(TI);
+                } else {
                 constexpr int gs = decltype(TI)::value, t = gs % S_CS, cch = gs / S_CS;
                 constexpr int cur = 2 * P + cch, nxt = (cur + 1) % C::NR;
                 // (a wave none of whose 32 queries exist -- batches below 97 queries in the one-tile form -- only carries its DMA pieces)
@@ -479,6 +598,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
                     np += 2 * S_RT;
                 }
                 __builtin_amdgcn_sched_barrier(0);
+                }
             };
             step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{}); step(std::integral_constant<int, 2>{});
             step(std::integral_constant<int, 3>{}); step(std::integral_constant<int, 4>{}); step(std::integral_constant<int, 5>{});
@@ -512,6 +632,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
                 last[r] = last_in_a ? accA[r] : accB[r];
                 inmask |= (rbl + (r & 3) + 8 * (r >> 2) < row_end) ? (1u << r) : 0u;
             }
+            if constexpr (M16) last = to_owner(last);
             // (round 6, second session) COLD tile of the ladder's first launch -- one tile per chunk, empty thresholds: every row of the tile is a
             // candidate of every query.  Through slow_path that is 16 store instructions of 64 scattered 8-byte keys per wave (the slots are
             // query-major, a query's lanes 384 B apart: every lane its own line request -- 112 k of a wave's 174 k cycles in the debug build), a
@@ -636,9 +757,9 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
 #pragma unroll
         for (int e = 0; e < GE; ++e) {
             const int jj = j0 + e;
-            nn[e] = (u32)__builtin_amdgcn_readlane((int)cnt, jj);
-            const u64* slot = (const u64*)(((u64)(u32)__builtin_amdgcn_readlane((int)(u32)((u64)gslot >> 32), jj) << 32) |
-                                           (u64)(u32)__builtin_amdgcn_readlane((int)(u32)(u64)gslot, jj));
+            nn[e] = (u32)__builtin_amdgcn_readlane((int)cnt, qlane(jj));
+            const u64* slot = (const u64*)(((u64)(u32)__builtin_amdgcn_readlane((int)(u32)((u64)gslot >> 32), qlane(jj)) << 32) |
+                                           (u64)(u32)__builtin_amdgcn_readlane((int)(u32)(u64)gslot, qlane(jj)));
 #pragma unroll
             for (int pp = 0; pp < C::NPL; ++pp)
                 key[e][pp] = (u32)(lane + 64 * pp) < nn[e] ? __hip_atomic_load(slot + lane + 64 * pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
