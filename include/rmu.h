@@ -468,6 +468,21 @@ int rmu_bert_search_hybrid(rmu_bert_t* m, rmu_hybrid_t* h, const int32_t* ids, c
                            double lambda_mult, const double* weights, int c, int k_out, double* out_scores, int64_t* out_ids,
                            int32_t* out_member);
 
+/* ---- semantic chunker: the cosine distance of adjacent rows (semantic.hip) ------------------------------------------------------------
+ * Serves: SemanticChunker(self.embeddings, breakpoint_threshold_type=..., ...) (RAGHelper.py:329-349): the splitter embeds one window per
+ * sentence and thresholds ONE number per adjacent pair of windows.  ragmeup_amd/chunker.py is the host half (sentences, windows, thresholds).
+ *
+ * out[i] = 1 - sim(x[i], x[i+1]), i in [0, n-1):  sim = dot / (sqrt(|a|^2) * sqrt(|b|^2)); dot, |a|^2, |b|^2 are fp64 sums of the
+ * (exact) fp64 products of the fp32 inputs; a quotient that is NaN or +-Inf (a zero row, a NaN / Inf element) counts as sim = 0, so out = 1.0.
+ * The order of the additions is fixed by the element index alone (element e belongs to lane (e >> 2) & 63, a lane adds its elements ascending,
+ * the lanes are folded by an xor butterfly over 32 .. 1): out[i] has the same bits whatever n, wherever the pair sits in the call, whether or
+ * not the base and stride allow 16-byte loads, and on any stream.
+ * x [n, stride] fp32, of which columns dim .. stride-1 are never read: a device address with RMU_F_Q_DEVICE, else a host array (uploaded
+ * asynchronously).  out [n-1] fp64: a device address with RMU_F_OUT_DEVICE, else a host array.  n == 1 writes nothing and launches nothing.
+ * 1 <= dim <= RMU_MAX_DIM_WIDE, stride >= dim, n >= 1; a NULL pointer, any other flag, any other value: RMU_E_INVALID before any HIP call.
+ * hip_stream as rmu_topk_merge: drained on return unless a caller stream is given with a device x AND a device out. */
+int rmu_adjacent_cosine(const float* x, int64_t n, int dim, int64_t stride, unsigned flags, double* out, uint64_t hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,12 @@ try:
     HAVE_LANGCHAIN = True
 except ImportError:
     HAVE_LANGCHAIN = False
+BaseDocumentTransformer = None
+if HAVE_LANGCHAIN:
+    try:      # the base of langchain_experimental's SemanticChunker (server/RAGHelper.py:336-341)
+        from langchain_core.documents import BaseDocumentTransformer  # type: ignore
+    except ImportError:      # a langchain_core that does not export it: the shim below
+        pass
 
 
 def _cross_encoder_bases() -> tuple:
@@ -187,6 +193,16 @@ if not HAVE_LANGCHAIN:
 
         async def acompress_documents(self, documents, query, callbacks=None):
             return self.compress_documents(documents, query, callbacks)
+
+
+
+if BaseDocumentTransformer is None:
+
+    class BaseDocumentTransformer(ABC):  # type: ignore[no-redef]
+        """`transform_documents(documents) -> documents`, as langchain_core's BaseDocumentTransformer."""
+
+        @abstractmethod
+        def transform_documents(self, documents: Sequence[Document], **kwargs: Any) -> Sequence[Document]: ...
 
 
 if not CROSS_ENCODER_BASES:

@@ -33,6 +33,9 @@ BM25_OPT_TILE_DOCS, BM25_OPT_MAX_WGS, BM25_OPT_REPACK_ON_REMOVE = 1, 2, 4
 BM25_OPT_REPACK_ON_ADD = 8
 BM25_STAT_IMAGE_PACKS, BM25_STAT_IMAGE_SPLICES, BM25_STAT_IMAGE_UPLOAD_BYTES = 16, 17, 18
 RRF_MAX_LISTS = 4
+# launch geometry of rmu_adjacent_cosine (semantic.hip: kWavePairs, kBlockPairs).  Results do not depend on it; the tests put their sizes on
+# both sides of these run boundaries
+ADJ_COS_WAVE_PAIRS, ADJ_COS_WG_PAIRS = 16, 64
 
 # every symbol include/rmu.h declares (tests check the .so exports all of them)
 SYMBOLS = [
@@ -46,6 +49,7 @@ SYMBOLS = [
     "rmu_bm25_create", "rmu_bm25_free", "rmu_bm25_add_texts", "rmu_bm25_stat", "rmu_bm25_df", "rmu_bm25_set_option", "rmu_bm25_search",
     "rmu_bm25_remove_docs", "rmu_bm25_search_subset", "rmu_bm25_compact", "rmu_bm25_save", "rmu_bm25_load",
     "rmu_rrf_fuse", "rmu_hybrid_create", "rmu_hybrid_free", "rmu_hybrid_set_keys", "rmu_hybrid_search", "rmu_bert_search_hybrid",
+    "rmu_adjacent_cosine",
 ]
 
 
@@ -118,6 +122,7 @@ def _declare(lib):
     lib.rmu_hybrid_free.argtypes = [vp]
     lib.rmu_hybrid_set_keys.argtypes = [vp, i32, i64, vp, i64]
     lib.rmu_hybrid_search.argtypes = [vp, vp, i64, c.c_char_p, i64, i32, i32, i32, c.c_double, f64p, i32, i32, vp, vp, vp, u64]
+    lib.rmu_adjacent_cosine.argtypes = [vp, i64, i32, i64, u32, vp, u64]
     if hasattr(lib, "rmu_bert_create"):
         lib.rmu_bert_create.argtypes = [c.POINTER(vp), vp, c.POINTER(vp), i32]
         lib.rmu_bert_free.argtypes = [vp]

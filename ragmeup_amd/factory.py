@@ -7,6 +7,8 @@ The reference builds its plug-ins from environment variables (loaded from `.env`
                                               `vector_store_initial_load`)
   reranker     server/RAGHelper.py:476-490   (`rerank`, `rerank_model`, `rerank_k`)
   retriever    server/RAGHelper.py:497-499   (`vector_store_k`)
+  splitter     server/RAGHelper.py:329-349   (`splitter`, `breakpoint_threshold_type`, `breakpoint_threshold_amount`,
+                                              `number_of_chunks`; parsed at :62, :73-76)
 `from_env()` reads the same variables with the same meaning and returns our implementations; the reference-side
 binding is one call to it from the `vector_store == "mi355x"` branches.
 
@@ -77,6 +79,25 @@ def reranker_from_env(env: Optional[Mapping[str, str]] = None, device: int = 0):
     from .reranker import ScoredCrossEncoderReranker
     return ScoredCrossEncoderReranker(model=MI355XCrossEncoder(model_dir=model, device=device),
                                       top_n=int(env.get("rerank_k", "3")))
+
+
+def text_splitter_from_env(embeddings: Any, env: Optional[Mapping[str, str]] = None):
+    """`_initialize_text_splitter()` (RAGHelper.py:343-349) for `splitter == "SemanticChunker"`: the chunker over `embeddings`, built from
+    `breakpoint_threshold_type`, `breakpoint_threshold_amount` (an int; unset or 'None' -> None) and `number_of_chunks` (an int; unset or
+    'none' in any case -> None), parsed as RAGHelper.py:73-76 parses them.  The recursive character splitter has no device work and stays
+    LangChain's: any other `splitter` raises."""
+    env = os.environ if env is None else env
+    kind = env.get("splitter")
+    if kind != "SemanticChunker":
+        raise ValueError(f"splitter={kind!r}: only 'SemanticChunker' is served here "
+                         "('RecursiveCharacterTextSplitter' stays LangChain's own RecursiveCharacterTextSplitter)")
+    amount = env.get("breakpoint_threshold_amount", "None")
+    amount = int(amount) if amount != "None" else None
+    chunks = env.get("number_of_chunks")
+    chunks = None if chunks is None or chunks.lower() == "none" else int(chunks)
+    from .chunker import MI355XSemanticChunker
+    return MI355XSemanticChunker(embeddings, breakpoint_threshold_type=env.get("breakpoint_threshold_type"),
+                                 breakpoint_threshold_amount=amount, number_of_chunks=chunks)
 
 
 @dataclass
