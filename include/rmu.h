@@ -63,6 +63,13 @@ extern "C" {
 #define RMU_OPT_SCREEN_BAND 7     /* tuning: 1 (default): the ladder's merges seed each launch's thresholds with max(K'-th best, k-th best - 2 EPS(q)),
                              * the lower edge of the sufficiency test's band; 0: with the K'-th best alone.  Results are identical either way. */
 
+#define RMU_OPT_SCREEN_SPILL 8    /* tuning: 1 (default): in the seeded launches of the ladder (full batches: over 128 queries) a lane whose scores pass
+                             * its threshold writes them out as they are and a sift kernel behind the launch files them (row ids, the query's
+                             * threshold, the merge with the running candidates); 0: they are appended inside the scan's tile loop and merged,
+                             * as before.  Results and re-run counts are identical either way. */
+#define RMU_OPT_SCREEN_SPILL_CAP 9 /* tuning: records per spill list of RMU_OPT_SCREEN_SPILL (1..4096; 0 = default, 256).  A wave whose list is full
+                             * goes on appending inside the tile loop; results are identical for every value (the tests force that path). */
+
 #define RMU_OPT_COMPACT_INPLACE 5 /* 0 (default): rmu_index_compact moves the rows into fresh, smaller allocations (in place when those do not
                              * fit); 1: always in place, the capacity stays.  Results are identical either way (the tests force the path). */
 

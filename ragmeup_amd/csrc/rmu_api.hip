@@ -85,7 +85,7 @@ struct Buf {
 struct Tls {
     hipStream_t stream = nullptr;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    Buf q, partial, out_s, out_r, in_s, in_r, qn, gthr, mscratch, qsplit, ckeys, flag, nrm, fbq, fb_s, fb_r, fb_i, mm_q, mm_s, mm_r, mm_p, gcand, sub_ids, sub_rows, eps;
+    Buf q, partial, out_s, out_r, in_s, in_r, qn, gthr, mscratch, qsplit, ckeys, flag, nrm, fbq, fb_s, fb_r, fb_i, mm_q, mm_s, mm_r, mm_p, gcand, sub_ids, sub_rows, eps, spill, spill_cnt;
     std::vector<hipEvent_t> lev;   // per-launch events of the screening ladder
     int ensure_events(int n) {
         while ((int)lev.size() < n) {
@@ -148,7 +148,7 @@ struct Tls {
         if (pend_ev) (void)hipEventDestroy(pend_ev);
         if (stream) (void)hipStreamSynchronize(stream);
         for (Buf* b : {&q, &partial, &out_s, &out_r, &in_s, &in_r, &qn, &gthr, &mscratch, &qsplit, &ckeys, &flag, &nrm, &fbq, &fb_s,
-                       &fb_r, &fb_i, &mm_q, &mm_s, &mm_r, &mm_p, &gcand, &sub_ids, &sub_rows})
+                       &fb_r, &fb_i, &mm_q, &mm_s, &mm_r, &mm_p, &gcand, &sub_ids, &sub_rows, &spill, &spill_cnt})
             b->release();
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -451,6 +451,8 @@ struct rmu_index {
     bool wide_scan = false;         // RMU_OPT_WIDE_SCAN: exact searches run scan_wide_kernel whatever the width; no screening while set
     int ladder_ratio = 0, ladder_first = 0;   // RMU_OPT_LADDER_RATIO / _FIRST (0 = defaults; tools/ladder_sweep.py)
     bool screen_band = true;        // RMU_OPT_SCREEN_BAND: the ladder's merges also seed the lower edge of the sufficiency band (screen_enqueue)
+    bool screen_spill = true;       // RMU_OPT_SCREEN_SPILL: seeded 8-wave launches spill passing lanes, rmu_sift_launch files them (screen_enqueue)
+    int spill_cap = 0;              // RMU_OPT_SCREEN_SPILL_CAP: records per spill list (0 = kSpillCap)
     int64_t screen_min_nq = 0;      // RMU_OPT_SCREEN_MIN_NQ: > 0 = screen every batch of at least this many queries, whatever the corpus size
     std::vector<uint8_t> alive;
     std::shared_mutex mu;
@@ -1179,7 +1181,7 @@ static void dbg_dump(const char* what, int64_t rows, hipStream_t s) {
     u64 h[16];
     (void)hipStreamSynchronize(s);
     (void)hipMemcpy(h, g_dbg, 128, hipMemcpyDeviceToHost);
-    fprintf(stderr, "[rmu dbg %s: %lld rows] slow_tiles=%llu compactions=%llu appends=%llu wave_tiles=%llu rounds=%llu clk_slow=%llu clk_bar=%llu clk_all=%llu clk_vmwait=%llu seg=%llu/%llu/%llu/%llu/%llu/%llu/%llu\n",
+    fprintf(stderr, "[rmu dbg %s: %lld rows] slow_tiles=%llu compactions=%llu appends=%llu wave_tiles=%llu spill_tiles=%llu clk_slow=%llu clk_bar=%llu clk_all=%llu clk_vmwait=%llu seg=%llu/%llu/%llu/%llu/%llu/%llu/%llu\n",
             what, (long long)rows, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15]);
     (void)hipMemset(g_dbg, 0, 128);
 }
@@ -1231,6 +1233,11 @@ static std::vector<int64_t> ladder_bounds(int64_t n, int64_t nb, int opt_ratio =
     return best;
 }
 
+static int nofilter_env() {        // RMU_SCREEN_NOFILTER: ScanLaunch::share_thr bit 1 (timing ablation)
+    static const int nofilter = rmu_env("RMU_SCREEN_NOFILTER") != nullptr ? 2 : 0;
+    return nofilter;
+}
+
 // Enqueue the screening ladder for `nb` device queries (fp32, [nb, 384]): on return (stream order) t.ckeys holds the best
 // K' approximate candidates per query, sorted.  No host synchronisation.  scan_ms_events: record per-launch events.
 // Threshold ladder: the corpus is scanned in row ranges of geometrically growing size (256 rows, x8 up to 64k, then x3);
@@ -1266,10 +1273,26 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
     for (int l = 0; l < nl; ++l)
         gcand_bytes = std::max(gcand_bytes, (size_t)lv[(size_t)l].parts * (size_t)nb * (kp > RMU_KS_CAP - 8 ? RMU_KS_CAP_DEEP : RMU_KS_CAP) * sizeof(u64));
     if (gcand_bytes && t.gcand.ensure(gcand_bytes)) return fail(RMU_E_OOM, "rmu_index_search: screening candidate slots");
+    // Spill path (RMU_OPT_SCREEN_SPILL, scan_screen.hip "Spill path"): the SEEDED launches of the 8-wave kernels leave the accumulators of
+    // passing lanes in per-wave lists and rmu_sift_launch takes the place of their merge.  The cold first launch, the 4-wave kernels and the
+    // filter's debugging modes (RMU_NO_SHARED_THR, RMU_SCREEN_NOFILTER) go the old way; switched off, the ladder is enqueued as it always was.
+    // kSpillCap records per list.  Debug counters of the headline (10M x 1024, band on, profiles/screen_spill.md): the fullest levels, 13 504
+    // and 108 032 rows, leave 69 384 / 68 465 passing scores in 1 952 / 2 048 lists -- 36 per list, and a record holds at least one of them;
+    // the four large levels leave 10 per list.  256 is seven times that mean (a Poisson count of mean 36 passes 256 with a probability
+    // below 1e-100; the scores of a list are those of 32 queries that each contribute one or two) and holds two tiles in which EVERY lane
+    // passes for both groups (2 x 128 records).  A list that still overflows costs nothing but time: its wave goes on through slow_path.
+    static constexpr int kSpillCap = 256;
+    const int spill_cap = idx->spill_cap > 0 ? idx->spill_cap : kSpillCap;
+    size_t spill_lists = 0;
+    if (idx->screen_spill && share && !nofilter_env())
+        for (int l = 1; l < nl; ++l)
+            if (lv[(size_t)l].wq == 8) spill_lists = std::max(spill_lists, (size_t)lv[(size_t)l].s_chunks * (size_t)lv[(size_t)l].nqt * 8);
+    if (spill_lists && (t.spill.ensure(spill_lists * (size_t)spill_cap * RMU_SPILL_REC) || t.spill_cnt.ensure(spill_lists * sizeof(u32))))
+        return fail(RMU_E_OOM, "rmu_index_search: screening spill lists");
     if (t.partial.ensure((size_t)slots * part_keys * sizeof(u64)) || t.qsplit.ensure((size_t)nb * RMU_IMG_ROW_BYTES) ||
         t.gthr.ensure(gbytes) || t.ckeys.ensure(part_keys * sizeof(u64)) || t.eps.ensure((size_t)nb * sizeof(float)) || t.ensure_events(2 * nl))
         return fail(RMU_E_OOM, "rmu_index_search: screening workspace");
-    static const int nofilter = rmu_env("RMU_SCREEN_NOFILTER") != nullptr ? 2 : 0;
+    const int nofilter = nofilter_env();
     const int sflags = share | nofilter;
     // (an L2 index holds its queries as (2q, 1): the image is fp16(64 q) all the same)
     // (round 6) the conversion's first workgroup also zeroes the ladder's thresholds + pacing words and the caller's word: was two memsets
@@ -1299,6 +1322,8 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
         const int raw = l == 0 ? emit_raw : 0;
         S.gthr = (u32*)t.gthr.p; S.share_thr = sflags | raw; S.dbg = g_dbg; S.q = (const float*)t.qsplit.p;
         S.gcand = (u64*)t.gcand.p;
+        const bool spill = spill_lists != 0 && l > 0 && S.wq == 8;
+        if (spill) { S.spill = (char*)t.spill.p; S.spill_cnt = (u32*)t.spill_cnt.p; S.spill_cap = spill_cap; }
         if (timed) HIP_TRY(hipEventRecord(t.lev[(size_t)(2 * l)], s));
         rc = rmu_screen_launch(&S, s);
         if (rc) return fail(rc, "rmu_index_search: screening launch");
@@ -1306,6 +1331,10 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
         cursor += S.parts;
         if (g_dbg) dbg_dump("screen range", S.n_rows, s);
         u64* merged = l + 1 < nl ? base + (size_t)cursor * part_keys : (u64*)t.ckeys.p;
+        if (spill)       // the running top-K' (slot `first`) + this launch's spill lists (+ the part lists of waves that fell back)
+            rc = rmu_sift_launch(&S, base + (size_t)first * part_keys, nb, kp, merged, l + 1 < nl ? (u32*)t.gthr.p : nullptr, s, k,
+                                 band ? (const float*)t.eps.p : nullptr);
+        else
         rc = rmu_merge_to_keys_band_launch(base + (size_t)first * part_keys, cursor - first, nb, kp, merged,
                                            l + 1 < nl ? (u32*)t.gthr.p : nullptr /* merge + seed in one launch */, s, raw ? 1 : 0, k,
                                            band ? (const float*)t.eps.p : nullptr);
@@ -1750,6 +1779,8 @@ extern "C" int rmu_index_set_option(rmu_index_t* idx, int option, int64_t value)
         case RMU_OPT_LADDER_RATIO: idx->ladder_ratio = value > 0 && value <= 4096 ? (int)value : 0; return RMU_OK;
         case RMU_OPT_LADDER_FIRST: idx->ladder_first = value > 0 && value <= (1 << 30) ? (int)value : 0; return RMU_OK;
         case RMU_OPT_SCREEN_BAND: idx->screen_band = value != 0; return RMU_OK;
+        case RMU_OPT_SCREEN_SPILL: idx->screen_spill = value != 0; return RMU_OK;
+        case RMU_OPT_SCREEN_SPILL_CAP: idx->spill_cap = value > 0 && value <= 4096 ? (int)value : 0; return RMU_OK;
         case RMU_OPT_COMPACT_INPLACE: idx->compact_inplace = value != 0; return RMU_OK;
         case RMU_OPT_WIDE_SCAN:
             if (idx->metric == RMU_METRIC_L2SQ) return fail(RMU_E_INVALID, "rmu_index_set_option: RMU_OPT_WIDE_SCAN serves RMU_METRIC_IP / RMU_METRIC_COSINE indexes only");

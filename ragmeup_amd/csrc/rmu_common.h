@@ -195,8 +195,16 @@ struct ScanLaunch {
     // exact scan only: 1 = scan_wide_kernel (scan_wide.hip: queries streamed through the ring, any dpad that is a multiple of 32 up to 3072).  Set by
     // rmu_scan_plan for dpad > 768, or by the caller in front of it (RMU_OPT_WIDE_SCAN) for a width scan_topk_kernel would take
     int wide;
+    // screening scan only, seeded launches of the 8-wave kernels (scan_screen.hip, "Spill path"): a lane whose running maximum beats its query
+    // group's threshold writes its 8 accumulators of that group + (tile, lane, group) as one RMU_SPILL_REC-byte record into the list of its
+    // (row chunk, query tile, wave); rmu_sift_launch files the records.  spill = nullptr: off (every passing tile takes slow_path)
+    char* spill;           // [s_chunks * nqt * 8][spill_cap] records
+    u32* spill_cnt;        // [s_chunks * nqt * 8] records written; bit 31 = the wave ran out of room and went on through slow_path (its slots are emitted)
+    int spill_cap;         // records per list
 };
-#define RMU_KS_CAP 48     /* K' <= 40 kept candidates + 8 free slots between compactions (one key per lane in the rank: <= 64) */
+#define RMU_SPILL_REC 48  /* 8 fp32 accumulators (element 4 t + c = tile row 16 t + 4 (lane >> 4) + c) + {tile of the chunk, lane | group << 8, 0, 0} */
+#define RMU_SPILL_FELL 0x80000000u
+#define RMU_KS_CAP 48    /* K' <= 40 kept candidates + 8 free slots between compactions (one key per lane in the rank: <= 64) */
 #define RMU_KS_CAP_DEEP 128   /* (round 6) 32 < k <= 104: K' <= 120 kept candidates + 8 free slots, two keys per lane in the rank */
 
 // Row chunks of a scan launch of nqt query tiles over tiles_total row tiles (every planner's: rmu_scan_plan, rmu_subset_plan,
@@ -246,8 +254,12 @@ int rmu_merge_to_keys_launch(const u64* partial, int parts, int64_t nq, int k, u
 // the same merge; seed_thr also receives the lower edge of the sufficiency band of the caller's k = band_k < k (band_eps: EPS(q) per query, or null)
 int rmu_merge_to_keys_band_launch(const u64* partial, int parts, int64_t nq, int k, u64* out_keys, u32* seed_thr, hipStream_t s, int unsorted,
                                   int band_k, const float* band_eps);
+// the merge of a seeded launch that spilled (S.spill != nullptr; topk_merge.hip: sift_kernel): the running top-k `running` [nq, k] + the
+// launch's spill records above gthr[q] + the part lists S.partial of the waves that fell back -> out_keys [nq, k]; seeds as the band merge does
+int rmu_sift_launch(const ScanLaunch* S, const u64* running, int64_t nq, int k, u64* out_keys, u32* seed_thr, hipStream_t s, int band_k,
+                    const float* band_eps);
 // fp16 screening path (scan_screen.hip)
-#define RMU_IMG_ROW_BYTES 768                          /* fp16(64 x) image of a 384-d row */
+#define RMU_IMG_ROW_BYTES 768                        /* fp16(64 x) image of a 384-d row */
 int rmu_split_launch(const float* src, void* dst, int64_t n_rows, hipStream_t s, int stride = 384,
                      float scale = 64.0f, u32* zero_a = nullptr, int n_zero_a = 0, u32* zero_b = nullptr, int n_zero_b = 0,
                      float* eps_out = nullptr /* [n_rows]: EPS(q) of each row taken as a query (l2: rows are (2q, 1)) */, float xnorm_max = 0.f,

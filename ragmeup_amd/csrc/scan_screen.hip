@@ -37,6 +37,21 @@
 // when EPS is finite, and when k < K' (rmu_index_screen_candidates asks for k = K' and still gets the true approximate top-K').
 // RMU_OPT_SCREEN_BAND = 0 seeds the K'-th key alone.  On random unit rows the band's edge sits near rank 11-12 of K' = 32 at k = 10: a seeded
 // level appends about a third of the K' (ratio - 1) candidates per query it appended before (tests/test_screen_band_cpu.py: 0.34).
+// Spill path (RMU_OPT_SCREEN_SPILL; the SEEDED launches of the 8-wave kernels): a tile in which some lane passes used to enter slow_path --
+// owner change, a walk over the rows, an exchange with the partner lane per row, per-query slot counts, scattered 8-byte stores -- while the
+// workgroup's other seven waves wait for that wave at the pair barrier.  None of that per-query work has to happen there.  A lane whose
+// running maximum beats its group's threshold stores the 8 scores it holds of that group, in the MFMA's own layout, with (tile, lane, group)
+// into a list of its wave (spill_tile below), and a sift kernel behind the launch (topk_merge.hip: sift_kernel) decides which query and row a
+// score belongs to and whether it survives.  Why deferring is sound: in a seeded launch a query's threshold is the word the last merge
+// published (gthr[q]); only a compaction raises it during the launch, to some chunk's own K'-th best, and thresholds only rise.  The lane
+// spilled because its maximum beat the threshold of that moment; the sift tests every score of the record, strictly, against gthr[q] as it
+// stands after the launch -- the same word or a higher one.  So the sift keeps exactly {rows of the range with s~ > gthr[q]}; an append
+// would have kept a superset of the best K' of that set and the merge would have cut it to those.  A score the sift drops for a raised
+// threshold is below K' rows of this range, as with appends: nothing is dropped that an append would have kept in the merged top-K'.  The
+// merged keys, their order and the seeds of the next launch (K'-th key and band edge: seed_band, unchanged) are the same, bit for bit.
+// A list holds spill_cap records; a wave whose list cannot take a tile's records takes slow_path for that tile and every later one, its
+// slots are emitted as before and the sift folds that part list in (RMU_SPILL_FELL in the wave's count word).  The cold first launch, its
+// direct path, its raw emit and the unsorted merge are untouched, and so are the 4-wave kernels.
 // (An earlier hi/lo split variant, 3 MFMAs per 16 k with EPS = 1e-4, ran at 25 ms for the 10M x 1024 headline; its
 // ablations showed the LDS/L2 path, not the MFMA pipe, setting the time, which is what halving the bytes attacks.)
 #include <cstdlib>
@@ -463,6 +478,43 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
             }
         return p;
     };
+    // ---- spill path (NWV = 8, seeded launches: a.spill; see the file header) ---------------------------------------------------------------
+    // A lane whose running maximum beats its group's threshold stores the 8 scores it holds of that group, as the MFMA left them, and
+    // {tile, lane | group << 8} behind them: three 16-byte stores into the list of this (row chunk, query tile, wave).  The fill count is a
+    // wave-uniform register, a lane's place is the count + its rank in the two ballots: no owner change, no walk over rows, no exchange with a
+    // partner lane, no per-query count, no atomic and no wait.  Inline asm like every store of this path (a store hipcc can see costs the
+    // tile loop an s_waitcnt vmcnt(0)); the s_nop 1 covers the data registers of a store wider than 64 bits (NOTES_r06.md 8).  A tile that
+    // does not fit ends the wave's spilling: it and every later one take slow_path, whose slots are then emitted as ever (RMU_SPILL_FELL).
+    typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+    const bool spill_launch = M16 && a.spill != nullptr;  // (uniform over the grid)
+    const int sp_list = (s_idx * a.nqt + qt) * NW + w;    // (uniform)
+    char* const sp_base = a.spill + (size_t)sp_list * (size_t)a.spill_cap * RMU_SPILL_REC;
+    u32 sp_cnt = 0, d_spill = 0;                          // (uniform)
+    bool sp_live = spill_launch;                          // (uniform) still spilling
+    auto spill_tile = [&](const f32x16& nat, int tile, bool p0, bool p1) -> bool {
+        const u64 b0 = __ballot(p0), b1 = __ballot(p1);
+        const u32 n0 = (u32)__builtin_popcountll(b0), n1 = (u32)__builtin_popcountll(b1);
+        if (sp_cnt + n0 + n1 > (u32)a.spill_cap) { sp_live = false; return false; }
+        unsigned long long c0 = 0;
+        if (DBG) { ++d_spill; c0 = clock64(); }
+        const u32 r0 = sp_cnt + __builtin_amdgcn_mbcnt_hi((u32)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((u32)b0, 0u));
+        const u32 r1 = sp_cnt + n0 + __builtin_amdgcn_mbcnt_hi((u32)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((u32)b1, 0u));
+        if (p0) {
+            const f32x4 v0 = {nat[0], nat[1], nat[2], nat[3]}, v1 = {nat[4], nat[5], nat[6], nat[7]};
+            const u32x4 hd = {(u32)tile, (u32)lane, 0u, 0u};
+            asm volatile("global_store_dwordx4 %0, %1, off\n\tglobal_store_dwordx4 %0, %2, off offset:16\n\tglobal_store_dwordx4 %0, %3, off offset:32\n\ts_nop 1"
+                         ::"v"(sp_base + (size_t)r0 * RMU_SPILL_REC), "v"(v0), "v"(v1), "v"(hd) : "memory");
+        }
+        if (p1) {
+            const f32x4 v0 = {nat[8], nat[9], nat[10], nat[11]}, v1 = {nat[12], nat[13], nat[14], nat[15]};
+            const u32x4 hd = {(u32)tile, (u32)lane | 256u, 0u, 0u};
+            asm volatile("global_store_dwordx4 %0, %1, off\n\tglobal_store_dwordx4 %0, %2, off offset:16\n\tglobal_store_dwordx4 %0, %3, off offset:32\n\ts_nop 1"
+                         ::"v"(sp_base + (size_t)r1 * RMU_SPILL_REC), "v"(v0), "v"(v1), "v"(hd) : "memory");
+        }
+        sp_cnt += n0 + n1;
+        if (DBG) d_clk_slow += clock64() - c0;
+        return true;
+    };
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
     using I4 = std::integral_constant<int, 4>; using I5 = std::integral_constant<int, 5>;
@@ -533,8 +585,10 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
                 constexpr int cur = 2 * P + cch, nxt = (cur + 1) % C::NR;
                 constexpr int tt = i & 1, sk = 6 * cch + (i >> 1), e0 = 4 * tt, e1 = 8 + 4 * tt;
                 if (gs == 18 && !(a.share_thr & 2) && !(EXP & 8) && __builtin_expect(__ballot(mx > thr_g0 || mx1 > thr_g1) != 0, 0)) {
-                    slow_path(to_owner(prev), lane_r0 + (int64_t)(tl - 1) * S_RT, 0xffffu);
-                    share_thr16();
+                    if (!(sp_live && spill_tile(prev, tl - 1, mx > thr_g0, mx1 > thr_g1))) {
+                        slow_path(to_owner(prev), lane_r0 + (int64_t)(tl - 1) * S_RT, 0xffffu);
+                        share_thr16();
+                    }
                 }
                 if (L2N && gs >= 13 && gs <= 16) frag_wait_nrm(fr[gs % S_PRE]);
                 else frag_wait(fr[gs % S_PRE]);
@@ -632,7 +686,18 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
                 last[r] = last_in_a ? accA[r] : accB[r];
                 inmask |= (rbl + (r & 3) + 8 * (r >> 2) < row_end) ? (1u << r) : 0u;
             }
-            if constexpr (M16) last = to_owner(last);
+            // spill launch: the last tile of the chunk is spilled like the others (rows past the range's end are dropped by the sift)
+            bool last_spilled = false;
+            if constexpr (M16) {
+                if (sp_live && !(a.share_thr & 2)) {
+                    float m0 = last[0], m1 = last[8];
+#pragma unroll
+                    for (int r = 1; r < 8; ++r) { m0 = fmaxf(m0, last[r]); m1 = fmaxf(m1, last[8 + r]); }
+                    const bool p0 = m0 > thr_g0, p1 = m1 > thr_g1;
+                    last_spilled = __ballot(p0 || p1) == 0ull || spill_tile(last, ntiles - 1, p0, p1);
+                }
+                last = to_owner(last);
+            }
             // (round 6, second session) COLD tile of the ladder's first launch -- one tile per chunk, empty thresholds: every row of the tile is a
             // candidate of every query.  Through slow_path that is 16 store instructions of 64 scattered 8-byte keys per wave (the slots are
             // query-major, a query's lanes 384 B apart: every lane its own line request -- 112 k of a wave's 174 k cycles in the debug build), a
@@ -668,7 +733,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
                     if (q_base + qq < a.nq) pbase[(size_t)qq * a.k + pos] = 0ull;
                 }
                 direct = true;
-            } else if (!(a.share_thr & 2)) slow_path(last, rbl, inmask);
+            } else if (!(a.share_thr & 2) && !last_spilled) slow_path(last, rbl, inmask);
         }
     }
     if (DBG) {
@@ -680,6 +745,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
             atomicAdd((unsigned long long*)a.dbg + 1, (unsigned long long)d_comp);
             atomicAdd((unsigned long long*)a.dbg + 2, (unsigned long long)app);
             atomicAdd((unsigned long long*)a.dbg + 3, (unsigned long long)ntiles);
+            atomicAdd((unsigned long long*)a.dbg + 4, (unsigned long long)d_spill);      // spilled tiles (their cycles are part of clk_slow)
             atomicAdd((unsigned long long*)a.dbg + 5, d_clk_slow);
             atomicAdd((unsigned long long*)a.dbg + 6, d_clk_bar);
             atomicAdd((unsigned long long*)a.dbg + 8, d_clk_vm);
@@ -689,6 +755,8 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
     }
     // ---- emit: best K' approximate candidates of this (chunk, query), sorted.  All 32 slots (DEEP: 8 at a time) are read back in ONE round trip (the query fragments are dead: registers are free).
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // spill launch: the list's fill count goes to memory once, here; a wave that never fell back has nothing in its slots and skips the emit
+    if (spill_launch && lane == 0) a.spill_cnt[sp_list] = sp_cnt | (sp_live ? 0u : RMU_SPILL_FELL);
     const int part = s_idx;
     constexpr int GE = DEEP ? 8 : 32;
     // share_thr bit 2 (the ladder's FIRST launch: rmu_api.hip screen_enqueue): slots of at most K' entries are written as they are -- compact,
@@ -751,7 +819,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
         }
     } else {
     for (int j0 = 0; j0 < 32; j0 += GE) {
-        if (q_base + j0 >= a.nq || direct) break;
+        if (q_base + j0 >= a.nq || direct || (spill_launch && sp_live)) break;
         u64 key[GE][C::NPL];
         u32 nn[GE];
 #pragma unroll

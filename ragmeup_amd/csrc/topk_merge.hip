@@ -303,6 +303,226 @@ __global__ __launch_bounds__(BLOCK) void merge_select_kernel(const u64* __restri
         if ((u32)e >= m) emit(e, 0ull);
 }
 
+// ---- sift: the merge of a seeded screening launch that SPILLED (scan_screen.hip, "Spill path") ------------------------------------------------
+// The launch's 8-wave workgroups left, per (row chunk, query tile, wave), a list of records: the 8 accumulators a lane held of one query group
+// of one tile, whenever the lane's maximum beat the group's threshold.  One workgroup per query does afterwards what slow_path did inside
+// the barrier-coupled loop.  Its threads walk the records of the query's wave in every chunk (a flat index over all lists through a prefix
+// of the fill counts; eight headers in flight per thread), take those of the query's own column (lane & 15, group), turn element e of a record
+// into the row id and the key slow_path would have stored -- row0 + 32 (chunk's first tile + tile) + 16 (e >> 2) + 4 (lane >> 4) + (e & 3),
+// score = acc / 4096 -- and keep what is STRICTLY above the query's threshold (gthr[q]: the word the launch itself filtered with, or a later
+// and higher one) and inside the range.  Those keys, the running top-k and the part lists of the waves that ran out of room and fell back
+// to their slots meet in one LDS array and are ranked by enumeration, as merge_select_kernel ranks its candidates; the seeds are its emit's.
+// More than CAPM keys (a query that thousands of rows of one range pass): the first wave folds everything through the bitonic stream
+// merge of merge_stream instead (sift_stream: 128 staged keys, any number of candidates).
+struct SiftIn {
+    const u64* running;       // [nq, k] merged keys of the ranges before this one (sorted, zeros last), or null
+    const char* spill;        // ScanLaunch::spill / spill_cnt / spill_cap of the launch
+    const u32* spill_cnt;
+    const u64* parts;         // [s_chunks, nq, k] the launch's part lists: valid for the waves whose count carries RMU_SPILL_FELL
+    const u32* gthr;          // [nq] the thresholds the launch filtered with
+    int spill_cap, s_chunks, nqt, tiles_per_chunk;
+    int64_t row0, row_end;    // the launch's rows [row0, row_end)
+};
+typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
+
+// which list and which record of it is flat record f: the largest c with pre[c] <= f (pre[c] = records in the lists of the chunks below c)
+__device__ __forceinline__ int sift_chunk_of(const volatile u32* pre, u32 f) {
+    int c = 0;
+#pragma unroll
+    for (int step = 128; step > 0; step >>= 1)
+        if (pre[c + step] <= f) c += step;
+    return c;
+}
+__device__ __forceinline__ const char* sift_record(const SiftIn& in, int list0, const volatile u32* pre, u32 f, int& c) {
+    c = sift_chunk_of(pre, f);
+    return in.spill + ((size_t)(list0 + c * in.nqt * 8) * (size_t)in.spill_cap + (f - pre[c])) * RMU_SPILL_REC;
+}
+__device__ __forceinline__ int64_t sift_row_base(const SiftIn& in, int c, const u32x4_t& hd) {
+    return in.row0 + ((int64_t)c * in.tiles_per_chunk + (int64_t)hd[0]) * 32 + 4 * (int64_t)((hd[1] >> 4) & 3u);
+}
+
+// one wave, any number of candidates: -> top = the best k of running + records + fallen-back parts, sorted
+template <int NPL>
+__device__ __forceinline__ void sift_stream(const SiftIn& in, int64_t q, int64_t nq, int k, float thr, int lane, volatile u64* st,
+                                            const volatile u32* pre, u32 total, const volatile u32* fellw, u64 (&top)[NPL]) {
+    const int list0 = (int)(q >> 8) * 8 + ((int)(q >> 5) & 7);
+    const u32 want = (u32)q & 15u, gsel = ((u32)q >> 4) & 1u;
+#pragma unroll
+    for (int p = 0; p < NPL; ++p) top[p] = (in.running && lane + 64 * p < k) ? in.running[q * k + lane + 64 * p] : 0ull;
+    // staged keys: at most 63 stay behind a push, a push adds at most 64
+    u32 ns = 0;
+    auto drain = [&](u32 keep) {
+        while (ns > keep) {
+            __builtin_amdgcn_wave_barrier();
+            u64 bk[1] = {(u32)lane < ns ? st[lane] : 0ull};
+            const u64 up = (u32)lane + 64u < ns ? st[lane + 64] : 0ull;
+            __builtin_amdgcn_wave_barrier();
+            rmu_bitonic_sort_desc<1>(bk, lane);
+            const u64 rev = __shfl(bk[0], 63 - lane);
+            u64& tail = top[NPL - 1];
+            tail = tail > rev ? tail : rev;
+            rmu_bitonic_merge_desc<NPL>(top, lane);
+            if (ns > 64u) { st[lane] = up; ns -= 64u; } else ns = 0u;
+        }
+    };
+    auto push = [&](bool has, u64 key) {
+        const u64 b = __ballot(has);
+        if (!b) return;
+        const u32 pos = ns + __builtin_amdgcn_mbcnt_hi((u32)(b >> 32), __builtin_amdgcn_mbcnt_lo((u32)b, 0u));
+        if (has) st[pos] = key;
+        ns += (u32)__builtin_popcountll(b);
+        drain(63u);
+    };
+    for (u32 f0 = 0; f0 < total; f0 += 64u) {
+        const u32 f = f0 + (u32)lane;
+        int c = 0;
+        u32x4_t hd = {0u, 0u, 0u, 0u};
+        f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+        if (f < total) {
+            const char* rec = sift_record(in, list0, pre, f, c);
+            v0 = *(const f32x4*)rec;
+            v1 = *(const f32x4*)(rec + 16);
+            hd = *(const u32x4_t*)(rec + 32);
+        }
+        const bool match = f < total && (hd[1] & 15u) == want && (hd[1] >> 8) == gsel;
+        if (!__any(match)) continue;
+        const int64_t rb = sift_row_base(in, c, hd);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float sv = e < 4 ? v0[e & 3] : v1[e & 3];
+            const int64_t row = rb + 16 * (e >> 2) + (e & 3);
+            push(match && sv > thr && row < in.row_end, rmu_make_key(sv * (1.0f / 4096.0f) + 0.0f, (u32)row));
+        }
+    }
+    for (int c = 0; c < in.s_chunks; ++c) {
+        if (!((fellw[c >> 2] >> (c & 3)) & 1u)) continue;
+        const u64* part = in.parts + ((int64_t)c * nq + q) * k;
+#pragma unroll
+        for (int p = 0; p < NPL; ++p) {
+            const u64 key = lane + 64 * p < k ? part[lane + 64 * p] : 0ull;
+            push(key != 0ull, key);
+        }
+    }
+    drain(0u);
+}
+
+template <int NPL, int CAPM>
+__global__ __launch_bounds__(256) void sift_kernel(const SiftIn in, int64_t nq, int k, MergeOut o) {
+    __shared__ u64 cand[CAPM];
+    __shared__ u64 stage[128];
+    __shared__ u32 pre[257];
+    __shared__ u32 fellw[64];         // bit j of word l: the wave of chunk 4 l + j fell back
+    __shared__ u32 count, anyfell;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t q = blockIdx.x;
+    const int list0 = (int)(q >> 8) * 8 + ((int)(q >> 5) & 7);   // the scan's (query tile, wave) of this query: 256 queries per workgroup, 32 per wave
+    const u32 want = (u32)q & 15u, gsel = ((u32)q >> 4) & 1u;
+    const u32 go = in.gthr[q];
+    const float thr = go ? rmu_ord2f(go - 1u) * 4096.0f : -INFINITY;      // (scan_screen_lean3_kernel's thr_s)
+    if (tid < 64) {           // fill counts of the wave's lists (this lane: chunks 4 lane .. 4 lane + 3) -> pre[0 .. 256]
+        const u32 cap = (u32)in.spill_cap;
+        u32 c4[4], sum = 0, fell = 0;
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const int sc = 4 * lane + jj;
+            const u32 c = sc < in.s_chunks ? in.spill_cnt[list0 + sc * in.nqt * 8] : 0u;
+            fell |= (c & RMU_SPILL_FELL) ? (1u << jj) : 0u;
+            const u32 n = c & ~RMU_SPILL_FELL;
+            c4[jj] = n < cap ? n : cap;
+            sum += c4[jj];
+        }
+        u32 inc = sum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const u32 v = (u32)__shfl_up((int)inc, d);
+            if (lane >= d) inc += v;
+        }
+        u32 ex = inc - sum;
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) { pre[4 * lane + jj] = ex; ex += c4[jj]; }
+        if (lane == 63) pre[256] = inc;
+        fellw[lane] = fell;
+        const u64 af = __ballot(fell != 0u);
+        if (lane == 0) { count = 0u; anyfell = af != 0ull ? 1u : 0u; }
+    }
+    __syncthreads();
+    const u32 total = pre[256];
+    auto add = [&](u64 key) {
+        const u32 at = atomicAdd(&count, 1u);
+        if (at < (u32)CAPM) cand[at] = key;
+    };
+    if (in.running && tid < k) {
+        const u64 key = in.running[q * k + tid];
+        if (key) add(key);
+    }
+    constexpr int UN = 8;                                  // records per thread and trip: their headers are requested together
+    for (u32 f0 = 0; f0 < total; f0 += 256u * UN) {
+        const char* rec[UN];
+        int ch[UN];
+        u32x4_t hd[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const u32 f = f0 + 256u * u + (u32)tid;
+            hd[u] = u32x4_t{0u, 0xffffffffu, 0u, 0u};
+            rec[u] = nullptr; ch[u] = 0;
+            if (f < total) {
+                rec[u] = sift_record(in, list0, pre, f, ch[u]);
+                hd[u] = *(const u32x4_t*)(rec[u] + 32);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            if ((hd[u][1] & 15u) != want || (hd[u][1] >> 8) != gsel) continue;
+            const f32x4 v0 = *(const f32x4*)rec[u], v1 = *(const f32x4*)(rec[u] + 16);
+            const int64_t rb = sift_row_base(in, ch[u], hd[u]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float sv = e < 4 ? v0[e & 3] : v1[e & 3];
+                const int64_t row = rb + 16 * (e >> 2) + (e & 3);
+                if (sv > thr && row < in.row_end) add(rmu_make_key(sv * (1.0f / 4096.0f) + 0.0f, (u32)row));
+            }
+        }
+    }
+    if (anyfell)
+        for (int c = 0; c < in.s_chunks; ++c)
+            if (((fellw[c >> 2] >> (c & 3)) & 1u) && tid < k) {
+                const u64 key = in.parts[((int64_t)c * nq + q) * k + tid];
+                if (key) add(key);
+            }
+    __syncthreads();
+    const u32 cnt = count;
+    const bool band = o.seed_thr && o.band_eps && o.band_k >= 1 && o.band_k < k;      // (uniform)
+    auto emit = [&](int e, u64 key, bool full) {
+        o.keys[q * k + e] = key;
+        if (o.seed_thr && e == k - 1 && key) atomicMax(o.seed_thr + q, (u32)(key >> 32));
+        if (band && e == o.band_k - 1) seed_band(o, q, key, full);
+    };
+    if (cnt > (u32)CAPM) {
+        if (tid >= 64) return;
+        u64 top[NPL];
+        sift_stream<NPL>(in, q, nq, k, thr, lane, stage, pre, total, fellw, top);
+        u64 kth = 0ull;
+#pragma unroll
+        for (int p = 0; p < NPL; ++p) {
+            const u64 v = __shfl(top[p], (k - 1) & 63);
+            if (((k - 1) >> 6) == p) kth = v;
+        }
+#pragma unroll
+        for (int p = 0; p < NPL; ++p)
+            if (lane + 64 * p < k) emit(lane + 64 * p, top[p], kth != 0ull);
+        return;
+    }
+    const bool full = cnt >= (u32)k;            // the merged k-th key exists: the candidates are distinct keys > 0
+    for (u32 i = tid; i < cnt; i += 256) {
+        const u64 mine = cand[i];
+        u32 rank = 0;
+        for (u32 jj = 0; jj < cnt; ++jj) rank += cand[jj] > mine ? 1u : 0u;
+        if (rank < (u32)k) emit((int)rank, mine, full);
+    }
+    for (int e = tid; e < k; e += 256)
+        if ((u32)e >= cnt) emit(e, 0ull, full);
+}
+
 // generic lists (scores fp32 + int64 rows; part p at scores + p*stride_s / rows + p*stride_r, each [nq, k]); ties resolve
 // to the lower candidate index, i.e. the lower part, then the earlier position -- equal to (score, row) order when
 // parts arrive in ascending row ranges.  smaller_better: the scores are distances (keys are built from -score).
@@ -387,6 +607,24 @@ int rmu_merge_to_keys_band_launch(const u64* partial, int parts, int64_t nq, int
     MergeOut o{};
     o.keys = out_keys; o.seed_thr = seed_thr; o.unsorted = unsorted; o.band_k = band_k; o.band_eps = band_eps;
     return merge_wg_launch(partial, parts, nq, k, o, RmuCond{}, s);
+}
+
+// ... of a seeded launch that spilled (S: the launch as it was enqueued): sift_kernel instead of the merge; same keys, same seeds
+int rmu_sift_launch(const ScanLaunch* S, const u64* running, int64_t nq, int k, u64* out_keys, u32* seed_thr, hipStream_t s, int band_k,
+                    const float* band_eps) {
+    if (!S || !S->spill || !S->spill_cnt || !S->partial || !S->gthr || !out_keys || S->spill_cap < 1 || S->wq != 8 || S->s_chunks < 1 ||
+        S->s_chunks > 256 || S->parts != S->s_chunks || nq != S->nq || k != S->k || k < 1 || k > 128)
+        return RMU_E_INVALID;
+    SiftIn in{};
+    in.running = running; in.spill = S->spill; in.spill_cnt = S->spill_cnt; in.parts = S->partial; in.gthr = S->gthr;
+    in.spill_cap = S->spill_cap; in.s_chunks = S->s_chunks; in.nqt = S->nqt; in.tiles_per_chunk = S->tiles_per_chunk;
+    in.row0 = S->row0; in.row_end = S->row0 + S->n_rows;
+    MergeOut o{};
+    o.keys = out_keys; o.seed_thr = seed_thr; o.band_k = band_k; o.band_eps = band_eps;
+    const dim3 grid((unsigned)nq), block(256);
+    if (k <= 64) hipLaunchKernelGGL((sift_kernel<1, 1024>), grid, block, 0, s, in, nq, k, o);
+    else hipLaunchKernelGGL((sift_kernel<2, 1024>), grid, block, 0, s, in, nq, k, o);
+    return hipGetLastError() == hipSuccess ? RMU_OK : RMU_E_HIP;
 }
 
 int rmu_merge_lists_launch(const float* scores, const int64_t* rows, int parts, int64_t stride_s, int64_t stride_r, int64_t nq, int k,

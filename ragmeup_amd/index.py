@@ -293,6 +293,13 @@ class FlatIndex:
         or with the K'-th best alone.  Results and re-run counts are identical either way."""
         N.check(self._lib.rmu_index_set_option(self._h, N.OPT_SCREEN_BAND, 1 if on else 0), "rmu_index_set_option")
 
+    def set_screen_spill(self, on: bool = True, cap: int = 0):
+        """Tuning (RMU_OPT_SCREEN_SPILL / RMU_OPT_SCREEN_SPILL_CAP): the seeded launches of a full batch's ladder write passing scores out as they
+        are and a sift kernel files them behind the launch (default), or append them inside the scan's tile loop as before; `cap` = records
+        per spill list (0 = the default), a full list sends its wave back to appending.  Results and re-run counts are identical either way."""
+        N.check(self._lib.rmu_index_set_option(self._h, N.OPT_SCREEN_SPILL, 1 if on else 0), "rmu_index_set_option")
+        N.check(self._lib.rmu_index_set_option(self._h, N.OPT_SCREEN_SPILL_CAP, int(cap)), "rmu_index_set_option")
+
     def screen_candidates(self, q):
         """Test hook (rmu_index_screen_candidates): per query the screening pass's 32 candidates ->
         (approx scores [nq,32], rows [nq,32], exact fp32 scores of the same rows [nq,32], EPS [nq])."""
