@@ -490,6 +490,37 @@ int rmu_bert_search_hybrid(rmu_bert_t* m, rmu_hybrid_t* h, const int32_t* ids, c
  * hip_stream as rmu_topk_merge: drained on return unless a caller stream is given with a device x AND a device out. */
 int rmu_adjacent_cosine(const float* x, int64_t n, int dim, int64_t stride, unsigned flags, double* out, uint64_t hip_stream);
 
+/* ---- similarity provenance: the share of an answer each retrieved document accounts for (provenance.hip) ------------------------------
+ * Serves: DocumentSimilarityAttribution.compute_similarity(query, context, answer) (provenance.py:164-202, provenance_method=similarity;
+ * RAGHelper_local.py:294-295 calls it once per /chat request).  ragmeup_amd/provenance.py is the host half (texts, the group table, the class).
+ *
+ * A group is one request: an answer row, an optional query row and n_docs consecutive document rows of x.  For document i of a group
+ *   sim_a = sim(doc_i, answer), sim_q = sim(doc_i, query);  s_i = sim_a without a query, else (sim_a + sim_q) / 2;
+ *   T = s_0 + s_1 + ..., accumulated from +0.0 in document order;  out_scores = s_i / T (a true division) if T > 0, else s_i.
+ * sim = dot / (sqrt(|a|^2) * sqrt(|b|^2)); dot, |a|^2, |b|^2 are fp64 sums of the (exact) fp64 products of the fp32 inputs; a quotient that is
+ * NaN or +-Inf (a zero row, a NaN / Inf element) counts as sim = 0.  The order of the additions is fixed by the element index alone (element e
+ * belongs to lane (e >> 2) & 63, a lane adds its elements ascending with fma from +0.0, the lanes are folded by an xor butterfly over 32 .. 1):
+ * a group's outputs have the same bits wherever the group and its rows sit in the call, whether or not the base and stride allow 16-byte loads,
+ * at every width and on any stream.
+ * x [n, stride] fp32, of which columns dim .. stride-1 are never read: a device address with RMU_F_Q_DEVICE, else a host array (uploaded
+ * asynchronously).  groups: ALWAYS a host array, [n_groups, 4] int32 = answer_row, query_row (-1: none), first_doc_row, n_docs.  Rows may be
+ * shared between groups and may coincide with an anchor.  The outputs are packed in group order -- out_scores [sum n_docs] fp64, out_sims
+ * [sum n_docs, 2] fp64 = the unnormalised (sim_a, sim_q; sim_q = 0.0 without a query), or NULL -- device addresses with RMU_F_OUT_DEVICE,
+ * else host arrays.  n_groups == 0 and groups with n_docs == 0 write nothing (no document at all: nothing is launched).
+ * 1 <= dim <= RMU_MAX_DIM_WIDE, stride >= dim, n >= 1, n_groups >= 0; every row in [0, n), n_docs >= 0, first_doc_row + n_docs <= n, the sum
+ * of n_docs fits in an int32; a NULL pointer (out_sims aside), any other flag, any other value: RMU_E_INVALID before any HIP call.
+ * hip_stream: the stream the work is enqueued on (0: the calling thread's own).  The call ALWAYS drains it before it returns: the table
+ * travels through the thread's pinned workspace, so nothing may stay in flight. */
+int rmu_attribution(const float* x, int64_t n, int dim, int64_t stride, const int32_t* groups, int n_groups, unsigned flags,
+                    double* out_scores, double* out_sims, uint64_t hip_stream);
+/* The same behind the encoder forward (the pattern of rmu_bert_search_mmr): HOST token ids of the answers, queries and contexts of one or more
+ * requests in (as rmu_bert_encode_host, with its shape limits; a pooling mode); the group table names rows of that batch (n = batch, dim = 384).
+ * The pooled vectors stay on the device, the kernel is enqueued behind the graph replay on the encoder's stream, one synchronisation.  HOST
+ * outputs as above; out_vecs, if not NULL, receives the pooled vectors [batch, 384] fp32.  The table is checked before anything is enqueued.
+ * Results equal rmu_bert_encode_host followed by rmu_attribution on its output. */
+int rmu_bert_attribute(rmu_bert_t* m, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch, int max_len, int mode,
+                       const int32_t* groups, int n_groups, double* out_scores, double* out_sims, float* out_vecs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,7 +50,7 @@ SYMBOLS = [
     "rmu_bm25_create", "rmu_bm25_free", "rmu_bm25_add_texts", "rmu_bm25_stat", "rmu_bm25_df", "rmu_bm25_set_option", "rmu_bm25_search",
     "rmu_bm25_remove_docs", "rmu_bm25_search_subset", "rmu_bm25_compact", "rmu_bm25_save", "rmu_bm25_load",
     "rmu_rrf_fuse", "rmu_hybrid_create", "rmu_hybrid_free", "rmu_hybrid_set_keys", "rmu_hybrid_search", "rmu_bert_search_hybrid",
-    "rmu_adjacent_cosine",
+    "rmu_adjacent_cosine", "rmu_attribution", "rmu_bert_attribute",
 ]
 
 
@@ -124,6 +124,7 @@ def _declare(lib):
     lib.rmu_hybrid_set_keys.argtypes = [vp, i32, i64, vp, i64]
     lib.rmu_hybrid_search.argtypes = [vp, vp, i64, c.c_char_p, i64, i32, i32, i32, c.c_double, f64p, i32, i32, vp, vp, vp, u64]
     lib.rmu_adjacent_cosine.argtypes = [vp, i64, i32, i64, u32, vp, u64]
+    lib.rmu_attribution.argtypes = [vp, i64, i32, i64, vp, i32, u32, vp, vp, u64]
     if hasattr(lib, "rmu_bert_create"):
         lib.rmu_bert_create.argtypes = [c.POINTER(vp), vp, c.POINTER(vp), i32]
         lib.rmu_bert_free.argtypes = [vp]
@@ -131,6 +132,7 @@ def _declare(lib):
         lib.rmu_bert_encode_host.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i64]
         lib.rmu_bert_search_mmr.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, c.c_double, i64, vp, vp, vp]
         lib.rmu_bert_search_hybrid.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, c.c_char_p, i64, i32, i32, i32, c.c_double, f64p, i32, i32, vp, vp, vp]
+        lib.rmu_bert_attribute.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]
 
 
 def lib():

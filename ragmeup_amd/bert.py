@@ -204,6 +204,24 @@ class BertEncoder:
                                               scores.ctypes.data, vecs.ctypes.data if vecs is not None else None), "rmu_bert_search_mmr")
         return (rows[:B], scores[:B], vecs[:B]) if want_vectors else (rows[:B], scores[:B])
 
+    def attribute_host(self, ids, lens, mode: int, groups, want_vectors: bool = False):
+        """rmu_bert_attribute: the token ids of the answers, queries and contexts of one or more requests in, the similarity provenance of
+        every context out -- forward (graph replay) and the attribution kernel behind it in ONE library call with ONE synchronisation.
+        groups [g, 4] int32 (answer_row, query_row or -1, first_doc_row, n_docs) names rows of `ids`.
+        -> scores [sum n_docs] fp64, sims [sum n_docs, 2] fp64 (, vectors [B, 384] fp32)."""
+        pi, pl, pt, B, bb, lb = self._host_arrays(ids, lens, None, mode)
+        g = np.ascontiguousarray(np.asarray(groups, dtype=np.int32)).reshape(-1, 4)
+        if len(g) and (int(g[:, (0, 2)].max()) >= B or int(g[:, 1].max()) >= B or int((g[:, 2] + np.maximum(g[:, 3], 0)).max()) > B):
+            raise ValueError(f"attribute_host: the group table names rows beyond the {B} sequences of the call")
+        total = int(np.maximum(g[:, 3], 0).sum()) if len(g) else 0
+        scores = np.empty(total, dtype=np.float64)
+        sims = np.empty((total, 2), dtype=np.float64)
+        vecs = np.empty((bb, self.HIDDEN), dtype=np.float32) if want_vectors else None
+        N.check(self._lib.rmu_bert_attribute(self._h, pi.ctypes.data, None, pl.ctypes.data, int(bb), int(lb), int(mode), g.ctypes.data, len(g),
+                                             scores.ctypes.data, sims.ctypes.data, vecs.ctypes.data if vecs is not None else None),
+                "rmu_bert_attribute")
+        return (scores, sims, vecs[:B]) if want_vectors else (scores, sims)
+
     def encode_ids(self, ids, lens, type_ids=None, mode: int = 0, out=None, stream=None):
         """ids [B, L] int (numpy or torch, padded), lens [B].  mode = MODE_MEAN / MODE_CLS (| NO_NORMALIZE) -> [B, 384] fp32
         (torch CUDA); MODE_CE -> [B] fp32 logits; MODE_TOKENS -> [sum(min(lens, L)), 384] fp32, sequences packed in batch order.

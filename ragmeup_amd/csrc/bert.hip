@@ -3728,6 +3728,41 @@ extern "C" int rmu_bert_search_mmr(rmu_bert_t* m, rmu_index_t* idx, const int32_
     return RMU_OK;
 }
 
+// Similarity provenance in ONE call with ONE synchronisation (DocumentSimilarityAttribution.compute_similarity, server/provenance.py:164-202: three
+// encode calls, 2 n cosines on the host): the token ids of the answers, queries and contexts of one or more requests in, n scores out.  The forward
+// is the graph replay above; its pooled vectors stay on the device and feed the attribution kernel (provenance.hip) enqueued BEHIND the replay on
+// the same stream -- not inside the capture: the captured graph keeps its single chain.
+extern "C" int rmu_attribution_check_(const char* who, int64_t n, int dim, const int32_t* groups, int n_groups, const double* out_scores, int64_t* total);
+extern "C" int rmu_attribution_dev_(const char* who, const float* x_dev, int64_t n, int dim, int64_t stride, const int32_t* groups, int n_groups,
+                                    int64_t total, double* out_scores, double* out_sims, void* hip_stream);
+extern "C" int rmu_bert_attribute(rmu_bert_t* m, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch, int max_len, int mode,
+                                  const int32_t* groups, int n_groups, double* out_scores, double* out_sims, float* out_vecs) {
+    RMU_ENTRY();
+    if (!ids || !lens || !groups || !out_scores) return bfail(RMU_E_INVALID, "rmu_bert_attribute: null argument");
+    if (batch < 1 || batch > 65535) return bfail(RMU_E_INVALID, "rmu_bert_attribute: 1 <= batch <= 65535");
+    const int kind = mode & 0xff;
+    if (kind != RMU_BERT_POOL_MEAN && kind != RMU_BERT_POOL_CLS) return bfail(RMU_E_INVALID, "rmu_bert_attribute: mode must be a pooling mode");
+    int64_t total = 0;
+    int rc = rmu_attribution_check_("rmu_bert_attribute", batch, H, groups, n_groups, out_scores, &total);
+    if (rc) return rc;
+    if (!m) return bfail(RMU_E_INVALID, "rmu_bert_attribute: null argument");
+    rc = check_encode_args(m, ids, lens, out_scores, batch, max_len, mode, H);
+    if (rc) return rc;
+    std::unique_lock<std::mutex> lk;
+    m = acquire_ctx(m, lk);
+    rc = host_forward_locked(m, ids, type_ids, lens, batch, max_len, mode, "rmu_bert_attribute");
+    if (rc) return rc;
+    // drains m->stream: forward, attribution and the copy of the results
+    if (total > 0) {
+        rc = rmu_attribution_dev_("rmu_bert_attribute", m->d_out, batch, H, H, groups, n_groups, total, out_scores, out_sims, (void*)m->stream);
+        if (rc) { (void)hipStreamSynchronize(m->stream); return rc; }
+    } else {
+        B_TRY(hipStreamSynchronize(m->stream));
+    }
+    if (out_vecs) memcpy(out_vecs, m->h_out, (size_t)batch * H * sizeof(float));
+    return RMU_OK;
+}
+
 // The reference's whole retrieval step behind the forward (EnsembleRetriever([bm25, dense_mmr]).invoke, server/RAGHelper.py:497-503): token ids and
 // the query texts in, fused hits out.  The pooled vectors stay on the device and feed rmu_hybrid_search's work (rrf_fuse.hip: BM25 search, dense
 // search + selection, fusion) enqueued behind the forward on the encoder's stream; one synchronisation.

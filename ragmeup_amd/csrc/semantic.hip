@@ -21,64 +21,14 @@
 // group of four that lies inside the row; the last, partial group and the whole row otherwise take 4-byte loads.  Columns dim .. stride - 1
 // are never read.  No LDS, no atomics, no scratch.
 #include <cmath>
-#include <cstring>
-#include <string>
 
-#include "../../include/rmu.h"
-#include "rmu_common.h"
-
-extern "C" void rmu_set_error_(const char* msg);
-static int sfail(int code, const std::string& m) { rmu_set_error_(m.c_str()); return code; }
-#define SEM_TRY(expr)                                                                                               \
-    do {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                     \
-        if (e_ != hipSuccess)                                                                                       \
-            return sfail(e_ == hipErrorOutOfMemory ? RMU_E_OOM : RMU_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+#include "cosine_common.h"      // load_row, wave_sum, lane_norm2, the thread's workspace (CosCtx), COS_TRY / cos_fail
 
 namespace {
 
 constexpr int kBlock = 256;                                  // 4 waves
 constexpr int kWavePairs = 16;                               // pairs one wave owns (ragmeup_amd/_native.py: ADJ_COS_WAVE_PAIRS)
 constexpr int kBlockPairs = kWavePairs * (kBlock / 64);      // pairs one workgroup owns (ADJ_COS_WG_PAIRS)
-
-// the lane's NJ groups of four elements of one row; elements at or past dim are +0.0
-template <int NJ, bool VEC>
-__device__ __forceinline__ void load_row(const float* __restrict__ row, int dim, int lane, f32x4 (&f)[NJ]) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int e = 4 * (lane + 64 * j);
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (VEC && e + 4 <= dim) {
-            v = *reinterpret_cast<const f32x4*>(row + e);
-        } else {
-            if (e < dim) v.x = row[e];
-            if (e + 1 < dim) v.y = row[e + 1];
-            if (e + 2 < dim) v.z = row[e + 2];
-            if (e + 3 < dim) v.w = row[e + 3];
-        }
-        f[j] = v;
-    }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-template <int NJ>
-__device__ __forceinline__ double lane_norm2(const f32x4 (&f)[NJ]) {
-    double acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const double v = (double)f[j][c];
-            acc = __builtin_fma(v, v, acc);
-        }
-    return acc;
-}
 
 template <int NJ, bool VEC>
 __global__ __launch_bounds__(kBlock) void adjacent_cosine_kernel(const float* __restrict__ x, int64_t n_pairs, int dim, int64_t stride,
@@ -143,74 +93,37 @@ void launch(const float* x, int64_t n_pairs, int dim, int64_t stride, double* ou
     else launch_nj<12>(vec, grid, s, x, n_pairs, dim, stride, out);
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)rmu_free(p);
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return e; }
-        cap = want;
-        return hipSuccess;
-    }
-};
-bool g_sem_down = false;       // static destructors have begun: thread-local destructors must leave HIP alone
-struct DownGuard { ~DownGuard() { g_sem_down = true; } } g_down_guard;
 // the calling thread's workspace: the uploaded rows, the distances and their pinned landing place.  Only a call that drains its stream uses it
 // (a call with a caller stream and device buffers on both sides touches none of it), so nothing of it is ever in flight between two calls
-struct Ctx {
-    DevBuf in, out;
-    char* pin = nullptr;
-    size_t pin_cap = 0;
-    int ensure_pin(size_t bytes) {
-        if (bytes <= pin_cap) return RMU_OK;
-        if (pin) (void)hipHostFree(pin);
-        pin = nullptr; pin_cap = 0;
-        const size_t cap = bytes < 8192 ? 8192 : bytes * 2;
-        if (hipHostMalloc((void**)&pin, cap) != hipSuccess) { pin = nullptr; (void)hipGetLastError(); return RMU_E_OOM; }
-        pin_cap = cap;
-        return RMU_OK;
-    }
-    ~Ctx() {
-        if (g_sem_down) return;
-        RMU_ENTRY();
-        for (DevBuf* b : {&in, &out})
-            if (b->p) (void)rmu_free(b->p);
-        if (pin) (void)hipHostFree(pin);
-    }
-};
-thread_local Ctx g_ctx;
+thread_local CosCtx g_ctx;
 
 }  // namespace
 
 extern "C" int rmu_adjacent_cosine(const float* x, int64_t n, int dim, int64_t stride, unsigned flags, double* out, uint64_t hip_stream) {
     RMU_ENTRY();
-    if (!x || !out) return sfail(RMU_E_INVALID, "rmu_adjacent_cosine: null pointer");
+    if (!x || !out) return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: null pointer");
     if (flags & ~(RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE))
-        return sfail(RMU_E_INVALID, "rmu_adjacent_cosine: flags other than RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE");
-    if (dim < 1 || dim > RMU_MAX_DIM_WIDE) return sfail(RMU_E_INVALID, "rmu_adjacent_cosine: 1 <= dim <= RMU_MAX_DIM_WIDE (3072)");
-    if (stride < dim) return sfail(RMU_E_INVALID, "rmu_adjacent_cosine: stride must be >= dim");
-    if (n < 1) return sfail(RMU_E_INVALID, "rmu_adjacent_cosine: n must be >= 1");
+        return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: flags other than RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE");
+    if (dim < 1 || dim > RMU_MAX_DIM_WIDE) return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: 1 <= dim <= RMU_MAX_DIM_WIDE (3072)");
+    if (stride < dim) return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: stride must be >= dim");
+    if (n < 1) return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: n must be >= 1");
     // the matrix in bytes and the grid (one workgroup per kBlockPairs pairs) must stay representable
     if (n > (int64_t)0x7FFFFFFFll * kBlockPairs || stride > INT64_MAX / 4 / n)
-        return sfail(RMU_E_INVALID, "rmu_adjacent_cosine: n * stride is too large");
+        return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: n * stride is too large");
     if (n == 1) return RMU_OK;                                  // no pair: nothing is written, nothing is launched
     const bool in_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE;
     const int64_t n_pairs = n - 1;
 
-    Ctx& c = g_ctx;
+    CosCtx& c = g_ctx;
     hipStream_t s = nullptr;
     int rc = rmu_thread_stream_((hipStream_t)hip_stream, &s);
     if (rc) return rc;
     const size_t in_bytes = ((size_t)n_pairs * (size_t)stride + (size_t)dim) * sizeof(float);      // (the last row's pad columns are not touched)
     const size_t out_bytes = (size_t)n_pairs * sizeof(double);
-    if (!in_dev) SEM_TRY(c.in.ensure(in_bytes));
+    if (!in_dev) COS_TRY(c.in.ensure(in_bytes));
     if (!out_dev) {
-        SEM_TRY(c.out.ensure(out_bytes));
-        if (c.ensure_pin(out_bytes) != RMU_OK) return sfail(RMU_E_OOM, "rmu_adjacent_cosine: pinned result buffer");
+        COS_TRY(c.out.ensure(out_bytes));
+        if (c.ensure_pin(out_bytes) != RMU_OK) return cos_fail(RMU_E_OOM, "rmu_adjacent_cosine: pinned result buffer");
     }
     const bool drained = !hip_stream || !out_dev || !in_dev;
     const float* dx = x;
@@ -229,12 +142,12 @@ extern "C" int rmu_adjacent_cosine(const float* x, int64_t n, int dim, int64_t s
     if (e != hipSuccess) {                                      // nothing of a failed call stays in flight on the thread's workspace
         (void)hipStreamSynchronize(s);
         rmu_thread_finished_(s, true);
-        return sfail(RMU_E_HIP, std::string("rmu_adjacent_cosine: ") + hipGetErrorString(e));
+        return cos_fail(RMU_E_HIP, std::string("rmu_adjacent_cosine: ") + hipGetErrorString(e));
     }
     if (drained) {
         e = hipStreamSynchronize(s);
         rmu_thread_finished_(s, true);
-        if (e != hipSuccess) return sfail(RMU_E_HIP, std::string("rmu_adjacent_cosine: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return cos_fail(RMU_E_HIP, std::string("rmu_adjacent_cosine: ") + hipGetErrorString(e));
         if (!out_dev) memcpy(out, c.pin, out_bytes);
         return RMU_OK;
     }

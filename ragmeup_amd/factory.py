@@ -9,6 +9,7 @@ The reference builds its plug-ins from environment variables (loaded from `.env`
   retriever    server/RAGHelper.py:497-499   (`vector_store_k`)
   splitter     server/RAGHelper.py:329-349   (`splitter`, `breakpoint_threshold_type`, `breakpoint_threshold_amount`,
                                               `number_of_chunks`; parsed at :62, :73-76)
+  provenance   server/RAGHelper_local.py:40, server/provenance.py:164-169   (`provenance_method`, `provenance_similarity_llm`)
 `from_env()` reads the same variables with the same meaning and returns our implementations; the reference-side
 binding is one call to it from the `vector_store == "mi355x"` branches.
 
@@ -98,6 +99,34 @@ def text_splitter_from_env(embeddings: Any, env: Optional[Mapping[str, str]] = N
     from .chunker import MI355XSemanticChunker
     return MI355XSemanticChunker(embeddings, breakpoint_threshold_type=env.get("breakpoint_threshold_type"),
                                  breakpoint_threshold_amount=amount, number_of_chunks=chunks)
+
+
+def provenance_from_env(env: Optional[Mapping[str, str]] = None, embeddings: Any = None, device: int = 0):
+    """`self.attributor` (RAGHelper_local.py:40): for `provenance_method == "similarity"` the attribution object over the local checkpoint
+    directory `provenance_similarity_llm` -- over `embeddings` itself when that object serves the same directory (one encoder on the device
+    instead of two).  `rerank` is served by the compressor (`provenance.compute_rerank_provenance`) and needs no object: None.  `attention`
+    and `llm` need the LLM, which is out of scope: ValueError.  Unset or anything else: None, as in the reference."""
+    env = os.environ if env is None else env
+    method = env.get("provenance_method")
+    if method in ("attention", "llm"):
+        raise ValueError(f"provenance_method={method!r} needs the LLM, which is out of scope here: "
+                         "'similarity' and 'rerank' are served")
+    if method != "similarity":
+        return None
+    if _flag(env, "force_cpu"):
+        raise RuntimeError("force_cpu=True: the MI355X retrieval path has no CPU fallback")
+    model = env.get("provenance_similarity_llm")
+    if not model:
+        raise KeyError("provenance_similarity_llm is not set")
+    if not os.path.isdir(model):
+        raise FileNotFoundError(f"provenance_similarity_llm={model!r}: a local checkpoint directory is required "
+                                "(the hub id of the reference's SentenceTransformer cannot be downloaded here)")
+    from .provenance import DocumentSimilarityAttribution
+    spec = getattr(embeddings, "spec", None)
+    if spec is not None and os.path.realpath(spec.path) == os.path.realpath(model):
+        return DocumentSimilarityAttribution(embeddings)
+    from .embeddings import MI355XEmbeddings
+    return DocumentSimilarityAttribution(MI355XEmbeddings(model_dir=model, device=device))
 
 
 @dataclass
