@@ -68,10 +68,10 @@ namespace { struct RuntimeGuard { ~RuntimeGuard() { g_runtime_down = true; } } g
 struct Buf {
     void* p = nullptr;
     size_t cap = 0;
-    void release() {
-        if (p && !g_runtime_down) (void)rmu_free(p);
-        p = nullptr; cap = 0;
-    }
+    Buf() = default;
+    Buf(const Buf&) = delete;              // (one owner: the destructor frees)
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { if (p && !g_runtime_down) (void)rmu_free(p); }     // (a thread-local destructor may run while the runtime winds down)
     int ensure(size_t bytes) {
         if (bytes <= cap) return RMU_OK;
         if (p) (void)rmu_free(p);
@@ -85,7 +85,7 @@ struct Buf {
 struct Tls {
     hipStream_t stream = nullptr;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    Buf q, partial, out_s, out_r, in_s, in_r, qn, gthr, mscratch, qsplit, ckeys, flag, nrm, fbq, fb_s, fb_r, fb_i, mm_q, mm_s, mm_r, mm_p, gcand, sub_ids, sub_rows, eps, spill, spill_cnt;
+    Buf q, partial, out_s, out_r, in_s, in_r, qn, gthr, qsplit, ckeys, flag, nrm, fbq, fb_i, mm_q, mm_s, mm_r, mm_p, gcand, sub_ids, sub_rows, eps, spill, spill_cnt;
     std::vector<hipEvent_t> lev;   // per-launch events of the screening ladder
     int ensure_events(int n) {
         while ((int)lev.size() < n) {
@@ -108,12 +108,22 @@ struct Tls {
         hpin_cap = cap;
         return RMU_OK;
     }
+    int ensure_hflag() {
+        if (hflag) return RMU_OK;
+        if (hipHostMalloc((void**)&hflag, sizeof(int)) != hipSuccess) { hflag = nullptr; (void)hipGetLastError(); return RMU_E_OOM; }
+        *hflag = 0;
+        if (hipHostGetDevicePointer((void**)&hflag_dev, hflag, 0) != hipSuccess) { (void)hipGetLastError(); hflag_dev = hflag; }   // (unified addressing: the same pointer)
+        return RMU_OK;
+    }
     bool timing = false;
     float scan_ms = -1.f, search_ms = -1.f;
     int grid = 0, block = 0, lds = 0, passes = 0, screened = 0;
+    // what rmu_last_scan_geometry reports: the geometry of the last scan enqueued, the launches of the whole call
+    template <class Launch>          // (ScanLaunch, SubsetLaunch)
+    void note_geometry(const Launch& L, int launches) { grid = L.grid; block = 256; lds = L.lds_bytes; passes += launches; }
     int device = -1;
     // A search / merge given a caller stream and device buffers returns with its kernels still in flight -- on workspaces
-    // (q, qsplit, partial, gthr, ckeys, flag, fb_*) that belong to this thread, not to that stream.  `pend_ev` marks the end
+    // (q, qsplit, partial, gthr, ckeys, flag, fbq, fb_i) that belong to this thread, not to that stream.  `pend_ev` marks the end
     // of the last such call: the next user of the workspaces on ANY OTHER stream is ordered behind it (same stream: stream
     // order already does that), so a second call can neither memset thresholds nor overwrite partials under running kernels.
     hipEvent_t pend_ev = nullptr;
@@ -140,24 +150,20 @@ struct Tls {
         else { (void)hipStreamSynchronize(s); pending = false; }
     }
     // A server that spawns a thread per request (Flask's threaded dev server, server/server.py:394) creates one of
-    // these per request: everything it owns goes back when the thread exits.
+    // these per request: everything it owns goes back when the thread exits.  Only what has an order is done here -- the work in flight
+    // ends first; the workspaces free themselves (~Buf) once this body has run, i.e. behind the drained stream.
     ~Tls() {
         if (g_runtime_down) return;
         RMU_ENTRY();
         if (pending) (void)hipEventSynchronize(pend_ev);
         if (pend_ev) (void)hipEventDestroy(pend_ev);
         if (stream) (void)hipStreamSynchronize(stream);
-        for (Buf* b : {&q, &partial, &out_s, &out_r, &in_s, &in_r, &qn, &gthr, &mscratch, &qsplit, &ckeys, &flag, &nrm, &fbq, &fb_s,
-                       &fb_r, &fb_i, &mm_q, &mm_s, &mm_r, &mm_p, &gcand, &sub_ids, &sub_rows, &spill, &spill_cnt})
-            b->release();
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
         for (auto& e : lev) (void)hipEventDestroy(e);
         if (hflag) (void)hipHostFree(hflag);
         if (hpin) (void)hipHostFree(hpin);
-        hflag = nullptr; hflag_dev = nullptr; hpin = nullptr; hpin_cap = 0;
         if (stream) (void)hipStreamDestroy(stream);
-        stream = nullptr;
     }
 };
 static thread_local Tls g_tls;
@@ -1193,11 +1199,8 @@ static void dbg_dump(const char* what, int64_t rows, hipStream_t s) {
 // a colder start does not.  Full batches keep 256 (1.25M rows x 1024: 1.245 ms at 256, 1.372 at 2048, 1.794 at 16384).
 static constexpr int LADDER_FIRST_SMALL = 2048;
 static std::vector<int64_t> ladder_bounds(int64_t n, int64_t nb, int opt_ratio = 0, int opt_first = 0) {
-    static const int lvl_min_env = rmu_env("RMU_SCREEN_MINLVL") ? atoi(rmu_env("RMU_SCREEN_MINLVL")) : 0;
-    static const int lvl_ratio_env0 = rmu_env("RMU_SCREEN_RATIO") ? atoi(rmu_env("RMU_SCREEN_RATIO")) : 0;   // <= 1: single launch
-    // (per-index options RMU_OPT_LADDER_RATIO / _FIRST first, then the environment, then the defaults)
-    const int lvl_ratio_env = opt_ratio ? opt_ratio : lvl_ratio_env0;
-    const int lvl_min = opt_first ? opt_first : lvl_min_env ? lvl_min_env : (nb <= 128 ? LADDER_FIRST_SMALL : 256);
+    // (per-index options RMU_OPT_LADDER_RATIO / _FIRST, then the defaults; a ratio of 1: a single cold launch)
+    const int lvl_min = opt_first ? opt_first : (nb <= 128 ? LADDER_FIRST_SMALL : 256);
     // ratio 3 for full batches; small batches (one query tile, HBM-bound: 7.68 GB image per batch) have few appends to
     // save and pay for every launch gap and merge, so they climb faster
     // (round 4: from 4 096 rows up -- was 262 144.  A single COLD launch over 200k rows x 1024 queries takes 1.74 ms, twice what the ladder
@@ -1214,7 +1217,7 @@ static std::vector<int64_t> ladder_bounds(int64_t n, int64_t nb, int opt_ratio =
         }
         return b;
     };
-    if (lvl_ratio_env) return build(lvl_ratio_env);
+    if (opt_ratio) return build(opt_ratio);
     if (nb <= 128) return build(8);
     // (round 6, second session) Full batches over a corpus below ~6M rows: a ladder level costs 40-60 us whatever its range (launch, query
     // fragments, emit, merge) while a seeded level's appends are cheap -- the ratio with the FEWEST levels wins there (ties: the smaller ratio).
@@ -1233,9 +1236,28 @@ static std::vector<int64_t> ladder_bounds(int64_t n, int64_t nb, int opt_ratio =
     return best;
 }
 
-static int nofilter_env() {        // RMU_SCREEN_NOFILTER: ScanLaunch::share_thr bit 1 (timing ablation)
-    static const int nofilter = rmu_env("RMU_SCREEN_NOFILTER") != nullptr ? 2 : 0;
-    return nofilter;
+// RMU_SCREEN_NOFILTER: ScanLaunch::share_thr bit 1 (timing ablation); RMU_NO_SHARED_THR: bit 0 off -- launches publish their thresholds, none
+// reads them (debugging aid).  Each is read here and nowhere else.
+static int nofilter_env() { static const int nofilter = rmu_env("RMU_SCREEN_NOFILTER") != nullptr ? 2 : 0; return nofilter; }
+static int share_env() { static const int share = rmu_env("RMU_NO_SHARED_THR") ? 0 : 1; return share; }
+
+// ---- the slot walk both threshold ladders share (screen_enqueue, search_block_deep).  One partial buffer holds, in slots of `part_keys`
+// keys: [range 0's parts][merged 0 .. 0][range 1's parts][merged 0 .. 1][range 2's parts] ... -- a level's merge reads ONE contiguous run, the
+// running top (absent at level 0) and behind it the level's own parts, and writes the slot behind that run, which heads the next level's.
+static int ladder_slots(const std::vector<ScanLaunch>& lv) {
+    int slots = (int)lv.size() - 1;
+    for (const ScanLaunch& S : lv) slots += S.parts;
+    return slots;
+}
+// A level's launch writes its part lists at `parts`; its merge reads `n_lists` lists from `merge_in` on and writes `merged`: the next
+// level's running top, or `final_keys` behind the last level.
+struct LadderLevel { u64* parts; const u64* merge_in; int n_lists; u64* merged; };
+// level l of nl, whose launch writes `parts` lists; *slot (0 before level 0) walks the buffer `base`: call once per level, in order
+static LadderLevel ladder_level(u64* base, size_t part_keys, int* slot, int l, int nl, int parts, u64* final_keys) {
+    u64* const in = base + (size_t)*slot * part_keys;     // the running top (l > 0), else this range's first part
+    const int n_lists = parts + (l > 0 ? 1 : 0);
+    *slot += n_lists;                                     // -> the slot behind the run
+    return {in + (size_t)(n_lists - parts) * part_keys, in, n_lists, l + 1 < nl ? in + (size_t)n_lists * part_keys : final_keys};
 }
 
 // Enqueue the screening ladder for `nb` device queries (fp32, [nb, 384]): on return (stream order) t.ckeys holds the best
@@ -1248,12 +1270,12 @@ static int nofilter_env() {        // RMU_SCREEN_NOFILTER: ScanLaunch::share_thr
 // the sufficiency band (see `band` below), about a third of those appends.
 static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb, hipStream_t s, bool timed, int* n_launches,
                           ScanLaunch* last_geom, int k, int kp = kScreenKp, u32* zero_word = nullptr /* one more word the query conversion zeroes (the re-run count) */) {
-    const int dpad = idx->dpad;
-    static const int share = rmu_env("RMU_NO_SHARED_THR") ? 0 : 1;
+    const int share = share_env();
     const std::vector<int64_t> bounds = ladder_bounds(idx->n, nb, idx->ladder_ratio, idx->ladder_first);
     const int nl = (int)bounds.size();
     std::vector<ScanLaunch> lv((size_t)nl);
-    int slots = nl - 1;
+    size_t pwords = 0;                                   // sibling-pacing progress words: [s_chunks][4] per paced launch
+    size_t gcand_bytes = 0;                              // global candidate slots (reused by every launch of the ladder)
     for (int l = 0; l < nl; ++l) {
         ScanLaunch& S = lv[(size_t)l];
         S = ScanLaunch{};
@@ -1261,17 +1283,12 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
         S.dpad = 384; S.nq = (int)nb; S.k = kp;       // (the image's geometry; an L2 index keeps its fp32 rows 768 floats apart)
         S.nrm = idx->nrm;
         if (rmu_screen_plan(&S) != RMU_OK) return fail(RMU_E_INVALID, "rmu_index_search: screening geometry");
-        slots += S.parts;
+        if (S.pace) pwords += (size_t)S.s_chunks * 4;
+        gcand_bytes = std::max(gcand_bytes, (size_t)S.parts * (size_t)nb * (kp > RMU_KS_CAP - 8 ? RMU_KS_CAP_DEEP : RMU_KS_CAP) * sizeof(u64));
     }
     const size_t part_keys = (size_t)nb * kp;
     const size_t gwords = (size_t)((nb + 255) / 256 * 256 + 64);
-    size_t pwords = 0;                                   // sibling-pacing progress words: [s_chunks][4] per paced launch
-    for (int l = 0; l < nl; ++l)
-        if (lv[(size_t)l].pace) pwords += (size_t)lv[(size_t)l].s_chunks * 4;
     const size_t gbytes = (gwords + pwords) * sizeof(u32);    // one memset zeroes thresholds and progress words
-    size_t gcand_bytes = 0;                              // global candidate slots (reused by every launch of the ladder)
-    for (int l = 0; l < nl; ++l)
-        gcand_bytes = std::max(gcand_bytes, (size_t)lv[(size_t)l].parts * (size_t)nb * (kp > RMU_KS_CAP - 8 ? RMU_KS_CAP_DEEP : RMU_KS_CAP) * sizeof(u64));
     if (gcand_bytes && t.gcand.ensure(gcand_bytes)) return fail(RMU_E_OOM, "rmu_index_search: screening candidate slots");
     // Spill path (RMU_OPT_SCREEN_SPILL, scan_screen.hip "Spill path"): the SEEDED launches of the 8-wave kernels leave the accumulators of
     // passing lanes in per-wave lists and rmu_sift_launch takes the place of their merge.  The cold first launch, the 4-wave kernels and the
@@ -1289,11 +1306,10 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
             if (lv[(size_t)l].wq == 8) spill_lists = std::max(spill_lists, (size_t)lv[(size_t)l].s_chunks * (size_t)lv[(size_t)l].nqt * 8);
     if (spill_lists && (t.spill.ensure(spill_lists * (size_t)spill_cap * RMU_SPILL_REC) || t.spill_cnt.ensure(spill_lists * sizeof(u32))))
         return fail(RMU_E_OOM, "rmu_index_search: screening spill lists");
-    if (t.partial.ensure((size_t)slots * part_keys * sizeof(u64)) || t.qsplit.ensure((size_t)nb * RMU_IMG_ROW_BYTES) ||
+    if (t.partial.ensure((size_t)ladder_slots(lv) * part_keys * sizeof(u64)) || t.qsplit.ensure((size_t)nb * RMU_IMG_ROW_BYTES) ||
         t.gthr.ensure(gbytes) || t.ckeys.ensure(part_keys * sizeof(u64)) || t.eps.ensure((size_t)nb * sizeof(float)) || t.ensure_events(2 * nl))
         return fail(RMU_E_OOM, "rmu_index_search: screening workspace");
-    const int nofilter = nofilter_env();
-    const int sflags = share | nofilter;
+    const int sflags = share | nofilter_env();
     // (an L2 index holds its queries as (2q, 1): the image is fp16(64 q) all the same)
     // (round 6) the conversion's first workgroup also zeroes the ladder's thresholds + pacing words and the caller's word: was two memsets
     // Band seeding (scan_screen.hip header): a seeded launch needs only the rows that can reach the caller's top-k or decide its sufficiency
@@ -1302,20 +1318,19 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
     // k = K' (rmu_index_screen_candidates) or RMU_OPT_SCREEN_BAND = 0: the K'-th key alone, as before.
     const bool band = idx->screen_band && k < kp && nl > 1;
     const bool l2q = idx->metric == RMU_METRIC_L2SQ;
-    int rc = rmu_split_launch(qdev, t.qsplit.p, nb, s, dpad, l2q ? 32.0f : 64.0f, (u32*)t.gthr.p,
+    int rc = rmu_split_launch(qdev, t.qsplit.p, nb, s, idx->dpad, l2q ? 32.0f : 64.0f, (u32*)t.gthr.p,
                               (int)(gbytes / sizeof(u32)), zero_word, zero_word ? 1 : 0, band ? (float*)t.eps.p : nullptr, idx->xnorm_max, idx->dx_max,
                               l2q ? 1 : 0);
     if (rc) return fail(rc, "rmu_index_search: query conversion");
-    u64* base = (u64*)t.partial.p;
-    int cursor = 0;     // slot index: [merged keys of the ranges so far][this range's parts] ...
+    int slot = 0;
     u32* prog_next = (u32*)t.gthr.p + gwords;
     for (int l = 0; l < nl; ++l) {
         ScanLaunch& S = lv[(size_t)l];
-        const int first = cursor;               // slot of the running top-K' (l > 0), else of this range's first part
-        if (l > 0) cursor += 1;
+        const LadderLevel lvl = ladder_level((u64*)t.partial.p, part_keys, &slot, l, nl, S.parts, (u64*)t.ckeys.p);
+        u32* const seed = l + 1 < nl ? (u32*)t.gthr.p : nullptr;       // merge + seed the next launch's thresholds in one launch
         S.prog = nullptr;
         if (S.pace) { S.prog = prog_next; prog_next += (size_t)S.s_chunks * 4; }
-        S.partial = base + (size_t)cursor * part_keys;
+        S.partial = lvl.parts;
         // (round 6) the FIRST launch is cold -- one tile per chunk, every row a candidate -- and its slots leave unsorted (share_thr bit 2; its merge
         // below is told): sorting 32 keys for each of a workgroup's 256 queries was ~25 us of a launch that scans 2 000 rows.  RMU_EMIT_RAW=0: never.
         static const int emit_raw = (rmu_env("RMU_EMIT_RAW") && atoi(rmu_env("RMU_EMIT_RAW")) == 0) ? 0 : 4;
@@ -1328,16 +1343,12 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
         rc = rmu_screen_launch(&S, s);
         if (rc) return fail(rc, "rmu_index_search: screening launch");
         if (timed) HIP_TRY(hipEventRecord(t.lev[(size_t)(2 * l + 1)], s));
-        cursor += S.parts;
         if (g_dbg) dbg_dump("screen range", S.n_rows, s);
-        u64* merged = l + 1 < nl ? base + (size_t)cursor * part_keys : (u64*)t.ckeys.p;
-        if (spill)       // the running top-K' (slot `first`) + this launch's spill lists (+ the part lists of waves that fell back)
-            rc = rmu_sift_launch(&S, base + (size_t)first * part_keys, nb, kp, merged, l + 1 < nl ? (u32*)t.gthr.p : nullptr, s, k,
-                                 band ? (const float*)t.eps.p : nullptr);
+        if (spill)       // the running top-K' (the head of the merge's run) + this launch's spill lists (+ the part lists of waves that fell back)
+            rc = rmu_sift_launch(&S, lvl.merge_in, nb, kp, lvl.merged, seed, s, k, band ? (const float*)t.eps.p : nullptr);
         else
-        rc = rmu_merge_to_keys_band_launch(base + (size_t)first * part_keys, cursor - first, nb, kp, merged,
-                                           l + 1 < nl ? (u32*)t.gthr.p : nullptr /* merge + seed in one launch */, s, raw ? 1 : 0, k,
-                                           band ? (const float*)t.eps.p : nullptr);
+            rc = rmu_merge_to_keys_band_launch(lvl.merge_in, lvl.n_lists, nb, kp, lvl.merged, seed, s, raw ? 1 : 0, k,
+                                               band ? (const float*)t.eps.p : nullptr);
         if (rc) return fail(rc, "rmu_index_search: screening merge / threshold seeding");
     }
     *n_launches = nl;
@@ -1425,6 +1436,22 @@ static int copy_outputs(float* out_scores, int64_t* out_rows, int64_t q0, int64_
     return RMU_OK;
 }
 
+static float elapsed_ms(hipEvent_t a, hipEvent_t b) { float ms = 0.f; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f; }
+
+// ---- one block of at most kMaxQueriesPerLaunch queries, as the path that answers it sees it (rmu_index_search fills it in) ----------
+struct SearchBlock {
+    rmu_index* idx; Tls& t; hipStream_t s;
+    const float* qdev; int64_t nb; int k; int64_t row_base;    // the prepared queries (prepare_queries)
+    float* d_s; int64_t* d_r;                                   // where the block's results go on the device (stage_outputs)
+    bool timed, l2;
+    // ... and what the path hands back
+    float scan_ms = 0.f;        // scan time it has measured itself (the screening ladder's per-launch events)
+    bool exact_timed = false;   // t.ev[2] .. t.ev[3] bracket its scans: read by rmu_index_search behind the block's drain
+};
+
+// the three paths that answer a block (defined behind rmu_index_search, which chooses among them)
+static int search_block_screened(SearchBlock& b), search_block_deep(SearchBlock& b), search_block_exact(SearchBlock& b);
+
 extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, int k, unsigned flags, int64_t row_base,
                                 float* out_scores, int64_t* out_rows, uint64_t hip_stream) {
     RMU_ENTRY();
@@ -1440,172 +1467,27 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
     (void)dbg_buffer();
 
     std::shared_lock<std::shared_mutex> lk(idx->mu);
-    const int dpad = idx->dpad, dim = idx->dim;
     const bool l2 = idx->metric == RMU_METRIC_L2SQ;     // dpad > dim by construction: queries are always copied and augmented
     t.scan_ms = -1.f; t.search_ms = -1.f; t.passes = 0; t.screened = 0;
     float scan_total = 0.f;
     bool any_screened = false;
     int rerun_total = 0;
     if (timed) HIP_TRY(hipEventRecord(t.ev[0], s));
-    if (!t.hflag) {
-        if (hipHostMalloc((void**)&t.hflag, sizeof(int)) != hipSuccess) { t.hflag = nullptr; return fail(RMU_E_OOM, "rmu_index_search: pinned flag"); }
-        *t.hflag = 0;
-        if (hipHostGetDevicePointer((void**)&t.hflag_dev, t.hflag, 0) != hipSuccess) { (void)hipGetLastError(); t.hflag_dev = t.hflag; }   // (unified addressing: the same pointer)
-    }
+    if (t.ensure_hflag()) return fail(RMU_E_OOM, "rmu_index_search: pinned flag");
 
     for (int64_t q0 = 0; q0 < nq; q0 += kMaxQueriesPerLaunch) {
         const int64_t nb = (nq - q0) < kMaxQueriesPerLaunch ? (nq - q0) : kMaxQueriesPerLaunch;
         const float* qdev;
-        if ((rc = prepare_queries(idx, t, q + q0 * dim, nb, q_dev, s, &qdev, "rmu_index_search"))) return rc;
+        if ((rc = prepare_queries(idx, t, q + q0 * idx->dim, nb, q_dev, s, &qdev, "rmu_index_search"))) return rc;
         float* d_s = out_scores + q0 * k; int64_t* d_r = out_rows + q0 * k;
         if ((rc = stage_outputs(t, nb, k, out_dev, &d_s, &d_r, "rmu_index_search"))) return rc;
-        static const int share = rmu_env("RMU_NO_SHARED_THR") ? 0 : 1;
-        bool exact_timed = false;
-        // ---- the exact fp32 fused scan + merge of `nqq` device queries.  plan first (all workspace is sized before anything
-        // is enqueued: a grow-only buffer must not be re-allocated under work already in flight), then run.  `cond`
-        // (optional) makes both launches conditional on the device-side count of flagged queries; `scatter` redirects
-        // result row i to batch row scatter[i]. ------------------------------------------------------------------------
-        size_t need_partial = 0, need_gthr = 0;
-        auto plan_exact = [&](const float* qd, int64_t nqq, const RmuCond* cond, ScanLaunch* L, int kk = 0) -> int {
-            *L = ScanLaunch{};
-            if (kk <= 0) kk = k;
-            L->x = idx->x; L->n_rows = idx->n; L->dpad = dpad; L->q = qd; L->nq = (int)nqq; L->k = kk; L->dbg = g_dbg;
-            L->wide = idx->wide_scan ? 1 : 0;       // (a dpad above 768 is routed to the wide kernel by the planner itself)
-            if (cond) L->cond = *cond;
-            const int rc2 = rmu_scan_plan(L);
-            if (rc2) return fail(rc2, "rmu_index_search: no scan geometry for this (dim, k)");
-            need_partial = std::max(need_partial, (size_t)L->parts * nqq * kk * sizeof(u64));
-            need_gthr = std::max(need_gthr, gthr_bytes(nqq));
-            return RMU_OK;
-        };
-        // zero_gthr_bytes: bytes of the shared thresholds to zero in front of the launch (0: an earlier launch of a mutually exclusive
-        // group already did -- only ONE launch of such a group ever runs, and a launch that does not run touches nothing)
-        auto run_exact = [&](ScanLaunch& L, float* os, int64_t* orr, const int64_t* scatter, bool time_it, size_t zero_gthr_bytes) -> int {
-            const bool has_cond = L.cond.p != nullptr;
-            const size_t pbytes = (size_t)L.parts * L.nq * L.k * sizeof(u64);
-            L.partial = (u64*)t.partial.p;
-            L.gthr = (u32*)t.gthr.p;
-            L.share_thr = share;
-            if (zero_gthr_bytes) HIP_TRY(hipMemsetAsync(t.gthr.p, 0, zero_gthr_bytes, s));
-            int rc2;
-            if (idx->n > 0) {
-                if (time_it) HIP_TRY(hipEventRecord(t.ev[2], s));
-                rc2 = rmu_scan_launch(&L, s);
-                if (rc2) return fail(rc2, std::string("rmu_index_search: scan launch: ") + hipGetErrorString(hipGetLastError()));
-                if (time_it) { HIP_TRY(hipEventRecord(t.ev[3], s)); exact_timed = true; }
-                if (!has_cond) { t.grid = L.grid; t.block = 256; t.lds = L.lds_bytes; t.passes += 1; }
-            } else {
-                HIP_TRY(hipMemsetAsync(L.partial, 0, pbytes, s));
-            }
-            rc2 = rmu_merge_final_launch(L.partial, L.parts, L.nq, L.k, row_base, l2 ? 1 : 0, l2 ? (const float*)t.qn.p : nullptr, os, orr,
-                                         scatter, has_cond ? &L.cond : nullptr, s);
-            if (rc2) return fail(rc2, "rmu_index_search: merge launch");
-            if (g_dbg && !has_cond) dbg_dump("exact", idx->n, s);
-            return RMU_OK;
-        };
+        SearchBlock b{idx, t, s, qdev, nb, k, row_base, d_s, d_r, timed, l2};
         const bool screened = screen_applies(idx, nb, k);
-        if (screened) {
-            // ---- screened path: fp16 scan proposes K' = 32 candidates, exact fp32 re-score decides --------------------------
-            // Flagged queries -> exact scan, decided ON THE DEVICE: three mutually exclusive conditional launches
-            //   1..32 flagged: the 32-query HBM-bound geometry; 33..nb/8: a batch of nb/8; more: the whole batch.
-            // With nothing flagged (the normal case) each costs one empty grid (~2 us); no host round trip either way, so
-            // the whole search is asynchronous on the stream it was given.
-            // (round 5) Every dependent launch of a search costs ~4.4 us of kernel boundary on this part, run or not, and a batch of <= 32
-            // queries already IS the 32-query geometry: one class there -- "anything flagged: the exact scan of the whole batch" -- without
-            // the gather (3 stream operations behind the re-score instead of 7); the classes of a larger batch share ONE threshold memset.
-            const bool one_class = nb <= 32;
-            const int small_n = (int)(nb < 32 ? nb : 32), mid_n = one_class ? 0 : (int)(nb / 8);
-            const int gather_n = mid_n > small_n ? mid_n : small_n;
-            const int lim_small = one_class ? 0 : (mid_n > small_n ? small_n : mid_n);    // no mid launch: the small one covers 1..nb/8
-            if (t.flag.ensure(2 * sizeof(int)) || t.fb_i.ensure((size_t)nb * sizeof(int64_t)) ||
-                t.fbq.ensure((size_t)gather_n * dpad * sizeof(float)))
-                return fail(RMU_E_OOM, "rmu_index_search: re-run workspace");
-            const int* cnt = (const int*)t.flag.p;
-            const RmuCond c1{cnt, 1, lim_small, 1}, c2{cnt, small_n + 1, mid_n, 1}, c3{cnt, (lim_small > 0 || mid_n > small_n ? mid_n : 0) + 1, 0x7fffffff, 0};
-            ScanLaunch L1{}, L2{}, L3{};
-            if (lim_small > 0 && (rc = plan_exact((const float*)t.fbq.p, small_n, &c1, &L1))) return rc;
-            if (mid_n > small_n && (rc = plan_exact((const float*)t.fbq.p, mid_n, &c2, &L2))) return rc;
-            if ((rc = plan_exact(qdev, nb, &c3, &L3))) return rc;
-            if (t.partial.ensure(need_partial) || t.gthr.ensure(need_gthr)) return fail(RMU_E_OOM, "rmu_index_search: re-run partials");
-            int nl = 0;
-            ScanLaunch lastg{};
-            rc = screen_enqueue(idx, t, qdev, nb, s, timed, &nl, &lastg, k, screen_kp(k), (u32*)t.flag.p);    // (flag[0] = 0 by the query conversion)
-            if (rc) return rc;
-            // |s~ - s_fp32| <= EPS(q) from the measured image errors (derivation in scan_screen.hip); queries failing the
-            // sufficiency test are appended to the list fb_i (count in flag[0])
-            rc = rmu_rescore_launch((const u64*)t.ckeys.p, screen_kp(k), idx->x, qdev, nb, k, idx->xnorm_max, idx->dx_max, row_base, d_s, d_r,
-                                    (int*)t.flag.p, (int64_t*)t.fb_i.p, nullptr, s, dpad, l2 ? (const float*)t.qn.p : nullptr);
-            if (rc) return fail(rc, "rmu_index_search: re-score launch");
-            t.grid = lastg.grid; t.block = 256; t.lds = lastg.lds_bytes; t.passes += nl;
-            {
-                // gather (batches above 32 queries) + the re-runs' threshold zeroing + the count to the host, one launch (see the kernel)
-                const int g_n = (lim_small > 0 || mid_n > small_n) ? gather_n : 0;
-                hipLaunchKernelGGL(k_gather_flagged, dim3((unsigned)(g_n > 0 ? g_n : 1)), dim3(128), 0, s, qdev, dpad, (const int64_t*)t.fb_i.p, cnt,
-                                   (float*)t.fbq.p, g_n, (u32*)t.gthr.p, (int)(need_gthr / sizeof(u32)), t.hflag_dev);
-                HIP_TRY(hipGetLastError());
-            }
-            size_t zero_once = 0;                  // (the thresholds of the mutually exclusive re-run launches were zeroed by the launch above)
-            if (lim_small > 0) { if ((rc = run_exact(L1, d_s, d_r, (const int64_t*)t.fb_i.p, false, zero_once))) return rc; zero_once = 0; }
-            if (mid_n > small_n) { if ((rc = run_exact(L2, d_s, d_r, (const int64_t*)t.fb_i.p, false, zero_once))) return rc; zero_once = 0; }
-            if ((rc = run_exact(L3, d_s, d_r, nullptr, false, zero_once))) return rc;
-            if (timed)
-                for (int l = 0; l < nl; ++l) {
-                    HIP_TRY(hipEventSynchronize(t.lev[(size_t)(2 * l + 1)]));
-                    float ms = 0.f;
-                    if (hipEventElapsedTime(&ms, t.lev[(size_t)(2 * l)], t.lev[(size_t)(2 * l + 1)]) == hipSuccess) scan_total += ms;
-                }
-        } else if (deep_applies(idx, k)) {
-            // ---- deep k (32 < k <= 112) over a large corpus (BASELINE config 5's dense top-100): the 128-deep scan is slow COLD --
-            // k ln(rows / k) appends per query and chunk, each stalling a barrier-coupled workgroup -- not per byte.  So the
-            // threshold ladder of the screening path, with exact arithmetic: the corpus is scanned in row ranges of growing size
-            // (~8k rows, then x4), after each range the candidates are merged with the running top-k (keys) and its k-th best
-            // seeds the shared per-query thresholds of the next launch; the last merge writes the results.  Every launch is
-            // the exact fp32 scan, every bound is a real k-th best: results are those of the single launch, bit for bit.
-            const std::vector<int64_t> bounds = deep_bounds(idx->n);
-            const int nl = (int)bounds.size();
-            std::vector<ScanLaunch> lv((size_t)nl);
-            int slots = nl - 1;
-            const size_t gthr_need = gthr_bytes(nb);
-            for (int l = 0; l < nl; ++l) {
-                ScanLaunch& S = lv[(size_t)l];
-                S = ScanLaunch{};
-                S.row0 = l ? bounds[(size_t)l - 1] : 0;
-                S.x = idx->x + S.row0 * dpad; S.n_rows = bounds[(size_t)l] - S.row0; S.dpad = dpad; S.q = qdev; S.nq = (int)nb; S.k = k; S.dbg = g_dbg;
-                S.wide = idx->wide_scan ? 1 : 0;
-                if ((rc = rmu_scan_plan(&S))) return fail(rc, "rmu_index_search: no scan geometry for this (dim, k)");
-                slots += S.parts;
-            }
-            const size_t part_keys = (size_t)nb * k;
-            if (t.partial.ensure((size_t)slots * part_keys * sizeof(u64)) || t.gthr.ensure(gthr_need))
-                return fail(RMU_E_OOM, "rmu_index_search: ladder workspace");
-            HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_need, s));
-            u64* base = (u64*)t.partial.p;
-            int cursor = 0;
-            if (timed) HIP_TRY(hipEventRecord(t.ev[2], s));
-            for (int l = 0; l < nl; ++l) {
-                ScanLaunch& S = lv[(size_t)l];
-                const int first = cursor;           // slot of the running top-k (l > 0), else of this range's first part
-                if (l > 0) cursor += 1;
-                S.partial = base + (size_t)cursor * part_keys; S.gthr = (u32*)t.gthr.p; S.share_thr = share;
-                rc = rmu_scan_launch(&S, s);
-                if (rc) return fail(rc, std::string("rmu_index_search: scan launch: ") + hipGetErrorString(hipGetLastError()));
-                cursor += S.parts;
-                if (l + 1 < nl)
-                    rc = rmu_merge_to_keys_launch(base + (size_t)first * part_keys, cursor - first, nb, k, base + (size_t)cursor * part_keys,
-                                                  (u32*)t.gthr.p, s);
-                else
-                    rc = rmu_merge_final_launch(base + (size_t)first * part_keys, cursor - first, nb, k, row_base, l2 ? 1 : 0,
-                                                l2 ? (const float*)t.qn.p : nullptr, d_s, d_r, nullptr, nullptr, s);
-                if (rc) return fail(rc, "rmu_index_search: ladder merge");
-            }
-            if (timed) { HIP_TRY(hipEventRecord(t.ev[3], s)); exact_timed = true; }
-            t.grid = lv.back().grid; t.block = 256; t.lds = lv.back().lds_bytes; t.passes += nl;
-        } else {
-            ScanLaunch L{};
-            if ((rc = plan_exact(qdev, nb, nullptr, &L))) return rc;
-            if (t.partial.ensure(need_partial) || t.gthr.ensure(need_gthr)) return fail(RMU_E_OOM, "rmu_index_search: partial workspace");
-            if ((rc = run_exact(L, d_s, d_r, nullptr, timed, need_gthr))) return rc;
-        }
+        if (screened) rc = search_block_screened(b);
+        else if (deep_applies(idx, k)) rc = search_block_deep(b);
+        else rc = search_block_exact(b);
+        if (rc) return rc;
+        scan_total += b.scan_ms;
         if ((rc = copy_outputs(out_scores, out_rows, q0, nb, k, out_dev, d_s, d_r, s))) return rc;
         // workspace is reused by the next query block (and host outputs must land): drain per block.  With a caller stream,
         // device outputs and a single block nothing here waits: the work is merely ordered on that stream.
@@ -1617,10 +1499,9 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
             any_screened = true;
             if (drained) rerun_total += *t.hflag;
         }
-        if (exact_timed) {
+        if (b.exact_timed) {
             HIP_TRY(hipEventSynchronize(t.ev[3]));
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, t.ev[2], t.ev[3]) == hipSuccess) scan_total += ms;
+            scan_total += elapsed_ms(t.ev[2], t.ev[3]);
         }
     }
     t.screened = any_screened ? (rerun_total ? -rerun_total : 1) : 0;
@@ -1632,6 +1513,159 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
         t.scan_ms = scan_total;
     }
     return RMU_OK;
+}
+
+// ---- the exact fp32 fused scan + merge of `nqq` device queries: plan first, then run.  ALL workspace of a block is sized before anything
+// that uses it is enqueued (a grow-only buffer must not be re-allocated under work already in flight), and no Buf::ensure may run between
+// taking a buffer's pointer and the launch that uses it -- so a path plans every launch it may need, sizes t.partial / t.gthr for the largest
+// (exact_partial_bytes, gthr_bytes), and only then runs them; run_exact takes the pointers itself.  `cond` (optional) makes both launches
+// conditional on the device-side count of flagged queries; `scatter` redirects result row i to batch row scatter[i]. ---------------------
+static int plan_exact(const SearchBlock& b, const float* qd, int64_t nqq, const RmuCond* cond, ScanLaunch* L) {
+    *L = ScanLaunch{};
+    L->x = b.idx->x; L->n_rows = b.idx->n; L->dpad = b.idx->dpad; L->q = qd; L->nq = (int)nqq; L->k = b.k; L->dbg = g_dbg;
+    L->wide = b.idx->wide_scan ? 1 : 0;     // (a dpad above 768 is routed to the wide kernel by the planner itself)
+    if (cond) L->cond = *cond;
+    const int rc = rmu_scan_plan(L);
+    return rc ? fail(rc, "rmu_index_search: no scan geometry for this (dim, k)") : RMU_OK;
+}
+// bytes of a planned launch's partial lists (a launch that was never planned: 0)
+static size_t exact_partial_bytes(const ScanLaunch& L) { return (size_t)L.parts * L.nq * L.k * sizeof(u64); }
+
+// zero_gthr_bytes: bytes of the shared thresholds to zero in front of the launch (0: an earlier launch of a mutually exclusive
+// group already did -- only ONE launch of such a group ever runs, and a launch that does not run touches nothing)
+static int run_exact(SearchBlock& b, ScanLaunch& L, float* os, int64_t* orr, const int64_t* scatter, bool time_it, size_t zero_gthr_bytes) {
+    Tls& t = b.t; hipStream_t s = b.s;
+    const bool has_cond = L.cond.p != nullptr;
+    L.partial = (u64*)t.partial.p;
+    L.gthr = (u32*)t.gthr.p;
+    L.share_thr = share_env();
+    if (zero_gthr_bytes) HIP_TRY(hipMemsetAsync(t.gthr.p, 0, zero_gthr_bytes, s));
+    int rc;
+    if (b.idx->n > 0) {
+        if (time_it) HIP_TRY(hipEventRecord(t.ev[2], s));
+        rc = rmu_scan_launch(&L, s);
+        if (rc) return fail(rc, std::string("rmu_index_search: scan launch: ") + hipGetErrorString(hipGetLastError()));
+        if (time_it) { HIP_TRY(hipEventRecord(t.ev[3], s)); b.exact_timed = true; }
+        if (!has_cond) t.note_geometry(L, 1);
+    } else {
+        HIP_TRY(hipMemsetAsync(L.partial, 0, exact_partial_bytes(L), s));
+    }
+    rc = rmu_merge_final_launch(L.partial, L.parts, L.nq, L.k, b.row_base, b.l2 ? 1 : 0, b.l2 ? (const float*)t.qn.p : nullptr, os, orr,
+                                scatter, has_cond ? &L.cond : nullptr, s);
+    if (rc) return fail(rc, "rmu_index_search: merge launch");
+    if (g_dbg && !has_cond) dbg_dump("exact", b.idx->n, s);
+    return RMU_OK;
+}
+
+// ---- screened path: fp16 scan proposes K' = 32 candidates, exact fp32 re-score decides ------------------------------------------------
+// Flagged queries -> exact scan, decided ON THE DEVICE: three mutually exclusive conditional launches
+//   1..32 flagged: the 32-query HBM-bound geometry; 33..nb/8: a batch of nb/8; more: the whole batch.
+// With nothing flagged (the normal case) each costs one empty grid (~2 us); no host round trip either way, so
+// the whole search is asynchronous on the stream it was given.
+// (round 5) Every dependent launch of a search costs ~4.4 us of kernel boundary on this part, run or not, and a batch of <= 32
+// queries already IS the 32-query geometry: one class there -- "anything flagged: the exact scan of the whole batch" -- without
+// the gather (3 stream operations behind the re-score instead of 7); the classes of a larger batch share ONE threshold memset.
+static int search_block_screened(SearchBlock& b) {
+    rmu_index* idx = b.idx; Tls& t = b.t; hipStream_t s = b.s;
+    const float* qdev = b.qdev; const int64_t nb = b.nb; const int k = b.k, dpad = idx->dpad;
+    float* d_s = b.d_s; int64_t* d_r = b.d_r;
+    int rc;
+    const bool one_class = nb <= 32;
+    const int small_n = (int)(nb < 32 ? nb : 32), mid_n = one_class ? 0 : (int)(nb / 8);
+    const int gather_n = mid_n > small_n ? mid_n : small_n;
+    const int lim_small = one_class ? 0 : (mid_n > small_n ? small_n : mid_n);    // no mid launch: the small one covers 1..nb/8
+    if (t.flag.ensure(2 * sizeof(int)) || t.fb_i.ensure((size_t)nb * sizeof(int64_t)) ||
+        t.fbq.ensure((size_t)gather_n * dpad * sizeof(float)))
+        return fail(RMU_E_OOM, "rmu_index_search: re-run workspace");
+    const int* cnt = (const int*)t.flag.p;
+    const RmuCond c1{cnt, 1, lim_small, 1}, c2{cnt, small_n + 1, mid_n, 1}, c3{cnt, (lim_small > 0 || mid_n > small_n ? mid_n : 0) + 1, 0x7fffffff, 0};
+    ScanLaunch L1{}, L2{}, L3{};
+    if (lim_small > 0 && (rc = plan_exact(b, (const float*)t.fbq.p, small_n, &c1, &L1))) return rc;
+    if (mid_n > small_n && (rc = plan_exact(b, (const float*)t.fbq.p, mid_n, &c2, &L2))) return rc;
+    if ((rc = plan_exact(b, qdev, nb, &c3, &L3))) return rc;
+    const size_t need_partial = std::max({exact_partial_bytes(L1), exact_partial_bytes(L2), exact_partial_bytes(L3)});
+    const size_t need_gthr = gthr_bytes(nb);           // (L3's: the gathered launches are planned for fewer queries)
+    if (t.partial.ensure(need_partial) || t.gthr.ensure(need_gthr)) return fail(RMU_E_OOM, "rmu_index_search: re-run partials");
+    int nl = 0;
+    ScanLaunch lastg{};
+    if ((rc = screen_enqueue(idx, t, qdev, nb, s, b.timed, &nl, &lastg, k, screen_kp(k), (u32*)t.flag.p))) return rc;    // (flag[0] = 0 by the query conversion)
+    // |s~ - s_fp32| <= EPS(q) from the measured image errors (derivation in scan_screen.hip); queries failing the
+    // sufficiency test are appended to the list fb_i (count in flag[0])
+    rc = rmu_rescore_launch((const u64*)t.ckeys.p, screen_kp(k), idx->x, qdev, nb, k, idx->xnorm_max, idx->dx_max, b.row_base, d_s, d_r,
+                            (int*)t.flag.p, (int64_t*)t.fb_i.p, nullptr, s, dpad, b.l2 ? (const float*)t.qn.p : nullptr);
+    if (rc) return fail(rc, "rmu_index_search: re-score launch");
+    t.note_geometry(lastg, nl);
+    // gather (batches above 32 queries) + the re-runs' threshold zeroing + the count to the host, one launch (see the kernel)
+    const int g_n = (lim_small > 0 || mid_n > small_n) ? gather_n : 0;
+    hipLaunchKernelGGL(k_gather_flagged, dim3((unsigned)(g_n > 0 ? g_n : 1)), dim3(128), 0, s, qdev, dpad, (const int64_t*)t.fb_i.p, cnt,
+                       (float*)t.fbq.p, g_n, (u32*)t.gthr.p, (int)(need_gthr / sizeof(u32)), t.hflag_dev);
+    HIP_TRY(hipGetLastError());
+    // (zero_gthr_bytes = 0: the thresholds of the mutually exclusive re-run launches were zeroed by the launch above)
+    if (lim_small > 0 && (rc = run_exact(b, L1, d_s, d_r, (const int64_t*)t.fb_i.p, false, 0))) return rc;
+    if (mid_n > small_n && (rc = run_exact(b, L2, d_s, d_r, (const int64_t*)t.fb_i.p, false, 0))) return rc;
+    if ((rc = run_exact(b, L3, d_s, d_r, nullptr, false, 0))) return rc;
+    if (b.timed)
+        for (int l = 0; l < nl; ++l) {
+            HIP_TRY(hipEventSynchronize(t.lev[(size_t)(2 * l + 1)]));
+            b.scan_ms += elapsed_ms(t.lev[(size_t)(2 * l)], t.lev[(size_t)(2 * l + 1)]);
+        }
+    return RMU_OK;
+}
+
+// ---- deep k (32 < k <= 112) over a large corpus (BASELINE config 5's dense top-100): the 128-deep scan is slow COLD --
+// k ln(rows / k) appends per query and chunk, each stalling a barrier-coupled workgroup -- not per byte.  So the
+// threshold ladder of the screening path, with exact arithmetic: the corpus is scanned in row ranges of growing size
+// (~8k rows, then x4), after each range the candidates are merged with the running top-k (keys) and its k-th best
+// seeds the shared per-query thresholds of the next launch; the last merge writes the results.  Every launch is
+// the exact fp32 scan, every bound is a real k-th best: results are those of the single launch, bit for bit.
+static int search_block_deep(SearchBlock& b) {
+    rmu_index* idx = b.idx; Tls& t = b.t; hipStream_t s = b.s;
+    const int64_t nb = b.nb; const int k = b.k, dpad = idx->dpad;
+    int rc;
+    const std::vector<int64_t> bounds = deep_bounds(idx->n);
+    const int nl = (int)bounds.size();
+    std::vector<ScanLaunch> lv((size_t)nl);
+    for (int l = 0; l < nl; ++l) {
+        ScanLaunch& S = lv[(size_t)l];
+        S = ScanLaunch{};
+        S.row0 = l ? bounds[(size_t)l - 1] : 0;
+        S.x = idx->x + S.row0 * dpad; S.n_rows = bounds[(size_t)l] - S.row0; S.dpad = dpad; S.q = b.qdev; S.nq = (int)nb; S.k = k; S.dbg = g_dbg;
+        S.wide = idx->wide_scan ? 1 : 0;
+        if ((rc = rmu_scan_plan(&S))) return fail(rc, "rmu_index_search: no scan geometry for this (dim, k)");
+    }
+    const size_t part_keys = (size_t)nb * k;
+    const size_t gthr_need = gthr_bytes(nb);
+    if (t.partial.ensure((size_t)ladder_slots(lv) * part_keys * sizeof(u64)) || t.gthr.ensure(gthr_need))
+        return fail(RMU_E_OOM, "rmu_index_search: ladder workspace");
+    HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_need, s));
+    int slot = 0;
+    if (b.timed) HIP_TRY(hipEventRecord(t.ev[2], s));
+    for (int l = 0; l < nl; ++l) {
+        ScanLaunch& S = lv[(size_t)l];
+        const LadderLevel lvl = ladder_level((u64*)t.partial.p, part_keys, &slot, l, nl, S.parts, nullptr /* the last merge writes results, not keys */);
+        S.partial = lvl.parts; S.gthr = (u32*)t.gthr.p; S.share_thr = share_env();
+        rc = rmu_scan_launch(&S, s);
+        if (rc) return fail(rc, std::string("rmu_index_search: scan launch: ") + hipGetErrorString(hipGetLastError()));
+        if (l + 1 < nl)
+            rc = rmu_merge_to_keys_launch(lvl.merge_in, lvl.n_lists, nb, k, lvl.merged, (u32*)t.gthr.p, s);
+        else
+            rc = rmu_merge_final_launch(lvl.merge_in, lvl.n_lists, nb, k, b.row_base, b.l2 ? 1 : 0, b.l2 ? (const float*)t.qn.p : nullptr,
+                                        b.d_s, b.d_r, nullptr, nullptr, s);
+        if (rc) return fail(rc, "rmu_index_search: ladder merge");
+    }
+    if (b.timed) { HIP_TRY(hipEventRecord(t.ev[3], s)); b.exact_timed = true; }
+    t.note_geometry(lv.back(), nl);
+    return RMU_OK;
+}
+
+// ---- everything else: one exact scan of the whole block ---------------------------------------------------------------------------------
+static int search_block_exact(SearchBlock& b) {
+    Tls& t = b.t;
+    ScanLaunch L{};
+    int rc;
+    if ((rc = plan_exact(b, b.qdev, b.nb, nullptr, &L))) return rc;
+    if (t.partial.ensure(exact_partial_bytes(L)) || t.gthr.ensure(gthr_bytes(b.nb))) return fail(RMU_E_OOM, "rmu_index_search: partial workspace");
+    return run_exact(b, L, b.d_s, b.d_r, nullptr, b.timed, gthr_bytes(b.nb));
 }
 
 // Exact top-k over the rows one ascending list names (include/rmu.h): the gathered scan of scan_subset.hip, whose keys carry list
@@ -1697,7 +1731,7 @@ extern "C" int rmu_index_search_subset(rmu_index_t* idx, const float* q, int64_t
             HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_bytes(nb), s));
             rc = rmu_subset_launch(&L, s);
             if (rc) return fail(rc, std::string("rmu_index_search_subset: scan launch: ") + hipGetErrorString(hipGetLastError()));
-            t.grid = L.grid; t.block = 256; t.lds = L.lds_bytes; t.passes += 1;
+            t.note_geometry(L, 1);
             parts = L.parts;
         } else {               // nothing to scan: one all-empty partial, every slot comes out (-inf | +inf, -1)
             if (t.partial.ensure((size_t)nb * k * sizeof(u64))) return fail(RMU_E_OOM, "rmu_index_search_subset: partial workspace");
@@ -1735,17 +1769,17 @@ extern "C" int rmu_index_screen_candidates(rmu_index_t* idx, const float* q_host
     if (!idx->split || idx->dim != 384 || idx->n <= 0) return fail(RMU_E_INVALID, "rmu_index_screen_candidates: index has no screening image");
     if (idx->metric == RMU_METRIC_L2SQ) return fail(RMU_E_INVALID, "rmu_index_screen_candidates: inner-product / cosine indexes only");
     const int kp = kScreenKp;
-    if (t.q.ensure((size_t)nq * 384 * sizeof(float)) || t.flag.ensure((size_t)(nq + 1) * sizeof(int)) || t.fb_i.ensure((size_t)nq * sizeof(int64_t)) ||
+    if (t.flag.ensure((size_t)(nq + 1) * sizeof(int)) || t.fb_i.ensure((size_t)nq * sizeof(int64_t)) ||
         t.out_s.ensure((size_t)nq * kp * sizeof(float)) || t.out_r.ensure((size_t)nq * kp * sizeof(int64_t)) || t.nrm.ensure((size_t)nq * sizeof(float)))
         return fail(RMU_E_OOM, "rmu_index_screen_candidates: workspace");
-    HIP_TRY(hipMemcpyAsync(t.q.p, q_host, (size_t)nq * 384 * sizeof(float), hipMemcpyHostToDevice, s));
-    if (idx->metric == RMU_METRIC_COSINE) hipLaunchKernelGGL(k_row_norm, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, 384, nq, 1, (float*)nullptr);
+    const float* qdev;
+    if ((rc = prepare_queries(idx, t, q_host, nq, false, s, &qdev, "rmu_index_screen_candidates"))) return rc;
     HIP_TRY(hipMemsetAsync(t.flag.p, 0, sizeof(int), s));
     int nl = 0;
-    rc = screen_enqueue(idx, t, (const float*)t.q.p, nq, s, false, &nl, nullptr, kp /* k = K': no band -- the true approximate top-K' */);
+    rc = screen_enqueue(idx, t, qdev, nq, s, false, &nl, nullptr, kp /* k = K': no band -- the true approximate top-K' */);
     if (rc) return rc;
     // k = K': the re-score kernel writes the exact fp32 score of EVERY candidate (rank order) and EPS(q)
-    rc = rmu_rescore_launch((const u64*)t.ckeys.p, kp, idx->x, (const float*)t.q.p, nq, kp, idx->xnorm_max, idx->dx_max, 0, (float*)t.out_s.p,
+    rc = rmu_rescore_launch((const u64*)t.ckeys.p, kp, idx->x, qdev, nq, kp, idx->xnorm_max, idx->dx_max, 0, (float*)t.out_s.p,
                             (int64_t*)t.out_r.p, (int*)t.flag.p, (int64_t*)t.fb_i.p, (float*)t.nrm.p, s);
     if (rc) return fail(rc, "rmu_index_screen_candidates: re-score");
     std::vector<u64> keys((size_t)nq * kp);
@@ -1807,8 +1841,7 @@ extern "C" int rmu_topk_merge(const float* scores, const int64_t* rows, int part
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : t.stream;
     const bool in_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE;
     const size_t cnt = (size_t)parts * nq * k;
-    const float* ds = scores;
-    const int64_t* dr = rows;
+    const float* ds = scores; const int64_t* dr = rows;
     if (!in_dev) {
         if (t.in_s.ensure(cnt * sizeof(float)) || t.in_r.ensure(cnt * sizeof(int64_t)))
             return fail(RMU_E_OOM, "rmu_topk_merge: input workspace");
@@ -1817,20 +1850,11 @@ extern "C" int rmu_topk_merge(const float* scores, const int64_t* rows, int part
         ds = (const float*)t.in_s.p;
         dr = (const int64_t*)t.in_r.p;
     }
-    float* os = out_scores;
-    int64_t* orr = out_rows;
-    if (!out_dev) {
-        if (t.out_s.ensure((size_t)nq * k * sizeof(float)) || t.out_r.ensure((size_t)nq * k * sizeof(int64_t)))
-            return fail(RMU_E_OOM, "rmu_topk_merge: output workspace");
-        os = (float*)t.out_s.p;
-        orr = (int64_t*)t.out_r.p;
-    }
+    float* os = out_scores; int64_t* orr = out_rows;
+    if ((rc = stage_outputs(t, nq, k, out_dev, &os, &orr, "rmu_topk_merge"))) return rc;
     rc = rmu_merge_lists_launch(ds, dr, parts, nq * k, nq * k, nq, k, (flags & RMU_F_SMALLER_BETTER) ? 1 : 0, os, orr, s);
     if (rc) return fail(rc, "rmu_topk_merge: launch");
-    if (!out_dev) {
-        HIP_TRY(hipMemcpyAsync(out_scores, os, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_rows, orr, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    }
+    if ((rc = copy_outputs(out_scores, out_rows, 0, nq, k, out_dev, os, orr, s))) return rc;
     const bool drained = !hip_stream || !out_dev || !in_dev;
     if (drained) HIP_TRY(hipStreamSynchronize(s));
     t.finished(s, drained);

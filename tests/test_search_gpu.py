@@ -1196,3 +1196,69 @@ def test_a_torch_graph_capture_on_another_thread_survives_growth_removal_search_
     side.synchronize()
     # the search that was left in flight over 12 000 rows while the matrix was re-allocated under it read the OLD matrix to the end
     assert_topk_parity(out_s.cpu().numpy(), out_r.cpu().numpy(), *O.flat_search(q, x[:12_000], 12))
+
+
+def test_every_search_path_on_a_cold_thread_whose_workspaces_grow_at_every_call(rmu):
+    """Every path of the dispatcher -- screened, exact, subset, deep ladder, topk_merge -- on a fresh thread, in ASCENDING batch order: each step
+    at least doubles nb, a workspace grows by 1.25 x + 256 bytes, so every per-query buffer is re-allocated at every call (a workspace sized, or its
+    pointer taken, at the wrong moment shows here), and joining the thread frees them all (a buffer freed twice shows there).  The reference is
+    the main thread's own answer to the same call, taken in DESCENDING batch order -- nothing re-allocates after a path's first call -- so
+    the comparison is bit for bit, re-run count and launch count included; the oracle comparisons of these paths are tests/test_search_regimes_gpu.py's."""
+    rng = np.random.default_rng(20261)
+    x = rng.standard_normal((20_000, 384), dtype=np.float32)
+    q = rng.standard_normal((1024, 384), dtype=np.float32)
+    sub = np.sort(rng.choice(20_000, 500, replace=False)).astype(np.int64)
+    xd = rng.standard_normal((262_144, 384), dtype=np.float32)       # the smallest corpus deep_applies accepts
+    qd = rng.standard_normal((100, 384), dtype=np.float32)
+    idx, deep = rmu.FlatIndex(384), rmu.FlatIndex(384)
+    idx.add(x)
+    deep.add(xd)
+    deep.set_screening(False)
+
+    def call(path, nb):
+        if path == "screened":
+            idx.set_screening(True)
+            idx.set_screen_min_batch(1)
+            s, r = idx.search(q[:nb], 10)
+            assert idx.last_screened() != 0
+        elif path == "exact":
+            idx.set_screening(False)
+            s, r = idx.search(q[:nb], 10)
+            assert idx.last_screened() == 0
+        elif path == "subset":
+            s, r = idx.search(q[:nb], 10, rows=sub)
+        elif path == "deep":
+            s, r = deep.search(qd[:nb], 40)
+            assert deep.last_screened() == 0 and deep.last_geometry()["launches"] > 1
+        else:                                                        # 4 parts of the nb = 40 exact answer
+            idx.set_screening(False)
+            es, er = idx.search(q[:40], 10)
+            s, r = rmu.topk_merge(es.reshape(4, 10, 10), er.reshape(4, 10, 10))
+        return s, r, idx.last_screened(), idx.last_geometry()["launches"]
+
+    paths = [("screened", (16, 128, 1024)), ("exact", (3, 40)), ("subset", (3, 40)), ("deep", (16, 40, 100)), ("merge", (40,))]
+    want = {(p, nb): call(p, nb) for p, nbs in paths for nb in sorted(nbs, reverse=True)}
+    got, errors = {}, []
+
+    def worker():
+        try:
+            for p, nbs in paths:
+                for nb in nbs:
+                    got[(p, nb)] = call(p, nb)
+        except BaseException as e:                                   # noqa: BLE001 -- re-raised on the main thread
+            errors.append(e)
+
+    t = threading.Thread(target=worker)
+    t.start()
+    t.join()                                                         # ... which runs the thread's ~Tls
+    if errors:
+        raise errors[0]
+    assert set(got) == set(want)
+    for key, (s, r, screened, launches) in want.items():
+        gs, gr, gscreened, glaunches = got[key]
+        assert np.array_equal(gs.view(np.uint32), s.view(np.uint32)) and np.array_equal(gr, r), key
+        assert (gscreened, glaunches) == (screened, launches), key
+    s, r, _, _ = call("screened", 1024)                              # the main thread's workspaces are its own, untouched
+    assert np.array_equal(s.view(np.uint32), want[("screened", 1024)][0].view(np.uint32)) and np.array_equal(r, want[("screened", 1024)][1])
+    idx.close()
+    deep.close()

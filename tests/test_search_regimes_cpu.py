@@ -94,17 +94,18 @@ SOURCE_SHAPES = {
         r"idx->xnorm_max > 0\.f && idx->xnorm_max < "),
     "a minimum batch that was set makes the screen pay": (_api, r"const bool min_nq_set = env_set \|\| idx->screen_min_nq > 0;"),
     "branch order: screen, deep ladder, exact": (_search_body,
-        r"const bool screened = screen_applies\(idx, nb, k\); if \(screened\) \{.*\} else if \(deep_applies\(idx, k\)\) \{.*\} else \{ ScanLaunch L\{\};"),
+        r"const bool screened = screen_applies\(idx, nb, k\); if \(screened\) rc = search_block_screened\(b\); "
+        r"else if \(deep_applies\(idx, k\)\) rc = search_block_deep\(b\); else rc = search_block_exact\(b\); if \(rc\) return rc;"),
     "the block loop": (_search_body,
         r"for \(int64_t q0 = 0; q0 < nq; q0 \+= kMaxQueriesPerLaunch\) \{ const int64_t nb = \(nq - q0\) < kMaxQueriesPerLaunch \? \(nq - q0\) : kMaxQueriesPerLaunch;"),
     "outputs of block q0 start at q0 * k": (_search_body, r"float\* d_s = out_scores \+ q0 \* k; int64_t\* d_r = out_rows \+ q0 \* k;"),
     # (anchored on the identifiers only: the launch a predicate belongs to, the query count it is planned for, gathered list or in place)
     "small launch: planned for small_n, gathered, scattered": (_search_body,
-        r"lim_small > 0 && \(rc = plan_exact\([^;]*\bsmall_n, &c1, &L1\).*if \(lim_small > 0\) [^;]*run_exact\(L1, d_s, d_r, [^,;]*\bfb_i\b"),
+        r"lim_small > 0 && \(rc = plan_exact\(b, [^;]*\bsmall_n, &c1, &L1\).*if \(lim_small > 0 && \(rc = run_exact\(b, L1, d_s, d_r, [^,;]*\bfb_i\b"),
     "mid launch: planned for mid_n, gathered, scattered": (_search_body,
-        r"mid_n > small_n && \(rc = plan_exact\([^;]*\bmid_n, &c2, &L2\).*if \(mid_n > small_n\) [^;]*run_exact\(L2, d_s, d_r, [^,;]*\bfb_i\b"),
+        r"mid_n > small_n && \(rc = plan_exact\(b, [^;]*\bmid_n, &c2, &L2\).*if \(mid_n > small_n && \(rc = run_exact\(b, L2, d_s, d_r, [^,;]*\bfb_i\b"),
     "whole launch: planned for nb, in place": (_search_body,
-        r"\(rc = plan_exact\(qdev, nb, &c3, &L3\)\).*[^{] if \(\(rc = run_exact\(L3, d_s, d_r, nullptr,"),
+        r"\(rc = plan_exact\(b, qdev, nb, &c3, &L3\)\).*[^{] if \(\(rc = run_exact\(b, L3, d_s, d_r, nullptr,"),
     "the re-run count is summed over the drained blocks": (_search_body,
         r"if \(drained\) rerun_total \+= [^;]*hflag;.*screened = any_screened \? \(rerun_total \? -rerun_total : 1\) : 0;"),
 }
