@@ -521,6 +521,56 @@ int rmu_attribution(const float* x, int64_t n, int dim, int64_t stride, const in
 int rmu_bert_attribute(rmu_bert_t* m, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch, int max_len, int mode,
                        const int32_t* groups, int n_groups, double* out_scores, double* out_sims, float* out_vecs);
 
+/* ---- rerank by key: passage tokens in HBM, pairs assembled and the top-n selected on the device (rerank.hip) ---------------------------
+ * Serves: ContextualCompressionRetriever(base_compressor=ScoredCrossEncoderReranker(model, top_n), base_retriever=ensemble).invoke
+ * (RAGHelper.py:476-490, RAGHelper_local.py:157-159), and the same compressor run once more per /chat request with the answer as the query
+ * (provenance.py:100-108): score every (query, page_content) pair, Python's stable sorted(..., reverse=True), keep top_n
+ * (ScoredCrossEncoderReranker.py:42-45).  ragmeup_amd/rerank.py is the host half (the text -> key dictionary, the retriever).
+ *
+ * The table holds one entry per KEY (a distinct passage text; the host numbers them): the passage's WordPiece ids WITHOUT special tokens.  An
+ * entry keeps the first max_len - 3 of its tokens -- the most a pair can ever hold of its second text -- and remembers how long it was: the
+ * truncation rule below asks which side was longer.  Host side and device image; create / free / size / set never touch a GPU (the image
+ * follows at the next rerank call: the tail only, re-allocated when it does not fit).  8 <= max_len <= 512, special ids >= 0. */
+typedef struct rmu_passages rmu_passages_t;
+#define RMU_RERANK_MAX_M 256      /* candidates per query */
+int rmu_passages_create(rmu_passages_t** out, int cls_id, int sep_id, int pad_id, int max_len);
+int rmu_passages_free(rmu_passages_t* p);
+int rmu_passages_size(rmu_passages_t* p, int64_t* n_entries, int64_t* n_tokens);      /* either may be NULL; n_tokens: the tokens KEPT */
+/* entries [first, first + n) := tokens[offsets[i] .. offsets[i + 1]), i in [0, n); the table ends at first + n afterwards: first = size appends,
+ * first < size truncates first, n = 0 only truncates; first > size is RMU_E_INVALID with a message that contains "out of step".  HOST arrays;
+ * offsets [n + 1] ascending from 0; a token id < 0 is RMU_E_INVALID.  RMU_E_INVALID changes nothing. */
+int rmu_passages_set(rmu_passages_t* p, int64_t first, const int32_t* tokens, const int64_t* offsets, int64_t n);
+/* The assembled pairs themselves: row q * m + j = [CLS] query q [SEP] passage keys[q, j] [SEP] [PAD]..., token types 0 0 0 1 1 0..., its length;
+ * what rmu_tok_encode writes for the two texts at this max_len, id for id.  (n1, n2) tokens of the two sides follow "longest_first": nothing
+ * is cut when both fit max_len - 3; only the longer side when that suffices; else both go to half the budget, the odd token to the longer
+ * side, to the passage on equal lengths.  A key of -1 (rmu_hybrid_search's padding) gives a row of [PAD] with length 0.
+ * HOST arrays throughout.  q_tokens [nq, q_stride]: the queries' WordPiece ids without special tokens, q_lens [nq]: their lengths -- which may
+ * exceed q_stride as long as the row holds the head the pair can use, min(length, max_len - 3) tokens; keys [nq, m] in [-1, size);
+ * outputs ids / type_ids [nq * m, max_len], lens [nq * m].  1 <= m <= RMU_RERANK_MAX_M, 1 <= nq, nq * m <= 65535, 8 <= max_len <= the
+ * table's; anything else is RMU_E_INVALID before anything is enqueued.  Runs on the calling thread's stream, drained on return. */
+int rmu_passages_pairs(rmu_passages_t* p, const int32_t* q_tokens, const int32_t* q_lens, int64_t nq, int q_stride,
+                       const int64_t* keys /* [nq, m] */, int m, int max_len, int32_t* ids, int32_t* type_ids, int32_t* lens);
+/* The stable top-n of m candidates per query: logits [nq, m] fp32, keys [nq, m] int64 (< 0: absent, never output).  out_pos [nq, top_n] int32
+ * = positions in the candidate list, out_scores [nq, top_n] fp32 = their logits, bit for bit, in the order of Python's
+ * sorted(zip(docs, scores), key=itemgetter(1), reverse=True): logit descending, equal logits (+0.0 == -0.0) by position; a NaN ranks behind
+ * every number, NaNs among themselves by position.  Slots beyond the present candidates hold (-1, -inf).
+ * 1 <= m <= RMU_RERANK_MAX_M, 1 <= top_n <= 65535, 1 <= nq <= 65535.  flags: RMU_F_Q_DEVICE (logits and keys are device addresses),
+ * RMU_F_OUT_DEVICE (the two outputs are).  hip_stream as rmu_topk_merge: drained on return unless a caller stream is given with device inputs
+ * AND device outputs. */
+int rmu_rerank_select(const float* logits, const int64_t* keys, int64_t nq, int m, int top_n, unsigned flags,
+                      int32_t* out_pos, float* out_scores, uint64_t hip_stream);
+/* The rerank step in ONE call with ONE synchronisation: HOST query tokens and keys in (as rmu_passages_pairs), HOST top-n out (as
+ * rmu_rerank_select; out_logits [nq, m_cand], may be NULL, receives every pair's logit).  On the encoder's stream: the copy of queries and keys,
+ * the table's pending tail, the pair assembly, the RMU_BERT_CE_LOGIT forward over batch_pad rows of max_len (rows past nq * m_cand have length
+ * 0), the selection, the copies back.  (batch_pad, max_len) is the shape the forward runs at -- the caller's bucketing, as for
+ * rmu_bert_encode_host: up to batch_pad * max_len = 4096 the forward is that call's captured graph in a form that reads its inputs from the
+ * device, beyond it rmu_bert_encode's launches.  out_logits has the bits of rmu_bert_encode_host (rmu_bert_encode beyond 4096 tokens) over
+ * rmu_passages_pairs' arrays padded to the same shape.  The model needs a classification head; nq * m_cand <= batch_pad <= 65535,
+ * max_len <= the table's and the model's; every limit of the two calls above; otherwise RMU_E_INVALID before anything is enqueued. */
+int rmu_bert_rerank(rmu_bert_t* m, rmu_passages_t* p, const int32_t* q_tokens, const int32_t* q_lens, int64_t nq, int q_stride,
+                    const int64_t* keys, int m_cand, int batch_pad, int max_len, int top_n,
+                    int32_t* out_pos, float* out_scores, float* out_logits /* [nq, m_cand], may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,12 +11,13 @@ from .bm25 import BM25Index, MI355XBM25Retriever  # noqa: F401
 from .hybrid import HybridIndex, MI355XHybridRetriever  # noqa: F401
 from .chunker import MI355XSemanticChunker  # noqa: F401
 from .provenance import DocumentSimilarityAttribution, MI355XSimilarityAttribution  # noqa: F401
+from .rerank import MI355XRerankRetriever, PassageTable  # noqa: F401
 
 from .vectorstore import MI355XRetriever  # noqa: F401
 from . import factory  # noqa: F401
 
 __all__ = ["FlatIndex", "topk_merge", "Document", "ScoredCrossEncoderReranker", "MI355XVectorStore", "MI355XRetriever",
-           "BM25Index", "MI355XBM25Retriever", "HybridIndex", "MI355XHybridRetriever", "MI355XSemanticChunker", "DocumentSimilarityAttribution", "MI355XSimilarityAttribution", "BertEncoder", "MI355XEmbeddings", "MI355XCrossEncoder", "factory"]
+           "BM25Index", "MI355XBM25Retriever", "HybridIndex", "MI355XHybridRetriever", "MI355XSemanticChunker", "DocumentSimilarityAttribution", "MI355XSimilarityAttribution", "MI355XRerankRetriever", "PassageTable", "BertEncoder", "MI355XEmbeddings", "MI355XCrossEncoder", "factory"]
 
 
 def __getattr__(name):   # torch-dependent classes are imported lazily

@@ -34,6 +34,7 @@ BM25_OPT_TILE_DOCS, BM25_OPT_MAX_WGS, BM25_OPT_REPACK_ON_REMOVE = 1, 2, 4
 BM25_OPT_REPACK_ON_ADD = 8
 BM25_STAT_IMAGE_PACKS, BM25_STAT_IMAGE_SPLICES, BM25_STAT_IMAGE_UPLOAD_BYTES = 16, 17, 18
 RRF_MAX_LISTS = 4
+RERANK_MAX_M = 256
 # launch geometry of rmu_adjacent_cosine (semantic.hip: kWavePairs, kBlockPairs).  Results do not depend on it; the tests put their sizes on
 # both sides of these run boundaries
 ADJ_COS_WAVE_PAIRS, ADJ_COS_WG_PAIRS = 16, 64
@@ -51,6 +52,7 @@ SYMBOLS = [
     "rmu_bm25_remove_docs", "rmu_bm25_search_subset", "rmu_bm25_compact", "rmu_bm25_save", "rmu_bm25_load",
     "rmu_rrf_fuse", "rmu_hybrid_create", "rmu_hybrid_free", "rmu_hybrid_set_keys", "rmu_hybrid_search", "rmu_bert_search_hybrid",
     "rmu_adjacent_cosine", "rmu_attribution", "rmu_bert_attribute",
+    "rmu_passages_create", "rmu_passages_free", "rmu_passages_size", "rmu_passages_set", "rmu_passages_pairs", "rmu_rerank_select", "rmu_bert_rerank",
 ]
 
 
@@ -125,6 +127,12 @@ def _declare(lib):
     lib.rmu_hybrid_search.argtypes = [vp, vp, i64, c.c_char_p, i64, i32, i32, i32, c.c_double, f64p, i32, i32, vp, vp, vp, u64]
     lib.rmu_adjacent_cosine.argtypes = [vp, i64, i32, i64, u32, vp, u64]
     lib.rmu_attribution.argtypes = [vp, i64, i32, i64, vp, i32, u32, vp, vp, u64]
+    lib.rmu_passages_create.argtypes = [c.POINTER(vp), i32, i32, i32, i32]
+    lib.rmu_passages_free.argtypes = [vp]
+    lib.rmu_passages_size.argtypes = [vp, c.POINTER(i64), c.POINTER(i64)]
+    lib.rmu_passages_set.argtypes = [vp, i64, vp, vp, i64]
+    lib.rmu_passages_pairs.argtypes = [vp, vp, vp, i64, i32, vp, i32, i32, vp, vp, vp]
+    lib.rmu_rerank_select.argtypes = [vp, vp, i64, i32, i32, u32, vp, vp, u64]
     if hasattr(lib, "rmu_bert_create"):
         lib.rmu_bert_create.argtypes = [c.POINTER(vp), vp, c.POINTER(vp), i32]
         lib.rmu_bert_free.argtypes = [vp]
@@ -133,6 +141,7 @@ def _declare(lib):
         lib.rmu_bert_search_mmr.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, c.c_double, i64, vp, vp, vp]
         lib.rmu_bert_search_hybrid.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, c.c_char_p, i64, i32, i32, i32, c.c_double, f64p, i32, i32, vp, vp, vp]
         lib.rmu_bert_attribute.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]
+        lib.rmu_bert_rerank.argtypes = [vp, vp, vp, vp, i64, i32, vp, i32, i32, i32, i32, vp, vp, vp]
 
 
 def lib():

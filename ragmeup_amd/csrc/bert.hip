@@ -3570,8 +3570,18 @@ extern "C" int rmu_bert_encode(rmu_bert_t* m, const int32_t* ids, const int32_t*
 // binding pads batch and max_len up to a few sizes -- padded sequences have length 0 and cost nothing in the packed-token kernels).
 // The cache holds MAX_GRAPHS shapes, least recently used out.  m->mu is held by the caller; the forward is left IN FLIGHT on
 // m->stream (result in m->d_out, and on its way to m->h_out): the caller synchronises.
+// in_dev (rmu_bert_rerank): ids, type ids and lens are in m->d_in already, written there by a kernel enqueued on m->stream after
+// host_staging_locked (the three pointers are not read): the same launches without the H2D node, under graph keys of their own.
+static int host_staging_locked(rmu_bert* m, const char* who) {
+    if (!m->h_in) {
+        if (hipHostMalloc((void**)&m->h_in, SMALL_IN_INTS * sizeof(int32_t)) != hipSuccess || hipHostMalloc((void**)&m->h_out, SMALL_OUT_FLOATS * sizeof(float)) != hipSuccess ||
+            hipMalloc((void**)&m->d_in, SMALL_IN_INTS * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&m->d_out, SMALL_OUT_FLOATS * sizeof(float)) != hipSuccess)
+            return bfail(RMU_E_OOM, std::string(who) + ": staging buffers");
+    }
+    return RMU_OK;
+}
 static int host_forward_locked(rmu_bert* m, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch, int max_len, int mode,
-                               const char* who) {
+                               const char* who, bool in_dev = false) {
     const int64_t cap = (int64_t)batch * max_len;
     const int kind = mode & 0xff;
     if (cap > HOST_TOKENS) return bfail(RMU_E_INVALID, std::string(who) + ": batch * max_len must be <= 4096 (use rmu_bert_encode for bulk work)");
@@ -3579,27 +3589,27 @@ static int host_forward_locked(rmu_bert* m, const int32_t* ids, const int32_t* t
         return bfail(RMU_E_INVALID, std::string(who) + ": at most 256 result rows (pooled vectors, or token states of a <= 256-token call)");
     int rc = ensure_ws(m, cap, batch);
     if (rc) return bfail(rc, std::string(who) + ": workspace");
-    if (!m->h_in) {
-        if (hipHostMalloc((void**)&m->h_in, SMALL_IN_INTS * sizeof(int32_t)) != hipSuccess || hipHostMalloc((void**)&m->h_out, SMALL_OUT_FLOATS * sizeof(float)) != hipSuccess ||
-            hipMalloc((void**)&m->d_in, SMALL_IN_INTS * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&m->d_out, SMALL_OUT_FLOATS * sizeof(float)) != hipSuccess)
-            return bfail(RMU_E_OOM, std::string(who) + ": staging buffers");
-    }
+    if ((rc = host_staging_locked(m, who))) return rc;
+    const bool types = in_dev || type_ids;
     // staging layout: ids [cap] | type ids [cap] | lens [batch]
-    memcpy(m->h_in, ids, (size_t)cap * 4);
-    if (type_ids) memcpy(m->h_in + cap, type_ids, (size_t)cap * 4);
-    memcpy(m->h_in + 2 * cap, lens, (size_t)batch * 4);
+    if (!in_dev) {
+        memcpy(m->h_in, ids, (size_t)cap * 4);
+        if (type_ids) memcpy(m->h_in + cap, type_ids, (size_t)cap * 4);
+        memcpy(m->h_in + 2 * cap, lens, (size_t)batch * 4);
+    }
     const int64_t rows_out = kind == RMU_BERT_TOKENS ? cap : batch;                       // (the graph copies the shape's upper bound)
     const size_t out_floats = kind == RMU_BERT_CE_LOGIT ? (size_t)batch : (size_t)rows_out * H;
     const size_t in_bytes = (size_t)(2 * cap + batch) * 4;
     hipStream_t s = m->stream;
     if ((rc = order_behind_tail(m, s))) return bfail(rc, std::string(who) + ": ordering behind the forward in flight");
     auto enqueue_all = [&]() {
-        (void)hipMemcpyAsync(m->d_in, m->h_in, in_bytes, hipMemcpyHostToDevice, s);
-        enqueue_forward(m, m->d_in, type_ids ? m->d_in + cap : nullptr, m->d_in + 2 * cap, batch, max_len, mode, m->d_out, kind == RMU_BERT_CE_LOGIT ? 1 : H, s);
+        if (!in_dev) (void)hipMemcpyAsync(m->d_in, m->h_in, in_bytes, hipMemcpyHostToDevice, s);
+        enqueue_forward(m, m->d_in, types ? m->d_in + cap : nullptr, m->d_in + 2 * cap, batch, max_len, mode, m->d_out, kind == RMU_BERT_CE_LOGIT ? 1 : H, s);
         (void)hipMemcpyAsync(m->h_out, m->d_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, s);
     };
     static const bool use_graph = !(rmu_env_kill("RMU_GRAPH") && atoi(rmu_env_kill("RMU_GRAPH")) == 0);
-    const uint64_t key = ((uint64_t)batch << 32) | ((uint64_t)max_len << 16) | ((uint64_t)(mode & 0xfff) << 1) | (type_ids ? 1u : 0u);
+    // (batch <= 4096: bit 63 is free for the form whose inputs are on the device)
+    const uint64_t key = ((uint64_t)batch << 32) | ((uint64_t)max_len << 16) | ((uint64_t)(mode & 0xfff) << 1) | (types ? 1u : 0u) | (in_dev ? 1ull << 63 : 0ull);
     if (use_graph && !m->graphs.count(key) && m->graphs.size() >= MAX_GRAPHS) {          // full: the least recently used shape goes
         auto victim = m->graphs.begin();
         for (auto it = m->graphs.begin(); it != m->graphs.end(); ++it)
@@ -3633,6 +3643,7 @@ static int host_forward_locked(rmu_bert* m, const int32_t* ids, const int32_t* t
             clear_errors();
             hipStream_t ns = nullptr;
             if (hipStreamCreateWithFlags(&ns, hipStreamNonBlocking) == hipSuccess) {
+                (void)hipStreamSynchronize(m->stream);          // (in_dev: the kernel that filled m->d_in was enqueued on it in front of the capture)
                 (void)hipStreamDestroy(m->stream);
                 m->stream = ns;
                 s = ns;
@@ -3795,5 +3806,68 @@ extern "C" int rmu_bert_search_hybrid(rmu_bert_t* m, rmu_hybrid_t* h, const int3
     rc = rmu_hybrid_search_dev_(h, m->d_out, batch, query_blob, bytes, k_sparse, fetch_k, k_dense, lambda_mult, weights, c, k_out, out_scores, out_ids,
                                 out_member, (void*)m->stream);
     if (rc) { (void)hipStreamSynchronize(m->stream); return rc; }
+    return RMU_OK;
+}
+
+// The rerank step in ONE call with ONE synchronisation (ContextualCompressionRetriever(base_compressor=ScoredCrossEncoderReranker, ...).invoke,
+// server/RAGHelper.py:476-490, and the same compressor with the answer as the query, server/provenance.py:100-108): query tokens and passage KEYS
+// in, the stable top-n out.  On the context's stream: the H2D of queries and keys and the table's pending tail (rerank.hip), the pair assembly
+// straight into the staging layout, the forward -- the graph replay above in its in_dev form up to HOST_TOKENS, the eager launches over the
+// thread's assembly workspace beyond -- and the selection over its logits; the assembly and selection kernels run in front of and behind the
+// replay, not inside the capture (the rmu_bert_attribute pattern).
+extern "C" int rmu_rerank_check_(rmu_passages_t* p, const int32_t* q_tokens, const int32_t* q_lens, int64_t nq, int q_stride, const int64_t* keys,
+                                 int m, int batch_pad, int max_len, int top_n, const void* out_pos, const void* out_scores, void* lock);
+extern "C" int rmu_rerank_workspace_(int batch_pad, int max_len, int32_t** d_in, float** d_logits);
+extern "C" int rmu_rerank_assemble_(rmu_passages_t* p, const int32_t* q_tokens, const int32_t* q_lens, int64_t nq, int q_stride, const int64_t* keys,
+                                    int m, int batch_pad, int max_len, int top_n, int32_t* d_in, void* hip_stream, void* lock);
+extern "C" int rmu_rerank_select_(const float* d_logits, int64_t nq, int m, int top_n, int want_logits, void* hip_stream);
+extern "C" void rmu_rerank_take_(int64_t nq, int m, int top_n, int32_t* out_pos, float* out_scores, float* out_logits);
+extern "C" int rmu_bert_rerank(rmu_bert_t* m, rmu_passages_t* p, const int32_t* q_tokens, const int32_t* q_lens, int64_t nq, int q_stride,
+                               const int64_t* keys, int m_cand, int batch_pad, int max_len, int top_n, int32_t* out_pos, float* out_scores,
+                               float* out_logits) {
+    RMU_ENTRY();
+    const char* who = "rmu_bert_rerank";
+    // every limit, the table's included, before a context is taken; the table's again under the lock the call keeps -- taken BEHIND the
+    // context's (a call that waits for the table's exclusive lock to upload holds a context: nobody may wait for a context with the table's)
+    int rc = rmu_rerank_check_(p, q_tokens, q_lens, nq, q_stride, keys, m_cand, batch_pad, max_len, top_n, out_pos, out_scores, nullptr);
+    if (rc) return rc;
+    if (!m) return bfail(RMU_E_INVALID, "rmu_bert_rerank: null pointer");
+    if (!m->cfg.has_head) return bfail(RMU_E_INVALID, "rmu_bert_rerank: model has no classification head");
+    if (max_len > m->cfg.max_pos) return bfail(RMU_E_INVALID, "rmu_bert_rerank: max_len > max_pos");
+    const int64_t cap = (int64_t)batch_pad * max_len;
+    std::unique_lock<std::mutex> lk;
+    m = acquire_ctx(m, lk);
+    std::shared_lock<std::shared_mutex> table_lk;              // (released first, behind the drained stream)
+    rc = rmu_rerank_check_(p, q_tokens, q_lens, nq, q_stride, keys, m_cand, batch_pad, max_len, top_n, out_pos, out_scores, &table_lk);
+    if (rc) return rc;
+    (void)hipGetLastError();                     // (an error some earlier call of this thread left behind is not this call's)
+    hipStream_t s = m->stream;
+    const float* d_logits = nullptr;
+    if (cap <= HOST_TOKENS) {
+        if ((rc = host_staging_locked(m, who))) return rc;
+        rc = rmu_rerank_assemble_(p, q_tokens, q_lens, nq, q_stride, keys, m_cand, batch_pad, max_len, top_n, m->d_in, (void*)s, &table_lk);
+        if (!rc) rc = host_forward_locked(m, nullptr, nullptr, nullptr, batch_pad, max_len, RMU_BERT_CE_LOGIT, who, true);
+        s = m->stream;                           // (a lost capture replaces the stream, after draining what was enqueued in front of it)
+        d_logits = m->d_out;
+    } else {
+        int32_t* d_in = nullptr;
+        float* d_out = nullptr;
+        rc = ensure_ws(m, cap, batch_pad);
+        if (rc) return bfail(rc, "rmu_bert_rerank: workspace");
+        if ((rc = rmu_rerank_workspace_(batch_pad, max_len, &d_in, &d_out))) return rc;
+        if ((rc = order_behind_tail(m, s))) return bfail(rc, "rmu_bert_rerank: ordering behind the forward in flight");
+        rc = rmu_rerank_assemble_(p, q_tokens, q_lens, nq, q_stride, keys, m_cand, batch_pad, max_len, top_n, d_in, (void*)s, &table_lk);
+        if (!rc) {
+            enqueue_forward(m, d_in, d_in + cap, d_in + 2 * cap, batch_pad, max_len, RMU_BERT_CE_LOGIT, d_out, 1, s);
+            if (hipGetLastError() != hipSuccess) rc = bfail(RMU_E_HIP, "rmu_bert_rerank: launching the forward");
+        }
+        d_logits = d_out;
+    }
+    if (!rc) rc = rmu_rerank_select_(d_logits, nq, m_cand, top_n, out_logits ? 1 : 0, (void*)s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (rc) return rc;
+    B_TRY(es);
+    m->tail_set = false;                         // (everything this context ever enqueued has finished)
+    rmu_rerank_take_(nq, m_cand, top_n, out_pos, out_scores, out_logits);
     return RMU_OK;
 }

@@ -28,6 +28,7 @@
 
 #include "../../include/rmu.h"
 #include "rmu_common.h"
+#include "pair_truncate.h"
 #include "wordpiece_tables.h"
 
 extern "C" void rmu_set_error_(const char* msg);
@@ -401,20 +402,15 @@ extern "C" int rmu_tok_encode(rmu_tok_t* tk, const char* const* texts_a, const c
             if (pair) encode_text(tk, texts_b[i], b);
             const int special = pair ? 3 : 2;
             // truncation as the `tokenizers` library does it (AutoTokenizer's default fast backend): single -> keep the
-            // head; pair "longest_first" -> only the longer side is cut when that suffices, else both to budget/2 with the
-            // odd token going to the longer side (to the second on equal lengths)
+            // head; pair -> "longest_first" (pair_truncate.h)
             const size_t budget = (size_t)(max_len - special);
             if (a.size() + b.size() > budget) {
                 if (!pair) a.resize(budget);
                 else {
-                    size_t n1 = a.size(), n2 = b.size();
-                    const bool swap = n1 > n2;
-                    if (swap) std::swap(n1, n2);
-                    n2 = n1 > budget ? n1 : std::max(n1, budget - n1);
-                    if (n1 + n2 > budget) { n1 = budget / 2; n2 = n1 + budget % 2; }
-                    if (swap) std::swap(n1, n2);
-                    a.resize(std::min(a.size(), n1));
-                    b.resize(std::min(b.size(), n2));
+                    int n1 = 0, n2 = 0;
+                    rmu_longest_first((int)a.size(), (int)b.size(), (int)budget, &n1, &n2);
+                    a.resize((size_t)n1);
+                    b.resize((size_t)n2);
                 }
             }
             int32_t* row = ids + (size_t)i * max_len;

@@ -29,6 +29,7 @@ from typing import Any, Optional, Sequence
 
 import numpy as np
 
+from . import _native as N
 from . import bert as B
 from ._lc import CROSS_ENCODER_BASES, Embeddings
 from .bert import BertEncoder
@@ -409,3 +410,63 @@ class MI355XCrossEncoder(_EncoderBase, *CROSS_ENCODER_BASES):
                 logits = 1.0 / (1.0 + np.exp(-logits))
             return logits.tolist()
         return self.score_id_arrays(ids, tt, lens).cpu().numpy().astype(np.float64).tolist()
+
+    # ---- rerank by key (rmu_bert_rerank): passage tokens cached in HBM, pairs assembled and the top-n selected on the device -------------
+    _passages = None
+    _passages_lock = threading.Lock()
+
+    @property
+    def passages(self):
+        """The model's PassageTable (ragmeup_amd.rerank), created on first use; None unless the tokenizer is the native WordPieceTokenizer."""
+        from .tokenizer import WordPieceTokenizer
+        if self._passages is None and isinstance(self.tokenizer, WordPieceTokenizer) and 8 <= self.max_seq_length <= 512:
+            from .rerank import PassageTable
+            with MI355XCrossEncoder._passages_lock:
+                if self._passages is None:
+                    # (rows are laid out at the bucketed length of host_shape, which may exceed max_seq_length: the table allows it)
+                    self._passages = PassageTable.for_tokenizer(self.tokenizer, max_len=min(512, max(16, -(-self.max_seq_length // 32) * 32)))
+        return self._passages
+
+    def rerank(self, query: str, texts: Sequence[str], top_n: int):
+        """-> (positions, scores): what ``sorted(zip(range(len(texts)), self.score([(query, t) for t in texts])), key=itemgetter(1),
+        reverse=True)[:top_n]`` gives, position for position and float for float, in ONE library call with one synchronisation -- or None
+        when that call does not serve the request (the caller then takes ``score``): another encoder or tokenizer, a sigmoid activation (the
+        activated scores can tie where the logits do not), no text or more than 256, a query longer than the pair budget (which side gets
+        the odd token of the budget then depends on the passages' lengths before their cut, which the table does not keep)."""
+        from .tokenizer import WordPieceTokenizer
+        enc, tok = self.encoder, self.tokenizer
+        texts = list(texts)
+        m = len(texts)
+        if (not isinstance(enc, BertEncoder) or not isinstance(tok, WordPieceTokenizer) or self.activation != "identity"
+                or not 1 <= m <= N.RERANK_MAX_M or int(top_n) < 1):
+            return None
+        table = self.passages
+        if table is None:
+            return None
+        cap = self.max_seq_length - 3
+        qi, _, ql = tok.encode([query], None, max_len=cap + 3)          # single mode: up to cap + 1 tokens between [CLS] and [SEP]
+        nq_tok = int(ql[0]) - 2
+        if nq_tok > cap:
+            return None
+        gen, keys, plens = table._checkout(texts, tok)
+        try:
+            # the shape `score` runs these pairs at: the longest pair, bucketed as encode_host buckets it, else the exact (m, Lmax) of encode_ids
+            Lmax = min(self.max_seq_length, 3 + nq_tok + int(plens.max()))
+            shape = enc.host_shape(m, Lmax, B.MODE_CE)
+            if shape is None:
+                if not (self.one_forward and m * Lmax <= self.token_budget) or Lmax < 8:
+                    return None
+                shape = (m, Lmax)
+            bb, lb = shape
+            if Lmax >= self.max_seq_length and lb != self.max_seq_length:
+                return None                                  # a pair may need the cut: the row length must then BE the tokenizer's max_length
+            n = min(int(top_n), m)
+            q_tok = np.ascontiguousarray(qi[0, 1:1 + max(nq_tok, 1)], dtype=np.int32)
+            q_len = np.array([nq_tok], dtype=np.int32)
+            pos = np.empty(n, dtype=np.int32)
+            scores = np.empty(n, dtype=np.float32)
+            N.check(enc._lib.rmu_bert_rerank(enc._h, gen.h, q_tok.ctypes.data, q_len.ctypes.data, 1, int(q_tok.size), keys.ctypes.data, m,
+                                             int(bb), int(lb), n, pos.ctypes.data, scores.ctypes.data, None), "rmu_bert_rerank")
+        finally:
+            table._checkin(gen)
+        return pos.tolist(), scores.astype(np.float64).tolist()

@@ -5,7 +5,8 @@ The reference builds its plug-ins from environment variables (loaded from `.env`
                (`embedding_model`, `force_cpu`)
   vector store server/RAGHelper.py:385-415   (`vector_store`, `vector_store_uri`, `vector_store_collection`,
                                               `vector_store_initial_load`)
-  reranker     server/RAGHelper.py:476-490   (`rerank`, `rerank_model`, `rerank_k`)
+  reranker     server/RAGHelper.py:476-490   (`rerank`, `rerank_model`, `rerank_k`; `rerank_retriever_from_env`: the
+                                              ContextualCompressionRetriever around it, reranking by key in one call)
   retriever    server/RAGHelper.py:497-499   (`vector_store_k`)
   splitter     server/RAGHelper.py:329-349   (`splitter`, `breakpoint_threshold_type`, `breakpoint_threshold_amount`,
                                               `number_of_chunks`; parsed at :62, :73-76)
@@ -80,6 +81,22 @@ def reranker_from_env(env: Optional[Mapping[str, str]] = None, device: int = 0):
     from .reranker import ScoredCrossEncoderReranker
     return ScoredCrossEncoderReranker(model=MI355XCrossEncoder(model_dir=model, device=device),
                                       top_n=int(env.get("rerank_k", "3")))
+
+
+def rerank_retriever_from_env(base_retriever: Any, env: Optional[Mapping[str, str]] = None, device: int = 0, compressor: Any = None):
+    """`self.rerank_retriever` (RAGHelper.py:487-490, RAGHelper_local.py:157-159): the reference wraps its ensemble in
+    ``ContextualCompressionRetriever(base_compressor=self.compressor, base_retriever=...)``; this is that object with the rerank answered by
+    one library call per request (ragmeup_amd.rerank.MI355XRerankRetriever: the passages' tokens cached in HBM, the pairs assembled and the
+    top-n selected on the device) -- same documents, order and ``relevance_score``.  `compressor`: the one `reranker_from_env` built (so the
+    provenance pass and the retriever share one model and one passage table); None builds it.  None when `rerank != "True"`.  The retriever
+    also serves ``provenance.compute_rerank_provenance`` in the compressor's place."""
+    env = os.environ if env is None else env
+    if compressor is None:
+        compressor = reranker_from_env(env, device)
+    if compressor is None:
+        return None
+    from .rerank import MI355XRerankRetriever
+    return MI355XRerankRetriever(base_compressor=compressor, base_retriever=base_retriever)
 
 
 def text_splitter_from_env(embeddings: Any, env: Optional[Mapping[str, str]] = None):
