@@ -69,6 +69,10 @@ extern "C" {
                              * as before.  Results and re-run counts are identical either way. */
 #define RMU_OPT_SCREEN_SPILL_CAP 9 /* tuning: records per spill list of RMU_OPT_SCREEN_SPILL (1..4096; 0 = default, 256).  A wave whose list is full
                              * goes on appending inside the tile loop; results are identical for every value (the tests force that path). */
+#define RMU_OPT_SCREEN_REFRESH 10 /* tuning: 0 (default): in a spill launch of RMU_OPT_SCREEN_SPILL a wave re-reads its queries' shared thresholds only
+                             * while it can use them -- at its first pair of tiles, once its spill list is full, and the wave that paces the
+                             * workgroup; 1: every wave re-reads and refreshes them at every pair of tiles, as before.  Results and re-run
+                             * counts are identical either way (0 is 1.3-1.5 % faster on the 10M x 1024 headline: profiles/screen_refresh.md). */
 
 #define RMU_OPT_COMPACT_INPLACE 5 /* 0 (default): rmu_index_compact moves the rows into fresh, smaller allocations (in place when those do not
                              * fit); 1: always in place, the capacity stays.  Results are identical either way (the tests force the path). */

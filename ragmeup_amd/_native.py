@@ -23,6 +23,7 @@ OPT_COMPACT_INPLACE = 5
 OPT_WIDE_SCAN = 6
 OPT_SCREEN_BAND = 7
 OPT_SCREEN_SPILL, OPT_SCREEN_SPILL_CAP = 8, 9
+OPT_SCREEN_REFRESH = 10
 STAT_CAPACITY, STAT_GROW_COUNT, STAT_GROW_MS, STAT_LIVE_ROWS = 1, 2, 3, 4
 STAT_COMPACT_COUNT, STAT_COMPACT_MS = 5, 6
 COMM_ID_BYTES = 128

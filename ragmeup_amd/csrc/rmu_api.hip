@@ -459,6 +459,8 @@ struct rmu_index {
     bool screen_band = true;        // RMU_OPT_SCREEN_BAND: the ladder's merges also seed the lower edge of the sufficiency band (screen_enqueue)
     bool screen_spill = true;       // RMU_OPT_SCREEN_SPILL: seeded 8-wave launches spill passing lanes, rmu_sift_launch files them (screen_enqueue)
     int spill_cap = 0;              // RMU_OPT_SCREEN_SPILL_CAP: records per spill list (0 = kSpillCap)
+    bool screen_refresh = false;    // RMU_OPT_SCREEN_REFRESH: every wave of a spill launch re-reads and refreshes its thresholds at every pair of tiles
+                                    // (0, the default: only the waves that can use them -- 1.3-1.5 % of the headline: profiles/screen_refresh.md)
     int64_t screen_min_nq = 0;      // RMU_OPT_SCREEN_MIN_NQ: > 0 = screen every batch of at least this many queries, whatever the corpus size
     std::vector<uint8_t> alive;
     std::shared_mutex mu;
@@ -1173,23 +1175,24 @@ static inline int screen_kp(int k) {
 }
 
 static u64* g_dbg = nullptr;         // RMU_SCAN_EXP=7: cycle / event counters of the scan kernels (diagnostics only)
+static constexpr int kDbgWords = 17;   // (the kernels' counters: ScanLaunch::dbg)
 static u64* dbg_buffer() {
 #ifndef RMU_DEBUG_KERNELS
     return nullptr;          // the counter instantiations exist only in a --debug-kernels build
 #endif
     static std::once_flag once;
     std::call_once(once, [] {
-        if (rmu_env("RMU_SCAN_EXP") && atoi(rmu_env("RMU_SCAN_EXP")) == 7) (void)hipMalloc((void**)&g_dbg, 128);
+        if (rmu_env("RMU_SCAN_EXP") && atoi(rmu_env("RMU_SCAN_EXP")) == 7) (void)hipMalloc((void**)&g_dbg, kDbgWords * sizeof(u64));
     });
     return g_dbg;
 }
 static void dbg_dump(const char* what, int64_t rows, hipStream_t s) {
-    u64 h[16];
+    u64 h[kDbgWords];
     (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h, g_dbg, 128, hipMemcpyDeviceToHost);
-    fprintf(stderr, "[rmu dbg %s: %lld rows] slow_tiles=%llu compactions=%llu appends=%llu wave_tiles=%llu spill_tiles=%llu clk_slow=%llu clk_bar=%llu clk_all=%llu clk_vmwait=%llu seg=%llu/%llu/%llu/%llu/%llu/%llu/%llu\n",
-            what, (long long)rows, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15]);
-    (void)hipMemset(g_dbg, 0, 128);
+    (void)hipMemcpy(h, g_dbg, sizeof(h), hipMemcpyDeviceToHost);
+    fprintf(stderr, "[rmu dbg %s: %lld rows] slow_tiles=%llu compactions=%llu appends=%llu wave_tiles=%llu spill_tiles=%llu clk_slow=%llu clk_bar=%llu clk_all=%llu clk_vmwait=%llu seg=%llu/%llu/%llu/%llu/%llu/%llu/%llu clk_pro=%llu\n",
+            what, (long long)rows, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15], h[16]);
+    (void)hipMemset(g_dbg, 0, sizeof(h));
 }
 
 // row ranges of the threshold ladder over n rows (see the comment in screen_enqueue)
@@ -1223,10 +1226,10 @@ static std::vector<int64_t> ladder_bounds(int64_t n, int64_t nb, int opt_ratio =
     // fragments, emit, merge) while a seeded level's appends are cheap -- the ratio with the FEWEST levels wins there (ties: the smaller ratio).
     // tools/ladder_sweep.py, same box, step ms at ratio 3 / 4 / 8: 1M x 1024 0.970 / 1.004 / 0.949, x 512 0.632 / 0.643 / 0.604, x 256 0.434 / 0.445 / 0.402;
     // 1.25M x 1024 1.169 / 1.144 / 1.161, x 512 0.762 / 0.727 / 0.729, x 256 0.530 / 0.488 / 0.495; 2.5M x 1024 at 3 / 5: 1.97 / 1.92, x 256 0.699 / 0.670;
-    // 4.5M x 1024 at 3 / 6: 3.30 / 3.25, x 256 1.092 / 1.022; but 10M x 1024 6.71 / 6.77 / 6.78 at 3 / 4 / 8 (ratio 6: 6.77): there the appends of a
-    // wider level cost more than the level it saves, and the ratio stays 3.
-    // (These sweeps predate band seeding -- RMU_OPT_SCREEN_BAND: a seeded level appends about a third of what it did -- and have not been
-    // re-run with it; cheaper appends favour fewer levels, so the 10M figure is the one to re-measure first.)
+    // 4.5M x 1024 at 3 / 6: 3.30 / 3.25, x 256 1.092 / 1.022.  (Those sweeps predate band seeding and the spill path.)
+    // 10M x 1024 with band and spill on (profiles/screen_refresh.md 5; one process, the ratios in turn): ratio 3 6.372 / 6.362 / 6.348 / 6.359
+    // (mean 6.360, spread 0.024), ratio 4 6.304 / 6.376 / 6.358 (6.346), ratio 6 6.324 / 6.371 / 6.379 (6.358), ratio 8 6.359 / 6.383 / 6.382
+    // (6.375): no ratio beats 3 by twice the spread of its own legs, with one level fewer or not, and the ratio stays 3.
     std::vector<int64_t> best = build(3);
     if (n < 6000000)
         for (int r : {4, 5, 6, 8}) {
@@ -1339,6 +1342,7 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
         S.gcand = (u64*)t.gcand.p;
         const bool spill = spill_lists != 0 && l > 0 && S.wq == 8;
         if (spill) { S.spill = (char*)t.spill.p; S.spill_cnt = (u32*)t.spill_cnt.p; S.spill_cap = spill_cap; }
+        if (spill && idx->screen_refresh) S.share_thr |= 8;     // RMU_OPT_SCREEN_REFRESH = 1: no wave of the launch drops its refresh (scan_screen.hip "Refresh")
         if (timed) HIP_TRY(hipEventRecord(t.lev[(size_t)(2 * l)], s));
         rc = rmu_screen_launch(&S, s);
         if (rc) return fail(rc, "rmu_index_search: screening launch");
@@ -1815,6 +1819,7 @@ extern "C" int rmu_index_set_option(rmu_index_t* idx, int option, int64_t value)
         case RMU_OPT_SCREEN_BAND: idx->screen_band = value != 0; return RMU_OK;
         case RMU_OPT_SCREEN_SPILL: idx->screen_spill = value != 0; return RMU_OK;
         case RMU_OPT_SCREEN_SPILL_CAP: idx->spill_cap = value > 0 && value <= 4096 ? (int)value : 0; return RMU_OK;
+        case RMU_OPT_SCREEN_REFRESH: idx->screen_refresh = value != 0; return RMU_OK;
         case RMU_OPT_COMPACT_INPLACE: idx->compact_inplace = value != 0; return RMU_OK;
         case RMU_OPT_WIDE_SCAN:
             if (idx->metric == RMU_METRIC_L2SQ) return fail(RMU_E_INVALID, "rmu_index_set_option: RMU_OPT_WIDE_SCAN serves RMU_METRIC_IP / RMU_METRIC_COSINE indexes only");

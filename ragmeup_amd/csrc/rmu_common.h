@@ -174,10 +174,12 @@ struct ScanLaunch {
     int k;
     u64* partial;          // [parts, nq, k] keys
     int share_thr;         // bit 0 = read the shared thresholds (0: publish only; debugging aid); bit 1 = no filter (timing ablation); bit 2 (screening scan) =
-                           // emit slots of <= k entries unsorted (the launch's merge must be told: rmu_merge_to_keys_launch(..., unsorted = 1))
+                           // emit slots of <= k entries unsorted (the launch's merge must be told: rmu_merge_to_keys_launch(..., unsorted = 1));
+                           // bit 3 (screening scan, spill launches) = every wave re-reads and refreshes its thresholds at every pair of tiles
+                           // (RMU_OPT_SCREEN_REFRESH = 1; 0: only the waves that can use them -- scan_screen.hip "Refresh")
     u32* gthr;             // [nq] shared per-query threshold (order-preserving u32 image, 0 = none), zeroed per launch
     int parts;             // filled by the planner
-    u64* dbg;              // optional debug counters (nullptr in production): [0] slow tiles, [1] compactions, [2] appends, [3] tiles
+    u64* dbg;              // optional debug counters (nullptr in production): [0] slow tiles, [1] compactions, [2] appends, [3] tiles ... [16] pair prologue cycles
     // filled by rmu_scan_plan
     int wq, kv, s_chunks, nqt, tiles_per_chunk, grid, lds_bytes;
     int qg;                // screening scan only: 32-query groups per wave, always 1 (rmu_screen_plan)

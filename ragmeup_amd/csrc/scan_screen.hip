@@ -52,6 +52,20 @@
 // A list holds spill_cap records; a wave whose list cannot take a tile's records takes slow_path for that tile and every later one, its
 // slots are emitted as before and the sift folds that part list in (RMU_SPILL_FELL in the wave's count word).  The cold first launch, its
 // direct path, its raw emit and the unsorted merge are untouched, and so are the 4-wave kernels.
+// Refresh (RMU_OPT_SCREEN_REFRESH; spill launches only): at the start of every pair of tiles a wave used to read its queries' words from LDS (a
+// load hipcc can see: its use waits lgkmcnt(0) and drains the four prefetched fragments right behind the ring barrier), raise thr_s, share it
+// between the lane halves, and at step 4 issue the 4-byte LDS-DMA that fetches the words again.  A spilling wave cannot use any of it: the word
+// is the one the last sift or merge published, only a compaction raises it, only a wave that fell back compacts, and the argument above never
+// needed a wave to see a raise -- a wave that filters with an older, lower word spills a superset, the sift tests against the word as it stands
+// after the launch, the merged keys and the next seeds are the same bits.  So a wave does that work only while `thr_live` holds: the launch is
+// no spill launch, the wave has fallen back (it compacts and appends again: shared thresholds matter again; until its next DMA lands it reads
+// the words of its first refresh -- older, lower, safe), it is at its first pair (the seeds arrive through this very path), it is the pacing
+// wave (its DMA carries the siblings' progress words), or option 10 asks for it (ScanLaunch::share_thr bit 3: every wave, every pair, as it
+// always was).  Dropping refreshes from a wave's VMEM stream only makes the ring's counted waits cover more.  Measured (profiles/
+// screen_refresh.md): the pair prologue 350 -> 162 cycles per wave and pair in the debug build, the headline -0.08 .. -0.10 ms (1.3-1.5 %) in
+// eight interleaved pairs of two records -- twice the span of the parent's legs in one record, short of it in the other; a third of what the
+// prologue gives back is spent waiting at the pair barrier.  With option 10 = 1 this kernel is 0.9 % SLOWER than the one that had no branch
+// there (the two scalar branches and what they do to the schedule around the barrier), so the default is 0.
 // (An earlier hi/lo split variant, 3 MFMAs per 16 k with EPS = 1e-4, ran at 25 ms for the 10M x 1024 headline; its
 // ablations showed the LDS/L2 path, not the MFMA pipe, setting the time, which is what halving the bytes attacks.)
 #include <cstdlib>
@@ -257,7 +271,11 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
     bool pace_live = pace_on;
     const u32* gsrc = gthr_w + (lane & 31);              // (LDS word l comes from lane l: word jj is query jj's threshold in either lane mapping)
     if (pace_on && lane >= 32 && lane < 36) gsrc = prog_w + (lane - 32);
+    // (uniform) this wave still reads and refreshes its thresholds at every pair: see "Refresh" in the file header.  Set where a pair starts
+    // (NWV = 8 only: the 4-wave kernels never assign it and compile as they did); the prologue's refresh carries the launch's seeds.
+    int thr_live = 1;       // (an int: as a second bool beside pace_live the two end up in scratch, their stores sunk into one through a pointer)
     auto refresh_gthr = [&]() {
+        if (!thr_live) return;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                          (__attribute__((address_space(3))) void*)(ssm + C::GT_OFF + w * 256), 4, 0, 16);
     };
@@ -383,7 +401,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
                      : "v"(ad), "n"(o), "n"(o + 32), "n"(o + 64), "n"(o + 96));
     };
     u32 d_slow = 0, d_comp = 0, d_app = 0;
-    unsigned long long d_clk_slow = 0, d_clk_bar = 0, d_clk_vm = 0, d_clk_all = DBG ? clock64() : 0;
+    unsigned long long d_clk_slow = 0, d_clk_bar = 0, d_clk_vm = 0, d_clk_pro = 0, d_clk_all = DBG ? clock64() : 0;
     // keep the best K' of query lane jj's slot (sorted), raise its threshold, publish it.  Every VMEM operation of compact and slow_path is
     // inline asm: one the compiler can see puts an s_waitcnt vmcnt(0) in front of the tile loop's first MFMA -- the join of this path -- and
     // drains the DMA ring once per tile.
@@ -560,6 +578,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
         // one tile; P = its position in the six-tile ring (compile time): its chunks sit in slots 2P and 2P + 1
         auto tile_body = [&](auto PI, f32x16& acc, const f32x16& prev, int tl) {
             constexpr int P = decltype(PI)::value;
+            unsigned long long cp = 0;                     // (debug counters) the pair barrier's release: d_clk_pro runs from here to step 0's wait
             if (P % 2 == 0) {                              // a pair of tiles starts
                 unsigned long long cb = 0;
                 if (DBG) cb = clock64();
@@ -567,10 +586,17 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::NIW) : "memory");
                 if (DBG) { const unsigned long long cv = clock64(); d_clk_vm += cv - cb; cb = cv; }
                 __builtin_amdgcn_s_barrier();              // tiles up to tl + 2 have landed; nobody reads the previous pair any more
-                if (DBG) d_clk_bar += clock64() - cb;
-                const u32 go = gt_lds[j];
-                if (go && (a.share_thr & 1)) thr_s = fmaxf(thr_s, rmu_ord2f(go - 1u) * 4096.0f);
-                share_thr16();
+                if (DBG) { cp = clock64(); d_clk_bar += cp - cb; }
+                // A spill launch's thresholds are the words its seeds left: only a compaction raises one, only a wave that fell back compacts,
+                // and the sift tests every spilled score against the final word.  Such a wave re-reads nothing from its second pair on (the
+                // pacing wave goes on: its refresh carries the siblings' progress words).  A wave that falls back reads again from its next
+                // pair on -- until its next refresh lands, the words of its first one: older, lower, a superset passes.
+                if constexpr (M16) thr_live = (!sp_live || tl == 0 || (a.share_thr & 8) != 0 || (w == PW && pace_live)) ? 1 : 0;
+                if (thr_live) {
+                    const u32 go = gt_lds[j];
+                    if (go && (a.share_thr & 1)) thr_s = fmaxf(thr_s, rmu_ord2f(go - 1u) * 4096.0f);
+                    share_thr16();
+                }
                 if (w == PW && pace_live) pace_step(tl);
             }
             // (Measured per wave: waves 0-3 wait ~600 cycles per tile at the pair barrier, waves 4-7 ~75 -- issue arbitration between the two waves
@@ -592,6 +618,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
                 }
                 if (L2N && gs >= 13 && gs <= 16) frag_wait_nrm(fr[gs % S_PRE]);
                 else frag_wait(fr[gs % S_PRE]);
+                if (DBG && gs == 0 && P % 2 == 0) d_clk_pro += clock64() - cp;   // the pair prologue: threshold read, update, share, pacing
                 f32x4 c0, c1;
                 if (sk == 0) {
                     c0 = L2N ? zq[tt] : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -751,6 +778,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
             atomicAdd((unsigned long long*)a.dbg + 8, d_clk_vm);
             if (w < 7) atomicAdd((unsigned long long*)a.dbg + 9 + w, d_clk_bar);     // barrier wait of waves 0..6 ("seg" + following words in the dump)
             atomicAdd((unsigned long long*)a.dbg + 7, (unsigned long long)(clock64() - d_clk_all));
+            atomicAdd((unsigned long long*)a.dbg + 16, d_clk_pro);                   // pair prologue: barrier release -> step 0's fragment wait
         }
     }
     // ---- emit: best K' approximate candidates of this (chunk, query), sorted.  All 32 slots (DEEP: 8 at a time) are read back in ONE round trip (the query fragments are dead: registers are free).

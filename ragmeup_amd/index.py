@@ -300,6 +300,11 @@ class FlatIndex:
         N.check(self._lib.rmu_index_set_option(self._h, N.OPT_SCREEN_SPILL, 1 if on else 0), "rmu_index_set_option")
         N.check(self._lib.rmu_index_set_option(self._h, N.OPT_SCREEN_SPILL_CAP, int(cap)), "rmu_index_set_option")
 
+    def set_screen_refresh(self, on: bool = False):
+        """Tuning (RMU_OPT_SCREEN_REFRESH): in a spill launch only the waves that can use their queries' shared thresholds re-read them
+        (default), or every wave re-reads and refreshes them at every pair of tiles.  Results and re-run counts are identical either way."""
+        N.check(self._lib.rmu_index_set_option(self._h, N.OPT_SCREEN_REFRESH, 1 if on else 0), "rmu_index_set_option")
+
     def screen_candidates(self, q):
         """Test hook (rmu_index_screen_candidates): per query the screening pass's 32 candidates ->
         (approx scores [nq,32], rows [nq,32], exact fp32 scores of the same rows [nq,32], EPS [nq])."""

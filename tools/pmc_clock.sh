@@ -1,5 +1,6 @@
 #!/bin/bash
 # clock and MFMA-busy of the screening kernel, one PMC pass (run on the GPU box): bash tools/pmc_clock.sh <outdir>
+# (counters only, no tracing beside them: the counter table carries each dispatch's timestamps; RMU_LIB=<another build> in the environment is honoured)
 # the longest launches: duration, GRBM_GUI_ACTIVE (summed over 8 XCDs) / 8 / duration = the clock the kernel got, MFMA busy cycles / (GUI_ACTIVE / 8 x 1024 SIMDs)
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -8,7 +9,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run() {  # name
   name=$1
-  env RMU_TUNING=1 timeout 240 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-include-regex "scan_screen" \
+  env RMU_TUNING=1 timeout -k 10 240 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-include-regex "scan_screen" \
       --output-format csv -d $OUT/$name -o a -- python $R/tools/pace_probe.py --env RMU_X --pace 0 --steps 3 > $OUT/$name.txt 2>&1
   f=$(find $OUT/$name -name "*counter_collection.csv" | head -1)
   python3 - "$f" "$name" <<'PY' | tee -a $OUT/summary.txt
