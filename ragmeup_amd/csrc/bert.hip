@@ -19,6 +19,7 @@
 // LDS-DMA (global_load_lds_dwordx4) with the XOR swizzle applied to the per-lane SOURCE address (the DMA writes lane-linear) or
 // baked into a tiled copy of the operand.  In the GEMMs the operands are swapped (D^T = W . A^T) so that a lane ends up with
 // consecutive output features of one token.
+// Which of these a call runs is decided in bert_plan.h (thresholds, the RMU_* switches, enc_plan); enqueue_forward below launches the plan.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,6 +33,8 @@
 
 #include "rmu_common.h"
 #include "../../include/rmu.h"
+#include "bert_plan.h"
+#include "rmu_internal.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -588,13 +591,7 @@ __global__ __launch_bounds__(128 * WM) void k_gemm(const bf16* __restrict__ A, c
 // sit in registers as MFMA A fragments (K/64 of them), token fragments come straight from global memory (no LDS staging), the
 // four partial sums meet in LDS and all 256 threads run the epilogue (bias | + GELU | + residual).
 // ------------------------------------------------------------------------------------------------------------
-constexpr int SMALL_M = 256;                           // tokens (upper bound batch * max_len) below which launch_gemm's callers take k_gemm_small
-// ... and up to which QKV projection + attention are one launch (k_qkv_attn_small).  tools/small_ab.sh, one box, every output bit-identical:
-// a 16-token query forward 0.182 ms fused / 0.183 apart (no gain: inside a replayed graph a kernel boundary is not the 4.4 us it costs under
-// the profiler, a kernel's own load -> MFMA -> store chain is), the 14-pair rerank forward (1.5k tokens) 0.417 fused / 0.437 apart: the
-// whole folded path takes it.
-constexpr int QKV_ATTN_TOKENS = 2560, QKV_ATTN_MIN_TOKENS = 128;
-constexpr int FOLD_TOKENS = 2560;                      // ... and up to which a whole forward runs on it with the LayerNorms folded (enqueue_forward)
+// (Up to how many tokens it is taken -- SMALL_M, QKV_ATTN_TOKENS, FOLD_TOKENS -- and the measurements behind them: bert_plan.h.)
 // Round 4: the token dimension is a grid dimension too -- workgroup (x, y) takes features [32 x, +32) of tokens [SMALL_TB y, +SMALL_TB)
 // -- so the same kernel serves a few THOUSAND tokens (the reference's rerank call: <= 14 (query, passage) pairs, ~1.5k tokens,
 // twice per /chat request): the tiled kernels run 6-36 workgroups there (10-17 us per launch), this one N/32 x M/128 short ones.
@@ -2902,7 +2899,13 @@ struct rmu_bert {
     // small-batch host path (rmu_bert_encode_host): one captured graph per (batch, max_len, mode, token types) shape -- H2D of the
     // ids, the ~45 launches of a forward, D2H of the result -- replayed with ONE hipGraphLaunch.  All addresses inside are
     // the fixed staging buffers below, so a replay needs no node updates.
-    struct SmallGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; bool warm = false; bool no_graph = false; uint64_t last_use = 0; };
+    struct SmallGraph {
+        hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; bool warm = false; bool no_graph = false; uint64_t last_use = 0;
+        void destroy() {
+            if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
+            if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
+        }
+    };
     std::map<uint64_t, SmallGraph> graphs;
     uint64_t graph_clock = 0;                      // bumps per host call: the least recently used graph goes when the cache is full
     int32_t *h_in = nullptr, *d_in = nullptr;      // [ids | type ids | lens], pinned host / device
@@ -2922,11 +2925,8 @@ struct rmu_bert {
     bool tail_set = false;
 };
 static constexpr size_t MAX_CLONES = 3;
-// rmu_bert_encode_host / rmu_bert_search_mmr carry up to HOST_TOKENS tokens (batch * max_len): one query, or the <= 14 (query, passage)
-// pairs of one rerank call (server/ScoredCrossEncoderReranker.py:42) -- staging: ids | type ids | lens; results: <= 256 rows of 384
-// floats (pooled vectors / the token states of a 256-token call) or one logit per sequence
-static constexpr int HOST_TOKENS = 4096;
-static constexpr int SMALL_IN_INTS = 3 * HOST_TOKENS, SMALL_OUT_FLOATS = 256 * 384 > HOST_TOKENS ? 256 * 384 : HOST_TOKENS;
+// the host path's staging (HOST_TOKENS, HOST_ROWS: bert_plan.h): ids | type ids | lens; results: HOST_ROWS rows of 384 floats or one logit per sequence
+static constexpr int SMALL_IN_INTS = 3 * HOST_TOKENS, SMALL_OUT_FLOATS = HOST_ROWS * H > HOST_TOKENS ? HOST_ROWS * H : HOST_TOKENS;
 static constexpr size_t MAX_GRAPHS = 64;
 
 extern "C" void rmu_set_error_(const char* msg);   // rmu_api.hip: thread-local message behind rmu_last_error()
@@ -2959,6 +2959,18 @@ static int conv_bf16(bf16* dst, const void* src, size_t n, float scale, hipStrea
 }
 
 static void quiesce(rmu_bert* m);
+static void drop_graphs(rmu_bert* m) {       // the captured launches hold workspace addresses
+    for (auto& kv : m->graphs) kv.second.destroy();
+    m->graphs.clear();
+}
+// the token-sized half of the workspace (ensure_ws; the caller has quiesced the context)
+static void free_token_ws(rmu_bert* m) {
+    for (void* p : {(void*)m->h, (void*)m->h1, (void*)m->y, (void*)m->qkv, (void*)m->ctx, (void*)m->mid, (void*)m->st1, (void*)m->st2})
+        if (p) (void)hipFree(p);
+    m->h = m->h1 = m->y = m->qkv = m->ctx = m->mid = nullptr;
+    m->st1 = m->st2 = nullptr;
+    m->ws_tokens = 0;
+}
 extern "C" int rmu_bert_free(rmu_bert_t* m) {
     RMU_ENTRY();
     if (!m) return RMU_OK;
@@ -2966,12 +2978,10 @@ extern "C" int rmu_bert_free(rmu_bert_t* m) {
     for (rmu_bert* c : m->clones) (void)rmu_bert_free(c);      // (their `owned` lists are empty: workspaces, staging, graphs, stream)
     m->clones.clear();
     for (void* p : m->owned) (void)hipFree(p);
-    for (void* p : {(void*)m->h, (void*)m->h1, (void*)m->y, (void*)m->qkv, (void*)m->ctx, (void*)m->mid, (void*)m->cu, (void*)m->qa_items, (void*)m->st1, (void*)m->st2})
-        if (p) (void)hipFree(p);
-    for (auto& kv : m->graphs) {
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-    }
+    free_token_ws(m);
+    if (m->cu) (void)hipFree(m->cu);
+    if (m->qa_items) (void)hipFree(m->qa_items);
+    drop_graphs(m);
     if (m->h_in) (void)hipHostFree(m->h_in);
     if (m->h_out) (void)hipHostFree(m->h_out);
     if (m->d_in) (void)hipFree(m->d_in);
@@ -3126,25 +3136,11 @@ static rmu_bert* acquire_ctx(rmu_bert* m, std::unique_lock<std::mutex>& lk) {
     return m;
 }
 
-static void drop_graphs(rmu_bert* m) {       // the captured launches hold workspace addresses
-    for (auto& kv : m->graphs) {
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-    }
-    m->graphs.clear();
-}
-
 static int ensure_ws(rmu_bert* m, int64_t tokens, int batch) {
     if (tokens > m->ws_tokens || batch + 1 > m->ws_batch) drop_graphs(m);
     if (tokens > m->ws_tokens) {
-        if (m->h) {                                   // (a fresh context -- a clone's first call -- has nothing in flight and nothing to free)
-            quiesce(m);                               // the workspace's only users: this context's stream and the forward marked by its tail event
-            for (void* p : {(void*)m->h, (void*)m->h1, (void*)m->y, (void*)m->qkv, (void*)m->ctx, (void*)m->mid, (void*)m->st1, (void*)m->st2})
-                if (p) (void)hipFree(p);
-        }
-        m->h = m->h1 = m->y = m->qkv = m->ctx = m->mid = nullptr;
-        m->st1 = m->st2 = nullptr;
-        m->ws_tokens = 0;
+        if (m->h) quiesce(m);                         // the workspace's only users: this context's stream and the forward marked by its tail event
+        free_token_ws(m);                             // (a fresh context -- a clone's first call -- has nothing in flight and nothing to free)
         const int64_t t = tokens + tokens / 8 + 512;       // (+ a whole 256-token tile: the tiled out-proj operand is read in full blocks)
         if (hipMalloc((void**)&m->h, t * H * 2) != hipSuccess || hipMalloc((void**)&m->h1, t * H * 2) != hipSuccess ||
             hipMalloc((void**)&m->y, t * H * 2) != hipSuccess || hipMalloc((void**)&m->qkv, t * 3 * H * 2) != hipSuccess ||
@@ -3186,47 +3182,52 @@ static void launch_gemm_cfg(const bf16* A, const bf16* W, const float* bias, con
 #endif
     hipLaunchKernelGGL((k_gemm<EPI, WM, BK, ST, TA>), grid, dim3(128 * WM), lds, s, A, W, bias, resid, out, cu, batch, N, K, dbg | (resid_tiled ? 256 : 0));
 }
-// Tokens (batch * max_len) up to which all four GEMMs of a layer take k_gemm_small, and from which the QKV projection takes the
-// persistent k_gemm3.  Round 4 measured the rerank shape (14 pairs, ~1.5k tokens, tools/ce_probe.py) with k_gemm_small over token blocks
-// of 32 / 64 / 128 up to 4k-64k tokens and with deeper / smaller tiled configurations (128x128 x 3-4 stages, 64x128 x 4-6): nothing beat
-// the round-3 choice (0.48-0.50 ms per call either way; every launch there is 5-15 us of latency, not of work), so the thresholds stay.
-// (The deeper / smaller configurations were selectable once, RMU_GEMM_CFG, and are retired.)  Debug builds keep the threshold knobs:
-// RMU_MID_TOKENS, RMU_SMALL_TB, RMU_G3_MIN.
-static int64_t mid_tokens() {
+// The RMU_* switches of the forward, read once per process (defaults, meanings and the debug-build threshold knobs: bert_plan.h)
+const EncSwitches& enc_switches() {
+    static const EncSwitches sw = [] {
+        auto on = [](const char* name) { return !(rmu_env(name) && atoi(rmu_env(name)) == 0); };
+        auto num = [](const char* name, int64_t dflt) { return rmu_env(name) ? (int64_t)atoll(rmu_env(name)) : dflt; };
+        EncSwitches v;
+        v.small_fuse = on("RMU_SMALL_FUSE");
+        v.embed_seq = on("RMU_EMBED_SEQ");
+        v.gemm_small = on("RMU_GEMM_SMALL");
+        v.ln_fuse = on("RMU_LN_FUSE");
+        v.fold_tokens = num("RMU_FOLD_TOKENS", v.fold_tokens);
+        v.qkv_attn_tokens = num("RMU_QKV_ATTN_TOKENS", v.qkv_attn_tokens);
+        v.qkv_attn_min = num("RMU_QKV_ATTN_MIN", v.qkv_attn_min);
+        v.qa = num("RMU_QA", 0) != 0;
+        v.gemm3 = (int)num("RMU_GEMM3", v.gemm3);
+        v.qkv_hm = on("RMU_QKV_HM");
+        v.ctx_tiled = on("RMU_CTX_TILED");
+        v.fused_ffn = (int)num("RMU_FUSED_FFN", v.fused_ffn);
+        v.ffn_v = num("RMU_FFN_V", 3) == 2 ? 2 : 3;
+        v.ffn_lnin = on("RMU_FFN_LNIN");
+        v.h_tiled = on("RMU_H_TILED");
+        v.ffn_gelu = (int)num("RMU_FFN_GELU", v.ffn_gelu);
+        v.ffn_pf = (int)num("RMU_FFN_PF", v.ffn_pf);
+        v.qa_dbg = (int)num("RMU_QA_DBG", v.qa_dbg);
 #ifdef RMU_DEBUG_KERNELS
-    const int64_t v = rmu_env("RMU_MID_TOKENS") ? atoll(rmu_env("RMU_MID_TOKENS")) : SMALL_M;
-    return v < SMALL_M ? SMALL_M : v;
-#else
-    return SMALL_M;
+        v.mid_tokens = std::max<int64_t>(num("RMU_MID_TOKENS", SMALL_M), SMALL_M);
+        v.g3_min = std::max<int64_t>(num("RMU_G3_MIN", 0), v.mid_tokens);
+        v.small_tb = (int)num("RMU_SMALL_TB", 128) / 32 * 32;
 #endif
+        return v;
+    }();
+    return sw;
 }
-static int64_t g3_min_tokens() {
-#ifdef RMU_DEBUG_KERNELS
-    const int64_t v = rmu_env("RMU_G3_MIN") ? atoll(rmu_env("RMU_G3_MIN")) : 0;
-    return v > mid_tokens() ? v : mid_tokens();
-#else
-    return SMALL_M;
-#endif
-}
+
+// one GEMM of the bulk path that is neither k_gemm3's nor a fused kernel's, in the form the plan chose for this cap (EncPlan::gemm)
 template <int EPI>
-static void launch_gemm(const bf16* A, const bf16* W, const float* bias, const bf16* resid, bf16* out, const int* cu,
+static void launch_gemm(EncGemm form, const bf16* A, const bf16* W, const float* bias, const bf16* resid, bf16* out, const int* cu,
                         int batch, int64_t m_cap, int N, int K, hipStream_t s) {
-    static const bool small_ok = !(rmu_env("RMU_GEMM_SMALL") && atoi(rmu_env("RMU_GEMM_SMALL")) == 0);
-    if (small_ok && m_cap <= mid_tokens() && (K == H || K == FF)) {
-#ifdef RMU_DEBUG_KERNELS
-        const int tb = rmu_env("RMU_SMALL_TB") ? atoi(rmu_env("RMU_SMALL_TB")) / 32 * 32 : 128;
-#else
-        const int tb = 128;
-#endif
-        if (K == H) launch_small<EPI, H>(s, m_cap, tb, A, W, bias, resid, out, cu, batch, N);
-        else launch_small<EPI, FF>(s, m_cap, tb, A, W, bias, resid, out, cu, batch, N);
+    switch (form) {
+    case EncGemm::Small:
+        if (K == H) launch_small<EPI, H>(s, m_cap, enc_switches().small_tb, A, W, bias, resid, out, cu, batch, N);
+        else launch_small<EPI, FF>(s, m_cap, enc_switches().small_tb, A, W, bias, resid, out, cu, batch, N);
         return;
+    case EncGemm::T128: return launch_gemm_cfg<EPI, 2, 64, 2>(A, W, bias, resid, out, cu, batch, m_cap, N, K, s);
+    case EncGemm::T256: return launch_gemm_cfg<EPI, 4, 32, 2>(A, W, bias, resid, out, cu, batch, m_cap, N, K, s);
     }
-    // few tiles (latency-bound: every workgroup walks K alone): 128 x 128 tiles in 64-k stages halve the stage count and double
-    // the workgroups -- 4k tokens 0.70 -> 0.60 ms per forward, 16k tokens 1.12 -> 1.07; big batches keep 256 x 128 / 32-k stages
-    // (best of the seven tile / stage / ring combinations measured in round 2)
-    if (m_cap <= 32768) return launch_gemm_cfg<EPI, 2, 64, 2>(A, W, bias, resid, out, cu, batch, m_cap, N, K, s);
-    return launch_gemm_cfg<EPI, 4, 32, 2>(A, W, bias, resid, out, cu, batch, m_cap, N, K, s);
 }
 
 // The cycle-counter / ablation instantiations (k_ffn3<*, *, true>, k_gemm3<*, true>, k_qa<true>: RMU_FFN3_DBG, RMU_G3_DBG, RMU_QA_CLK) exist
@@ -3242,8 +3243,7 @@ static void launch_ffn2_t(const bf16* x, const BertLayer& L, float eps, bf16* ou
 }
 // x = h1 (ln_in false) or the pre-LN out-proj sum y (ln_in true: LN1 happens in the kernel's prologue)
 static void launch_ffn2(const bf16* x, bool ln_in, const BertLayer& L, float eps, bf16* out, const int* cu, int batch, int64_t m_cap, hipStream_t s) {
-    static const int gv = rmu_env("RMU_FFN_GELU") ? atoi(rmu_env("RMU_FFN_GELU")) : 0;   // 1: scalar v_fma_f32 polynomial (A/B measurement)
-    static const int pf = rmu_env("RMU_FFN_PF") ? atoi(rmu_env("RMU_FFN_PF")) : 4;       // 8: eight weight fragments read ahead (A/B measurement)
+    const int gv = enc_switches().ffn_gelu, pf = enc_switches().ffn_pf;      // (both A/B measurements: RMU_FFN_GELU=1, RMU_FFN_PF=8)
     if (pf == 8 && ln_in && !gv) return launch_ffn2_t<true, 0, 8>(x, L, eps, out, cu, batch, m_cap, s);
     if (ln_in) { if (gv) launch_ffn2_t<true, 1, 4>(x, L, eps, out, cu, batch, m_cap, s); else launch_ffn2_t<true, 0, 4>(x, L, eps, out, cu, batch, m_cap, s); }
     else { if (gv) launch_ffn2_t<false, 1, 4>(x, L, eps, out, cu, batch, m_cap, s); else launch_ffn2_t<false, 0, 4>(x, L, eps, out, cu, batch, m_cap, s); }
@@ -3315,7 +3315,7 @@ static void launch_attn3(int batch, const bf16* qkv, const int* cu, bf16* ctx, b
 
 static void launch_qa(int batch, const bf16* x, bool x_tiled, const bf16* wstream, const float* bias, const int* cu, const int2* items, int items_cap,
                       bf16* ctx, bool ctx_tiled, hipStream_t s) {
-    static const int dbg_flags = rmu_env("RMU_QA_DBG") ? atoi(rmu_env("RMU_QA_DBG")) : 0;
+    const int dbg_flags = enc_switches().qa_dbg;
 #ifdef RMU_DEBUG_KERNELS
     static const bool want_clk = rmu_env("RMU_QA_CLK") != nullptr;
     if (want_clk) {          // phase cycle counters (per wave, summed over the grid)
@@ -3365,6 +3365,107 @@ static int check_encode_args(rmu_bert_t* m, const void* ids, const void* lens, c
     return RMU_OK;
 }
 
+static void launch_attn3_kt(int kt, int batch, const bf16* qkv, const int* cu, bf16* ctx, bool ctx_tiled, int64_t hm_stride, hipStream_t s) {
+    if (kt == 4) launch_attn3<4>(batch, qkv, cu, ctx, ctx_tiled, hm_stride, s);
+    else if (kt == 8) launch_attn3<8>(batch, qkv, cu, ctx, ctx_tiled, hm_stride, s);
+    else launch_attn3<16>(batch, qkv, cu, ctx, ctx_tiled, hm_stride, s);
+}
+static void launch_layernorm(const bf16* x, const int* cu, int batch, int64_t cap, const float* g, const float* b, float eps, bf16* out, hipStream_t s) {
+    const dim3 grid((unsigned)((cap + 4 * LN_ROWS - 1) / (4 * LN_ROWS)));
+    hipLaunchKernelGGL(k_layernorm, grid, dim3(256), 0, s, x, cu, batch, g, b, eps, out);
+}
+
+// The layers at the interactive sizes (one query; the <= 14 pairs of a rerank call, ~1.5k tokens; anything up to FOLD_TOKENS): five launches
+// per layer instead of seven -- both LayerNorms are folded into the k_gemm_small launches that consume them (see there): y1 = out-proj +
+// residual lives in m->y, y2 = FFN2 + residual in m->h1, neither is ever normalised in memory; one k_layernorm after the last layer
+// feeds the pooling heads.
+static void forward_small(rmu_bert* m, const EncPlan& plan, int batch, int64_t cap, hipStream_t s) {
+    const float eps = m->cfg.ln_eps;
+    const int* cu = m->cu;
+    bf16 *y1 = m->y, *y2 = m->h1;
+    const BertLayer* prev = nullptr;
+    // MEASURED and retired (NOTES_r01_r05.md 4.5, profiles/r04_ab_interactive.txt): a GEMM with a wave per output tile, both operands as MFMA fragments straight
+    // from global memory, nothing shared -- 14 pairs / 1548 tokens: 0.58 ms per forward against 0.42 with k_gemm_small and 0.47 with the tiled
+    // kernels; per launch 8-28 us: a fragment-shaped load touches 32 cache lines for 1 KiB and the CU's address path is paid per line
+    for (const BertLayer& L : m->layers) {
+        if (plan.qkv == EncQkv::AttnSmall) {
+            if (plan.attn_kt == 4) {
+                if (!prev) launch_qkv_attn_small<4, false>(s, batch, m->h, L.wqkv, L.bqkv, cu, nullptr, nullptr, eps, nullptr, m->ctx);
+                else launch_qkv_attn_small<4, true>(s, batch, y2, L.wqkv, L.bqkv, cu, prev->ln2g, prev->ln2b, eps, m->st2, m->ctx);
+            } else {
+                if (!prev) launch_qkv_attn_small<8, false>(s, batch, m->h, L.wqkv, L.bqkv, cu, nullptr, nullptr, eps, nullptr, m->ctx);
+                else launch_qkv_attn_small<8, true>(s, batch, y2, L.wqkv, L.bqkv, cu, prev->ln2g, prev->ln2b, eps, m->st2, m->ctx);
+            }
+        } else {
+            if (!prev) launch_small<EPI_BIAS, H>(s, cap, plan.tq, m->h, L.wqkv, L.bqkv, nullptr, m->qkv, cu, batch, 3 * H);
+            else launch_small<EPI_BIAS, H, true>(s, cap, plan.tq, y2, L.wqkv, L.bqkv, nullptr, m->qkv, cu, batch, 3 * H, prev->ln2g, prev->ln2b, eps, m->st2);
+            launch_attn3_kt(plan.attn_kt, batch, m->qkv, cu, m->ctx, false, 0, s);
+        }
+        if (!prev) launch_small<EPI_RESID, H>(s, cap, plan.th, m->ctx, L.wo, L.bo, m->h, y1, cu, batch, H);
+        else launch_small<EPI_RESID, H, false, true>(s, cap, plan.th, m->ctx, L.wo, L.bo, y2, y1, cu, batch, H, nullptr, nullptr, eps, nullptr, prev->ln2g, prev->ln2b, m->st2);
+        launch_small<EPI_GELU, H, true>(s, cap, plan.tf, y1, L.w1, L.b1, nullptr, m->mid, cu, batch, FF, L.ln1g, L.ln1b, eps, m->st1);
+        launch_small<EPI_RESID, FF, false, true>(s, cap, plan.th, m->mid, L.w2, L.b2, y1, y2, cu, batch, H, nullptr, nullptr, eps, nullptr, L.ln1g, L.ln1b, m->st1);
+        prev = &L;
+    }
+    // (measured and dropped, round 5: the last LayerNorm inside the pooling launch -- one wave per sequence normalising its rows four at a
+    // time -- made a 16-token query forward SLOWER, 0.182 vs 0.171-0.176 ms: k_layernorm spreads the rows over the chip, the fold serialises them)
+    if (prev) launch_layernorm(y2, cu, batch, cap, prev->ln2g, prev->ln2b, eps, m->h, s);
+}
+
+// The layers above that: QKV projection, attention, out-proj + residual, FFN, each in the form the plan names.
+// The round-1/2 kernels (RMU_ATTN_V=1, RMU_FFN_V=1) are retired, their A/B numbers are in NOTES_r01_r05.md 4.3; the library carries the kernels
+// it takes by default plus k_ffn2 (RMU_FFN_V=2) and k_qa (RMU_QA=1).
+static void forward_bulk(rmu_bert* m, const EncPlan& plan, int batch, int64_t cap, hipStream_t s) {
+    const float eps = m->cfg.ln_eps;
+    const int* cu = m->cu;
+    const EncQkv qkv = plan.qkv == EncQkv::Qa && !m->qa_items ? EncQkv::Gemm3 : plan.qkv;       // (k_qa needs its work list)
+    const int64_t hm_stride = plan.qkv_head_major ? m->ws_tokens : 0;     // between (part, head) planes: the workspace's token capacity
+    if (qkv == EncQkv::Qa)
+        hipLaunchKernelGGL(k_qa_items, dim3(1), dim3(1024), 0, s, cu, batch, m->qa_items, (int*)(m->qa_items + m->ws_batch));
+    size_t li = 0;
+    bool h_in_tiled = false;                   // m->h as this layer reads it: row-major from k_embed_ln, tiled from a k_ffn3 that was told so
+    for (const BertLayer& L : m->layers) {
+        ++li;
+        const bool h_out_tiled = plan.h_tiled && li < m->layers.size();         // (the last layer writes row-major for the pooling heads)
+        // MEASURED and retired (NOTES_r01_r05.md 4.5, profiles/r04_ab_encoder.txt): k_attn3 made PERSISTENT, a workgroup walking a static list of (sequence, head)
+        // items with the next item's pieces prefetched -- SLOWER in every variant: 8192 chunks, per layer under rocprofv3 k_attn3 837-851 us,
+        // the persistent form 1372-1384 us (2 workgroups per CU), 1244 us with an L2 touch of the next item and k_attn3's occupancy; bench.py's
+        // embed leg 33.8-34.0 ms vs 35.7-36.2.  The hardware dispatcher already overlaps one workgroup's cold start with three others'
+        // arithmetic AND balances the 16..256-token items dynamically; a static item list loses both.
+        if (qkv == EncQkv::Qa) {
+            launch_qa(batch, m->h, h_in_tiled, L.wqkv_s, L.bqkv, cu, m->qa_items, m->ws_batch, m->ctx, plan.ctx_tiled, s);
+        } else {
+            if (qkv == EncQkv::Gemm3) launch_gemm3<EPI_BIAS>(m->h, L.wqkv_t, L.bqkv, nullptr, m->qkv, cu, batch, 3 * H, H, s, h_in_tiled, hm_stride);
+            else launch_gemm<EPI_BIAS>(plan.gemm, m->h, L.wqkv, L.bqkv, nullptr, m->qkv, cu, batch, cap, 3 * H, H, s);
+            launch_attn3_kt(plan.attn_kt, batch, m->qkv, cu, m->ctx, plan.ctx_tiled, hm_stride, s);
+        }
+        switch (plan.out_proj) {
+        case EncOutProj::Gemm3: launch_gemm3<EPI_RESID>(m->ctx, L.wo_t, L.bo, m->h, m->y, cu, batch, H, H, s); break;
+        case EncOutProj::TiledA: launch_gemm_cfg<EPI_RESID, 4, 32, 2, true>(m->ctx, L.wo_t, L.bo, m->h, m->y, cu, batch, cap, H, H, s, h_in_tiled); break;
+        case EncOutProj::Plain: launch_gemm<EPI_RESID>(plan.gemm, m->ctx, L.wo, L.bo, m->h, m->y, cu, batch, cap, H, H, s); break;
+        }
+        // the FFN reads h1 = LN1(y), or y itself where a fused kernel forms h1 in its prologue
+        if (!plan.ffn_ln_in) launch_layernorm(m->y, cu, batch, cap, L.ln1g, L.ln1b, eps, m->h1, s);
+        const bf16* x = plan.ffn_ln_in ? m->y : m->h1;
+        switch (plan.ffn) {
+        case EncFfn::Ffn3: launch_ffn3(x, plan.ffn_ln_in, L, eps, m->h, cu, batch, cap, s, h_out_tiled); break;
+        case EncFfn::Ffn2: launch_ffn2(x, plan.ffn_ln_in, L, eps, m->h, cu, batch, cap, s); break;
+        case EncFfn::Gemm3Pair:
+            launch_gemm3<EPI_GELU>(x, L.w1_t, L.b1, nullptr, m->mid, cu, batch, FF, H, s);
+            launch_gemm3<EPI_RESID>(m->mid, L.w2_t, L.b2, x, m->y, cu, batch, H, FF, s);
+            launch_layernorm(m->y, cu, batch, cap, L.ln2g, L.ln2b, eps, m->h, s);
+            break;
+        case EncFfn::PairLn:
+        case EncFfn::GemmSmall:       // (the small path's name for it; the plan never gives it here)
+            launch_gemm<EPI_GELU>(plan.gemm, x, L.w1, L.b1, nullptr, m->mid, cu, batch, cap, FF, H, s);
+            launch_gemm<EPI_RESID>(plan.gemm, m->mid, L.w2, L.b2, x, m->y, cu, batch, cap, H, FF, s);
+            launch_layernorm(m->y, cu, batch, cap, L.ln2g, L.ln2b, eps, m->h, s);
+            break;
+        }
+        h_in_tiled = h_out_tiled;
+    }
+}
+
 // every launch of one forward on stream s (device pointers; no allocation, no synchronisation: capturable)
 static void enqueue_forward(rmu_bert* m, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch, int max_len, int mode,
                             float* out_dev, int64_t out_stride, hipStream_t s) {
@@ -3372,165 +3473,25 @@ static void enqueue_forward(rmu_bert* m, const int32_t* ids, const int32_t* type
     const bool normalize = !(mode & RMU_BERT_NO_NORMALIZE);
     const int64_t cap = (int64_t)batch * max_len;
     const float eps = m->cfg.ln_eps;
+    const EncPlan plan = enc_plan(batch, max_len, (int)m->layers.size(), enc_switches());
 
-    // (thread 0 folds one partial per thread serially: a block no wider than the batch needs -- 1024 threads cost 12 us for 14 sequences)
-    // (round 5) the interactive sizes: the sequence offsets are built inside k_embed_ln (RMU_SMALL_FUSE=0: the separate k_cu_seqlens launch)
-    static const bool small_fuse = !(rmu_env("RMU_SMALL_FUSE") && atoi(rmu_env("RMU_SMALL_FUSE")) == 0);
-    const bool cu_here = small_fuse && batch <= 256 && cap <= FOLD_TOKENS;
-    if (cu_here) {
+    if (plan.offsets_fused) {
         hipLaunchKernelGGL(k_embed_ln<true>, dim3((unsigned)((cap + 3) / 4)), dim3(256), 0, s, (const int*)ids, (const int*)type_ids,
                            (const int*)nullptr, batch, max_len, m->wemb, m->pemb, m->temb, m->elng, m->elnb, eps, m->cfg.vocab_size,
                            m->cfg.type_vocab, m->h, (const int*)lens, m->cu);
     } else {
+        // (thread 0 folds one partial per thread serially: a block no wider than the batch needs -- 1024 threads cost 12 us for 14 sequences)
         hipLaunchKernelGGL(k_cu_seqlens, dim3(1), dim3(batch <= 64 ? 64 : batch <= 256 ? 256 : 1024), 0, s, (const int*)lens, batch, max_len, m->cu);
-        // bulk batches: a workgroup per sequence (k_embed_ln_seq); RMU_EMBED_SEQ=0: a wave per (sequence, position) slot as before
-        static const bool embed_seq = !(rmu_env("RMU_EMBED_SEQ") && atoi(rmu_env("RMU_EMBED_SEQ")) == 0);
-        if (embed_seq && batch >= 512)
+        if (plan.embed == EncEmbed::Seq)
             hipLaunchKernelGGL(k_embed_ln_seq, dim3((unsigned)batch), dim3(256), 0, s, (const int*)ids, (const int*)type_ids, (const int*)m->cu, batch, max_len,
                                m->wemb, m->pemb, m->temb, m->elng, m->elnb, eps, m->cfg.vocab_size, m->cfg.type_vocab, m->h);
         else
-        hipLaunchKernelGGL(k_embed_ln<false>, dim3((unsigned)((cap + 3) / 4)), dim3(256), 0, s, (const int*)ids, (const int*)type_ids,
-                           (const int*)m->cu, batch, max_len, m->wemb, m->pemb, m->temb, m->elng, m->elnb, eps, m->cfg.vocab_size,
-                           m->cfg.type_vocab, m->h);
+            hipLaunchKernelGGL(k_embed_ln<false>, dim3((unsigned)((cap + 3) / 4)), dim3(256), 0, s, (const int*)ids, (const int*)type_ids,
+                               (const int*)m->cu, batch, max_len, m->wemb, m->pemb, m->temb, m->elng, m->elnb, eps, m->cfg.vocab_size,
+                               m->cfg.type_vocab, m->h);
     }
-    const dim3 ln_grid((unsigned)((cap + 4 * LN_ROWS - 1) / (4 * LN_ROWS)));
-    size_t li = 0;
-    bool h_in_tiled = false;                   // m->h as this layer reads it: row-major from k_embed_ln, tiled from a k_ffn3 that was told so
-    // ---- the interactive sizes (one query; the <= 14 pairs of a rerank call, ~1.5k tokens; anything up to FOLD_TOKENS): five launches per
-    // layer instead of seven -- both LayerNorms are folded into the k_gemm_small launches that consume them (see there): y1 = out-proj +
-    // residual lives in m->y, y2 = FFN2 + residual in m->h1, neither is ever normalised in memory; one k_layernorm after the last layer
-    // feeds the pooling heads.  Token blocks per workgroup: enough of them to fill the chip, few enough to amortise the weight rows a
-    // workgroup keeps in registers (N / 32 feature blocks x cap / tb token blocks ~ 256-512 workgroups).
-    static const bool small_ok_f = !(rmu_env("RMU_GEMM_SMALL") && atoi(rmu_env("RMU_GEMM_SMALL")) == 0);
-    static const bool ln_fuse = !(rmu_env("RMU_LN_FUSE") && atoi(rmu_env("RMU_LN_FUSE")) == 0);
-    // measured (tools/ce_probe.py, cross-encoder forward per call): 14 pairs / 1548 tokens 0.464-0.468 ms on the tiled kernels, 0.412-0.424 here;
-    // 30 pairs / 3360 tokens (cap 4800: above the threshold) 0.50-0.51 tiled vs 0.65 here -- the fold pays up to ~2.5k tokens
-    static const int64_t fold_tokens = rmu_env("RMU_FOLD_TOKENS") ? atoll(rmu_env("RMU_FOLD_TOKENS")) : FOLD_TOKENS;
-    if (cap <= fold_tokens && max_len <= 256 && small_ok_f && ln_fuse) {
-        auto tb_for = [&](int n_feature_blocks) {       // tokens per workgroup: ~384 workgroups in all, a multiple of 32, at least 32
-            const int64_t blocks = std::max<int64_t>(1, 384 / n_feature_blocks);
-            int64_t tb = (cap + blocks - 1) / blocks;
-            tb = (tb + 31) / 32 * 32;
-            return (int)std::min<int64_t>(std::max<int64_t>(tb, 32), 1024);
-        };
-        const int tq = tb_for(3 * H / 32), th = tb_for(H / 32), tf = tb_for(FF / 32);
-        const int* cu = m->cu;
-        bf16 *y1 = m->y, *y2 = m->h1;
-        const BertLayer* prev = nullptr;
-        // MEASURED and retired (NOTES_r01_r05.md 4.5, profiles/r04_ab_interactive.txt): a GEMM with a wave per output tile, both operands as MFMA fragments straight
-        // from global memory, nothing shared -- 14 pairs / 1548 tokens: 0.58 ms per forward against 0.42 with k_gemm_small and 0.47 with the tiled
-        // kernels; per launch 8-28 us: a fragment-shaped load touches 32 cache lines for 1 KiB and the CU's address path is paid per line
-        for (const BertLayer& L : m->layers) {
-            // (round 5) up to QKV_ATTN_TOKENS tokens the QKV projection and the attention are ONE launch
-            // (k_qkv_attn_small: a workgroup per (head, sequence); bit-identical to the pair below); RMU_QKV_ATTN_TOKENS=0 keeps them apart
-            static const int64_t qa_tokens = rmu_env("RMU_QKV_ATTN_TOKENS") ? atoll(rmu_env("RMU_QKV_ATTN_TOKENS")) : QKV_ATTN_TOKENS;
-            // (round 6) ... but not below QKV_ATTN_MIN_TOKENS: one short query (16-48 tokens) runs 2.6-4.5 % faster on the two launches (a
-            // workgroup per (head, sequence) is 12 workgroups for one query), the 14-pair rerank call 3.7 % faster on the fused one
-            // (profiles/r06_ab_interactive.txt).  Bit-identical either way.  RMU_QKV_ATTN_MIN=0: fused from the first token on.
-            static const int64_t qa_min = rmu_env("RMU_QKV_ATTN_MIN") ? atoll(rmu_env("RMU_QKV_ATTN_MIN")) : QKV_ATTN_MIN_TOKENS;
-            if (cap <= qa_tokens && cap > qa_min) {
-                if (max_len <= 128) {
-                    if (!prev) launch_qkv_attn_small<4, false>(s, batch, m->h, L.wqkv, L.bqkv, cu, nullptr, nullptr, eps, nullptr, m->ctx);
-                    else launch_qkv_attn_small<4, true>(s, batch, y2, L.wqkv, L.bqkv, cu, prev->ln2g, prev->ln2b, eps, m->st2, m->ctx);
-                } else {
-                    if (!prev) launch_qkv_attn_small<8, false>(s, batch, m->h, L.wqkv, L.bqkv, cu, nullptr, nullptr, eps, nullptr, m->ctx);
-                    else launch_qkv_attn_small<8, true>(s, batch, y2, L.wqkv, L.bqkv, cu, prev->ln2g, prev->ln2b, eps, m->st2, m->ctx);
-                }
-            } else {
-            if (!prev) launch_small<EPI_BIAS, H>(s, cap, tq, m->h, L.wqkv, L.bqkv, nullptr, m->qkv, cu, batch, 3 * H);
-            else launch_small<EPI_BIAS, H, true>(s, cap, tq, y2, L.wqkv, L.bqkv, nullptr, m->qkv, cu, batch, 3 * H, prev->ln2g, prev->ln2b, eps, m->st2);
-            if (max_len <= 128) launch_attn3<4>(batch, m->qkv, m->cu, m->ctx, false, 0, s);
-            else launch_attn3<8>(batch, m->qkv, m->cu, m->ctx, false, 0, s);
-            }
-            if (!prev) launch_small<EPI_RESID, H>(s, cap, th, m->ctx, L.wo, L.bo, m->h, y1, cu, batch, H);
-            else launch_small<EPI_RESID, H, false, true>(s, cap, th, m->ctx, L.wo, L.bo, y2, y1, cu, batch, H, nullptr, nullptr, eps, nullptr, prev->ln2g, prev->ln2b, m->st2);
-            launch_small<EPI_GELU, H, true>(s, cap, tf, y1, L.w1, L.b1, nullptr, m->mid, cu, batch, FF, L.ln1g, L.ln1b, eps, m->st1);
-            launch_small<EPI_RESID, FF, false, true>(s, cap, th, m->mid, L.w2, L.b2, y1, y2, cu, batch, H, nullptr, nullptr, eps, nullptr, L.ln1g, L.ln1b, m->st1);
-            prev = &L;
-        }
-        // (measured and dropped, round 5: the last LayerNorm inside the pooling launch -- one wave per sequence normalising its rows four at a
-        // time -- made a 16-token query forward SLOWER, 0.182 vs 0.171-0.176 ms: k_layernorm spreads the rows over the chip, the fold serialises them)
-        if (prev) hipLaunchKernelGGL(k_layernorm, ln_grid, dim3(256), 0, s, (const bf16*)y2, (const int*)m->cu, batch, prev->ln2g, prev->ln2b, eps, m->h);
-    } else {
-    // (round 6) RMU_QA=1: QKV projection + attention as ONE launch per layer (k_qa) for sequences up to 256 tokens.  Built, bit-identical to
-    // k_gemm3 + k_attn3 (tests), and NOT the default: 2.31 ms per layer in its lockstep form, 2.99 as a ping-pong of the two wave halves,
-    // against 1.90 for the pair -- at 8 waves per CU (the 96 token-fragment registers) one wave's attention chain takes ~6.6k cycles per
-    // head whatever runs beside it (profiles/r06_qa_fusion.md)
-    static const bool qa_env = rmu_env("RMU_QA") && atoi(rmu_env("RMU_QA")) != 0;
-    static const int g3_mask0 = rmu_env("RMU_GEMM3") ? atoi(rmu_env("RMU_GEMM3")) : 1;
-    const bool qa_on = qa_env && (g3_mask0 & 1) && max_len <= 256 && cap > g3_min_tokens() && batch <= 65536 && m->qa_items != nullptr;
-    if (qa_on)
-        hipLaunchKernelGGL(k_qa_items, dim3(1), dim3(1024), 0, s, (const int*)m->cu, batch, m->qa_items, (int*)(m->qa_items + m->ws_batch));
-    for (const BertLayer& L : m->layers) {
-        ++li;
-        static const int g3_mask = rmu_env("RMU_GEMM3") ? atoi(rmu_env("RMU_GEMM3")) : 1;   // k_gemm3 for: bit 0 QKV (default: 1.22 vs 1.38 ms), bit 1 out-proj (0.67 vs 0.61), bit 2 FFN1 + FFN2 instead of a fused FFN kernel (3.6 vs 3.35)
-        // The round-1/2 kernels (RMU_ATTN_V=1, RMU_FFN_V=1) are retired, their A/B numbers are in NOTES_r01_r05.md 4.3; the library carries the kernels
-        // it takes by default plus k_ffn2 (RMU_FFN_V=2).  attn_v names the one attention form left (k_attn3 / k_qa);
-        // the `attn_v == 3` terms below stay spelled out because tests/test_encoder_regimes_cpu.py reads these lines.
-        constexpr int attn_v = 3;
-        // QKV head-major when k_gemm3 writes it and k_attn3 reads it (RMU_QKV_HM=0: row-major); the stride between (part, head) planes is the
-        // workspace's token capacity
-        static const bool hm_env = !(rmu_env("RMU_QKV_HM") && atoi(rmu_env("RMU_QKV_HM")) == 0);
-        const int64_t hm_stride = (hm_env && (g3_mask & 1) && cap > g3_min_tokens() && attn_v == 3) ? m->ws_tokens : 0;
-        if (qa_on && attn_v == 3) { /* below */ }
-        else if ((g3_mask & 1) && cap > g3_min_tokens()) launch_gemm3<EPI_BIAS>(m->h, L.wqkv_t, L.bqkv, nullptr, m->qkv, m->cu, batch, 3 * H, H, s, h_in_tiled, hm_stride);
-        else launch_gemm<EPI_BIAS>(m->h, L.wqkv, L.bqkv, nullptr, m->qkv, m->cu, batch, cap, 3 * H, H, s);
-        // big batches: k_attn3 writes ctx as the 1-KiB operand blocks the out-proj GEMM's LDS-DMA reads whole (RMU_CTX_TILED=0: row-major)
-        static const bool tiled_env = !(rmu_env("RMU_CTX_TILED") && atoi(rmu_env("RMU_CTX_TILED")) == 0);
-        const bool ctx_tiled = tiled_env && attn_v == 3 && !(g3_mask & 2) && cap > 32768;
-        // MEASURED and retired (NOTES_r01_r05.md 4.5, profiles/r04_ab_encoder.txt): k_attn3 made PERSISTENT, a workgroup walking a static list of (sequence, head)
-        // items with the next item's pieces prefetched -- SLOWER in every variant: 8192 chunks, per layer under rocprofv3 k_attn3 837-851 us,
-        // the persistent form 1372-1384 us (2 workgroups per CU), 1244 us with an L2 touch of the next item and k_attn3's occupancy; bench.py's
-        // embed leg 33.8-34.0 ms vs 35.7-36.2.  The hardware dispatcher already overlaps one workgroup's cold start with three others'
-        // arithmetic AND balances the 16..256-token items dynamically; a static item list loses both.
-        if (qa_on && attn_v == 3) {
-            launch_qa(batch, m->h, h_in_tiled, L.wqkv_s, L.bqkv, m->cu, m->qa_items, m->ws_batch, m->ctx, ctx_tiled, s);
-        } else if (attn_v == 3) {
-            if (max_len <= 128) launch_attn3<4>(batch, m->qkv, m->cu, m->ctx, ctx_tiled, hm_stride, s);
-            else if (max_len <= 256) launch_attn3<8>(batch, m->qkv, m->cu, m->ctx, ctx_tiled, hm_stride, s);
-            else launch_attn3<16>(batch, m->qkv, m->cu, m->ctx, ctx_tiled, hm_stride, s);
-        }
-        if (g3_mask & 2) launch_gemm3<EPI_RESID>(m->ctx, L.wo_t, L.bo, m->h, m->y, m->cu, batch, H, H, s);
-        else if (ctx_tiled) launch_gemm_cfg<EPI_RESID, 4, 32, 2, true>(m->ctx, L.wo_t, L.bo, m->h, m->y, m->cu, batch, cap, H, H, s, h_in_tiled);
-        else launch_gemm<EPI_RESID>(m->ctx, L.wo, L.bo, m->h, m->y, m->cu, batch, cap, H, H, s);
-        // The fused kernels give each 128-token tile to ONE workgroup, which then streams all 2.36 MB of FFN weights through one
-        // CU (~100 us per layer whatever the batch): below ~128 tiles most CUs would idle and the GEMM pair, whose feature tiles
-        // spread over the chip, is faster (measured: 8k tokens 0.82 vs 0.95 ms per forward, one 16-token query 0.44 vs 0.63 ms;
-        // 32k tokens 1.70 vs 1.45).  RMU_FUSED_FFN=0 / 1 forces either path.
-        static const int fused_env = rmu_env("RMU_FUSED_FFN") ? atoi(rmu_env("RMU_FUSED_FFN")) : -1;
-        const bool fused_ffn = !(g3_mask & 4) && (fused_env < 0 ? cap > 16384 : fused_env != 0);
-        // k_ffn3 (default; two waves per SIMD) and k_ffn2 (RMU_FFN_V=2; one) also take LayerNorm 1 into their prologue: the out-proj sum y
-        // goes straight in (RMU_FFN_LNIN=0: separate k_layernorm launch)
-        static const int ffn_v = rmu_env("RMU_FFN_V") && atoi(rmu_env("RMU_FFN_V")) == 2 ? 2 : 3;
-        static const bool ln_in = !(rmu_env("RMU_FFN_LNIN") && atoi(rmu_env("RMU_FFN_LNIN")) == 0);
-        if (fused_ffn && ffn_v >= 2 && ln_in) {
-            // Between layers h travels TILED (1-KiB blocks of 16 tokens x 32 features: the next QKV GEMM's A pieces and the next out-proj's
-            // residual pieces become whole contiguous KiB); the last layer writes row-major for the pooling heads.  RMU_H_TILED=0: never.
-            static const bool h_env = !(rmu_env("RMU_H_TILED") && atoi(rmu_env("RMU_H_TILED")) == 0);
-            const bool h_out_tiled = h_env && ffn_v == 3 && ctx_tiled && (g3_mask & 1) && li < m->layers.size();
-            if (ffn_v == 3) launch_ffn3(m->y, true, L, eps, m->h, m->cu, batch, cap, s, h_out_tiled);
-            else launch_ffn2(m->y, true, L, eps, m->h, m->cu, batch, cap, s);
-            h_in_tiled = h_out_tiled;
-            continue;
-        }
-        h_in_tiled = false;
-        hipLaunchKernelGGL(k_layernorm, ln_grid, dim3(256), 0, s, (const bf16*)m->y, (const int*)m->cu, batch, L.ln1g, L.ln1b, eps, m->h1);
-        if (g3_mask & 4) {
-            launch_gemm3<EPI_GELU>(m->h1, L.w1_t, L.b1, nullptr, m->mid, m->cu, batch, FF, H, s);
-            launch_gemm3<EPI_RESID>(m->mid, L.w2_t, L.b2, m->h1, m->y, m->cu, batch, H, FF, s);
-            hipLaunchKernelGGL(k_layernorm, ln_grid, dim3(256), 0, s, (const bf16*)m->y, (const int*)m->cu, batch, L.ln2g, L.ln2b, eps, m->h);
-            continue;
-        }
-        if (fused_ffn) {          // FFN1 + GELU + FFN2 + residual + LayerNorm in one kernel: the 1536-wide intermediate stays on chip
-            if (ffn_v == 3) launch_ffn3(m->h1, false, L, eps, m->h, m->cu, batch, cap, s);
-            else if (ffn_v == 2) launch_ffn2(m->h1, false, L, eps, m->h, m->cu, batch, cap, s);
-            continue;
-        }
-        launch_gemm<EPI_GELU>(m->h1, L.w1, L.b1, nullptr, m->mid, m->cu, batch, cap, FF, H, s);
-        launch_gemm<EPI_RESID>(m->mid, L.w2, L.b2, m->h1, m->y, m->cu, batch, cap, H, FF, s);
-        hipLaunchKernelGGL(k_layernorm, ln_grid, dim3(256), 0, s, (const bf16*)m->y, (const int*)m->cu, batch, L.ln2g, L.ln2b, eps, m->h);
-    }
-    }
+    if (plan.path == EncPath::Small) forward_small(m, plan, batch, cap, s);
+    else forward_bulk(m, plan, batch, cap, s);
     if (kind == RMU_BERT_POOL_MEAN || kind == RMU_BERT_POOL_CLS)
         hipLaunchKernelGGL(k_pool, dim3((unsigned)batch), dim3(64), 0, s, (const bf16*)m->h, (const int*)m->cu, out_dev, out_stride,
                            kind == RMU_BERT_POOL_CLS ? 1 : 0, normalize ? 1 : 0);
@@ -3539,6 +3500,19 @@ static void enqueue_forward(rmu_bert* m, const int32_t* ids, const int32_t* type
                            out_dev, out_stride);
     else
         hipLaunchKernelGGL(k_cls_head, dim3((unsigned)batch), dim3(512), 0, s, (const bf16*)m->h, (const int*)m->cu, m->wp, m->bp, m->wc, m->bc, out_dev);
+}
+
+// The plan of a call of this shape under the process's switches, for the CPU tests (no HIP call): whole plans of ENC_PLAN_FIELDS int32 each
+// (order: bert_plan.h, at EncPlan) for max_len, max_len + 1, ... as long as another one fits into out[n_out].  Returns the plans written.
+extern "C" int rmu_bert_plan_(int batch, int max_len, int layers, int32_t* out, int n_out) {
+    int n = 0;
+    for (; out && (n + 1) * ENC_PLAN_FIELDS <= n_out; ++n) {
+        const EncPlan p = enc_plan(batch, max_len + n, layers, enc_switches());
+        const int32_t f[ENC_PLAN_FIELDS] = {p.offsets_fused, (int32_t)p.embed, (int32_t)p.path, (int32_t)p.qkv, p.attn_kt, (int32_t)p.gemm, (int32_t)p.out_proj,
+                                            (int32_t)p.ffn, p.ffn_ln_in, p.ctx_tiled, p.h_tiled, p.qkv_head_major, p.tq, p.th, p.tf};
+        memcpy(out + (size_t)n * ENC_PLAN_FIELDS, f, sizeof f);
+    }
+    return n;
 }
 
 extern "C" int rmu_bert_encode(rmu_bert_t* m, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch,
@@ -3584,9 +3558,11 @@ static int host_forward_locked(rmu_bert* m, const int32_t* ids, const int32_t* t
                                const char* who, bool in_dev = false) {
     const int64_t cap = (int64_t)batch * max_len;
     const int kind = mode & 0xff;
-    if (cap > HOST_TOKENS) return bfail(RMU_E_INVALID, std::string(who) + ": batch * max_len must be <= 4096 (use rmu_bert_encode for bulk work)");
-    if (kind != RMU_BERT_CE_LOGIT && (kind == RMU_BERT_TOKENS ? cap : (int64_t)batch) > 256)
-        return bfail(RMU_E_INVALID, std::string(who) + ": at most 256 result rows (pooled vectors, or token states of a <= 256-token call)");
+    if (cap > HOST_TOKENS)
+        return bfail(RMU_E_INVALID, std::string(who) + ": batch * max_len must be <= " + std::to_string(HOST_TOKENS) + " (use rmu_bert_encode for bulk work)");
+    if (kind != RMU_BERT_CE_LOGIT && (kind == RMU_BERT_TOKENS ? cap : (int64_t)batch) > HOST_ROWS)
+        return bfail(RMU_E_INVALID, std::string(who) + ": at most " + std::to_string(HOST_ROWS) + " result rows (pooled vectors, or token states of a <= " +
+                                    std::to_string(HOST_ROWS) + "-token call)");
     int rc = ensure_ws(m, cap, batch);
     if (rc) return bfail(rc, std::string(who) + ": workspace");
     if ((rc = host_staging_locked(m, who))) return rc;
@@ -3615,8 +3591,7 @@ static int host_forward_locked(rmu_bert* m, const int32_t* ids, const int32_t* t
         for (auto it = m->graphs.begin(); it != m->graphs.end(); ++it)
             if (it->second.last_use < victim->second.last_use) victim = it;
         B_TRY(hipStreamSynchronize(s));                                                   // (a replay of it may still be running)
-        if (victim->second.exec) (void)hipGraphExecDestroy(victim->second.exec);
-        if (victim->second.graph) (void)hipGraphDestroy(victim->second.graph);
+        victim->second.destroy();
         m->graphs.erase(victim);
     }
     rmu_bert::SmallGraph& g = m->graphs[key];
@@ -3633,8 +3608,7 @@ static int host_forward_locked(rmu_bert* m, const int32_t* ids, const int32_t* t
             (void)hipStreamEndCapture(s, &junk);
             if (junk) (void)hipGraphDestroy(junk);
         }
-        if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-        if (g.graph) { (void)hipGraphDestroy(g.graph); g.graph = nullptr; }
+        g.destroy();
         g.warm = false;
         g.no_graph = true;
         clear_errors();
@@ -3717,8 +3691,6 @@ extern "C" int rmu_bert_encode_host(rmu_bert_t* m, const int32_t* ids, const int
 // embed_query -> dense top-fetch_k -> maximal_marginal_relevance): the query's token ids in, row ids out.  The forward is the graph
 // replay above; its pooled vector stays on the device and feeds the search + selection enqueued behind it on the same stream
 // (rmu_api.hip), so the vector's round trip to the host, the second synchronisation and a second host call are gone.
-extern "C" int rmu_index_search_mmr_dev_(rmu_index_t* idx, const float* q_dev, int64_t nq, int fetch_k, int k, double lambda_mult, int64_t row_base,
-                                         int64_t* out_rows, float* out_scores, void* hip_stream);
 extern "C" int rmu_bert_search_mmr(rmu_bert_t* m, rmu_index_t* idx, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch,
                                    int max_len, int mode, int fetch_k, int k, double lambda_mult, int64_t row_base, int64_t* out_rows,
                                    float* out_scores, float* out_vecs) {
@@ -3743,9 +3715,6 @@ extern "C" int rmu_bert_search_mmr(rmu_bert_t* m, rmu_index_t* idx, const int32_
 // encode calls, 2 n cosines on the host): the token ids of the answers, queries and contexts of one or more requests in, n scores out.  The forward
 // is the graph replay above; its pooled vectors stay on the device and feed the attribution kernel (provenance.hip) enqueued BEHIND the replay on
 // the same stream -- not inside the capture: the captured graph keeps its single chain.
-extern "C" int rmu_attribution_check_(const char* who, int64_t n, int dim, const int32_t* groups, int n_groups, const double* out_scores, int64_t* total);
-extern "C" int rmu_attribution_dev_(const char* who, const float* x_dev, int64_t n, int dim, int64_t stride, const int32_t* groups, int n_groups,
-                                    int64_t total, double* out_scores, double* out_sims, void* hip_stream);
 extern "C" int rmu_bert_attribute(rmu_bert_t* m, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch, int max_len, int mode,
                                   const int32_t* groups, int n_groups, double* out_scores, double* out_sims, float* out_vecs) {
     RMU_ENTRY();
@@ -3777,11 +3746,6 @@ extern "C" int rmu_bert_attribute(rmu_bert_t* m, const int32_t* ids, const int32
 // The reference's whole retrieval step behind the forward (EnsembleRetriever([bm25, dense_mmr]).invoke, server/RAGHelper.py:497-503): token ids and
 // the query texts in, fused hits out.  The pooled vectors stay on the device and feed rmu_hybrid_search's work (rrf_fuse.hip: BM25 search, dense
 // search + selection, fusion) enqueued behind the forward on the encoder's stream; one synchronisation.
-extern "C" int rmu_hybrid_check_(rmu_hybrid_t* h, rmu_index_t** dense, int64_t nq, const char* query_blob, int64_t bytes, int k_sparse, int fetch_k,
-                                 int k_dense, const double* weights, int c, int k_out, double* out_scores, int64_t* out_ids, int32_t* out_member);
-extern "C" int rmu_hybrid_search_dev_(rmu_hybrid_t* h, const float* q_dev, int64_t nq, const char* query_blob, int64_t bytes, int k_sparse, int fetch_k,
-                                      int k_dense, double lambda_mult, const double* weights, int c, int k_out, double* out_scores, int64_t* out_ids,
-                                      int32_t* out_member, void* hip_stream);
 extern "C" int rmu_bert_search_hybrid(rmu_bert_t* m, rmu_hybrid_t* h, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch,
                                       int max_len, int mode, const char* query_blob, int64_t bytes, int k_sparse, int fetch_k, int k_dense,
                                       double lambda_mult, const double* weights, int c, int k_out, double* out_scores, int64_t* out_ids,
@@ -3815,13 +3779,6 @@ extern "C" int rmu_bert_search_hybrid(rmu_bert_t* m, rmu_hybrid_t* h, const int3
 // straight into the staging layout, the forward -- the graph replay above in its in_dev form up to HOST_TOKENS, the eager launches over the
 // thread's assembly workspace beyond -- and the selection over its logits; the assembly and selection kernels run in front of and behind the
 // replay, not inside the capture (the rmu_bert_attribute pattern).
-extern "C" int rmu_rerank_check_(rmu_passages_t* p, const int32_t* q_tokens, const int32_t* q_lens, int64_t nq, int q_stride, const int64_t* keys,
-                                 int m, int batch_pad, int max_len, int top_n, const void* out_pos, const void* out_scores, void* lock);
-extern "C" int rmu_rerank_workspace_(int batch_pad, int max_len, int32_t** d_in, float** d_logits);
-extern "C" int rmu_rerank_assemble_(rmu_passages_t* p, const int32_t* q_tokens, const int32_t* q_lens, int64_t nq, int q_stride, const int64_t* keys,
-                                    int m, int batch_pad, int max_len, int top_n, int32_t* d_in, void* hip_stream, void* lock);
-extern "C" int rmu_rerank_select_(const float* d_logits, int64_t nq, int m, int top_n, int want_logits, void* hip_stream);
-extern "C" void rmu_rerank_take_(int64_t nq, int m, int top_n, int32_t* out_pos, float* out_scores, float* out_logits);
 extern "C" int rmu_bert_rerank(rmu_bert_t* m, rmu_passages_t* p, const int32_t* q_tokens, const int32_t* q_lens, int64_t nq, int q_stride,
                                const int64_t* keys, int m_cand, int batch_pad, int max_len, int top_n, int32_t* out_pos, float* out_scores,
                                float* out_logits) {

@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "cosine_common.h"      // load_row, wave_sum, lane_norm2, the thread's workspace (CosCtx), COS_TRY / cos_fail
+#include "rmu_internal.h"      // rmu_attribution_check_ / _dev_: the prototypes bert.hip calls them by
 
 namespace {
 

@@ -29,6 +29,7 @@
 #include "../../include/rmu.h"
 #include "rmu_common.h"
 #include "pair_truncate.h"
+#include "rmu_internal.h"      // rmu_rerank_*_: the prototypes bert.hip calls them by
 
 extern "C" void rmu_set_error_(const char* msg);
 static int rfail(int code, const std::string& m) { rmu_set_error_(m.c_str()); return code; }

@@ -27,6 +27,7 @@
 
 #include "rmu_common.h"
 #include "../../include/rmu.h"
+#include "rmu_internal.h"      // rmu_index_search_mmr_dev_: the prototype bert.hip calls it by
 
 // ------------------------------------------------------------------------------------------------
 // error plumbing

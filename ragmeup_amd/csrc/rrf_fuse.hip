@@ -29,6 +29,7 @@
 
 #include "../../include/rmu.h"
 #include "rmu_common.h"
+#include "rmu_internal.h"      // rmu_hybrid_check_ / rmu_hybrid_search_dev_: the prototypes bert.hip calls them by
 
 extern "C" void rmu_set_error_(const char* msg);
 static int hfail(int code, const std::string& m) { rmu_set_error_(m.c_str()); return code; }

@@ -1,10 +1,12 @@
-"""The encoder's dispatch table (`enqueue_forward` in ragmeup_amd/csrc/bert.hip), restated in Python, and the GPU cases that
-pin each of its regimes from both sides of every threshold.
+"""The encoder's dispatch table (`enc_plan` in ragmeup_amd/csrc/bert_plan.h, launched by `enqueue_forward` in bert.hip), restated
+in Python, and the GPU cases that pin each of its regimes from both sides of every threshold.
 
 `regime(batch, max_len, layers, mode)` names the kernels a default build launches for one `rmu_bert_encode` call.  It is a
-plain helper module, not a fixture: tests/test_encoder_regimes_cpu.py reads the thresholds back out of bert.hip / bert.py and
-checks that CASES covers every regime and every threshold, and tests/test_encoder_regimes_gpu.py runs CASES against the fp64
-oracle.  A rework that moves a threshold makes the CPU test fail first: the boundary cases below are then stale.
+plain helper module, not a fixture: tests/test_encoder_regimes_cpu.py calls the library's own `enc_plan` (through the internal
+export `rmu_bert_plan_`) for every shape of the domain and requires it to equal regime() field by field, compares the constants
+below with those of the same name in bert_plan.h / bert.py, and checks that CASES covers every regime and every threshold;
+tests/test_encoder_regimes_gpu.py runs CASES against the fp64 oracle.  A rework that moves a threshold, or combines two of them
+differently, makes the CPU test fail first: the boundary cases below are then stale.
 """
 from __future__ import annotations
 

@@ -1,16 +1,25 @@
 """The encoder's dispatch table, guarded without a GPU.
 
-tests/encoder_regimes.py restates `enqueue_forward`'s kernel choice (ragmeup_amd/csrc/bert.hip); the GPU file
-tests/test_encoder_regimes_gpu.py holds every regime from both sides of each threshold.  Here:
-  * every threshold is read back out of bert.hip / bert.py and must equal the restated constant -- a rework that moves one fails
-    here, naming it, and the GPU boundary cases have to follow it;
+tests/encoder_regimes.py restates the encoder's kernel choice; the GPU file tests/test_encoder_regimes_gpu.py holds every regime
+from both sides of each threshold.  The choice itself is `enc_plan` in ragmeup_amd/csrc/bert_plan.h, a pure function that
+`enqueue_forward` (bert.hip) launches and that librmu.so exports for this file as `rmu_bert_plan_`.  Here:
+  * the plan must EQUAL the restated table for every shape of the domain (batch 1-640 x max_len 1-512, 1 and 6 layers) -- behaviour,
+    not the spelling of a condition: a rework that moves a threshold or combines two of them differently fails here, and the GPU
+    boundary cases have to follow it;
+  * every threshold constant of the restated table equals the one of the same name in bert_plan.h (bert.py's two as well);
+  * every RMU_* environment set the GPU variant tests run still selects something: it changes the plan, and only behind RMU_TUNING=1;
   * CASES must reach every distinct regime() value, and every threshold from both sides (the value itself and the next one up,
     with the regime field the threshold controls differing between them).
 """
+import ast
+import ctypes
 import os
 import re
+import subprocess
+import sys
 import types
 
+import numpy as np
 import pytest
 
 from tests import encoder_regimes as R
@@ -23,96 +32,64 @@ def _read(rel):
         return f.read()
 
 
-def _release_only(src: str) -> str:
-    """The source as a build without RMU_DEBUG_KERNELS sees it (the #ifdef blocks of bert.hip do not nest)."""
-    out, state = [], None
-    for line in src.splitlines():
-        t = line.strip()
-        if t.startswith("#ifdef RMU_DEBUG_KERNELS"):
-            state = "debug"
-            continue
-        if state and t.startswith("#else"):
-            state = "release"
-            continue
-        if state and t.startswith("#endif"):
-            state = None
-            continue
-        if state != "debug":
-            out.append(line)
-    return "\n".join(out)
-
-
-def _forward_body() -> str:
-    src = _release_only(_read("ragmeup_amd/csrc/bert.hip"))
-    i = src.index("static void enqueue_forward(")
-    j = src.index('extern "C" int rmu_bert_encode(', i)
-    return re.sub(r"\s+", " ", src[i:j])
-
-
-def _g3_min_body() -> str:
-    src = _release_only(_read("ragmeup_amd/csrc/bert.hip"))
-    i = src.index("static int64_t g3_min_tokens()")
-    return re.sub(r"\s+", " ", src[i:src.index("}", i) + 1])
-
-
-def _hip() -> str:
-    return re.sub(r"\s+", " ", _read("ragmeup_amd/csrc/bert.hip"))
-
-
-# name -> (where, pattern with one integer group; evaluated on whitespace-normalised text)
-SOURCE_THRESHOLDS = {
-    "SMALL_M": (_hip, r"constexpr int SMALL_M = (\d+);"),
-    "SMALL_M (g3_min_tokens)": (_g3_min_body, r"return (SMALL_M|\d+); \}"),
-    "QKV_ATTN_TOKENS": (_hip, r"constexpr int QKV_ATTN_TOKENS = (\d+),"),
-    "QKV_ATTN_MIN_TOKENS": (_hip, r"QKV_ATTN_MIN_TOKENS = (\d+);"),
-    "FOLD_TOKENS": (_hip, r"constexpr int FOLD_TOKENS = (\d+);"),
-    "FOLD_MAX_LEN": (_forward_body, r"if \(cap <= fold_tokens && max_len <= (\d+) &&"),
-    "CU_HERE_BATCH": (_forward_body, r"const bool cu_here = small_fuse && batch <= (\d+) && cap <= FOLD_TOKENS;"),
-    "EMBED_SEQ_BATCH": (_forward_body, r"if \(embed_seq && batch >= (\d+)\)"),
-    "KT4_MAX_LEN (small, fused)": (_forward_body, r"if \(max_len <= (\d+)\) \{ if \(!prev\) launch_qkv_attn_small<4, false>"),
-    "KT4_MAX_LEN (small, two launches)": (_forward_body, r"if \(max_len <= (\d+)\) launch_attn3<4>\(batch, m->qkv, m->cu, m->ctx, false, 0, s\);"),
-    "KT4_MAX_LEN": (_forward_body, r"if \(max_len <= (\d+)\) launch_attn3<4>\(batch, m->qkv, m->cu, m->ctx, ctx_tiled"),
-    "KT8_MAX_LEN": (_forward_body, r"else if \(max_len <= (\d+)\) launch_attn3<8>\(batch, m->qkv, m->cu, m->ctx, ctx_tiled, hm_stride, s\); "
-                                   r"else launch_attn3<16>"),
-    "FFN3_TOKENS": (_forward_body, r"const bool fused_ffn = !\(g3_mask & 4\) && \(fused_env < 0 \? cap > (\d+) :"),
-    "CTX_TILED_TOKENS": (_forward_body, r"const bool ctx_tiled = tiled_env && attn_v == 3 && !\(g3_mask & 2\) && cap > (\d+);"),
-    "HOST_TOKENS": (_hip, r"static constexpr int HOST_TOKENS = (\d+);"),
-    "HOST_ROWS": (_hip, r"\(kind == RMU_BERT_TOKENS \? cap : \(int64_t\)batch\) > (\d+)\)"),
-    "HOST_TOKENS (bert.py)": (lambda: _read("ragmeup_amd/bert.py"), r"HOST_TOKENS = (\d+)"),
-    "HOST_ROWS (bert.py)": (lambda: _read("ragmeup_amd/bert.py"), r"HOST_ROWS = (\d+)"),
-}
-
-# structural facts the restated table relies on (no number to compare: the pattern must simply be there)
-SOURCE_SHAPES = {
-    "fused QKV + attention for QKV_ATTN_MIN_TOKENS < cap <= QKV_ATTN_TOKENS": (_forward_body,
-        r"qa_tokens = rmu_env\(\"RMU_QKV_ATTN_TOKENS\"\) \? [^;]* : QKV_ATTN_TOKENS;.*qa_min = rmu_env\(\"RMU_QKV_ATTN_MIN\"\) \? [^;]* : "
-        r"QKV_ATTN_MIN_TOKENS;.*if \(cap <= qa_tokens && cap > qa_min\)"),
-    "small path up to FOLD_TOKENS": (_forward_body, r"fold_tokens = rmu_env\(\"RMU_FOLD_TOKENS\"\) \? [^;]* : FOLD_TOKENS;"),
-    "bulk QKV: k_gemm3 above g3_min_tokens()": (_forward_body,
-        r"else if \(\(g3_mask & 1\) && cap > g3_min_tokens\(\)\) launch_gemm3<EPI_BIAS>.* else launch_gemm<EPI_BIAS>"),
-    "h tiled between layers only (never out of the last one)": (_forward_body,
-        r"const bool h_out_tiled = h_env && ffn_v == 3 && ctx_tiled && \(g3_mask & 1\) && li < m->layers.size\(\);"),
-}
-
 _STALE = "the encoder's dispatch moved: update tests/encoder_regimes.py and its GPU boundary cases (tests/test_encoder_regimes_gpu.py)"
+
+# ---- the numbers -----------------------------------------------------------------------------------------------------------
+HEADER_NAMES = ["SMALL_M", "QKV_ATTN_TOKENS", "QKV_ATTN_MIN_TOKENS", "FOLD_TOKENS", "FOLD_MAX_LEN", "CU_HERE_BATCH", "EMBED_SEQ_BATCH",
+                "KT4_MAX_LEN", "KT8_MAX_LEN", "FFN3_TOKENS", "CTX_TILED_TOKENS", "HOST_TOKENS", "HOST_ROWS"]
+# name -> (file, pattern with one integer group): one uniform pattern for the header, bert.py's class attributes
+SOURCE_THRESHOLDS = {n: ("ragmeup_amd/csrc/bert_plan.h", rf"constexpr int {n} = (\d+);") for n in HEADER_NAMES}
+SOURCE_THRESHOLDS["HOST_TOKENS (bert.py)"] = ("ragmeup_amd/bert.py", r"HOST_TOKENS = (\d+)")
+SOURCE_THRESHOLDS["HOST_ROWS (bert.py)"] = ("ragmeup_amd/bert.py", r"HOST_ROWS = (\d+)")
 
 
 @pytest.mark.parametrize("name", list(SOURCE_THRESHOLDS))
 def test_threshold_matches_the_source(name):
-    where, pat = SOURCE_THRESHOLDS[name]
-    m = re.search(pat, where())
-    assert m, f"{name}: pattern not found in the source -- {_STALE}"
-    const = name.split(" ")[0]
-    want = getattr(R, const)
-    got = m.group(1)
-    got = getattr(R, got) if got.isidentifier() else int(got)
-    assert got == want, f"{name}: the source says {got}, tests/encoder_regimes.py says {want} -- {_STALE}"
+    rel, pat = SOURCE_THRESHOLDS[name]
+    m = re.search(pat, _read(rel))
+    assert m, f"{name}: not found in {rel} -- {_STALE}"
+    want = getattr(R, name.split(" ")[0])
+    assert int(m.group(1)) == want, f"{name}: {rel} says {m.group(1)}, tests/encoder_regimes.py says {want} -- {_STALE}"
 
 
-@pytest.mark.parametrize("name", list(SOURCE_SHAPES))
-def test_dispatch_shape_matches_the_source(name):
-    where, pat = SOURCE_SHAPES[name]
-    assert re.search(pat, where()), f"{name}: not found in the source -- {_STALE}"
+# ---- the plan --------------------------------------------------------------------------------------------------------------
+# EncPlan as rmu_bert_plan_ writes it out (bert_plan.h documents the order next to the struct)
+FIELDS = ("offsets_fused", "embed", "path", "qkv", "attn_kt", "gemm", "out_proj", "ffn", "ffn_ln_in", "ctx_tiled", "h_tiled",
+          "qkv_head_major", "tq", "th", "tf")
+QKV_KERNEL = {"GemmSmall": "k_gemm_small", "AttnSmall": "k_qkv_attn_small", "Gemm": "k_gemm", "Gemm3": "k_gemm3", "Qa": "k_qa"}
+FFN_KERNEL = {"GemmSmall": "k_gemm_small", "PairLn": "k_gemm+k_layernorm", "Gemm3Pair": "k_gemm3+k_layernorm", "Ffn2": "k_ffn2",
+              "Ffn3": "k_ffn3"}
+
+
+def _header_enums():
+    """enum class NAME : int32_t { A, B, ... } of bert_plan.h -> {NAME: [A, B, ...]} (the enumerators count from 0)"""
+    h = _read("ragmeup_amd/csrc/bert_plan.h")
+    enums = {n: [e.strip() for e in body.split(",")] for n, body in re.findall(r"enum class (\w+) : int32_t \{([^}]*)\}", h)}
+    assert int(re.search(r"constexpr int ENC_PLAN_FIELDS = (\d+);", h).group(1)) == len(FIELDS)
+    assert all(f in h[h.index("struct EncPlan {"):] for f in FIELDS)
+    return enums
+
+
+def _plan_fn(lib):
+    fn = lib.rmu_bert_plan_            # internal symbol: not in _native's list, so it is declared here
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+    return fn
+
+
+def _as_regime(row, enums):
+    """one plan (a sequence of len(FIELDS) ints) in regime()'s words"""
+    p = dict(zip(FIELDS, row))
+    qkv, gemm = enums["EncQkv"][p["qkv"]], enums["EncGemm"][p["gemm"]]
+    return {"embed": "k_embed_ln<true>" if p["offsets_fused"] else {"Wave": "k_embed_ln<false>", "Seq": "k_embed_ln_seq"}[enums["EncEmbed"][p["embed"]]],
+            "offsets": "k_embed_ln<true>" if p["offsets_fused"] else "k_cu_seqlens",
+            "path": enums["EncPath"][p["path"]].lower(),
+            "qkv": "k_gemm_small" if (qkv, gemm) == ("Gemm", "Small") else QKV_KERNEL[qkv],      # (launch_gemm's own small form)
+            "qkv_attn_fused": qkv == "AttnSmall", "attn_kt": p["attn_kt"], "ffn": FFN_KERNEL[enums["EncFfn"][p["ffn"]]],
+            "ctx_tiled": bool(p["ctx_tiled"]), "h_tiled": bool(p["h_tiled"])}
+
+
+REGIME_FIELDS = ("embed", "offsets", "path", "qkv", "qkv_attn_fused", "attn_kt", "ffn", "ctx_tiled", "h_tiled")
 
 
 def _domain():
@@ -124,6 +101,83 @@ def _domain():
                 yield b, L, layers
 
 
+def test_plan_equals_the_restated_table(librmu):
+    """enc_plan (what enqueue_forward launches) against regime() (what the GPU cases are built on), field by field, over the whole
+    domain -- and at 2 layers on the shapes of CASES.  One call sweeps max_len 1..512 for a (batch, layers)."""
+    enums, plan = _header_enums(), _plan_fn(librmu)
+    nf = len(FIELDS)
+    buf = np.full((512, nf), -1, dtype=np.int32)
+    said = {}                              # the plan's regime-relevant fields -> regime()'s words for them (a few dozen distinct rows)
+    wrong = []
+    for layers in (1, 6):
+        for b in range(1, 641):
+            assert plan(b, 1, layers, buf.ctypes.data, buf.size) == 512
+            for L, row in enumerate(map(tuple, buf[:, :12].tolist()), start=1):
+                got = said.get(row) or said.setdefault(row, _as_regime(row, enums))
+                want = R.regime(b, L, layers)
+                if any(got[f] != want[f] for f in REGIME_FIELDS) and len(wrong) < 5:
+                    wrong.append(((b, L, layers), {f: (got[f], want[f]) for f in REGIME_FIELDS if got[f] != want[f]}))
+    for c in R.CASES:
+        one = np.zeros(nf, dtype=np.int32)
+        assert plan(c.batch, c.max_len, 2, one.ctypes.data, nf) == 1
+        got, want = _as_regime(one.tolist(), enums), R.regime(c.batch, c.max_len, 2)
+        if any(got[f] != want[f] for f in REGIME_FIELDS):
+            wrong.append(((c.batch, c.max_len, 2), {f: (got[f], want[f]) for f in REGIME_FIELDS if got[f] != want[f]}))
+    assert not wrong, f"(shape, field: (plan, restated table)) {wrong} -- {_STALE}"
+
+
+# ---- the switches ----------------------------------------------------------------------------------------------------------
+def _variant_envs():
+    """The environment sets tests/test_encoder_gpu.py runs the kernel variants under: the parametrisation of its variant test, read
+    from its source (importing it would import torch), plus RMU_QA 0 / 1 of its k_qa test."""
+    tree = ast.parse(_read("tests/test_encoder_gpu.py"))
+    fn = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "test_every_switchable_kernel_variant_keeps_parity")
+    sets = next(ast.literal_eval(d.args[1]) for d in fn.decorator_list
+                if isinstance(d, ast.Call) and isinstance(d.args[0], ast.Constant) and d.args[0].value == "env")
+    assert len(sets) == 12, sets
+    return sets + [e for e in ({"RMU_QA": "1"}, {"RMU_QA": "0"}) if e not in sets]
+
+
+_PRINT_PLANS = """
+import ctypes, sys
+import numpy as np
+lib = ctypes.CDLL(sys.argv[1])
+lib.rmu_bert_plan_.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+out = []
+for batch, max_len in ((300, 250), (3, 40)):
+    p = np.zeros(int(sys.argv[2]), dtype=np.int32)
+    assert lib.rmu_bert_plan_(batch, max_len, 6, p.ctypes.data, p.size) == 1
+    out += p.tolist()
+print("PLANS", *out)
+"""
+
+
+def _child_plans(env, tuning=True):
+    """the plans at 300 x 250 (bulk, everything tiled) and 3 x 40 (small) as a fresh process with this environment sees them"""
+    from ragmeup_amd import _native
+    base = {k: v for k, v in os.environ.items() if not k.startswith("RMU_")}
+    if tuning:
+        base["RMU_TUNING"] = "1"
+    r = subprocess.run([sys.executable, "-c", _PRINT_PLANS, _native.SO_PATH, str(len(FIELDS))], env=dict(base, **env), capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return next(ln for ln in r.stdout.splitlines() if ln.startswith("PLANS "))
+
+
+def test_switches_still_steer_the_plan(librmu):
+    """The switches are read once per process, so each environment set gets a fresh child.  Every set of the GPU variant tests must
+    change at least one field of the plan at 300 x 250 or at 3 x 40 -- a switch that silently stops selecting anything fails here, not
+    only where a GPU is -- and without RMU_TUNING none of them may.  RMU_QA=0 spells out that switch's default: it is held to the
+    default plan, and RMU_QA=1 to a different one."""
+    default = _child_plans({})
+    envs = _variant_envs()
+    dead = [e for e in envs if e != {"RMU_QA": "0"} and _child_plans(e) == default]
+    assert not dead, f"environment sets that no longer change the plan: {dead}"
+    assert _child_plans({"RMU_QA": "0"}) == default != _child_plans({"RMU_QA": "1"})
+    everything = {k: v for e in envs for k, v in e.items()}
+    assert _child_plans(everything, tuning=False) == default, "a switch is honoured without RMU_TUNING=1"
+
+
+# ---- the cases -------------------------------------------------------------------------------------------------------------
 def test_cases_reach_every_regime():
     reach = {}
     for b, L, layers in _domain():
