@@ -77,6 +77,13 @@
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
+// the pacing wave of the 8-wave kernels (see "sibling pacing" in scan_screen_lean3_kernel): 0..3, a compile-time constant so that builds with
+// another wave can be set against each other under the debug counters (-DRMU_SCREEN_PW=n: profiles/screen_late_waves.md 2)
+#ifndef RMU_SCREEN_PW
+#define RMU_SCREEN_PW 0
+#endif
+static_assert(RMU_SCREEN_PW >= 0 && RMU_SCREEN_PW <= 3, "the pacing wave is the older wave of a SIMD");
+
 namespace {
 
 constexpr int SD = 384;                 // floats per row
@@ -262,10 +269,15 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
     // publishes ~tile (0 = not started / finished = "ignore me") once per pair of tiles, reads its siblings' words a pair stale through the
     // same 4-byte LDS-DMA that refreshes the shared thresholds (lanes 32..35: no extra VMEM instruction), and the pacing wave holds the
     // workgroup at the ring barrier while it is more than a.pace tiles ahead of the slowest sibling.  A HINT only: the wait is bounded (a
-    // sibling that is not resident -- another kernel on the device -- switches pacing off for this workgroup).  The pacing wave (the last
-    // one) publishes with a plain store issued a whole pair before its next counted ring wait: vmcnt retires in order, so a store that waits
+    // sibling that is not resident -- another kernel on the device -- switches pacing off for this workgroup).  The pacing wave (PW below)
+    // publishes with a plain store issued a whole pair before its next counted ring wait: vmcnt retires in order, so a store that waits
     // for an agent-scope acknowledgement in front of those waits holds the ring up (the first version, an agent-scope store, doubled the
     // kernel's time).  The siblings share this XCD's L2, where the store lands, and read it with sc1 (past their vector L1).
+    // Which wave paces (NWV = 8): one of the OLDER wave of each SIMD's two, 0..3.  Issue arbitration between the two is by age, so waves 0..3
+    // reach the pair barrier long before waves 4..7 and wait there (profiles/screen_refresh.md 2: ~1 360 against ~240 cycles per pair);
+    // the pacing wave's prologue -- threshold read and its lgkmcnt(0), update, progress store, the siblings' words and a second lgkmcnt(0)
+    // -- was on wave 7, the wave everybody else waited for.  On an early wave it is paid out of that wave's slack
+    // (profiles/screen_late_waves.md).  The 4-wave kernels never pace (rmu_screen_plan: 2..4 query tiles) and keep their constant.
     const bool pace_on = a.prog != nullptr;
     u32* prog_w = a.prog + (size_t)s_idx * 4;
     bool pace_live = pace_on;
@@ -279,7 +291,7 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                          (__attribute__((address_space(3))) void*)(ssm + C::GT_OFF + w * 256), 4, 0, 16);
     };
-    constexpr int PW = NW - 1;
+    constexpr int PW = M16 ? RMU_SCREEN_PW : NW - 1;
     auto pace_step = [&](int tile) {
         if (lane == 0) __hip_atomic_store(prog_w + qt, ~(u32)tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         const u32 m4 = max(max(gt_lds[32], gt_lds[33]), max(gt_lds[34], gt_lds[35]));
@@ -691,7 +703,30 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
             step(std::integral_constant<int, 21>{}); step(std::integral_constant<int, 22>{}); step(std::integral_constant<int, 23>{});
             tp += S_RT * IMGB;
         };
-        for (int tl = 0; tl < ntiles; tl += 6) {           // ring period: six bodies (the accumulator parity alternates with it)
+        // ring period: six bodies (the accumulator parity alternates with it)
+        if constexpr (M16) {
+            // NWV = 8: whole periods run their six bodies unconditionally.  With every body behind `if (tl + i < ntiles)` the odd tiles'
+            // accumulators were a phi of "body ran" and "body skipped", resolved by a 16-register copy (and the s_nop 5 that lets the last
+            // MFMA's result be read) at every merge point right in front of the pair barrier, plus a scalar compare and branch per tile.
+            // Here the two sets alternate in place; the last, partial period takes the conditional form, once per chunk.
+            int tl = 0;
+            for (; tl + 6 <= ntiles; tl += 6) {
+                tile_body(I0{}, accA, accB, tl);
+                tile_body(I1{}, accB, accA, tl + 1);
+                tile_body(I2{}, accA, accB, tl + 2);
+                tile_body(I3{}, accB, accA, tl + 3);
+                tile_body(I4{}, accA, accB, tl + 4);
+                tile_body(I5{}, accB, accA, tl + 5);
+            }
+            if (tl < ntiles) {                             // the remainder: one to five tiles
+                tile_body(I0{}, accA, accB, tl);
+                if (tl + 1 < ntiles) tile_body(I1{}, accB, accA, tl + 1);
+                if (tl + 2 < ntiles) tile_body(I2{}, accA, accB, tl + 2);
+                if (tl + 3 < ntiles) tile_body(I3{}, accB, accA, tl + 3);
+                if (tl + 4 < ntiles) tile_body(I4{}, accA, accB, tl + 4);
+            }
+        } else {
+        for (int tl = 0; tl < ntiles; tl += 6) {           // (NWV = 4: every period in the conditional form, as it was)
             tile_body(I0{}, accA, accB, tl);                 // (tile -1 = the -inf accumulators: nothing passes)
             if (tl + 1 < ntiles) tile_body(I1{}, accB, accA, tl + 1);
             if (tl + 2 < ntiles) tile_body(I2{}, accA, accB, tl + 2);
@@ -699,10 +734,14 @@ __global__ __launch_bounds__(64 * NWV) void scan_screen_lean3_kernel(const ScanL
             if (tl + 4 < ntiles) tile_body(I4{}, accA, accB, tl + 4);
             if (tl + 5 < ntiles) tile_body(I5{}, accB, accA, tl + 5);
         }
+        }
         if (pace_on && w == PW && lane == 0) __hip_atomic_store(prog_w + qt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #pragma unroll
         for (int m = 0; m < S_PRE; ++m) asm volatile("" : "+v"(fr[m]));
+        // (NWV = 8, L2 form) the same for the norms the last body read ahead: in the remainder period the compiler can see that nobody uses
+        // them, and a dead output of an asm ds_read is a register it hands to something else while the LDS data is still on its way
+        if constexpr (M16 && L2N != 0) asm volatile("" : "+v"(zq[0]), "+v"(zq[1]));
         {
             const bool last_in_a = ((ntiles - 1) & 1) == 0;
             f32x16 last;
