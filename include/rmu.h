@@ -90,7 +90,7 @@ extern "C" {
                              * such an index as on a narrow one -- add, reserve, remove_rows, compact, get_rows, mmr / search_mmr, save / load,
                              * caller streams, RMU_OPT_* (the screening and ladder options are accepted and change nothing) -- except:
                              *   - RMU_METRIC_L2SQ: dim <= 767 (rmu_index_create fails for a wide L2 index);
-                             *   - rmu_index_search_subset: rows of at most RMU_MAX_DIM dimensions (RMU_E_INVALID before anything is enqueued);
+                             *   - rmu_index_search_subset, rmu_index_search_groups: rows of at most RMU_MAX_DIM dimensions (RMU_E_INVALID before anything is enqueued);
                              *   - rmu_bert_search_mmr: 384-d rows (the encoder's width), as ever;
                              *   - the fp16 screening path exists at dim 384 only. */
 
@@ -205,9 +205,31 @@ int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, int k, unsign
  * gathered form of the wide scan does not exist yet).
  * Serves: VectorStore.similarity_search(**kwargs) with a filter -- Milvus col.search(expr='source == "a.pdf"') / PGVector
  * filter={"source": "a.pdf"} behind the retriever's search_kwargs (RAGHelper.py:497-499). */
-#define RMU_F_ROWS_DEVICE 8u   /* rmu_index_search_subset: `rows` is a device address */
+#define RMU_F_ROWS_DEVICE 8u   /* rmu_index_search_subset, rmu_index_search_groups: `rows` is a device address */
 int rmu_index_search_subset(rmu_index_t* idx, const float* q, int64_t nq, int k, unsigned flags, int64_t row_base,
                             const int64_t* rows, int64_t n_sub, float* out_scores, int64_t* out_rows, uint64_t hip_stream);
+
+/* rmu_index_search_subset with ONE LIST PER GROUP OF QUERIES, in one call: many concurrent requests, each filtered to its own rows, share
+ * one scan.  rows = n_lists lists laid end to end, list g = rows[list_ptr[g] .. list_ptr[g + 1]) (list_ptr[0] = 0), each strictly
+ * ascending index-local row ids; lists may overlap, repeat each other, be empty or go unused.  q_list[i] in [0, n_lists) = the list of
+ * query i; it must be NON-DECREASING, so that the queries of a list are adjacent (the caller reorders its queries, the library does not).
+ * list_ptr [n_lists + 1] and q_list [nq] are always HOST arrays (the plan is made from them); rows is a host array, or a device array
+ * with RMU_F_ROWS_DEVICE.  Host lists are checked as rmu_index_search_subset checks its list, before anything is enqueued; device lists
+ * are the caller's contract: ids outside [0, n) are ignored.
+ * Result of query i: exactly what rmu_index_search_subset(idx, q_i, 1, k, ..., list q_list[i]) returns -- the same order (score, then
+ * lower row id), the same (-inf | +inf for L2SQ, -1) padding, no tombstoned row, every score with the bits rmu_index_search gives that
+ * row (the two scans run one tile loop).  RMU_F_Q_DEVICE, RMU_F_OUT_DEVICE and row_base as there.
+ * Limits (RMU_E_INVALID with a message, before anything is enqueued): 1 <= nq <= 8192 (more queries: more calls), 1 <= k <= RMU_MAX_K,
+ * n_lists >= 1, the lists together and the index each hold fewer than 2^32 rows, rows of at most RMU_MAX_DIM dimensions (a wide index is
+ * refused, as by rmu_index_search_subset).
+ * Work: at most two scan launches however many lists there are (one per geometry of the gathered scan), one merge, one row-id pass.
+ * The call ALWAYS drains its stream, caller stream and device buffers included: its work table travels through the calling thread's
+ * pinned workspace, as rmu_attribution's group table does.
+ * Serves: the same filtered retrieval (RAGHelper.py:497-499 with search_kwargs) for a BATCH of requests whose filters differ -- every
+ * user asking about their own upload, expr='source == "<their file>"' -- which the reference answers one col.search per request. */
+int rmu_index_search_groups(rmu_index_t* idx, const float* q, int64_t nq, int k, unsigned flags, int64_t row_base,
+                            const int64_t* rows, const int64_t* list_ptr, int n_lists, const int32_t* q_list,
+                            float* out_scores, int64_t* out_rows, uint64_t hip_stream);
 
 /* Merge `parts` per-shard top-k lists ([parts, nq, k] each, best first; larger score = better unless
  * RMU_F_SMALLER_BETTER) into one [nq, k].  Ties: lower part index first (give shards in ascending row order).

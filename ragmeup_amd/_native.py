@@ -28,6 +28,7 @@ STAT_CAPACITY, STAT_GROW_COUNT, STAT_GROW_MS, STAT_LIVE_ROWS = 1, 2, 3, 4
 STAT_COMPACT_COUNT, STAT_COMPACT_MS = 5, 6
 COMM_ID_BYTES = 128
 MAX_K = 112
+MAX_QUERIES_PER_CALL = 8192   # rmu_index_search_groups takes one block of queries per call
 MAX_DIM = 768            # widest row of the register-resident scans
 MAX_DIM_WIDE = 3072      # widest row of an index (ip / cosine)
 BM25_STAT_DOCS, BM25_STAT_VOCAB, BM25_STAT_NNZ, BM25_STAT_AVGDL, BM25_STAT_LIVE_DOCS = 1, 2, 3, 4, 5
@@ -44,7 +45,7 @@ ADJ_COS_WAVE_PAIRS, ADJ_COS_WG_PAIRS = 16, 64
 SYMBOLS = [
     "rmu_init", "rmu_last_error", "rmu_version",
     "rmu_index_create", "rmu_index_free", "rmu_index_size", "rmu_index_dim", "rmu_index_metric", "rmu_index_set_option", "rmu_index_stat", "rmu_index_reserve", "rmu_index_add",
-    "rmu_index_remove_rows", "rmu_index_compact", "rmu_index_get_rows", "rmu_index_save", "rmu_index_load", "rmu_index_mmr", "rmu_index_search_mmr", "rmu_index_search", "rmu_index_search_subset", "rmu_topk_merge",
+    "rmu_index_remove_rows", "rmu_index_compact", "rmu_index_get_rows", "rmu_index_save", "rmu_index_load", "rmu_index_mmr", "rmu_index_search_mmr", "rmu_index_search", "rmu_index_search_subset", "rmu_index_search_groups", "rmu_topk_merge",
     "rmu_last_scan_ms", "rmu_last_search_ms", "rmu_last_scan_geometry", "rmu_set_timing", "rmu_last_screened", "rmu_probe_mfma_rate",
     "rmu_comm_unique_id", "rmu_comm_init", "rmu_comm_free", "rmu_comm_world", "rmu_shard_allgather_topk", "rmu_index_screen_candidates",
     "rmu_bert_create", "rmu_bert_free", "rmu_bert_encode", "rmu_bert_encode_host", "rmu_bert_search_mmr",
@@ -97,6 +98,7 @@ def _declare(lib):
     lib.rmu_index_load.argtypes = [c.POINTER(vp), c.c_char_p]
     lib.rmu_index_search.argtypes = [vp, vp, i64, i32, u32, i64, vp, vp, u64]
     lib.rmu_index_search_subset.argtypes = [vp, vp, i64, i32, u32, i64, vp, i64, vp, vp, u64]
+    lib.rmu_index_search_groups.argtypes = [vp, vp, i64, i32, u32, i64, vp, vp, i32, vp, vp, vp, u64]
     lib.rmu_topk_merge.argtypes = [vp, vp, i32, i64, i32, u32, vp, vp, u64]
     lib.rmu_last_scan_ms.restype = f32
     lib.rmu_last_search_ms.restype = f32

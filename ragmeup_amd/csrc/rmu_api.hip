@@ -86,7 +86,7 @@ struct Buf {
 struct Tls {
     hipStream_t stream = nullptr;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    Buf q, partial, out_s, out_r, in_s, in_r, qn, gthr, qsplit, ckeys, flag, nrm, fbq, fb_i, mm_q, mm_s, mm_r, mm_p, gcand, sub_ids, sub_rows, eps, spill, spill_cnt;
+    Buf q, partial, out_s, out_r, in_s, in_r, qn, gthr, qsplit, ckeys, flag, nrm, fbq, fb_i, mm_q, mm_s, mm_r, mm_p, gcand, sub_ids, sub_rows, gtab, eps, spill, spill_cnt;
     std::vector<hipEvent_t> lev;   // per-launch events of the screening ladder
     int ensure_events(int n) {
         while ((int)lev.size() < n) {
@@ -1755,6 +1755,117 @@ extern "C" int rmu_index_search_subset(rmu_index_t* idx, const float* q, int64_t
         else mark_reader(idx, s);
         t.finished(s, drained);
     }
+    return RMU_OK;
+}
+
+// One list per group of adjacent queries, every group in one call (include/rmu.h): the lists a query uses are narrowed end to end, the
+// planner (rmu_groups_plan) writes one descriptor per workgroup, at most two scan launches (one per geometry class) fill a ZEROED
+// [P, nq, k] partial buffer, then the ordinary final merge and positions -> row ids through each query's own list.  The work table, the
+// used lists and the per-query offsets travel through this thread's pinned buffer in ONE copy, so the call always drains its stream.
+extern "C" int rmu_index_search_groups(rmu_index_t* idx, const float* q, int64_t nq, int k, unsigned flags, int64_t row_base,
+                                       const int64_t* rows, const int64_t* list_ptr, int n_lists, const int32_t* q_list,
+                                       float* out_scores, int64_t* out_rows, uint64_t hip_stream) {
+    RMU_ENTRY();
+    // everything that needs neither the index nor the device comes first
+    if (nq < 1 || nq > kMaxQueriesPerLaunch) return fail(RMU_E_INVALID, "rmu_index_search_groups: nq must be in [1, 8192]");
+    if (k < 1 || k > RMU_MAX_K) return fail(RMU_E_INVALID, "rmu_index_search_groups: k must be in [1, 112]");
+    if (n_lists < 1) return fail(RMU_E_INVALID, "rmu_index_search_groups: n_lists must be >= 1");
+    if (!q || !out_scores || !out_rows || !list_ptr || !q_list) return fail(RMU_E_INVALID, "rmu_index_search_groups: null pointer");
+    if (list_ptr[0] != 0) return fail(RMU_E_INVALID, "rmu_index_search_groups: list_ptr[0] must be 0");
+    for (int g = 0; g < n_lists; ++g)
+        if (list_ptr[g + 1] < list_ptr[g]) return fail(RMU_E_INVALID, "rmu_index_search_groups: list_ptr must be non-decreasing: entry " + std::to_string(g + 1));
+    const int64_t n_all = list_ptr[n_lists];
+    if (n_all >= 0xFFFFFFFFll) return fail(RMU_E_INVALID, "rmu_index_search_groups: the lists together must hold fewer than 2^32 rows");
+    if (n_all > 0 && !rows) return fail(RMU_E_INVALID, "rmu_index_search_groups: rows is null");
+    for (int64_t i = 0; i < nq; ++i)
+        if (q_list[i] < 0 || q_list[i] >= n_lists || (i > 0 && q_list[i] < q_list[i - 1]))
+            return fail(RMU_E_INVALID, "rmu_index_search_groups: q_list must be non-decreasing list numbers in [0, n_lists): entry " + std::to_string(i));
+    if (!idx) return fail(RMU_E_INVALID, "rmu_index_search_groups: null index");
+    Tls& t = g_tls;
+    int rc = t.ensure_stream((hipStream_t)hip_stream);
+    if (rc) return fail(rc, "rmu_index_search_groups: stream");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : t.stream;
+    const bool q_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE, rows_dev = flags & RMU_F_ROWS_DEVICE;
+
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    const int dpad = idx->dpad;
+    const bool l2 = idx->metric == RMU_METRIC_L2SQ;
+    if (dpad > RMU_MAX_DIM)
+        return fail(RMU_E_INVALID, "rmu_index_search_groups: the index holds rows wider than 768 dimensions (RMU_MAX_DIM): the filtered search "
+                                   "does not serve a wide index yet");
+    if (idx->n >= 0xFFFFFFFFll) return fail(RMU_E_INVALID, "rmu_index_search_groups: row ids must fit 32 bits");
+    if (!rows_dev) {            // host lists are checked before anything is enqueued; device lists are the caller's contract
+        for (int g = 0; g < n_lists; ++g) {
+            int64_t prev = -1;
+            for (int64_t i = list_ptr[g]; i < list_ptr[g + 1]; ++i) {
+                const int64_t r = rows[i];
+                if (r <= prev || r >= idx->n)
+                    return fail(RMU_E_INVALID, "rmu_index_search_groups: every list must hold strictly ascending ids in [0, n): list " +
+                                               std::to_string(g) + ", entry " + std::to_string(i - list_ptr[g]));
+                prev = r;
+            }
+        }
+    }
+    GroupsPlan P;
+    if ((rc = rmu_groups_plan(dpad, k, (int)nq, list_ptr, q_list, &P))) return fail(rc, "rmu_index_search_groups: no scan geometry for this (dim, k)");
+    const bool scan = idx->n > 0 && !P.lists.empty();       // (an empty index: every id of a device list is absent)
+    const int parts = scan ? P.parts : 1;
+    t.scan_ms = -1.f; t.search_ms = -1.f; t.passes = 0; t.screened = 0;
+
+    const float* qdev;
+    if ((rc = prepare_queries(idx, t, q, nq, q_dev, s, &qdev, "rmu_index_search_groups"))) return rc;
+    float* d_s = out_scores; int64_t* d_r = out_rows;
+    if ((rc = stage_outputs(t, nq, k, out_dev, &d_s, &d_r, "rmu_index_search_groups"))) return rc;
+    const size_t partial_bytes = (size_t)parts * nq * k * sizeof(u64), gthr_len = (size_t)(nq + 128) * sizeof(u32);
+    if (t.partial.ensure(partial_bytes) || t.gthr.ensure(gthr_len)) return fail(RMU_E_OOM, "rmu_index_search_groups: partial workspace");
+    HIP_TRY(hipMemsetAsync(t.partial.p, 0, partial_bytes, s));     // a group's missing parts, and the queries of empty lists: empty
+    if (scan) {
+        // table: [descriptors of class 0][of class 1][used lists][per-query offsets], pinned -> device in one copy
+        const size_t b_t0 = P.tab[0].size() * sizeof(GroupDesc), b_t1 = P.tab[1].size() * sizeof(GroupDesc);
+        const size_t b_l = P.lists.size() * sizeof(GroupList), b_q = (size_t)nq * sizeof(u32), b_all = b_t0 + b_t1 + b_l + b_q;
+        if (t.ensure_hpin(b_all) || t.gtab.ensure(b_all) || t.sub_ids.ensure((size_t)P.ids_total * sizeof(u32)))
+            return fail(RMU_E_OOM, "rmu_index_search_groups: table / id workspace");
+        if (b_t0) memcpy(t.hpin, P.tab[0].data(), b_t0);
+        if (b_t1) memcpy(t.hpin + b_t0, P.tab[1].data(), b_t1);
+        memcpy(t.hpin + b_t0 + b_t1, P.lists.data(), b_l);
+        memcpy(t.hpin + b_t0 + b_t1 + b_l, P.q_off.data(), b_q);
+        HIP_TRY(hipMemcpyAsync(t.gtab.p, t.hpin, b_all, hipMemcpyHostToDevice, s));
+        const char* tab = (const char*)t.gtab.p;
+        const int64_t* drows = rows;
+        if (!rows_dev) {
+            if (t.sub_rows.ensure((size_t)n_all * sizeof(int64_t))) return fail(RMU_E_OOM, "rmu_index_search_groups: list workspace");
+            HIP_TRY(hipMemcpyAsync(t.sub_rows.p, rows, (size_t)n_all * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            drows = (const int64_t*)t.sub_rows.p;
+        }
+        if ((rc = rmu_groups_narrow_launch(drows, (const GroupList*)(tab + b_t0 + b_t1), (int)P.lists.size(), idx->n, (u32*)t.sub_ids.p, P.ids_total, s)))
+            return fail(rc, "rmu_index_search_groups: list conversion");
+        HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_len, s));
+        if (t.timing) HIP_TRY(hipEventRecord(t.ev[2], s));         // rmu_set_timing: the scan launches between two events
+        for (int cls = 0; cls < 2; ++cls) {
+            if (P.tab[cls].empty()) continue;
+            GroupsLaunch L{};
+            L.x = idx->x; L.n_rows = idx->n; L.dpad = dpad; L.ids = (const u32*)t.sub_ids.p; L.q = qdev; L.nq = (int)nq; L.k = k;
+            L.partial = (u64*)t.partial.p; L.gthr = (u32*)t.gthr.p;
+            L.tab = (const GroupDesc*)(tab + (cls ? b_t0 : 0));
+            L.wq = cls ? 4 : 1; L.kv = k <= 32 ? 0 : 1; L.grid = (int)P.tab[cls].size(); L.lds_bytes = P.lds_bytes[cls];
+            rc = rmu_groups_launch(&L, s);
+            if (rc) return fail(rc, std::string("rmu_index_search_groups: scan launch: ") + hipGetErrorString(hipGetLastError()));
+            t.note_geometry(L, 1);
+        }
+        if (t.timing) HIP_TRY(hipEventRecord(t.ev[3], s));
+    }
+    rc = rmu_merge_final_launch((const u64*)t.partial.p, parts, nq, k, 0, l2 ? 1 : 0, l2 ? (const float*)t.qn.p : nullptr, d_s, d_r, nullptr,
+                                nullptr, s);
+    if (rc) return fail(rc, "rmu_index_search_groups: merge launch");
+    if (scan) {
+        const size_t q_off_at = (P.tab[0].size() + P.tab[1].size()) * sizeof(GroupDesc) + P.lists.size() * sizeof(GroupList);
+        if ((rc = rmu_groups_map_launch(d_r, (const u32*)t.sub_ids.p, (const u32*)((const char*)t.gtab.p + q_off_at), nq * k, k, row_base, s)))
+            return fail(rc, "rmu_index_search_groups: row id launch");
+    }
+    if ((rc = copy_outputs(out_scores, out_rows, 0, nq, k, out_dev, d_s, d_r, s))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));          // always: the table went through the thread's pinned buffer
+    t.finished(s, true);
+    if (t.timing && scan) t.scan_ms = elapsed_ms(t.ev[2], t.ev[3]);
     return RMU_OK;
 }
 

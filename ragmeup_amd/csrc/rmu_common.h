@@ -2,6 +2,7 @@
 #pragma once
 #include <mutex>
 #include <shared_mutex>
+#include <vector>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -298,6 +299,41 @@ int rmu_subset_plan(SubsetLaunch* p);
 int rmu_subset_launch(const SubsetLaunch* p, hipStream_t s);
 int rmu_subset_narrow_launch(const int64_t* rows, int64_t n_sub, int64_t n_rows, u32* ids, hipStream_t s);
 int rmu_subset_map_launch(int64_t* out_rows, const u32* ids, int64_t total, int64_t row_base, hipStream_t s);   // position -> row id + row_base
+
+// ---- the grouped form (rmu_index_search_groups): one list per group of adjacent queries, every group in one launch per geometry class ----
+// what ONE workgroup of scan_groups_kernel does (scan_subset.hip: subset_scan's arguments)
+struct GroupDesc {
+    u32 ids_off;           // where its list starts in the narrowed ids (a multiple of 128)
+    u32 t0, ntiles;        // its tiles of that list (tiles of its class: 128 rows with wq = 1, 32 with wq = 4); ntiles = 0: nothing to scan
+    u32 q_first, q_end;    // its 32 * wq queries start at q_first (ANY index); those below q_end, the end of the group, exist
+    u32 part0;             // its first part of `partial` (list chunk * (4 / wq))
+    u32 pad[2];
+};
+// one list that some query uses: rows[src .. src + len) of the caller's array -> ids[ids_off .. ids_off + rmu_subset_ids_len(len))
+struct GroupList { int64_t src; u32 len, ids_off; };
+struct GroupsLaunch {
+    const float* x; int64_t n_rows; int dpad;
+    const u32* ids;        // every used list narrowed, each padded as rmu_subset_ids_len pads one, end to end
+    const float* q; int nq; int k;
+    u64* partial;          // [parts, nq, k], ZEROED by the caller: a group with fewer parts leaves empty lists
+    u32* gthr;             // [nq + 128]: published, never read (a tile of queries may start anywhere below nq)
+    const GroupDesc* tab;  // [grid] device
+    int wq, kv, grid, lds_bytes;
+};
+// the host's plan of a call: the work tables of the two geometry classes (0: wq = 1, 1: wq = 4), the used lists, each query's ids_off
+struct GroupsPlan {
+    std::vector<GroupDesc> tab[2];
+    std::vector<GroupList> lists;
+    std::vector<u32> q_off;
+    int64_t ids_total = 0;     // u32 entries of the narrowed ids
+    int parts = 1;             // P of the merge: the largest part count of any group
+    int lds_bytes[2] = {0, 0};
+};
+int rmu_groups_plan(int dpad, int k, int nq, const int64_t* list_ptr, const int32_t* q_list, GroupsPlan* out);
+int rmu_groups_launch(const GroupsLaunch* p, hipStream_t s);
+int rmu_groups_narrow_launch(const int64_t* rows, const GroupList* lists, int n_lists, int64_t n_rows, u32* ids, int64_t ids_total, hipStream_t s);
+// position in the query's own list -> row id + row_base; q_off [nq]: where that list starts in ids
+int rmu_groups_map_launch(int64_t* out_rows, const u32* ids, const u32* q_off, int64_t total, int k, int64_t row_base, hipStream_t s);
 
 // row moves of rmu_index_compact (rmu_compact.hip), one array of the index at a time: rows of row_bytes (a multiple of 256, or 4 for the
 // L2 norms); new row j in [first, n_live) comes from old row src_rows[j - first] (device list, strictly increasing, src_rows[i] >= first + i);

@@ -18,6 +18,47 @@ def _is_torch_cuda(t) -> bool:
     return hasattr(t, "data_ptr") and hasattr(t, "is_cuda") and bool(t.is_cuda)
 
 
+def search_groups_blocks(call, q: np.ndarray, k: int, lists, q_list, row_base: int = 0, block: int = N.MAX_QUERIES_PER_CALL):
+    """The host half of FlatIndex.search_groups, a pure function of its arguments: sort the queries by list (stable), cut them into blocks
+    of at most `block`, hand each block to `call(q_block, k, rows, list_ptr, q_list_block, row_base) -> (scores, rows)` with ONLY the lists
+    that block uses (laid end to end, list_ptr rebased to 0, q_list_block non-decreasing int32), and put the results back in the caller's
+    order."""
+    n_lists = len(lists)
+    ql = np.asarray(q_list, dtype=np.int64).reshape(-1)
+    nq = q.shape[0]
+    if ql.shape[0] != nq:
+        raise ValueError(f"q_list names the list of each query: expected {nq} entries, got {ql.shape[0]}")
+    if nq and (n_lists == 0 or ql.min() < 0 or ql.max() >= n_lists):
+        raise ValueError(f"q_list entries must be in [0, {n_lists})")
+    on_device = n_lists > 0 and all(_is_torch_cuda(x) for x in lists)
+    if on_device:
+        import torch
+        if any(x.dtype != torch.int64 or x.ndim != 1 for x in lists):
+            raise ValueError("device lists must be 1-d int64 tensors")
+        lens = [int(x.shape[0]) for x in lists]
+    else:
+        if any(_is_torch_cuda(x) for x in lists):
+            raise ValueError("the lists must be all host arrays or all device tensors")
+        lists = [np.ascontiguousarray(x, dtype=np.int64).reshape(-1) for x in lists]
+        lens = [int(x.shape[0]) for x in lists]
+    ptr = np.zeros(n_lists + 1, dtype=np.int64)
+    np.cumsum(lens, out=ptr[1:])
+    order = np.argsort(ql, kind="stable")
+    out_s = np.empty((nq, k), dtype=np.float32)
+    out_r = np.empty((nq, k), dtype=np.int64)
+    for b0 in range(0, nq, block):
+        sel = order[b0:b0 + block]
+        lo, hi = int(ql[sel[0]]), int(ql[sel[-1]]) + 1        # the lists of this block: a contiguous range, the queries are sorted
+        if on_device:
+            rows = torch.cat(list(lists[lo:hi])).contiguous()
+            torch.cuda.current_stream().synchronize()
+        else:
+            rows = np.concatenate(lists[lo:hi]) if hi > lo else np.empty(0, np.int64)
+        s, r = call(np.ascontiguousarray(q[sel]), k, rows, np.ascontiguousarray(ptr[lo:hi + 1] - ptr[lo]), (ql[sel] - lo).astype(np.int32), row_base)
+        out_s[sel], out_r[sel] = s, r
+    return out_s, out_r
+
+
 class FlatIndex:
     def __init__(self, dim: int, metric: int = N.METRIC_IP, capacity_hint: int = 0, device: int | None = None):
         """dim <= 3072 (N.MAX_DIM_WIDE) for METRIC_IP / METRIC_COSINE, <= 767 for METRIC_L2SQ; RmuError otherwise."""
@@ -266,6 +307,35 @@ class FlatIndex:
         out_r = np.empty((nq, k), dtype=np.int64)
         N.check(self._lib.rmu_index_search_subset(self._h, qq.ctypes.data, nq, k, 0, row_base, rr.ctypes.data, int(rr.shape[0]),
                                                   out_s.ctypes.data, out_r.ctypes.data, 0), "rmu_index_search_subset")
+        return out_s, out_r
+
+    def search_groups(self, q, k: int, lists, q_list, row_base: int = 0):
+        """Exact top-k of every query against ITS OWN list of rows, all in one scan (rmu_index_search_groups): `lists` is a sequence of
+        strictly ascending int64 row-id arrays (they may overlap, repeat each other, be empty or go unused), `q_list[i]` the list of
+        query i, in any order.  numpy in -> numpy out: for query i exactly what `search(q[i], k, rows=lists[q_list[i]])` returns.  The
+        queries are sorted by list (stably), sent in blocks of at most N.MAX_QUERIES_PER_CALL and put back in the caller's order.
+        The lists may also ALL be torch CUDA int64 tensors: they reach the library as a device array, which is not checked (ids outside
+        the index are ignored)."""
+        if self.dim > N.MAX_DIM:
+            raise ValueError(f"search_groups serves rows of at most {N.MAX_DIM} dimensions; this index holds {self.dim}-d rows "
+                             "(the filtered search of a wide index does not exist yet)")
+        qq = np.ascontiguousarray(q, dtype=np.float32)
+        if qq.ndim == 1:
+            qq = qq[None]
+        if qq.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] got {qq.shape}")
+        return search_groups_blocks(self._groups_call, qq, int(k), lists, q_list, int(row_base))
+
+    def _groups_call(self, qq: np.ndarray, k: int, rows, list_ptr: np.ndarray, q_list: np.ndarray, row_base: int):
+        """One rmu_index_search_groups call: qq [nq <= 8192, dim] float32, rows = the lists end to end (numpy int64, or a torch CUDA int64
+        tensor), list_ptr int64 [n_lists + 1], q_list int32 [nq] non-decreasing."""
+        nq = qq.shape[0]
+        out_s = np.empty((nq, k), dtype=np.float32)
+        out_r = np.empty((nq, k), dtype=np.int64)
+        flags, rows_ptr = (N.F_ROWS_DEVICE, rows.data_ptr()) if _is_torch_cuda(rows) else (0, rows.ctypes.data)
+        N.check(self._lib.rmu_index_search_groups(self._h, qq.ctypes.data, nq, k, flags, row_base, rows_ptr, list_ptr.ctypes.data,
+                                                  int(list_ptr.shape[0]) - 1, q_list.ctypes.data, out_s.ctypes.data, out_r.ctypes.data, 0),
+                "rmu_index_search_groups")
         return out_s, out_r
 
     def set_screening(self, on: bool = True):

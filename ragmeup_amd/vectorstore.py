@@ -101,13 +101,15 @@ class MI355XRetriever(VectorStoreRetriever):
             return [d for d, s in pairs if thr is None or s >= thr]
         return self.vectorstore.similarity_search(query, **self.search_kwargs)
 
-    def batch_invoke(self, queries: list[str]) -> list[list[Document]]:
-        """New capability beside the LangChain API: one fused scan for a whole query batch."""
+    def batch_invoke(self, queries: list[str], filters: Optional[list] = None, exprs: Optional[list] = None) -> list[list[Document]]:
+        """New capability beside the LangChain API: one fused scan for a whole query batch.  `filters` / `exprs`: one condition per
+        query (None = unfiltered), e.g. every request asking about its own upload; they share one scan all the same."""
         k = int(self.search_kwargs.get("k", 4))
+        each = {name: v for name, v in (("filters", filters), ("exprs", exprs)) if v is not None}
         if self.search_type == "mmr":
-            return self.vectorstore.max_marginal_relevance_search_batch(queries, **self.search_kwargs)
+            return self.vectorstore.max_marginal_relevance_search_batch(queries, **self.search_kwargs, **each)
         flt = {name: self.search_kwargs[name] for name in ("filter", "expr") if name in self.search_kwargs}
-        return [[d for d, _ in row] for row in self.vectorstore.similarity_search_with_score_batch(queries, k=k, **flt)]
+        return [[d for d, _ in row] for row in self.vectorstore.similarity_search_with_score_batch(queries, k=k, **flt, **each)]
 
 
 _METRICS = {"ip": N.METRIC_IP, "cosine": N.METRIC_COSINE, "l2": N.METRIC_L2SQ}
@@ -1057,6 +1059,70 @@ class MI355XVectorStore(VectorStore):
             return none
         return self._index.search(qvecs, kk, rows=rows)
 
+    # ---- one condition per query (filters= / exprs= of the batch entry points) ---------------------------------------------------
+    @classmethod
+    def _conditions_per_query(cls, nq: int, expr, filter, exprs, filters):
+        """-> None (no plural form given: the singular expr= / filter= hold for the whole batch, as ever) or a list with one entry per query:
+        its conditions, or None for an unfiltered query.  ValueError when a singular and a plural form are given together."""
+        if exprs is None and filters is None:
+            return None
+        if expr is not None or filter is not None:
+            raise ValueError("give either expr= / filter= (one condition for the whole batch) or exprs= / filters= (one per query), not both")
+        for name, v in (("exprs", exprs), ("filters", filters)):
+            if v is not None and (not isinstance(v, (list, tuple)) or len(v) != nq):
+                raise ValueError(f"{name} must be a list with one entry per query ({nq}); None = unfiltered")
+        return [cls._conditions(exprs[i] if exprs is not None else None, filters[i] if filters is not None else None) for i in range(nq)]
+
+    # the grouped call (FlatIndex.search_groups) answers two or more distinct lists in one scan.  profiles/groups_search.md measures it
+    # against the per-list calls it replaces (1M x 384, k = 10, host lists): faster by more than the run-to-run spread for 2 .. 128 lists
+    # of 1 000 .. 100 000 rows (0.03x .. 0.79x the time) as long as the lists together hold at most 3.2M rows; at 128 lists x 100 000
+    # rows (12.8M ids, 102 MB to lay end to end and upload in one piece) one run had it ahead and one behind, so the per-list loop stays
+    # there.  One list: the ordinary subset call (the grouped call's table costs 0.01 .. 0.05 ms more).
+    GROUPS_MAX_LIST_ROWS = 3_200_000
+
+    @classmethod
+    def _use_groups(cls, index, lists: list) -> bool:
+        return len(lists) >= 2 and hasattr(index, "search_groups") and sum(int(l.size) for l in lists) <= cls.GROUPS_MAX_LIST_ROWS
+
+    def _search_vecs_each(self, qvecs: np.ndarray, k: int, conds_each: list):
+        """_search_vecs with one condition per query, inside the caller's _consistent read: equal conditions share one list, the unfiltered
+        queries take the ordinary search, an empty selection costs no launch.  -> (scores, rows) [nq, kk], padded with (-inf, -1)."""
+        if self._pending:
+            self.flush()
+        nq = qvecs.shape[0]
+        if self._index is None or len(self._index) == 0:
+            return np.full((nq, 0), -np.inf, np.float32), np.full((nq, 0), -1, np.int64)
+        kk = max(1, min(int(k), N.MAX_K))
+        s = np.full((nq, kk), -np.inf, np.float32)
+        r = np.full((nq, kk), -1, np.int64)
+        plain = [i for i, c in enumerate(conds_each) if c is None]
+        if plain:
+            s[plain], r[plain] = self._index.search(qvecs[plain], kk)
+        if len(plain) == nq:
+            return s, r
+        if getattr(self._index, "dim", 0) > N.MAX_DIM:
+            raise ValueError(f"filtered search (exprs= / filters=) serves embeddings of at most {N.MAX_DIM} dimensions; this store holds "
+                             f"{self._index.dim}-d vectors")
+        keys, lists, q_of = {}, [], []                      # condition -> list number; the lists; the queries of each list
+        for i, c in enumerate(conds_each):
+            if c is None:
+                continue
+            key = repr(c)
+            if key not in keys:
+                keys[key] = len(lists)
+                lists.append(self._filter_rows(c))
+                q_of.append([])
+            q_of[keys[key]].append(i)
+        used = [g for g in range(len(lists)) if lists[g].size]      # (an empty selection: its queries keep the padding)
+        if self._use_groups(self._index, [lists[g] for g in used]):
+            qi = [i for g in used for i in q_of[g]]
+            ql = [n for n, g in enumerate(used) for _ in q_of[g]]
+            s[qi], r[qi] = self._index.search_groups(qvecs[qi], kk, [lists[g] for g in used], ql)
+        else:
+            for g in used:
+                s[q_of[g]], r[q_of[g]] = self._index.search(qvecs[q_of[g]], kk, rows=lists[g])
+        return s, r
+
     def similarity_search_with_score_by_vector(self, embedding, k: int = 4, filter: Optional[dict] = None, expr: Optional[str] = None,
                                                **kw) -> list[tuple[Document, float]]:
         q = np.asarray(embedding, dtype=np.float32)[None]
@@ -1109,12 +1175,17 @@ class MI355XVectorStore(VectorStore):
         return self._consistent(read)
 
     def similarity_search_with_score_batch(self, queries: list[str], k: int = 4, filter: Optional[dict] = None,
-                                           expr: Optional[str] = None, **kw) -> list[list[tuple[Document, float]]]:
+                                           expr: Optional[str] = None, filters: Optional[list] = None, exprs: Optional[list] = None,
+                                           **kw) -> list[list[tuple[Document, float]]]:
+        """`filter=` / `expr=`: one condition for the whole batch.  `filters=` / `exprs=`: a list with one entry per query (None =
+        unfiltered); queries with different conditions still share one scan (FlatIndex.search_groups)."""
+        queries = list(queries)
+        each = self._conditions_per_query(len(queries), expr, filter, exprs, filters)
         conds = self._conditions(expr, filter)
-        qv = self._embed_docs(list(queries))
+        qv = self._embed_docs(queries)
 
         def read():
-            s, r = self._search_vecs(qv, k, conds)
+            s, r = self._search_vecs(qv, k, conds) if each is None else self._search_vecs_each(qv, k, each)
             return [[(self._doc(int(row)), self._convert(float(sc))) for sc, row in zip(ss, rr) if row >= 0]
                     for ss, rr in zip(s, r)]
         return self._consistent(read)
@@ -1160,15 +1231,18 @@ class MI355XVectorStore(VectorStore):
 
     def max_marginal_relevance_search_batch(self, queries: list[str], k: int = 4, fetch_k: int = 20,
                                             lambda_mult: float = 0.5, filter: Optional[dict] = None, expr: Optional[str] = None,
-                                            **kw) -> list[list[Document]]:
+                                            filters: Optional[list] = None, exprs: Optional[list] = None, **kw) -> list[list[Document]]:
         """One dense search + ONE device-side MMR selection for the whole batch (`rmu_index_mmr`: fp64, same greedy rule and
-        tie order as the single-query path; no per-query vector re-fetch).  fetch_k > 64 falls back to the host loop."""
+        tie order as the single-query path; no per-query vector re-fetch).  fetch_k > 64 falls back to the host loop.
+        `filters=` / `exprs=`: one condition per query (None = unfiltered), as similarity_search_with_score_batch takes them."""
+        queries = list(queries)
+        each = self._conditions_per_query(len(queries), expr, filter, exprs, filters)
         conds = self._conditions(expr, filter)
-        qv = self._embed_docs(list(queries))
-        return self._consistent(lambda: self._mmr_batch(qv, k, fetch_k, lambda_mult, conds))
+        qv = self._embed_docs(queries)
+        return self._consistent(lambda: self._mmr_batch(qv, k, fetch_k, lambda_mult, conds, each))
 
-    def _mmr_batch(self, qv: np.ndarray, k: int, fetch_k: int, lambda_mult: float, conds=None) -> list[list[Document]]:
-        s, r = self._search_vecs(qv, fetch_k, conds)
+    def _mmr_batch(self, qv: np.ndarray, k: int, fetch_k: int, lambda_mult: float, conds=None, each=None) -> list[list[Document]]:
+        s, r = self._search_vecs(qv, fetch_k, conds) if each is None else self._search_vecs_each(qv, fetch_k, each)
         if r.shape[1] == 0:
             return [[] for _ in range(qv.shape[0])]
         if r.shape[1] <= 64 and hasattr(self._index, "mmr"):
