@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "rmu_common.h"
+#include "rmu_host.h"
 #include "../../include/rmu.h"
 #include "bert_plan.h"
 #include "rmu_internal.h"
@@ -2929,15 +2930,6 @@ static constexpr size_t MAX_CLONES = 3;
 static constexpr int SMALL_IN_INTS = 3 * HOST_TOKENS, SMALL_OUT_FLOATS = HOST_ROWS * H > HOST_TOKENS ? HOST_ROWS * H : HOST_TOKENS;
 static constexpr size_t MAX_GRAPHS = 64;
 
-extern "C" void rmu_set_error_(const char* msg);   // rmu_api.hip: thread-local message behind rmu_last_error()
-static int bfail(int code, const std::string& m) { rmu_set_error_(m.c_str()); return code; }
-
-#define B_TRY(expr)                                                                                      \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            return bfail(e_ == hipErrorOutOfMemory ? RMU_E_OOM : RMU_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 template <class T>
 static int dev_alloc(rmu_bert* m, T** p, size_t count) {
@@ -3015,19 +3007,19 @@ static int mark_tail(rmu_bert* m, hipStream_t s) {
 
 extern "C" int rmu_bert_create(rmu_bert_t** out, const rmu_bert_cfg* cfg, const void* const* wptr, int n_weights) {
     RMU_ENTRY();
-    if (!out || !cfg || !wptr) return bfail(RMU_E_INVALID, "rmu_bert_create: null argument");
+    if (!out || !cfg || !wptr) return rmu_fail(RMU_E_INVALID, "rmu_bert_create: null argument");
     if (cfg->hidden != H || cfg->heads != NH || cfg->ffn != FF || cfg->layers < 1 || cfg->layers > 48)
-        return bfail(RMU_E_INVALID, "rmu_bert_create: this build supports hidden 384, 12 heads, ffn 1536");
+        return rmu_fail(RMU_E_INVALID, "rmu_bert_create: this build supports hidden 384, 12 heads, ffn 1536");
     if (cfg->max_pos < 1 || cfg->max_pos > 512 || cfg->vocab_size < 1 || cfg->type_vocab < 1)
-        return bfail(RMU_E_INVALID, "rmu_bert_create: max_pos must be in [1, 512]");
+        return rmu_fail(RMU_E_INVALID, "rmu_bert_create: max_pos must be in [1, 512]");
     const int need = 5 + 16 * cfg->layers + (cfg->has_head ? 4 : 0);
-    if (n_weights != need) return bfail(RMU_E_INVALID, "rmu_bert_create: wrong number of weight tensors");
+    if (n_weights != need) return rmu_fail(RMU_E_INVALID, "rmu_bert_create: wrong number of weight tensors");
     for (int i = 0; i < need; ++i)
-        if (!wptr[i]) return bfail(RMU_E_INVALID, "rmu_bert_create: null weight pointer");
+        if (!wptr[i]) return rmu_fail(RMU_E_INVALID, "rmu_bert_create: null weight pointer");
     auto* m = new (std::nothrow) rmu_bert();
-    if (!m) return bfail(RMU_E_OOM, "rmu_bert_create: host alloc");
+    if (!m) return rmu_fail(RMU_E_OOM, "rmu_bert_create: host alloc");
     m->cfg = *cfg;
-    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { delete m; return bfail(RMU_E_HIP, "stream"); }
+    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { delete m; return rmu_fail(RMU_E_HIP, "stream"); }
     hipStream_t s = m->stream;
     int rc = RMU_OK;
     int wi = 0;
@@ -3089,7 +3081,7 @@ extern "C" int rmu_bert_create(rmu_bert_t** out, const rmu_bert_cfg* cfg, const 
     }
     if (rc || hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
         rmu_bert_free(m);
-        return bfail(rc ? rc : RMU_E_HIP, "rmu_bert_create: weight upload failed");
+        return rmu_fail(rc ? rc : RMU_E_HIP, "rmu_bert_create: weight upload failed");
     }
     *out = m;
     return RMU_OK;
@@ -3354,14 +3346,14 @@ static void launch_qkv_attn_small(hipStream_t s, int batch, const bf16* A, const
 }
 
 static int check_encode_args(rmu_bert_t* m, const void* ids, const void* lens, const void* out, int batch, int max_len, int mode, int64_t out_stride) {
-    if (!m || !ids || !lens || !out) return bfail(RMU_E_INVALID, "rmu_bert_encode: null argument");
+    if (!m || !ids || !lens || !out) return rmu_fail(RMU_E_INVALID, "rmu_bert_encode: null argument");
     if (batch < 1 || batch > 65535 || max_len < 1 || max_len > m->cfg.max_pos)
-        return bfail(RMU_E_INVALID, "rmu_bert_encode: 1 <= batch <= 65535, 1 <= max_len <= max_pos");
+        return rmu_fail(RMU_E_INVALID, "rmu_bert_encode: 1 <= batch <= 65535, 1 <= max_len <= max_pos");
     const int kind = mode & 0xff;
     if ((mode & ~(0xff | RMU_BERT_NO_NORMALIZE)) || kind > RMU_BERT_TOKENS)
-        return bfail(RMU_E_INVALID, "rmu_bert_encode: mode must be RMU_BERT_POOL_MEAN / CE_LOGIT / POOL_CLS / TOKENS (| RMU_BERT_NO_NORMALIZE)");
-    if (kind == RMU_BERT_CE_LOGIT && !m->cfg.has_head) return bfail(RMU_E_INVALID, "rmu_bert_encode: model has no classification head");
-    if (kind != RMU_BERT_CE_LOGIT && out_stride < H) return bfail(RMU_E_INVALID, "rmu_bert_encode: out_stride < hidden");
+        return rmu_fail(RMU_E_INVALID, "rmu_bert_encode: mode must be RMU_BERT_POOL_MEAN / CE_LOGIT / POOL_CLS / TOKENS (| RMU_BERT_NO_NORMALIZE)");
+    if (kind == RMU_BERT_CE_LOGIT && !m->cfg.has_head) return rmu_fail(RMU_E_INVALID, "rmu_bert_encode: model has no classification head");
+    if (kind != RMU_BERT_CE_LOGIT && out_stride < H) return rmu_fail(RMU_E_INVALID, "rmu_bert_encode: out_stride < hidden");
     return RMU_OK;
 }
 
@@ -3523,13 +3515,13 @@ extern "C" int rmu_bert_encode(rmu_bert_t* m, const int32_t* ids, const int32_t*
     std::lock_guard<std::mutex> lk(m->mu);
     (void)hipGetLastError();                     // (an error some earlier call of this thread left behind -- the caller's framework polls events -- is not this call's)
     rc = ensure_ws(m, (int64_t)batch * max_len, batch);
-    if (rc) return bfail(rc, "rmu_bert_encode: workspace");
+    if (rc) return rmu_fail(rc, "rmu_bert_encode: workspace");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m->stream;
-    if ((rc = order_behind_tail(m, s))) return bfail(rc, "rmu_bert_encode: ordering behind the forward in flight");
+    if ((rc = order_behind_tail(m, s))) return rmu_fail(rc, "rmu_bert_encode: ordering behind the forward in flight");
     enqueue_forward(m, ids, type_ids, lens, batch, max_len, mode, out_dev, out_stride, s);
-    B_TRY(hipGetLastError());
+    RMU_HIP_TRY(hipGetLastError());
     if (!hip_stream) {
-        B_TRY(hipStreamSynchronize(s));
+        RMU_HIP_TRY(hipStreamSynchronize(s));
         m->tail_set = false;                     // (everything this context ever enqueued has finished)
     } else if ((rc = mark_tail(m, s))) {
         (void)hipStreamSynchronize(s);           // no event: fall back to "complete on return"
@@ -3550,7 +3542,7 @@ static int host_staging_locked(rmu_bert* m, const char* who) {
     if (!m->h_in) {
         if (hipHostMalloc((void**)&m->h_in, SMALL_IN_INTS * sizeof(int32_t)) != hipSuccess || hipHostMalloc((void**)&m->h_out, SMALL_OUT_FLOATS * sizeof(float)) != hipSuccess ||
             hipMalloc((void**)&m->d_in, SMALL_IN_INTS * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&m->d_out, SMALL_OUT_FLOATS * sizeof(float)) != hipSuccess)
-            return bfail(RMU_E_OOM, std::string(who) + ": staging buffers");
+            return rmu_fail(RMU_E_OOM, std::string(who) + ": staging buffers");
     }
     return RMU_OK;
 }
@@ -3559,12 +3551,12 @@ static int host_forward_locked(rmu_bert* m, const int32_t* ids, const int32_t* t
     const int64_t cap = (int64_t)batch * max_len;
     const int kind = mode & 0xff;
     if (cap > HOST_TOKENS)
-        return bfail(RMU_E_INVALID, std::string(who) + ": batch * max_len must be <= " + std::to_string(HOST_TOKENS) + " (use rmu_bert_encode for bulk work)");
+        return rmu_fail(RMU_E_INVALID, std::string(who) + ": batch * max_len must be <= " + std::to_string(HOST_TOKENS) + " (use rmu_bert_encode for bulk work)");
     if (kind != RMU_BERT_CE_LOGIT && (kind == RMU_BERT_TOKENS ? cap : (int64_t)batch) > HOST_ROWS)
-        return bfail(RMU_E_INVALID, std::string(who) + ": at most " + std::to_string(HOST_ROWS) + " result rows (pooled vectors, or token states of a <= " +
+        return rmu_fail(RMU_E_INVALID, std::string(who) + ": at most " + std::to_string(HOST_ROWS) + " result rows (pooled vectors, or token states of a <= " +
                                     std::to_string(HOST_ROWS) + "-token call)");
     int rc = ensure_ws(m, cap, batch);
-    if (rc) return bfail(rc, std::string(who) + ": workspace");
+    if (rc) return rmu_fail(rc, std::string(who) + ": workspace");
     if ((rc = host_staging_locked(m, who))) return rc;
     const bool types = in_dev || type_ids;
     // staging layout: ids [cap] | type ids [cap] | lens [batch]
@@ -3577,7 +3569,7 @@ static int host_forward_locked(rmu_bert* m, const int32_t* ids, const int32_t* t
     const size_t out_floats = kind == RMU_BERT_CE_LOGIT ? (size_t)batch : (size_t)rows_out * H;
     const size_t in_bytes = (size_t)(2 * cap + batch) * 4;
     hipStream_t s = m->stream;
-    if ((rc = order_behind_tail(m, s))) return bfail(rc, std::string(who) + ": ordering behind the forward in flight");
+    if ((rc = order_behind_tail(m, s))) return rmu_fail(rc, std::string(who) + ": ordering behind the forward in flight");
     auto enqueue_all = [&]() {
         if (!in_dev) (void)hipMemcpyAsync(m->d_in, m->h_in, in_bytes, hipMemcpyHostToDevice, s);
         enqueue_forward(m, m->d_in, types ? m->d_in + cap : nullptr, m->d_in + 2 * cap, batch, max_len, mode, m->d_out, kind == RMU_BERT_CE_LOGIT ? 1 : H, s);
@@ -3590,7 +3582,7 @@ static int host_forward_locked(rmu_bert* m, const int32_t* ids, const int32_t* t
         auto victim = m->graphs.begin();
         for (auto it = m->graphs.begin(); it != m->graphs.end(); ++it)
             if (it->second.last_use < victim->second.last_use) victim = it;
-        B_TRY(hipStreamSynchronize(s));                                                   // (a replay of it may still be running)
+        RMU_HIP_TRY(hipStreamSynchronize(s));                                                   // (a replay of it may still be running)
         victim->second.destroy();
         m->graphs.erase(victim);
     }
@@ -3660,7 +3652,7 @@ static int host_forward_locked(rmu_bert* m, const int32_t* ids, const int32_t* t
         (void)hipStreamSynchronize(s);
         clear_errors();
         enqueue_all();
-        B_TRY(hipGetLastError());
+        RMU_HIP_TRY(hipGetLastError());
     }
     return RMU_OK;
 }
@@ -3675,7 +3667,7 @@ extern "C" int rmu_bert_encode_host(rmu_bert_t* m, const int32_t* ids, const int
     m = acquire_ctx(m, lk);
     rc = host_forward_locked(m, ids, type_ids, lens, batch, max_len, mode, "rmu_bert_encode_host");
     if (rc) return rc;
-    B_TRY(hipStreamSynchronize(m->stream));
+    RMU_HIP_TRY(hipStreamSynchronize(m->stream));
     if (kind == RMU_BERT_CE_LOGIT) {
         memcpy(out_host, m->h_out, (size_t)batch * sizeof(float));
     } else {
@@ -3695,11 +3687,11 @@ extern "C" int rmu_bert_search_mmr(rmu_bert_t* m, rmu_index_t* idx, const int32_
                                    int max_len, int mode, int fetch_k, int k, double lambda_mult, int64_t row_base, int64_t* out_rows,
                                    float* out_scores, float* out_vecs) {
     RMU_ENTRY();
-    if (!idx || !out_rows) return bfail(RMU_E_INVALID, "rmu_bert_search_mmr: null argument");
+    if (!idx || !out_rows) return rmu_fail(RMU_E_INVALID, "rmu_bert_search_mmr: null argument");
     int rc = check_encode_args(m, ids, lens, out_rows, batch, max_len, mode, H);
     if (rc) return rc;
     const int kind = mode & 0xff;
-    if (kind != RMU_BERT_POOL_MEAN && kind != RMU_BERT_POOL_CLS) return bfail(RMU_E_INVALID, "rmu_bert_search_mmr: mode must be a pooling mode");
+    if (kind != RMU_BERT_POOL_MEAN && kind != RMU_BERT_POOL_CLS) return rmu_fail(RMU_E_INVALID, "rmu_bert_search_mmr: mode must be a pooling mode");
     std::unique_lock<std::mutex> lk;
     m = acquire_ctx(m, lk);
     rc = host_forward_locked(m, ids, type_ids, lens, batch, max_len, mode, "rmu_bert_search_mmr");
@@ -3718,14 +3710,14 @@ extern "C" int rmu_bert_search_mmr(rmu_bert_t* m, rmu_index_t* idx, const int32_
 extern "C" int rmu_bert_attribute(rmu_bert_t* m, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch, int max_len, int mode,
                                   const int32_t* groups, int n_groups, double* out_scores, double* out_sims, float* out_vecs) {
     RMU_ENTRY();
-    if (!ids || !lens || !groups || !out_scores) return bfail(RMU_E_INVALID, "rmu_bert_attribute: null argument");
-    if (batch < 1 || batch > 65535) return bfail(RMU_E_INVALID, "rmu_bert_attribute: 1 <= batch <= 65535");
+    if (!ids || !lens || !groups || !out_scores) return rmu_fail(RMU_E_INVALID, "rmu_bert_attribute: null argument");
+    if (batch < 1 || batch > 65535) return rmu_fail(RMU_E_INVALID, "rmu_bert_attribute: 1 <= batch <= 65535");
     const int kind = mode & 0xff;
-    if (kind != RMU_BERT_POOL_MEAN && kind != RMU_BERT_POOL_CLS) return bfail(RMU_E_INVALID, "rmu_bert_attribute: mode must be a pooling mode");
+    if (kind != RMU_BERT_POOL_MEAN && kind != RMU_BERT_POOL_CLS) return rmu_fail(RMU_E_INVALID, "rmu_bert_attribute: mode must be a pooling mode");
     int64_t total = 0;
     int rc = rmu_attribution_check_("rmu_bert_attribute", batch, H, groups, n_groups, out_scores, &total);
     if (rc) return rc;
-    if (!m) return bfail(RMU_E_INVALID, "rmu_bert_attribute: null argument");
+    if (!m) return rmu_fail(RMU_E_INVALID, "rmu_bert_attribute: null argument");
     rc = check_encode_args(m, ids, lens, out_scores, batch, max_len, mode, H);
     if (rc) return rc;
     std::unique_lock<std::mutex> lk;
@@ -3737,7 +3729,7 @@ extern "C" int rmu_bert_attribute(rmu_bert_t* m, const int32_t* ids, const int32
         rc = rmu_attribution_dev_("rmu_bert_attribute", m->d_out, batch, H, H, groups, n_groups, total, out_scores, out_sims, (void*)m->stream);
         if (rc) { (void)hipStreamSynchronize(m->stream); return rc; }
     } else {
-        B_TRY(hipStreamSynchronize(m->stream));
+        RMU_HIP_TRY(hipStreamSynchronize(m->stream));
     }
     if (out_vecs) memcpy(out_vecs, m->h_out, (size_t)batch * H * sizeof(float));
     return RMU_OK;
@@ -3751,17 +3743,17 @@ extern "C" int rmu_bert_search_hybrid(rmu_bert_t* m, rmu_hybrid_t* h, const int3
                                       double lambda_mult, const double* weights, int c, int k_out, double* out_scores, int64_t* out_ids,
                                       int32_t* out_member) {
     RMU_ENTRY();
-    if (!h || !out_scores) return bfail(RMU_E_INVALID, "rmu_bert_search_hybrid: null argument");
+    if (!h || !out_scores) return rmu_fail(RMU_E_INVALID, "rmu_bert_search_hybrid: null argument");
     int rc = check_encode_args(m, ids, lens, out_scores, batch, max_len, mode, H);
     if (rc) return rc;
     const int kind = mode & 0xff;
-    if (kind != RMU_BERT_POOL_MEAN && kind != RMU_BERT_POOL_CLS) return bfail(RMU_E_INVALID, "rmu_bert_search_hybrid: mode must be a pooling mode");
+    if (kind != RMU_BERT_POOL_MEAN && kind != RMU_BERT_POOL_CLS) return rmu_fail(RMU_E_INVALID, "rmu_bert_search_hybrid: mode must be a pooling mode");
     rmu_index_t* idx = nullptr;
     rc = rmu_hybrid_check_(h, &idx, batch, query_blob, bytes, k_sparse, fetch_k, k_dense, weights, c, k_out, out_scores, out_ids, out_member);
     if (rc) return rc;
     int dim = 0;
     if (!idx || rmu_index_dim(idx, &dim) != RMU_OK || dim != 384)
-        return bfail(RMU_E_INVALID, "rmu_bert_search_hybrid: the dense member must be an index of 384-d rows (the encoder's width)");
+        return rmu_fail(RMU_E_INVALID, "rmu_bert_search_hybrid: the dense member must be an index of 384-d rows (the encoder's width)");
     std::unique_lock<std::mutex> lk;
     m = acquire_ctx(m, lk);
     rc = host_forward_locked(m, ids, type_ids, lens, batch, max_len, mode, "rmu_bert_search_hybrid");
@@ -3788,9 +3780,9 @@ extern "C" int rmu_bert_rerank(rmu_bert_t* m, rmu_passages_t* p, const int32_t* 
     // context's (a call that waits for the table's exclusive lock to upload holds a context: nobody may wait for a context with the table's)
     int rc = rmu_rerank_check_(p, q_tokens, q_lens, nq, q_stride, keys, m_cand, batch_pad, max_len, top_n, out_pos, out_scores, nullptr);
     if (rc) return rc;
-    if (!m) return bfail(RMU_E_INVALID, "rmu_bert_rerank: null pointer");
-    if (!m->cfg.has_head) return bfail(RMU_E_INVALID, "rmu_bert_rerank: model has no classification head");
-    if (max_len > m->cfg.max_pos) return bfail(RMU_E_INVALID, "rmu_bert_rerank: max_len > max_pos");
+    if (!m) return rmu_fail(RMU_E_INVALID, "rmu_bert_rerank: null pointer");
+    if (!m->cfg.has_head) return rmu_fail(RMU_E_INVALID, "rmu_bert_rerank: model has no classification head");
+    if (max_len > m->cfg.max_pos) return rmu_fail(RMU_E_INVALID, "rmu_bert_rerank: max_len > max_pos");
     const int64_t cap = (int64_t)batch_pad * max_len;
     std::unique_lock<std::mutex> lk;
     m = acquire_ctx(m, lk);
@@ -3810,20 +3802,20 @@ extern "C" int rmu_bert_rerank(rmu_bert_t* m, rmu_passages_t* p, const int32_t* 
         int32_t* d_in = nullptr;
         float* d_out = nullptr;
         rc = ensure_ws(m, cap, batch_pad);
-        if (rc) return bfail(rc, "rmu_bert_rerank: workspace");
+        if (rc) return rmu_fail(rc, "rmu_bert_rerank: workspace");
         if ((rc = rmu_rerank_workspace_(batch_pad, max_len, &d_in, &d_out))) return rc;
-        if ((rc = order_behind_tail(m, s))) return bfail(rc, "rmu_bert_rerank: ordering behind the forward in flight");
+        if ((rc = order_behind_tail(m, s))) return rmu_fail(rc, "rmu_bert_rerank: ordering behind the forward in flight");
         rc = rmu_rerank_assemble_(p, q_tokens, q_lens, nq, q_stride, keys, m_cand, batch_pad, max_len, top_n, d_in, (void*)s, &table_lk);
         if (!rc) {
             enqueue_forward(m, d_in, d_in + cap, d_in + 2 * cap, batch_pad, max_len, RMU_BERT_CE_LOGIT, d_out, 1, s);
-            if (hipGetLastError() != hipSuccess) rc = bfail(RMU_E_HIP, "rmu_bert_rerank: launching the forward");
+            if (hipGetLastError() != hipSuccess) rc = rmu_fail(RMU_E_HIP, "rmu_bert_rerank: launching the forward");
         }
         d_logits = d_out;
     }
     if (!rc) rc = rmu_rerank_select_(d_logits, nq, m_cand, top_n, out_logits ? 1 : 0, (void*)s);
     const hipError_t es = hipStreamSynchronize(s);
     if (rc) return rc;
-    B_TRY(es);
+    RMU_HIP_TRY(es);
     m->tail_set = false;                         // (everything this context ever enqueued has finished)
     rmu_rerank_take_(nq, m_cand, top_n, out_pos, out_scores, out_logits);
     return RMU_OK;

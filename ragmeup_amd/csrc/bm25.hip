@@ -55,15 +55,7 @@
 
 #include "../../include/rmu.h"
 #include "rmu_common.h"
-
-extern "C" void rmu_set_error_(const char* msg);
-static int mfail(int code, const std::string& m) { rmu_set_error_(m.c_str()); return code; }
-#define BM25_TRY(expr)                                                                                              \
-    do {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                     \
-        if (e_ != hipSuccess)                                                                                       \
-            return mfail(e_ == hipErrorOutOfMemory ? RMU_E_OOM : RMU_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+#include "rmu_host.h"
 
 namespace {
 
@@ -331,52 +323,23 @@ bool split_blob(const char* blob, int64_t bytes, int64_t n, std::vector<std::pai
     return (int64_t)out.size() == n && p == e;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)rmu_free(p);
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return e; }
-        cap = want;
-        return hipSuccess;
-    }
-};
-bool g_bm25_down = false;      // static destructors have begun: thread-local destructors must leave HIP alone
-struct DownGuard { ~DownGuard() { g_bm25_down = true; } } g_down_guard;
 // per-thread stream and workspaces of rmu_bm25_search (every call drains its stream, so nothing of a thread's is ever in flight between calls)
 struct Ctx {
     hipStream_t stream = nullptr;
     int device = -1;
-    DevBuf stage, partial, out;
-    char* pin = nullptr;
-    size_t pin_cap = 0;
+    RmuDevBuf stage, partial, out;
+    RmuPinBuf pin{4096};
     int ensure_stream() {
-        const int dev = rmu_device_ordinal();
-        if (dev >= 0 && device != dev) { (void)hipSetDevice(dev); device = dev; }
+        rmu_follow_device(device);
         if (!stream && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { stream = nullptr; return RMU_E_HIP; }
         return RMU_OK;
     }
-    int ensure_pin(size_t bytes) {
-        if (bytes <= pin_cap) return RMU_OK;
-        if (pin) (void)hipHostFree(pin);
-        pin = nullptr; pin_cap = 0;
-        const size_t cap = bytes < 4096 ? 4096 : bytes * 2;
-        if (hipHostMalloc((void**)&pin, cap) != hipSuccess) { pin = nullptr; (void)hipGetLastError(); return RMU_E_OOM; }
-        pin_cap = cap;
-        return RMU_OK;
-    }
+    // only what has an order: the stream is drained and destroyed; the buffers free themselves behind this body
     ~Ctx() {
-        if (g_bm25_down) return;
+        if (rmu_runtime_down() || !stream) return;
         RMU_ENTRY();
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (DevBuf* b : {&stage, &partial, &out})
-            if (b->p) (void)rmu_free(b->p);
-        if (pin) (void)hipHostFree(pin);
-        if (stream) (void)hipStreamDestroy(stream);
+        (void)hipStreamSynchronize(stream);
+        (void)hipStreamDestroy(stream);
     }
 };
 thread_local Ctx g_ctx;
@@ -459,14 +422,14 @@ static void live_bitmap(const rmu_bm25* h, u32* words, const int64_t* allow, int
 static int upload_norms_and_bitmap(rmu_bm25* h, const std::vector<float>& norm, hipStream_t s) {
     const size_t N = h->dl.size(), nw = (N + 31) / 32 + 1;
     std::vector<u32> bits;
-    if (N) BM25_TRY(hipMemcpyAsync(h->doc_norm, norm.data(), N * sizeof(float), hipMemcpyHostToDevice, s));
+    if (N) RMU_HIP_TRY(hipMemcpyAsync(h->doc_norm, norm.data(), N * sizeof(float), hipMemcpyHostToDevice, s));
     if (h->n_live != N) {
-        try { bits.resize(nw); } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory while packing the index"); }
+        try { bits.resize(nw); } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_search: out of memory while packing the index"); }
         live_bitmap(h, bits.data(), nullptr, 0, nullptr);
-        if (!h->live_bits) BM25_TRY(hipMalloc((void**)&h->live_bits, nw * sizeof(u32)));
-        BM25_TRY(hipMemcpyAsync(h->live_bits, bits.data(), nw * sizeof(u32), hipMemcpyHostToDevice, s));
+        if (!h->live_bits) RMU_HIP_TRY(hipMalloc((void**)&h->live_bits, nw * sizeof(u32)));
+        RMU_HIP_TRY(hipMemcpyAsync(h->live_bits, bits.data(), nw * sizeof(u32), hipMemcpyHostToDevice, s));
     }
-    BM25_TRY(hipStreamSynchronize(s));             // (the host vectors are pageable and go out of scope)
+    RMU_HIP_TRY(hipStreamSynchronize(s));             // (the host vectors are pageable and go out of scope)
     return RMU_OK;
 }
 
@@ -482,7 +445,7 @@ static int build_image(rmu_bm25* h, hipStream_t s) {
         h->imaged.resize(V);
         pk.resize(2 * (size_t)h->live_nnz);
         live_weights_and_norms(h, h->weight, norm);
-    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory while packing the index"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_search: out of memory while packing the index"); }
     u32* pdoc = pk.data();
     u32* ptf = pk.data() + h->live_nnz;
     u64 at = 0;
@@ -502,14 +465,14 @@ static int build_image(rmu_bm25* h, hipStream_t s) {
         }
     }
     h->post_ptr[V] = at;
-    if (at != h->live_nnz) return mfail(RMU_E_INVALID, "rmu_bm25_search: internal error, the live posting count is out of step");
+    if (at != h->live_nnz) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: internal error, the live posting count is out of step");
     const size_t pbytes = (size_t)h->live_nnz * sizeof(u32);
-    BM25_TRY(hipMalloc((void**)&h->post_doc, pbytes ? pbytes : 4));
-    BM25_TRY(hipMalloc((void**)&h->post_tf, pbytes ? pbytes : 4));
-    BM25_TRY(hipMalloc((void**)&h->doc_norm, N ? N * sizeof(float) : 4));
+    RMU_HIP_TRY(hipMalloc((void**)&h->post_doc, pbytes ? pbytes : 4));
+    RMU_HIP_TRY(hipMalloc((void**)&h->post_tf, pbytes ? pbytes : 4));
+    RMU_HIP_TRY(hipMalloc((void**)&h->doc_norm, N ? N * sizeof(float) : 4));
     if (pbytes) {
-        BM25_TRY(hipMemcpyAsync(h->post_doc, pdoc, pbytes, hipMemcpyHostToDevice, s));
-        BM25_TRY(hipMemcpyAsync(h->post_tf, ptf, pbytes, hipMemcpyHostToDevice, s));
+        RMU_HIP_TRY(hipMemcpyAsync(h->post_doc, pdoc, pbytes, hipMemcpyHostToDevice, s));
+        RMU_HIP_TRY(hipMemcpyAsync(h->post_tf, ptf, pbytes, hipMemcpyHostToDevice, s));
     }
     const int rc = upload_norms_and_bitmap(h, norm, s);
     if (rc != RMU_OK) return rc;
@@ -527,7 +490,7 @@ static int refresh_image(rmu_bm25* h, hipStream_t s) {
     std::vector<float> norm;
     try {
         live_weights_and_norms(h, h->weight, norm);
-    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory while refreshing the index"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_search: out of memory while refreshing the index"); }
     const int rc = upload_norms_and_bitmap(h, norm, s);
     if (rc != RMU_OK) return rc;
     h->stale = false;
@@ -547,7 +510,7 @@ static int splice_image(rmu_bm25* h, hipStream_t s) {
         new_ptr.resize(V + 1);
         dk.resize(2 * (size_t)nnz_delta);
         h->imaged.resize(V, 0);
-    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory while packing the added documents"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_search: out of memory while packing the added documents"); }
     u32* ddoc = dk.data();
     u32* dtf = dk.data() + nnz_delta;
     u64 at = 0;                   // in the delta
@@ -557,7 +520,7 @@ static int splice_image(rmu_bm25* h, hipStream_t s) {
         new_ptr[t] = old_ptr[t] + at;
         const size_t done = h->imaged[t], n = ps.doc.size() - done;
         if (n) {
-            if (n > nnz_delta - at) return mfail(RMU_E_INVALID, "rmu_bm25_search: internal error, the added posting count is out of step");
+            if (n > nnz_delta - at) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: internal error, the added posting count is out of step");
             memcpy(ddoc + at, ps.doc.data() + done, n * sizeof(u32));
             memcpy(dtf + at, ps.tf.data() + done, n * sizeof(u32));
             at += n;
@@ -565,7 +528,7 @@ static int splice_image(rmu_bm25* h, hipStream_t s) {
     }
     old_ptr[V] = nnz_old;
     new_ptr[V] = nnz_new;
-    if (at != nnz_delta) return mfail(RMU_E_INVALID, "rmu_bm25_search: internal error, the added posting count is out of step");
+    if (at != nnz_delta) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: internal error, the added posting count is out of step");
 
     struct Held {                 // device arrays that are not the handle's yet
         void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -573,17 +536,17 @@ static int splice_image(rmu_bm25* h, hipStream_t s) {
     } held;
     void*& d_ptr = held.p[0]; void*& d_delta = held.p[1]; void*& d_doc = held.p[2]; void*& d_tf = held.p[3]; void*& d_norm = held.p[4];
     const size_t ptr_bytes = (V + 1) * sizeof(u64), delta_bytes = (size_t)nnz_delta * sizeof(u32), new_bytes = (size_t)nnz_new * sizeof(u32);
-    BM25_TRY(hipMalloc(&d_ptr, 2 * ptr_bytes));
-    BM25_TRY(hipMalloc(&d_delta, delta_bytes ? 2 * delta_bytes : 4));
-    BM25_TRY(hipMalloc(&d_doc, new_bytes ? new_bytes : 4));
-    BM25_TRY(hipMalloc(&d_tf, new_bytes ? new_bytes : 4));
-    BM25_TRY(hipMalloc(&d_norm, N * sizeof(float)));
+    RMU_HIP_TRY(hipMalloc(&d_ptr, 2 * ptr_bytes));
+    RMU_HIP_TRY(hipMalloc(&d_delta, delta_bytes ? 2 * delta_bytes : 4));
+    RMU_HIP_TRY(hipMalloc(&d_doc, new_bytes ? new_bytes : 4));
+    RMU_HIP_TRY(hipMalloc(&d_tf, new_bytes ? new_bytes : 4));
+    RMU_HIP_TRY(hipMalloc(&d_norm, N * sizeof(float)));
     if (nnz_new) {
-        BM25_TRY(hipMemcpyAsync(d_ptr, old_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, s));
-        BM25_TRY(hipMemcpyAsync((char*)d_ptr + ptr_bytes, new_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, s));
-        if (delta_bytes) BM25_TRY(hipMemcpyAsync(d_delta, dk.data(), 2 * delta_bytes, hipMemcpyHostToDevice, s));
+        RMU_HIP_TRY(hipMemcpyAsync(d_ptr, old_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, s));
+        RMU_HIP_TRY(hipMemcpyAsync((char*)d_ptr + ptr_bytes, new_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, s));
+        if (delta_bytes) RMU_HIP_TRY(hipMemcpyAsync(d_delta, dk.data(), 2 * delta_bytes, hipMemcpyHostToDevice, s));
         const u64 wgs = (nnz_new + kSpliceSpan - 1) / kSpliceSpan;
-        if (wgs > 0x7FFFFFFFull) return mfail(RMU_E_INVALID, "rmu_bm25_search: too many postings for one splice launch");
+        if (wgs > 0x7FFFFFFFull) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: too many postings for one splice launch");
         SpliceLaunch L{};
         L.old_doc = h->post_doc; L.old_tf = h->post_tf;
         L.delta_doc = (const u32*)d_delta; L.delta_tf = (const u32*)d_delta + nnz_delta;
@@ -591,8 +554,8 @@ static int splice_image(rmu_bm25* h, hipStream_t s) {
         L.old_ptr = (const u64*)d_ptr; L.new_ptr = (const u64*)((const char*)d_ptr + ptr_bytes);
         L.nnz_new = nnz_new; L.n_terms = (u32)V;
         hipLaunchKernelGGL(bm25_splice_kernel, dim3((unsigned)wgs), dim3(kBlock), 0, s, L);
-        BM25_TRY(hipGetLastError());
-        BM25_TRY(hipStreamSynchronize(s));         // (the host vectors are pageable; the old arrays are free to go)
+        RMU_HIP_TRY(hipGetLastError());
+        RMU_HIP_TRY(hipStreamSynchronize(s));         // (the host vectors are pageable; the old arrays are free to go)
         h->upload_bytes += 2 * ptr_bytes + 2 * delta_bytes;
     }
     for (void* q : {(void*)h->post_doc, (void*)h->post_tf, (void*)h->doc_norm, (void*)h->live_bits})
@@ -610,11 +573,11 @@ static int splice_image(rmu_bm25* h, hipStream_t s) {
 
 extern "C" int rmu_bm25_create(rmu_bm25_t** out, double k1, double b, double epsilon) {
     RMU_ENTRY();
-    if (!out) return mfail(RMU_E_INVALID, "rmu_bm25_create: null argument");
+    if (!out) return rmu_fail(RMU_E_INVALID, "rmu_bm25_create: null argument");
     if (!(k1 >= 0.0) || !std::isfinite(k1) || !(b >= 0.0 && b <= 1.0) || !std::isfinite(epsilon))
-        return mfail(RMU_E_INVALID, "rmu_bm25_create: k1 must be finite and >= 0, b in [0, 1], epsilon finite");
+        return rmu_fail(RMU_E_INVALID, "rmu_bm25_create: k1 must be finite and >= 0, b in [0, 1], epsilon finite");
     rmu_bm25* h = new (std::nothrow) rmu_bm25();
-    if (!h) return mfail(RMU_E_OOM, "rmu_bm25_create: out of memory");
+    if (!h) return rmu_fail(RMU_E_OOM, "rmu_bm25_create: out of memory");
     h->k1 = k1; h->b = b; h->epsilon = epsilon;
     *out = h;
     return RMU_OK;
@@ -633,18 +596,18 @@ extern "C" int rmu_bm25_free(rmu_bm25_t* h) {
 
 extern "C" int rmu_bm25_add_texts(rmu_bm25_t* h, const char* blob, int64_t bytes, int64_t n, int64_t* first_doc) {
     RMU_ENTRY();
-    if (!h || n < 0 || bytes < n || (n > 0 && !blob)) return mfail(RMU_E_INVALID, "rmu_bm25_add_texts: bad argument");
+    if (!h || n < 0 || bytes < n || (n > 0 && !blob)) return rmu_fail(RMU_E_INVALID, "rmu_bm25_add_texts: bad argument");
     std::unique_lock<std::shared_mutex> lk(h->mu);
-    if (h->broken) return mfail(RMU_E_OOM, "rmu_bm25_add_texts: an earlier add ran out of memory, the index is unusable");
-    if ((uint64_t)h->dl.size() + (uint64_t)n > 0x7FFFFFFFull) return mfail(RMU_E_INVALID, "rmu_bm25_add_texts: more than 2^31 - 1 documents");
+    if (h->broken) return rmu_fail(RMU_E_OOM, "rmu_bm25_add_texts: an earlier add ran out of memory, the index is unusable");
+    if ((uint64_t)h->dl.size() + (uint64_t)n > 0x7FFFFFFFull) return rmu_fail(RMU_E_INVALID, "rmu_bm25_add_texts: more than 2^31 - 1 documents");
     if (first_doc) *first_doc = (int64_t)h->dl.size();
     if (n == 0) {
-        if (bytes != 0) return mfail(RMU_E_INVALID, "rmu_bm25_add_texts: the blob does not hold exactly n NUL-terminated strings");
+        if (bytes != 0) return rmu_fail(RMU_E_INVALID, "rmu_bm25_add_texts: the blob does not hold exactly n NUL-terminated strings");
         return RMU_OK;
     }
     try {
         std::vector<std::pair<const char*, size_t>> docs;
-        if (!split_blob(blob, bytes, n, docs)) return mfail(RMU_E_INVALID, "rmu_bm25_add_texts: the blob does not hold exactly n NUL-terminated strings");
+        if (!split_blob(blob, bytes, n, docs)) return rmu_fail(RMU_E_INVALID, "rmu_bm25_add_texts: the blob does not hold exactly n NUL-terminated strings");
         if (h->dirty || h->opt_repack_on_add) h->dirty = true;
         else h->grown = true;                   // (clean or stale: the next search splices the new postings in)
         h->broken = true;                       // until the add is complete
@@ -681,13 +644,13 @@ extern "C" int rmu_bm25_add_texts(rmu_bm25_t* h, const char* blob, int64_t bytes
             h->live_len += seen.size();
         }
         h->broken = false;
-    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_add_texts: out of memory, the index is unusable"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_add_texts: out of memory, the index is unusable"); }
     return RMU_OK;
 }
 
 extern "C" int rmu_bm25_stat(rmu_bm25_t* h, int what, double* out) {
     RMU_ENTRY();
-    if (!h || !out) return mfail(RMU_E_INVALID, "rmu_bm25_stat: null argument");
+    if (!h || !out) return rmu_fail(RMU_E_INVALID, "rmu_bm25_stat: null argument");
     std::shared_lock<std::shared_mutex> lk(h->mu);
     switch (what) {
         case RMU_BM25_STAT_DOCS: *out = (double)h->dl.size(); break;
@@ -698,45 +661,45 @@ extern "C" int rmu_bm25_stat(rmu_bm25_t* h, int what, double* out) {
         case RMU_BM25_STAT_IMAGE_PACKS: *out = (double)h->n_packs; break;
         case RMU_BM25_STAT_IMAGE_SPLICES: *out = (double)h->n_splices; break;
         case RMU_BM25_STAT_IMAGE_UPLOAD_BYTES: *out = (double)h->upload_bytes; break;
-        default: return mfail(RMU_E_INVALID, "rmu_bm25_stat: unknown statistic");
+        default: return rmu_fail(RMU_E_INVALID, "rmu_bm25_stat: unknown statistic");
     }
     return RMU_OK;
 }
 
 extern "C" int rmu_bm25_df(rmu_bm25_t* h, const char* term_utf8, int64_t* df) {
     RMU_ENTRY();
-    if (!h || !term_utf8 || !df) return mfail(RMU_E_INVALID, "rmu_bm25_df: null argument");
+    if (!h || !term_utf8 || !df) return rmu_fail(RMU_E_INVALID, "rmu_bm25_df: null argument");
     std::shared_lock<std::shared_mutex> lk(h->mu);
     try {
         const auto it = h->ids.find(term_utf8);
         *df = it == h->ids.end() ? 0 : (int64_t)h->df[it->second];
-    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_df: out of memory"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_df: out of memory"); }
     return RMU_OK;
 }
 
 extern "C" int rmu_bm25_set_option(rmu_bm25_t* h, int option, int64_t value) {
     RMU_ENTRY();
-    if (!h) return mfail(RMU_E_INVALID, "rmu_bm25_set_option: null handle");
+    if (!h) return rmu_fail(RMU_E_INVALID, "rmu_bm25_set_option: null handle");
     std::unique_lock<std::shared_mutex> lk(h->mu);
     switch (option) {
         case RMU_BM25_OPT_TILE_DOCS:
             if (value != 0 && (value < 64 || value > kMaxTile || (value & (value - 1))))
-                return mfail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_TILE_DOCS takes 0 or a power of two in [64, 8192]");
+                return rmu_fail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_TILE_DOCS takes 0 or a power of two in [64, 8192]");
             h->opt_tile = value;
             break;
         case RMU_BM25_OPT_MAX_WGS:
-            if (value < 0 || value > kMaxParts) return mfail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_MAX_WGS takes 0 .. 1024");
+            if (value < 0 || value > kMaxParts) return rmu_fail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_MAX_WGS takes 0 .. 1024");
             h->opt_max_wgs = value;
             break;
         case RMU_BM25_OPT_REPACK_ON_REMOVE:
-            if (value != 0 && value != 1) return mfail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_REPACK_ON_REMOVE takes 0 or 1");
+            if (value != 0 && value != 1) return rmu_fail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_REPACK_ON_REMOVE takes 0 or 1");
             h->opt_repack_on_remove = value;
             break;
         case RMU_BM25_OPT_REPACK_ON_ADD:
-            if (value != 0 && value != 1) return mfail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_REPACK_ON_ADD takes 0 or 1");
+            if (value != 0 && value != 1) return rmu_fail(RMU_E_INVALID, "rmu_bm25_set_option: RMU_BM25_OPT_REPACK_ON_ADD takes 0 or 1");
             h->opt_repack_on_add = value;
             break;
-        default: return mfail(RMU_E_INVALID, "rmu_bm25_set_option: unknown option");
+        default: return rmu_fail(RMU_E_INVALID, "rmu_bm25_set_option: unknown option");
     }
     return RMU_OK;
 }
@@ -750,19 +713,19 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
                           int64_t n_sub, int64_t expect_docs, uint64_t hip_stream, std::shared_lock<std::shared_mutex>& lk, hipStream_t* s_out,
                           int64_t** d_docs_out, float** d_scores_out, bool* empty) {
     *empty = false;
-    if (!h || !query_blob) return mfail(RMU_E_INVALID, "rmu_bm25_search: null argument");
-    if (nq < 1 || nq > 65535 || bytes < nq) return mfail(RMU_E_INVALID, "rmu_bm25_search: 1 <= nq <= 65535 queries, each NUL-terminated");
-    if (k < 1 || k > RMU_MAX_K) return mfail(RMU_E_INVALID, "rmu_bm25_search: 1 <= k <= RMU_MAX_K");
+    if (!h || !query_blob) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: null argument");
+    if (nq < 1 || nq > 65535 || bytes < nq) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: 1 <= nq <= 65535 queries, each NUL-terminated");
+    if (k < 1 || k > RMU_MAX_K) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: 1 <= k <= RMU_MAX_K");
     std::vector<std::pair<const char*, size_t>> qs;
     std::vector<std::vector<std::string>> toks;
     try {
-        if (!split_blob(query_blob, bytes, nq, qs)) return mfail(RMU_E_INVALID, "rmu_bm25_search: the blob does not hold exactly nq NUL-terminated strings");
+        if (!split_blob(query_blob, bytes, nq, qs)) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: the blob does not hold exactly nq NUL-terminated strings");
         toks.resize((size_t)nq);
         for (int64_t i = 0; i < nq; ++i) {
             split_tokens(qs[i].first, qs[i].second, [&](const char* p, size_t len) { toks[i].emplace_back(p, len); });
-            if (toks[i].size() > (size_t)kMaxTerms) return mfail(RMU_E_INVALID, "rmu_bm25_search: a query has more than 1024 tokens");
+            if (toks[i].size() > (size_t)kMaxTerms) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: a query has more than 1024 tokens");
         }
-    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory while tokenising"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_search: out of memory while tokenising"); }
 
     Ctx& c = g_ctx;
     hipStream_t s = nullptr;
@@ -772,19 +735,19 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
     };
     lk = std::shared_lock<std::shared_mutex>(h->mu);
     for (;;) {
-        if (h->broken) return mfail(RMU_E_OOM, "rmu_bm25_search: an earlier add ran out of memory, the index is unusable");
+        if (h->broken) return rmu_fail(RMU_E_OOM, "rmu_bm25_search: an earlier add ran out of memory, the index is unusable");
         if (expect_docs >= 0 && (int64_t)h->dl.size() != expect_docs)
-            return mfail(RMU_E_INVALID, "rmu_hybrid_search: the sparse key table (" + std::to_string(expect_docs) + " keys) and the BM25 index (" +
+            return rmu_fail(RMU_E_INVALID, "rmu_hybrid_search: the sparse key table (" + std::to_string(expect_docs) + " keys) and the BM25 index (" +
                                             std::to_string(h->dl.size()) + " documents) are out of step");
         if (subset) {                            // (again after the lock was given up: documents may have been added, never renumbered unseen)
             const int64_t n_docs = (int64_t)h->dl.size();
             for (int64_t i = 0; i < n_sub; ++i)
                 if (docs[i] < 0 || docs[i] >= n_docs || (i > 0 && docs[i] <= docs[i - 1]))
-                    return mfail(RMU_E_INVALID, "rmu_bm25_search_subset: docs must be strictly ascending document ids in [0, DOCS)");
+                    return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_subset: docs must be strictly ascending document ids in [0, DOCS)");
         }
         if (h->n_live == 0 || (subset && n_sub == 0)) return nothing();     // nothing to search: no device work at all
         if (!s) {
-            if (c.ensure_stream() != RMU_OK) return mfail(RMU_E_HIP, "rmu_bm25_search: cannot create a stream");
+            if (c.ensure_stream() != RMU_OK) return rmu_fail(RMU_E_HIP, "rmu_bm25_search: cannot create a stream");
             s = hip_stream ? (hipStream_t)hip_stream : c.stream;
         }
         if (!h->dirty && !h->stale && !h->grown) break;
@@ -806,10 +769,10 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
     for (const auto& t : toks) n_terms += t.size();
     const size_t ptr_bytes = ((size_t)(nq + 1) * sizeof(u32) + 15) & ~(size_t)15;
     const size_t mask_bytes = subset ? (((size_t)N + 31) / 32 + 1) * sizeof(u32) : 0;      // allow AND live, behind the descriptors
-    if (c.ensure_pin(ptr_bytes + (n_terms ? n_terms : 1) * sizeof(TermDesc) + mask_bytes) != RMU_OK)
-        return mfail(RMU_E_OOM, "rmu_bm25_search: pinned staging buffer");
-    u32* tp = (u32*)c.pin;
-    TermDesc* td = (TermDesc*)(c.pin + ptr_bytes);
+    if (c.pin.ensure(ptr_bytes + (n_terms ? n_terms : 1) * sizeof(TermDesc) + mask_bytes) != RMU_OK)
+        return rmu_fail(RMU_E_OOM, "rmu_bm25_search: pinned staging buffer");
+    u32* tp = (u32*)c.pin.p;
+    TermDesc* td = (TermDesc*)(c.pin.p + ptr_bytes);
     u32 nd = 0;
     try {
         for (int64_t i = 0; i < nq; ++i) {
@@ -822,12 +785,12 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
                 td[nd++] = TermDesc{h->post_ptr[id], (u32)(h->post_ptr[id + 1] - h->post_ptr[id]), h->weight[id]};
             }
         }
-    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_search: out of memory"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_search: out of memory"); }
     tp[nq] = nd;
     const size_t desc_bytes = ptr_bytes + (size_t)nd * sizeof(TermDesc);       // (a multiple of 16: the bitmap's word pairs are aligned)
     if (subset) {
         int64_t n_cand = 0;
-        live_bitmap(h, (u32*)(c.pin + desc_bytes), docs, n_sub, &n_cand);
+        live_bitmap(h, (u32*)(c.pin.p + desc_bytes), docs, n_sub, &n_cand);
         if (n_cand == 0) return nothing();
     }
     const size_t stage_bytes = desc_bytes + mask_bytes;
@@ -843,13 +806,13 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
     if (!max_wgs) max_wgs = std::min<int64_t>(kMaxParts, std::max<int64_t>(8, 4096 / nq));
     const int64_t tiles_per_wg = (tiles_total + max_wgs - 1) / max_wgs;
     const int parts = (int)((tiles_total + tiles_per_wg - 1) / tiles_per_wg);
-    if (tiles_per_wg * tile > 0x7FFFFFFFll) return mfail(RMU_E_INVALID, "rmu_bm25_search: document range of one workgroup too large");
+    if (tiles_per_wg * tile > 0x7FFFFFFFll) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: document range of one workgroup too large");
 
     const size_t out_bytes = (size_t)nq * k * (sizeof(int64_t) + sizeof(float));
-    BM25_TRY(c.stage.ensure(stage_bytes));
-    BM25_TRY(c.partial.ensure((size_t)parts * nq * k * sizeof(u64)));
-    BM25_TRY(c.out.ensure(out_bytes));
-    BM25_TRY(hipMemcpyAsync(c.stage.p, c.pin, stage_bytes, hipMemcpyHostToDevice, s));
+    RMU_HIP_TRY(c.stage.ensure(stage_bytes));
+    RMU_HIP_TRY(c.partial.ensure((size_t)parts * nq * k * sizeof(u64)));
+    RMU_HIP_TRY(c.out.ensure(out_bytes));
+    RMU_HIP_TRY(hipMemcpyAsync(c.stage.p, c.pin.p, stage_bytes, hipMemcpyHostToDevice, s));
     Bm25Launch L{};
     L.post_doc = h->post_doc; L.post_tf = h->post_tf; L.doc_norm = h->doc_norm;
     L.term_ptr = (const u32*)c.stage.p;
@@ -865,11 +828,11 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
         if (k <= 64) hipLaunchKernelGGL(bm25_masked_kernel<1>, grid, block, 0, s, L);
         else hipLaunchKernelGGL(bm25_masked_kernel<2>, grid, block, 0, s, L);
     }
-    BM25_TRY(hipGetLastError());
+    RMU_HIP_TRY(hipGetLastError());
     int64_t* d_docs = (int64_t*)c.out.p;
     float* d_scores = (float*)((char*)c.out.p + (size_t)nq * k * sizeof(int64_t));
     const int rc = rmu_merge_final_launch((const u64*)c.partial.p, parts, nq, k, doc_base, 0, nullptr, d_scores, d_docs, nullptr, nullptr, s);
-    if (rc != RMU_OK) { (void)hipStreamSynchronize(s); return mfail(rc, "rmu_bm25_search: merge launch failed"); }
+    if (rc != RMU_OK) { (void)hipStreamSynchronize(s); return rmu_fail(rc, "rmu_bm25_search: merge launch failed"); }
     *s_out = s;
     *d_docs_out = d_docs;
     *d_scores_out = d_scores;
@@ -880,7 +843,7 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
 // copies to the caller's arrays and the one synchronisation
 static int search_impl(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, bool subset, const int64_t* docs,
                        int64_t n_sub, float* out_scores, int64_t* out_docs, uint64_t hip_stream) {
-    if (!h || !query_blob || !out_scores || !out_docs) return mfail(RMU_E_INVALID, "rmu_bm25_search: null argument");
+    if (!h || !query_blob || !out_scores || !out_docs) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: null argument");
     std::shared_lock<std::shared_mutex> lk;
     hipStream_t s = nullptr;
     int64_t* d_docs = nullptr;
@@ -892,9 +855,9 @@ static int search_impl(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int
         for (int64_t i = 0; i < nq * k; ++i) { out_scores[i] = -INFINITY; out_docs[i] = -1; }
         return RMU_OK;
     }
-    BM25_TRY(hipMemcpyAsync(out_docs, d_docs, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    BM25_TRY(hipMemcpyAsync(out_scores, d_scores, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s));
-    BM25_TRY(hipStreamSynchronize(s));
+    RMU_HIP_TRY(hipMemcpyAsync(out_docs, d_docs, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipMemcpyAsync(out_scores, d_scores, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipStreamSynchronize(s));
     return RMU_OK;
 }
 
@@ -918,7 +881,7 @@ extern "C" int rmu_bm25_search(rmu_bm25_t* h, const char* query_blob, int64_t by
 extern "C" int rmu_bm25_search_subset(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, const int64_t* docs,
                                       int64_t n_sub, float* out_scores, int64_t* out_docs, uint64_t hip_stream) {
     RMU_ENTRY();
-    if (n_sub < 0 || (n_sub > 0 && !docs)) return mfail(RMU_E_INVALID, "rmu_bm25_search_subset: bad document list");
+    if (n_sub < 0 || (n_sub > 0 && !docs)) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_subset: bad document list");
     return search_impl(h, query_blob, bytes, nq, k, doc_base, true, docs, n_sub, out_scores, out_docs, hip_stream);
 }
 
@@ -942,12 +905,12 @@ static void recount_live(rmu_bm25* h) {
 
 extern "C" int rmu_bm25_remove_docs(rmu_bm25_t* h, const int64_t* docs, int64_t n, int64_t* n_removed) {
     RMU_ENTRY();
-    if (!h || n < 0 || (n > 0 && !docs)) return mfail(RMU_E_INVALID, "rmu_bm25_remove_docs: bad argument");
+    if (!h || n < 0 || (n > 0 && !docs)) return rmu_fail(RMU_E_INVALID, "rmu_bm25_remove_docs: bad argument");
     std::unique_lock<std::shared_mutex> lk(h->mu);
-    if (h->broken) return mfail(RMU_E_OOM, "rmu_bm25_remove_docs: an earlier add ran out of memory, the index is unusable");
+    if (h->broken) return rmu_fail(RMU_E_OOM, "rmu_bm25_remove_docs: an earlier add ran out of memory, the index is unusable");
     const int64_t N = (int64_t)h->dl.size();
     for (int64_t i = 0; i < n; ++i)
-        if (docs[i] < 0 || docs[i] >= N) return mfail(RMU_E_INVALID, "rmu_bm25_remove_docs: a document id is outside [0, DOCS)");
+        if (docs[i] < 0 || docs[i] >= N) return rmu_fail(RMU_E_INVALID, "rmu_bm25_remove_docs: a document id is outside [0, DOCS)");
     int64_t removed = 0;
     for (int64_t i = 0; i < n; ++i) {
         const size_t d = (size_t)docs[i];
@@ -967,11 +930,11 @@ extern "C" int rmu_bm25_remove_docs(rmu_bm25_t* h, const int64_t* docs, int64_t 
 
 extern "C" int rmu_bm25_compact(rmu_bm25_t* h, int64_t* old_to_new, int64_t map_len, int64_t* n_after) {
     RMU_ENTRY();
-    if (!h || !old_to_new) return mfail(RMU_E_INVALID, "rmu_bm25_compact: null argument");
+    if (!h || !old_to_new) return rmu_fail(RMU_E_INVALID, "rmu_bm25_compact: null argument");
     std::unique_lock<std::shared_mutex> lk(h->mu);
-    if (h->broken) return mfail(RMU_E_OOM, "rmu_bm25_compact: an earlier add ran out of memory, the index is unusable");
+    if (h->broken) return rmu_fail(RMU_E_OOM, "rmu_bm25_compact: an earlier add ran out of memory, the index is unusable");
     const size_t N = h->dl.size();
-    if (map_len < (int64_t)N) return mfail(RMU_E_INVALID, "rmu_bm25_compact: old_to_new holds fewer entries than the index has documents");
+    if (map_len < (int64_t)N) return rmu_fail(RMU_E_INVALID, "rmu_bm25_compact: old_to_new holds fewer entries than the index has documents");
     u32 next = 0;
     for (size_t d = 0; d < N; ++d) old_to_new[d] = h->live[d] ? (int64_t)next++ : -1;
     for (int64_t d = (int64_t)N; d < map_len; ++d) old_to_new[d] = -1;
@@ -1009,12 +972,12 @@ struct File {
 
 extern "C" int rmu_bm25_save(rmu_bm25_t* h, const char* path) {
     RMU_ENTRY();
-    if (!h || !path) return mfail(RMU_E_INVALID, "rmu_bm25_save: null argument");
+    if (!h || !path) return rmu_fail(RMU_E_INVALID, "rmu_bm25_save: null argument");
     std::shared_lock<std::shared_mutex> lk(h->mu);
-    if (h->broken) return mfail(RMU_E_OOM, "rmu_bm25_save: an earlier add ran out of memory, the index is unusable");
+    if (h->broken) return rmu_fail(RMU_E_OOM, "rmu_bm25_save: an earlier add ran out of memory, the index is unusable");
     File fl;
     fl.f = fopen(path, "wb");
-    if (!fl.f) return mfail(RMU_E_INVALID, std::string("rmu_bm25_save: cannot open ") + path + " for writing");
+    if (!fl.f) return rmu_fail(RMU_E_INVALID, std::string("rmu_bm25_save: cannot open ") + path + " for writing");
     bool ok = true;
     const auto put = [&](const void* p, size_t bytes) { if (bytes && fwrite(p, 1, bytes, fl.f) != bytes) ok = false; };
     const uint64_t N = h->dl.size(), V = h->terms.size();
@@ -1032,21 +995,21 @@ extern "C" int rmu_bm25_save(rmu_bm25_t* h, const char* path) {
             put(&len, 4);
             put(names[t]->data(), len);
         }
-    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_save: out of memory"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_save: out of memory"); }
     uint64_t at = 0;
     for (uint64_t t = 0; t < V; ++t) { put(&at, 8); at += h->terms[t].doc.size(); }
     put(&at, 8);
     for (const auto& ps : h->terms) put(ps.doc.data(), ps.doc.size() * sizeof(u32));
     for (const auto& ps : h->terms) put(ps.tf.data(), ps.tf.size() * sizeof(u32));
     if (fflush(fl.f) != 0) ok = false;
-    if (!ok) return mfail(RMU_E_INVALID, std::string("rmu_bm25_save: writing ") + path + " failed");
+    if (!ok) return rmu_fail(RMU_E_INVALID, std::string("rmu_bm25_save: writing ") + path + " failed");
     return RMU_OK;
 }
 
 extern "C" int rmu_bm25_load(rmu_bm25_t** out, const char* path) {
     RMU_ENTRY();
-    if (!out || !path) return mfail(RMU_E_INVALID, "rmu_bm25_load: null argument");
-    const auto bad = [&](const char* what) { return mfail(RMU_E_INVALID, std::string("rmu_bm25_load: ") + path + ": " + what); };
+    if (!out || !path) return rmu_fail(RMU_E_INVALID, "rmu_bm25_load: null argument");
+    const auto bad = [&](const char* what) { return rmu_fail(RMU_E_INVALID, std::string("rmu_bm25_load: ") + path + ": " + what); };
     File fl;
     fl.f = fopen(path, "rb");
     if (!fl.f) return bad("cannot open the file");
@@ -1075,7 +1038,7 @@ extern "C" int rmu_bm25_load(rmu_bm25_t** out, const char* path) {
         buf.resize((size_t)(size - kHeaderBytes));
         if (fread(buf.data(), 1, buf.size(), fl.f) != buf.size()) return bad("cannot read the file");
         h = new rmu_bm25();
-    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_load: out of memory"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_load: out of memory"); }
     struct Drop { rmu_bm25* h; ~Drop() { delete h; } } drop{h};
     h->k1 = k1; h->b = b; h->epsilon = eps;
     try {
@@ -1133,7 +1096,7 @@ extern "C" int rmu_bm25_load(rmu_bm25_t** out, const char* path) {
             if (sum[d] != h->dl[d]) return bad("a document's length differs from the sum of its term frequencies");
         h->nnz = nnz;
         recount_live(h);
-    } catch (...) { return mfail(RMU_E_OOM, "rmu_bm25_load: out of memory"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_load: out of memory"); }
     drop.h = nullptr;
     *out = h;
     return RMU_OK;

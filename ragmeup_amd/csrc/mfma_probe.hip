@@ -13,10 +13,8 @@
 #include <vector>
 
 #include "rmu_common.h"
+#include "rmu_host.h"
 #include "../../include/rmu.h"
-
-extern "C" void rmu_set_error_(const char* msg);
-static int pfail(int code, const std::string& m) { rmu_set_error_(m.c_str()); return code; }
 
 namespace {
 
@@ -103,11 +101,11 @@ unsigned short to_bf16(float f) { unsigned int u; memcpy(&u, &f, 4); u += 0x7fff
 extern "C" int rmu_probe_mfma_rate(int dtype, int variant, int millis, double* tflops_out) {
     RMU_ENTRY();
     if (!tflops_out || dtype < 0 || dtype > 1 || variant < 0 || variant > 1 || millis < 1 || millis > 10000)
-        return pfail(RMU_E_INVALID, "rmu_probe_mfma_rate: dtype 0 (f16) | 1 (bf16), variant 0 (registers only) | 1 (LDS fragment per MFMA + LDS-DMA fill), 1 <= millis <= 10000");
-    if (variant == 1 && dtype == 1) return pfail(RMU_E_INVALID, "rmu_probe_mfma_rate: the LDS / DMA skeleton is the f16 screening kernel's");
+        return rmu_fail(RMU_E_INVALID, "rmu_probe_mfma_rate: dtype 0 (f16) | 1 (bf16), variant 0 (registers only) | 1 (LDS fragment per MFMA + LDS-DMA fill), 1 <= millis <= 10000");
+    if (variant == 1 && dtype == 1) return rmu_fail(RMU_E_INVALID, "rmu_probe_mfma_rate: the LDS / DMA skeleton is the f16 screening kernel's");
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1)
-        return pfail(RMU_E_HIP, "rmu_probe_mfma_rate: no device");
+        return rmu_fail(RMU_E_HIP, "rmu_probe_mfma_rate: no device");
     // 128 fragments of 1 KiB, N(0, 3.3) -- fp16(64 x) of unit-vector elements in 384 dimensions (xorshift + Box-Muller: no libc state touched)
     const size_t nhalf = 128 * 512;
     std::vector<unsigned short> h(nhalf);
@@ -136,7 +134,7 @@ extern "C" int rmu_probe_mfma_rate(int dtype, int variant, int millis, double* t
         hipMemcpyAsync(d, h.data(), nhalf * 2, hipMemcpyHostToDevice, s) != hipSuccess ||
         (variant == 1 && hipMemsetAsync(strm, 1, sbytes, s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess) {
         cleanup();
-        return pfail(RMU_E_HIP, "rmu_probe_mfma_rate: set-up");
+        return rmu_fail(RMU_E_HIP, "rmu_probe_mfma_rate: set-up");
     }
     const int iters = 2000;                                        // 128k MFMAs per wave and launch: ~2-3 ms
     const double flop = (double)ncu * 8 * iters * 64 * 32768.0;
@@ -153,7 +151,7 @@ extern "C" int rmu_probe_mfma_rate(int dtype, int variant, int millis, double* t
         rates.push_back(flop / ms / 1e9);
     }
     cleanup();
-    if (rc || rates.empty()) return pfail(RMU_E_HIP, "rmu_probe_mfma_rate: launch / timing");
+    if (rc || rates.empty()) return rmu_fail(RMU_E_HIP, "rmu_probe_mfma_rate: launch / timing");
     // the power manager's steady state: mean over the last half of the launches (the first ones of a burst run 10-15 % slower)
     double sum = 0.0; size_t n = 0;
     for (size_t i = rates.size() / 2; i < rates.size(); ++i) { sum += rates[i]; ++n; }

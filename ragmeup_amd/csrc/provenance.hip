@@ -124,23 +124,23 @@ thread_local CosCtx g_ctx;
 // every argument but the encoder's; *total = sum of n_docs.  No HIP call
 int check_args(const std::string& w, const void* x, int64_t n, int dim, int64_t stride, const int32_t* groups, int n_groups, unsigned flags,
                const void* out_scores, int64_t* total) {
-    if (!x || !groups || !out_scores) return cos_fail(RMU_E_INVALID, w + ": null pointer");
-    if (flags & ~(RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE)) return cos_fail(RMU_E_INVALID, w + ": flags other than RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE");
-    if (dim < 1 || dim > RMU_MAX_DIM_WIDE) return cos_fail(RMU_E_INVALID, w + ": 1 <= dim <= RMU_MAX_DIM_WIDE (3072)");
-    if (stride < dim) return cos_fail(RMU_E_INVALID, w + ": stride must be >= dim");
-    if (n < 1) return cos_fail(RMU_E_INVALID, w + ": n must be >= 1");
-    if (stride > INT64_MAX / 4 / n) return cos_fail(RMU_E_INVALID, w + ": n * stride is too large");
-    if (n_groups < 0) return cos_fail(RMU_E_INVALID, w + ": n_groups must be >= 0");
+    if (!x || !groups || !out_scores) return rmu_fail(RMU_E_INVALID, w + ": null pointer");
+    if (flags & ~(RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE)) return rmu_fail(RMU_E_INVALID, w + ": flags other than RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE");
+    if (dim < 1 || dim > RMU_MAX_DIM_WIDE) return rmu_fail(RMU_E_INVALID, w + ": 1 <= dim <= RMU_MAX_DIM_WIDE (3072)");
+    if (stride < dim) return rmu_fail(RMU_E_INVALID, w + ": stride must be >= dim");
+    if (n < 1) return rmu_fail(RMU_E_INVALID, w + ": n must be >= 1");
+    if (stride > INT64_MAX / 4 / n) return rmu_fail(RMU_E_INVALID, w + ": n * stride is too large");
+    if (n_groups < 0) return rmu_fail(RMU_E_INVALID, w + ": n_groups must be >= 0");
     int64_t sum = 0;
     for (int g = 0; g < n_groups; ++g) {
         const int32_t* t = groups + 4 * (int64_t)g;
         const std::string at = w + ": group " + std::to_string(g);
-        if (t[0] < 0 || t[0] >= n) return cos_fail(RMU_E_INVALID, at + ": the answer row is outside [0, n)");
-        if (t[1] < -1 || t[1] >= n) return cos_fail(RMU_E_INVALID, at + ": the query row is outside [0, n) and not -1");
-        if (t[3] < 0) return cos_fail(RMU_E_INVALID, at + ": n_docs must be >= 0");
-        if (t[2] < 0 || t[2] >= n || (int64_t)t[2] + t[3] > n) return cos_fail(RMU_E_INVALID, at + ": the document rows are outside [0, n)");
+        if (t[0] < 0 || t[0] >= n) return rmu_fail(RMU_E_INVALID, at + ": the answer row is outside [0, n)");
+        if (t[1] < -1 || t[1] >= n) return rmu_fail(RMU_E_INVALID, at + ": the query row is outside [0, n) and not -1");
+        if (t[3] < 0) return rmu_fail(RMU_E_INVALID, at + ": n_docs must be >= 0");
+        if (t[2] < 0 || t[2] >= n || (int64_t)t[2] + t[3] > n) return rmu_fail(RMU_E_INVALID, at + ": the document rows are outside [0, n)");
         sum += t[3];
-        if (sum > INT32_MAX) return cos_fail(RMU_E_INVALID, w + ": the sum of n_docs does not fit in an int32");
+        if (sum > INT32_MAX) return rmu_fail(RMU_E_INVALID, w + ": the sum of n_docs does not fit in an int32");
     }
     *total = sum;
     return RMU_OK;
@@ -158,18 +158,18 @@ int attribution_on(const std::string& w, const float* x, int64_t n, int dim, int
     const size_t tab_bytes = ((size_t)n_groups * kTab * sizeof(int32_t) + 7) & ~(size_t)7;
     const size_t score_bytes = (size_t)total * sizeof(double);
     const size_t out_bytes = score_bytes * (out_sims ? 3 : 1);                                      // scores [total] | sims [total, 2]
-    if (!in_dev) COS_TRY(c.in.ensure(in_bytes));
-    COS_TRY(c.tab.ensure(tab_bytes));
-    if (!out_dev) COS_TRY(c.out.ensure(out_bytes));
-    if (c.ensure_pin(tab_bytes + (out_dev ? 0 : out_bytes)) != RMU_OK) return cos_fail(RMU_E_OOM, w + ": pinned buffer");
-    int32_t* tab = (int32_t*)c.pin;
+    if (!in_dev) RMU_HIP_TRY(c.in.ensure(in_bytes));
+    RMU_HIP_TRY(c.tab.ensure(tab_bytes));
+    if (!out_dev) RMU_HIP_TRY(c.out.ensure(out_bytes));
+    if (c.pin.ensure(tab_bytes + (out_dev ? 0 : out_bytes)) != RMU_OK) return rmu_fail(RMU_E_OOM, w + ": pinned buffer");
+    int32_t* tab = (int32_t*)c.pin.p;
     int32_t out0 = 0;
     for (int g = 0; g < n_groups; ++g) {
         memcpy(tab + (size_t)kTab * g, groups + 4 * (size_t)g, 4 * sizeof(int32_t));
         tab[(size_t)kTab * g + 4] = out0;
         out0 += groups[4 * (size_t)g + 3];
     }
-    char* land = c.pin + tab_bytes;
+    char* land = c.pin.p + tab_bytes;
     const float* dx = x;
     double* d_scores = out_scores;
     double* d_sims = out_sims;
@@ -190,7 +190,7 @@ int attribution_on(const std::string& w, const float* x, int64_t n, int dim, int
     const hipError_t es = hipStreamSynchronize(s);              // always: the table went through the thread's pinned buffer
     rmu_thread_finished_(s, true);
     if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return cos_fail(RMU_E_HIP, w + ": " + hipGetErrorString(e));
+    if (e != hipSuccess) return rmu_fail(RMU_E_HIP, w + ": " + hipGetErrorString(e));
     if (!out_dev) {
         memcpy(out_scores, land, score_bytes);
         if (out_sims) memcpy(out_sims, land + score_bytes, 2 * score_bytes);
@@ -219,6 +219,6 @@ extern "C" int rmu_attribution_check_(const char* who, int64_t n, int dim, const
 extern "C" int rmu_attribution_dev_(const char* who, const float* x_dev, int64_t n, int dim, int64_t stride, const int32_t* groups, int n_groups,
                                     int64_t total, double* out_scores, double* out_sims, void* hip_stream) {
     RMU_ENTRY();
-    if (!x_dev || !hip_stream) return cos_fail(RMU_E_INVALID, std::string(who) + ": null pointer");
+    if (!x_dev || !hip_stream) return rmu_fail(RMU_E_INVALID, std::string(who) + ": null pointer");
     return attribution_on(who, x_dev, n, dim, stride, groups, n_groups, RMU_F_Q_DEVICE, total, out_scores, out_sims, (hipStream_t)hip_stream);
 }

@@ -28,17 +28,10 @@
 
 #include "../../include/rmu.h"
 #include "rmu_common.h"
+#include "rmu_host.h"
 #include "pair_truncate.h"
 #include "rmu_internal.h"      // rmu_rerank_*_: the prototypes bert.hip calls them by
 
-extern "C" void rmu_set_error_(const char* msg);
-static int rfail(int code, const std::string& m) { rmu_set_error_(m.c_str()); return code; }
-#define RR_TRY(expr)                                                                                                \
-    do {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                     \
-        if (e_ != hipSuccess)                                                                                       \
-            return rfail(e_ == hipErrorOutOfMemory ? RMU_E_OOM : RMU_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 struct rmu_passages {
     int cls = 0, sep = 0, pad = 0, max_len = 0, cap = 0;      // cap = max_len - 3 tokens kept per entry
@@ -138,52 +131,15 @@ __global__ __launch_bounds__(kSelBlock) void rerank_select_kernel(const float* l
     }
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)rmu_free(p);
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return e; }
-        cap = want;
-        return hipSuccess;
-    }
-};
-bool g_rr_down = false;        // static destructors have begun: thread-local destructors must leave HIP alone
-struct DownGuard { ~DownGuard() { g_rr_down = true; } } g_down_guard;
 // per-thread workspaces.  Every call that uses them drains its stream before it returns (rmu_rerank_select with device inputs AND device outputs
 // uses none), so nothing of a thread's previous call is ever in flight on them.
 struct Ctx {
-    DevBuf in, work, out;      // queries | keys (| logits); assembled rows (+ logits) where the caller has no buffer of its own; positions | scores
-    char* pin = nullptr;       // [0, pin_in): the inputs on their way up; behind it: the results on their way down
-    size_t pin_cap = 0;
+    RmuDevBuf in, work, out;      // queries | keys (| logits); assembled rows (+ logits) where the caller has no buffer of its own; positions | scores
+    RmuPinBuf pin{8192};       // [0, pin_in): the inputs on their way up; behind it: the results on their way down
     int device = -1;
     // what the call in progress left for its later steps
     const int64_t* d_keys = nullptr;
     size_t pin_in = 0;
-    int ensure_pin(size_t bytes) {
-        if (bytes <= pin_cap) return RMU_OK;
-        if (pin) (void)hipHostFree(pin);
-        pin = nullptr; pin_cap = 0;
-        const size_t cap = bytes < 8192 ? 8192 : bytes * 2;
-        if (hipHostMalloc((void**)&pin, cap) != hipSuccess) { pin = nullptr; (void)hipGetLastError(); return RMU_E_OOM; }
-        pin_cap = cap;
-        return RMU_OK;
-    }
-    void follow_device() {
-        const int dev = rmu_device_ordinal();
-        if (dev >= 0 && device != dev) { (void)hipSetDevice(dev); device = dev; }
-    }
-    ~Ctx() {
-        if (g_rr_down) return;
-        RMU_ENTRY();
-        for (DevBuf* b : {&in, &work, &out})
-            if (b->p) (void)rmu_free(b->p);
-        if (pin) (void)hipHostFree(pin);
-    }
 };
 thread_local Ctx g_ctx;
 
@@ -191,17 +147,17 @@ size_t align8(size_t n) { return (n + 7) & ~(size_t)7; }
 
 // (shared lock held) everything a call asks of the table and of its own arrays, without touching HIP
 int validate(const rmu_passages* p, const int32_t* q_lens, int64_t nq, int q_stride, const int64_t* keys, int m, int max_len, const std::string& w) {
-    if (max_len < 8 || max_len > p->max_len) return rfail(RMU_E_INVALID, w + ": 8 <= max_len <= the table's max_len (" + std::to_string(p->max_len) + ")");
+    if (max_len < 8 || max_len > p->max_len) return rmu_fail(RMU_E_INVALID, w + ": 8 <= max_len <= the table's max_len (" + std::to_string(p->max_len) + ")");
     const int budget = max_len - 3;
     for (int64_t i = 0; i < nq; ++i) {
-        if (q_lens[i] < 0) return rfail(RMU_E_INVALID, w + ": a query length is negative");
+        if (q_lens[i] < 0) return rmu_fail(RMU_E_INVALID, w + ": a query length is negative");
         if ((q_lens[i] < budget ? q_lens[i] : budget) > q_stride)
-            return rfail(RMU_E_INVALID, w + ": q_stride is shorter than the head (max_len - 3 tokens) of a query");
+            return rmu_fail(RMU_E_INVALID, w + ": q_stride is shorter than the head (max_len - 3 tokens) of a query");
     }
     const int64_t size = (int64_t)p->entries();
     for (int64_t i = 0; i < nq * m; ++i)
         if (keys[i] < -1 || keys[i] >= size)
-            return rfail(RMU_E_INVALID, w + ": key " + std::to_string(keys[i]) + " is outside the table (" + std::to_string(size) + " entries; -1 = absent)");
+            return rmu_fail(RMU_E_INVALID, w + ": key " + std::to_string(keys[i]) + " is outside the table (" + std::to_string(size) + " entries; -1 = absent)");
     return RMU_OK;
 }
 
@@ -213,7 +169,7 @@ int upload_table(rmu_passages* p, hipStream_t s) {
     if (ntok > p->d_tok_cap) {
         const size_t cap = ntok + ntok / 4 + 4096;
         int32_t* nt = nullptr;
-        RR_TRY(hipMalloc((void**)&nt, cap * sizeof(int32_t)));
+        RMU_HIP_TRY(hipMalloc((void**)&nt, cap * sizeof(int32_t)));
         if (have_tok) (void)hipMemcpyAsync(nt, p->d_tok, have_tok * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
         old[0] = p->d_tok;
         p->d_tok = nt; p->d_tok_cap = cap;
@@ -227,7 +183,7 @@ int upload_table(rmu_passages* p, hipStream_t s) {
             if (no) (void)rmu_free(no);
             (void)hipStreamSynchronize(s);
             if (old[0]) (void)rmu_free(old[0]);                 // (its contents are in the new token array)
-            return rfail(RMU_E_OOM, "rmu_passages: device image of the offsets");
+            return rmu_fail(RMU_E_OOM, "rmu_passages: device image of the offsets");
         }
         if (have) {
             (void)hipMemcpyAsync(no, p->d_off, (have + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s);
@@ -248,7 +204,7 @@ int upload_table(rmu_passages* p, hipStream_t s) {
     const hipError_t el = hipGetLastError();
     if (es != hipSuccess || el != hipSuccess) {
         p->d_entries = 0;                                       // whatever arrived: the next call uploads everything again
-        return rfail(RMU_E_HIP, std::string("rmu_passages: uploading the table: ") + hipGetErrorString(es != hipSuccess ? es : el));
+        return rmu_fail(RMU_E_HIP, std::string("rmu_passages: uploading the table: ") + hipGetErrorString(es != hipSuccess ? es : el));
     }
     p->d_entries = n;
     return RMU_OK;
@@ -276,12 +232,12 @@ int assemble_enqueue(rmu_passages* p, const int32_t* q_tokens, const int32_t* q_
     const size_t pairs = (size_t)nq * m;
     const size_t b_tok = align8((size_t)nq * q_w * 4), b_len = align8((size_t)nq * 4), b_keys = pairs * 8;
     x.pin_in = b_tok + b_len + b_keys;
-    if (x.ensure_pin(x.pin_in + out_bytes) != RMU_OK) return rfail(RMU_E_OOM, w + ": pinned staging buffer");
-    RR_TRY(x.in.ensure(x.pin_in));
-    for (int64_t i = 0; i < nq; ++i) memcpy(x.pin + (size_t)i * q_w * 4, q_tokens + (size_t)i * q_stride, (size_t)q_w * 4);
-    memcpy(x.pin + b_tok, q_lens, (size_t)nq * 4);
-    memcpy(x.pin + b_tok + b_len, keys, b_keys);
-    RR_TRY(hipMemcpyAsync(x.in.p, x.pin, x.pin_in, hipMemcpyHostToDevice, s));
+    if (x.pin.ensure(x.pin_in + out_bytes) != RMU_OK) return rmu_fail(RMU_E_OOM, w + ": pinned staging buffer");
+    RMU_HIP_TRY(x.in.ensure(x.pin_in));
+    for (int64_t i = 0; i < nq; ++i) memcpy(x.pin.p + (size_t)i * q_w * 4, q_tokens + (size_t)i * q_stride, (size_t)q_w * 4);
+    memcpy(x.pin.p + b_tok, q_lens, (size_t)nq * 4);
+    memcpy(x.pin.p + b_tok + b_len, keys, b_keys);
+    RMU_HIP_TRY(hipMemcpyAsync(x.in.p, x.pin.p, x.pin_in, hipMemcpyHostToDevice, s));
     AsmLaunch a{};
     a.tok = p->d_tok; a.off = p->d_off; a.flen = p->d_flen;
     a.q_tok = (const int32_t*)x.in.p;
@@ -291,15 +247,15 @@ int assemble_enqueue(rmu_passages* p, const int32_t* q_tokens, const int32_t* q_
     a.pairs = (int)pairs; a.rows = rows; a.m = m; a.q_w = q_w; a.max_len = max_len;
     a.cls = p->cls; a.sep = p->sep; a.pad = p->pad;
     hipLaunchKernelGGL(pair_assemble_kernel, dim3((unsigned)((rows + kAsmRows - 1) / kAsmRows)), dim3(kAsmBlock), 0, s, a);
-    RR_TRY(hipGetLastError());
+    RMU_HIP_TRY(hipGetLastError());
     return RMU_OK;
 }
 
 int check_call(const rmu_passages* p, const void* q_tokens, const void* q_lens, int64_t nq, int q_stride, const void* keys, int m, const std::string& w) {
-    if (!p || !q_tokens || !q_lens || !keys) return rfail(RMU_E_INVALID, w + ": null pointer");
-    if (m < 1 || m > RMU_RERANK_MAX_M) return rfail(RMU_E_INVALID, w + ": 1 <= m <= RMU_RERANK_MAX_M (256) candidates per query");
-    if (nq < 1 || nq * m > 65535) return rfail(RMU_E_INVALID, w + ": 1 <= nq, nq * m <= 65535 pairs");
-    if (q_stride < 1) return rfail(RMU_E_INVALID, w + ": q_stride must be >= 1");
+    if (!p || !q_tokens || !q_lens || !keys) return rmu_fail(RMU_E_INVALID, w + ": null pointer");
+    if (m < 1 || m > RMU_RERANK_MAX_M) return rmu_fail(RMU_E_INVALID, w + ": 1 <= m <= RMU_RERANK_MAX_M (256) candidates per query");
+    if (nq < 1 || nq * m > 65535) return rmu_fail(RMU_E_INVALID, w + ": 1 <= nq, nq * m <= 65535 pairs");
+    if (q_stride < 1) return rmu_fail(RMU_E_INVALID, w + ": q_stride must be >= 1");
     return RMU_OK;
 }
 
@@ -308,11 +264,11 @@ int check_call(const rmu_passages* p, const void* q_tokens, const void* q_lens, 
 // ---- the table ----------------------------------------------------------------------------------------------------------------------------------
 extern "C" int rmu_passages_create(rmu_passages_t** out, int cls_id, int sep_id, int pad_id, int max_len) {
     RMU_ENTRY();
-    if (!out) return rfail(RMU_E_INVALID, "rmu_passages_create: out is null");
-    if (max_len < 8 || max_len > 512) return rfail(RMU_E_INVALID, "rmu_passages_create: 8 <= max_len <= 512");
-    if (cls_id < 0 || sep_id < 0 || pad_id < 0) return rfail(RMU_E_INVALID, "rmu_passages_create: a special token id is negative");
+    if (!out) return rmu_fail(RMU_E_INVALID, "rmu_passages_create: out is null");
+    if (max_len < 8 || max_len > 512) return rmu_fail(RMU_E_INVALID, "rmu_passages_create: 8 <= max_len <= 512");
+    if (cls_id < 0 || sep_id < 0 || pad_id < 0) return rmu_fail(RMU_E_INVALID, "rmu_passages_create: a special token id is negative");
     rmu_passages* p = new (std::nothrow) rmu_passages();
-    if (!p) return rfail(RMU_E_OOM, "rmu_passages_create: out of memory");
+    if (!p) return rmu_fail(RMU_E_OOM, "rmu_passages_create: out of memory");
     p->cls = cls_id; p->sep = sep_id; p->pad = pad_id; p->max_len = max_len; p->cap = max_len - 3;
     *out = p;
     return RMU_OK;
@@ -332,7 +288,7 @@ extern "C" int rmu_passages_free(rmu_passages_t* p) {
 
 extern "C" int rmu_passages_size(rmu_passages_t* p, int64_t* n_entries, int64_t* n_tokens) {
     RMU_ENTRY();
-    if (!p) return rfail(RMU_E_INVALID, "rmu_passages_size: null handle");
+    if (!p) return rmu_fail(RMU_E_INVALID, "rmu_passages_size: null handle");
     std::shared_lock<std::shared_mutex> lk(p->mu);
     if (n_entries) *n_entries = (int64_t)p->entries();
     if (n_tokens) *n_tokens = (int64_t)p->tok.size();
@@ -341,31 +297,31 @@ extern "C" int rmu_passages_size(rmu_passages_t* p, int64_t* n_entries, int64_t*
 
 extern "C" int rmu_passages_set(rmu_passages_t* p, int64_t first, const int32_t* tokens, const int64_t* offsets, int64_t n) {
     RMU_ENTRY();
-    if (!p || n < 0 || (n > 0 && !offsets)) return rfail(RMU_E_INVALID, "rmu_passages_set: bad argument");
+    if (!p || n < 0 || (n > 0 && !offsets)) return rmu_fail(RMU_E_INVALID, "rmu_passages_set: bad argument");
     std::unique_lock<std::shared_mutex> lk(p->mu);
     if (first < 0 || (uint64_t)first > p->entries())
-        return rfail(RMU_E_INVALID, "rmu_passages_set: first (" + std::to_string(first) + ") is beyond the table's length (" + std::to_string(p->entries()) +
+        return rmu_fail(RMU_E_INVALID, "rmu_passages_set: first (" + std::to_string(first) + ") is beyond the table's length (" + std::to_string(p->entries()) +
                                         "): out of step");
-    if (n > 0 && offsets[0] != 0) return rfail(RMU_E_INVALID, "rmu_passages_set: offsets must start at 0");
+    if (n > 0 && offsets[0] != 0) return rmu_fail(RMU_E_INVALID, "rmu_passages_set: offsets must start at 0");
     int64_t kept = 0;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t len = offsets[i + 1] - offsets[i];
-        if (len < 0) return rfail(RMU_E_INVALID, "rmu_passages_set: offsets must ascend");
-        if (len > 0x7FFFFFFFll) return rfail(RMU_E_INVALID, "rmu_passages_set: an entry is longer than 2^31 - 1 tokens");
+        if (len < 0) return rmu_fail(RMU_E_INVALID, "rmu_passages_set: offsets must ascend");
+        if (len > 0x7FFFFFFFll) return rmu_fail(RMU_E_INVALID, "rmu_passages_set: an entry is longer than 2^31 - 1 tokens");
         kept += len < p->cap ? len : p->cap;
     }
-    if (n > 0 && offsets[n] > 0 && !tokens) return rfail(RMU_E_INVALID, "rmu_passages_set: tokens is null");
+    if (n > 0 && offsets[n] > 0 && !tokens) return rmu_fail(RMU_E_INVALID, "rmu_passages_set: tokens is null");
     for (int64_t i = 0; i < n; ++i) {
         const int64_t len = offsets[i + 1] - offsets[i], keep = len < p->cap ? len : p->cap;
         for (int64_t j = 0; j < keep; ++j)
-            if (tokens[offsets[i] + j] < 0) return rfail(RMU_E_INVALID, "rmu_passages_set: a token id is negative");
+            if (tokens[offsets[i] + j] < 0) return rmu_fail(RMU_E_INVALID, "rmu_passages_set: a token id is negative");
     }
     const size_t tok0 = (size_t)p->off[first];
     try {
         p->tok.reserve(tok0 + (size_t)kept);
         p->off.reserve((size_t)(first + n) + 1);
         p->flen.reserve((size_t)(first + n));
-    } catch (...) { return rfail(RMU_E_OOM, "rmu_passages_set: out of memory"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_passages_set: out of memory"); }
     p->tok.resize(tok0);
     p->off.resize((size_t)first + 1);
     p->flen.resize((size_t)first);
@@ -386,16 +342,16 @@ extern "C" int rmu_passages_pairs(rmu_passages_t* p, const int32_t* q_tokens, co
     const std::string w = "rmu_passages_pairs";
     int rc = check_call(p, q_tokens, q_lens, nq, q_stride, keys, m, w);
     if (rc) return rc;
-    if (!ids || !type_ids || !lens) return rfail(RMU_E_INVALID, w + ": null pointer");
+    if (!ids || !type_ids || !lens) return rmu_fail(RMU_E_INVALID, w + ": null pointer");
     std::shared_lock<std::shared_mutex> lk(p->mu);
     if ((rc = validate(p, q_lens, nq, q_stride, keys, m, max_len, w))) return rc;
     Ctx& x = g_ctx;
-    x.follow_device();
+    rmu_follow_device(x.device);
     hipStream_t s = nullptr;
     if ((rc = rmu_thread_stream_(nullptr, &s))) return rc;
     const int rows = (int)(nq * m);
     const size_t cap = (size_t)rows * max_len;
-    RR_TRY(x.work.ensure((2 * cap + rows) * 4));
+    RMU_HIP_TRY(x.work.ensure((2 * cap + rows) * 4));
     int32_t* d_ids = (int32_t*)x.work.p;
     rc = assemble_enqueue(p, q_tokens, q_lens, nq, q_stride, keys, m, rows, max_len, d_ids, d_ids + cap, d_ids + 2 * cap, 0, s, lk, w);
     if (!rc) {
@@ -406,8 +362,8 @@ extern "C" int rmu_passages_pairs(rmu_passages_t* p, const int32_t* q_tokens, co
     const hipError_t es = hipStreamSynchronize(s);
     rmu_thread_finished_(s, true);
     if (rc) return rc;
-    RR_TRY(es);
-    RR_TRY(hipGetLastError());
+    RMU_HIP_TRY(es);
+    RMU_HIP_TRY(hipGetLastError());
     return RMU_OK;
 }
 
@@ -415,51 +371,51 @@ extern "C" int rmu_passages_pairs(rmu_passages_t* p, const int32_t* q_tokens, co
 extern "C" int rmu_rerank_select(const float* logits, const int64_t* keys, int64_t nq, int m, int top_n, unsigned flags, int32_t* out_pos,
                                  float* out_scores, uint64_t hip_stream) {
     RMU_ENTRY();
-    if (!logits || !keys || !out_pos || !out_scores) return rfail(RMU_E_INVALID, "rmu_rerank_select: null pointer");
-    if (m < 1 || m > RMU_RERANK_MAX_M) return rfail(RMU_E_INVALID, "rmu_rerank_select: 1 <= m <= RMU_RERANK_MAX_M (256) candidates per query");
-    if (top_n < 1 || top_n > 65535) return rfail(RMU_E_INVALID, "rmu_rerank_select: 1 <= top_n <= 65535");
-    if (nq < 1 || nq > 65535) return rfail(RMU_E_INVALID, "rmu_rerank_select: 1 <= nq <= 65535");
-    if (flags & ~(unsigned)(RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE)) return rfail(RMU_E_INVALID, "rmu_rerank_select: flags must be RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE");
+    if (!logits || !keys || !out_pos || !out_scores) return rmu_fail(RMU_E_INVALID, "rmu_rerank_select: null pointer");
+    if (m < 1 || m > RMU_RERANK_MAX_M) return rmu_fail(RMU_E_INVALID, "rmu_rerank_select: 1 <= m <= RMU_RERANK_MAX_M (256) candidates per query");
+    if (top_n < 1 || top_n > 65535) return rmu_fail(RMU_E_INVALID, "rmu_rerank_select: 1 <= top_n <= 65535");
+    if (nq < 1 || nq > 65535) return rmu_fail(RMU_E_INVALID, "rmu_rerank_select: 1 <= nq <= 65535");
+    if (flags & ~(unsigned)(RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE)) return rmu_fail(RMU_E_INVALID, "rmu_rerank_select: flags must be RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE");
     const bool in_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE;
     Ctx& x = g_ctx;
-    x.follow_device();
+    rmu_follow_device(x.device);
     hipStream_t s = nullptr;
     int rc = rmu_thread_stream_((hipStream_t)hip_stream, &s);
     if (rc) return rc;
     const size_t nm = (size_t)nq * m, nk = (size_t)nq * top_n;
     const size_t b_keys = nm * 8, b_in = b_keys + nm * 4, b_out = nk * 8;
-    if (x.ensure_pin((in_dev ? 0 : b_in) + (out_dev ? 0 : b_out)) != RMU_OK) return rfail(RMU_E_OOM, "rmu_rerank_select: pinned staging buffer");
+    if (x.pin.ensure((in_dev ? 0 : b_in) + (out_dev ? 0 : b_out)) != RMU_OK) return rmu_fail(RMU_E_OOM, "rmu_rerank_select: pinned staging buffer");
     const size_t pin_out = in_dev ? 0 : b_in;
     const float* d_logits = logits;
     const int64_t* d_keys = keys;
     if (!in_dev) {
-        RR_TRY(x.in.ensure(b_in));
-        memcpy(x.pin, keys, b_keys);
-        memcpy(x.pin + b_keys, logits, nm * 4);
-        RR_TRY(hipMemcpyAsync(x.in.p, x.pin, b_in, hipMemcpyHostToDevice, s));
+        RMU_HIP_TRY(x.in.ensure(b_in));
+        memcpy(x.pin.p, keys, b_keys);
+        memcpy(x.pin.p + b_keys, logits, nm * 4);
+        RMU_HIP_TRY(hipMemcpyAsync(x.in.p, x.pin.p, b_in, hipMemcpyHostToDevice, s));
         d_keys = (const int64_t*)x.in.p;
         d_logits = (const float*)((const char*)x.in.p + b_keys);
     }
     int32_t* d_pos = out_pos;
     float* d_scores = out_scores;
     if (!out_dev) {
-        RR_TRY(x.out.ensure(b_out));
+        RMU_HIP_TRY(x.out.ensure(b_out));
         d_pos = (int32_t*)x.out.p;
         d_scores = (float*)(d_pos + nk);
     }
     hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)nq), dim3(kSelBlock), 0, s, d_logits, d_keys, m, top_n, d_pos, d_scores);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess && !out_dev) e = hipMemcpyAsync(x.pin + pin_out, x.out.p, b_out, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && !out_dev) e = hipMemcpyAsync(x.pin.p + pin_out, x.out.p, b_out, hipMemcpyDeviceToHost, s);
     const bool drained = e != hipSuccess || !hip_stream || !out_dev || !in_dev;
     if (drained) {
         const hipError_t es = hipStreamSynchronize(s);
         if (e == hipSuccess) e = es;
     }
     rmu_thread_finished_(s, drained);
-    RR_TRY(e);
+    RMU_HIP_TRY(e);
     if (!out_dev) {
-        memcpy(out_pos, x.pin + pin_out, nk * 4);
-        memcpy(out_scores, x.pin + pin_out + nk * 4, nk * 4);
+        memcpy(out_pos, x.pin.p + pin_out, nk * 4);
+        memcpy(out_scores, x.pin.p + pin_out + nk * 4, nk * 4);
     }
     return RMU_OK;
 }
@@ -470,12 +426,12 @@ extern "C" int rmu_rerank_select(const float* logits, const int64_t* keys, int64
 extern "C" int rmu_rerank_check_(rmu_passages_t* p, const int32_t* q_tokens, const int32_t* q_lens, int64_t nq, int q_stride, const int64_t* keys,
                                  int m, int batch_pad, int max_len, int top_n, const void* out_pos, const void* out_scores, void* lock) {
     const std::string w = "rmu_bert_rerank";
-    if (m < 1 || m > RMU_RERANK_MAX_M) return rfail(RMU_E_INVALID, w + ": 1 <= m_cand <= RMU_RERANK_MAX_M (256) candidates per query");
-    if (top_n < 1 || top_n > 65535) return rfail(RMU_E_INVALID, w + ": 1 <= top_n <= 65535");
+    if (m < 1 || m > RMU_RERANK_MAX_M) return rmu_fail(RMU_E_INVALID, w + ": 1 <= m_cand <= RMU_RERANK_MAX_M (256) candidates per query");
+    if (top_n < 1 || top_n > 65535) return rmu_fail(RMU_E_INVALID, w + ": 1 <= top_n <= 65535");
     int rc = check_call(p, q_tokens, q_lens, nq, q_stride, keys, m, w);
     if (rc) return rc;
-    if (!out_pos || !out_scores) return rfail(RMU_E_INVALID, w + ": null pointer");
-    if (batch_pad < nq * m || batch_pad > 65535) return rfail(RMU_E_INVALID, w + ": nq * m_cand <= batch_pad <= 65535");
+    if (!out_pos || !out_scores) return rmu_fail(RMU_E_INVALID, w + ": null pointer");
+    if (batch_pad < nq * m || batch_pad > 65535) return rmu_fail(RMU_E_INVALID, w + ": nq * m_cand <= batch_pad <= 65535");
     std::shared_lock<std::shared_mutex> lk(p->mu);
     if ((rc = validate(p, q_lens, nq, q_stride, keys, m, max_len, w))) return rc;
     if (lock) *(std::shared_lock<std::shared_mutex>*)lock = std::move(lk);
@@ -484,9 +440,9 @@ extern "C" int rmu_rerank_check_(rmu_passages_t* p, const int32_t* q_tokens, con
 // the thread's workspace for the shapes the encoder's own staging does not hold: ids | type ids | lens | logits of batch_pad rows
 extern "C" int rmu_rerank_workspace_(int batch_pad, int max_len, int32_t** d_in, float** d_logits) {
     Ctx& x = g_ctx;
-    x.follow_device();
+    rmu_follow_device(x.device);
     const size_t cap = (size_t)batch_pad * max_len;
-    RR_TRY(x.work.ensure((2 * cap + 2 * (size_t)batch_pad) * 4));
+    RMU_HIP_TRY(x.work.ensure((2 * cap + 2 * (size_t)batch_pad) * 4));
     *d_in = (int32_t*)x.work.p;
     *d_logits = (float*)(*d_in + 2 * cap + batch_pad);
     return RMU_OK;
@@ -495,9 +451,9 @@ extern "C" int rmu_rerank_workspace_(int batch_pad, int max_len, int32_t** d_in,
 extern "C" int rmu_rerank_assemble_(rmu_passages_t* p, const int32_t* q_tokens, const int32_t* q_lens, int64_t nq, int q_stride, const int64_t* keys,
                                     int m, int batch_pad, int max_len, int top_n, int32_t* d_in, void* hip_stream, void* lock) {
     Ctx& x = g_ctx;
-    x.follow_device();
+    rmu_follow_device(x.device);
     const size_t cap = (size_t)batch_pad * max_len, nm = (size_t)nq * m, nk = (size_t)nq * top_n;
-    RR_TRY(x.out.ensure(nk * 8));                               // (nothing of this call is in flight yet: a re-allocation disturbs nothing)
+    RMU_HIP_TRY(x.out.ensure(nk * 8));                               // (nothing of this call is in flight yet: a re-allocation disturbs nothing)
     return assemble_enqueue(p, q_tokens, q_lens, nq, q_stride, keys, m, batch_pad, max_len, d_in, d_in + cap, d_in + 2 * cap, nk * 8 + nm * 4,
                             (hipStream_t)hip_stream, *(std::shared_lock<std::shared_mutex>*)lock, "rmu_bert_rerank");
 }
@@ -507,19 +463,19 @@ extern "C" int rmu_rerank_select_(const float* d_logits, int64_t nq, int m, int 
     Ctx& x = g_ctx;
     hipStream_t s = (hipStream_t)hip_stream;
     const size_t nm = (size_t)nq * m, nk = (size_t)nq * top_n;
-    if (x.pin_in + nk * 8 + nm * 4 > x.pin_cap || nk * 8 > x.out.cap) return rfail(RMU_E_INVALID, "rmu_bert_rerank: the selection does not follow its assembly");
+    if (x.pin_in + nk * 8 + nm * 4 > x.pin.cap || nk * 8 > x.out.cap) return rmu_fail(RMU_E_INVALID, "rmu_bert_rerank: the selection does not follow its assembly");
     int32_t* d_pos = (int32_t*)x.out.p;
     hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)nq), dim3(kSelBlock), 0, s, d_logits, x.d_keys, m, top_n, d_pos, (float*)(d_pos + nk));
-    RR_TRY(hipGetLastError());
-    RR_TRY(hipMemcpyAsync(x.pin + x.pin_in, x.out.p, nk * 8, hipMemcpyDeviceToHost, s));
-    if (want_logits) RR_TRY(hipMemcpyAsync(x.pin + x.pin_in + nk * 8, d_logits, nm * 4, hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipGetLastError());
+    RMU_HIP_TRY(hipMemcpyAsync(x.pin.p + x.pin_in, x.out.p, nk * 8, hipMemcpyDeviceToHost, s));
+    if (want_logits) RMU_HIP_TRY(hipMemcpyAsync(x.pin.p + x.pin_in + nk * 8, d_logits, nm * 4, hipMemcpyDeviceToHost, s));
     return RMU_OK;
 }
 // (the stream is drained)
 extern "C" void rmu_rerank_take_(int64_t nq, int m, int top_n, int32_t* out_pos, float* out_scores, float* out_logits) {
     const Ctx& x = g_ctx;
     const size_t nm = (size_t)nq * m, nk = (size_t)nq * top_n;
-    const char* src = x.pin + x.pin_in;
+    const char* src = x.pin.p + x.pin_in;
     memcpy(out_pos, src, nk * 4);
     memcpy(out_scores, src + nk * 4, nk * 4);
     if (out_logits) memcpy(out_logits, src + nk * 8, nm * 4);

@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "rmu_common.h"
+#include "rmu_host.h"
 #include "../../include/rmu.h"
 #include "rmu_internal.h"      // rmu_index_search_mmr_dev_: the prototype bert.hip calls it by
 
@@ -33,26 +34,17 @@
 // error plumbing
 // ------------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIP_TRY(expr)                                                                            \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(e_ == hipErrorOutOfMemory ? RMU_E_OOM : RMU_E_HIP,                       \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-    } while (0)
-
 extern "C" const char* rmu_last_error(void) { return g_err.c_str(); }
-extern "C" void rmu_set_error_(const char* msg) { g_err = msg ? msg : ""; }   // used by bert.hip
+extern "C" void rmu_set_error_(const char* msg) { g_err = msg ? msg : ""; }   // behind rmu_fail (rmu_host.h)
 extern "C" const char* rmu_version(void) { return "librmu 0.1 gfx950"; }
 
 static int g_device = -1;
 extern "C" int rmu_init(int device_ordinal) {
     RMU_ENTRY();
     int n = 0;
-    HIP_TRY(hipGetDeviceCount(&n));
-    if (device_ordinal < 0 || device_ordinal >= n) return fail(RMU_E_INVALID, "rmu_init: no such device");
-    HIP_TRY(hipSetDevice(device_ordinal));
+    RMU_HIP_TRY(hipGetDeviceCount(&n));
+    if (device_ordinal < 0 || device_ordinal >= n) return rmu_fail(RMU_E_INVALID, "rmu_init: no such device");
+    RMU_HIP_TRY(hipSetDevice(device_ordinal));
     g_device = device_ordinal;
     return RMU_OK;
 }
@@ -62,31 +54,15 @@ int rmu_device_ordinal() { return g_device; }
 // per-thread context: stream, events, grow-only workspace
 // ------------------------------------------------------------------------------------------------
 // Set once the process starts tearing the HIP runtime down (static destructors / atexit): thread-local destructors
-// that run after that point must not call into HIP any more.
+// that run after that point must not call into HIP any more (rmu_runtime_down, rmu_host.h: every unit's contexts ask here).
 static bool g_runtime_down = false;
 namespace { struct RuntimeGuard { ~RuntimeGuard() { g_runtime_down = true; } } g_runtime_guard; }
+bool rmu_runtime_down() { return g_runtime_down; }
 
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-    Buf() = default;
-    Buf(const Buf&) = delete;              // (one owner: the destructor frees)
-    Buf& operator=(const Buf&) = delete;
-    ~Buf() { if (p && !g_runtime_down) (void)rmu_free(p); }     // (a thread-local destructor may run while the runtime winds down)
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return RMU_OK;
-        if (p) (void)rmu_free(p);
-        p = nullptr; cap = 0;
-        size_t want = bytes + bytes / 4 + 256;
-        if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; return RMU_E_OOM; }
-        cap = want;
-        return RMU_OK;
-    }
-};
 struct Tls {
     hipStream_t stream = nullptr;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    Buf q, partial, out_s, out_r, in_s, in_r, qn, gthr, qsplit, ckeys, flag, nrm, fbq, fb_i, mm_q, mm_s, mm_r, mm_p, gcand, sub_ids, sub_rows, gtab, eps, spill, spill_cnt;
+    RmuDevBuf q, partial, out_s, out_r, in_s, in_r, qn, gthr, qsplit, ckeys, flag, nrm, fbq, fb_i, mm_q, mm_s, mm_r, mm_p, gcand, sub_ids, sub_rows, gtab, eps, spill, spill_cnt;
     std::vector<hipEvent_t> lev;   // per-launch events of the screening ladder
     int ensure_events(int n) {
         while ((int)lev.size() < n) {
@@ -98,17 +74,7 @@ struct Tls {
     }
     int* hflag = nullptr;          // pinned landing word of the screening path's re-run count
     int* hflag_dev = nullptr;      // ... as the device sees it (written by k_gather_flagged)
-    char* hpin = nullptr;          // pinned landing buffer of search_mmr_on's results (rows | scores in ONE device-to-host copy)
-    size_t hpin_cap = 0;
-    int ensure_hpin(size_t bytes) {
-        if (bytes <= hpin_cap) return RMU_OK;
-        if (hpin) (void)hipHostFree(hpin);
-        hpin = nullptr; hpin_cap = 0;
-        const size_t cap = bytes < 4096 ? 4096 : bytes * 2;
-        if (hipHostMalloc((void**)&hpin, cap) != hipSuccess) { hpin = nullptr; (void)hipGetLastError(); return RMU_E_OOM; }
-        hpin_cap = cap;
-        return RMU_OK;
-    }
+    RmuPinBuf hpin{4096};          // pinned landing buffer of search_mmr_on's results (rows | scores in ONE device-to-host copy)
     int ensure_hflag() {
         if (hflag) return RMU_OK;
         if (hipHostMalloc((void**)&hflag, sizeof(int)) != hipSuccess) { hflag = nullptr; (void)hipGetLastError(); return RMU_E_OOM; }
@@ -132,7 +98,7 @@ struct Tls {
     bool pending = false;
     // `user`: the stream the caller's work will be enqueued on (nullptr = this thread's internal stream)
     int ensure_stream(hipStream_t user = nullptr) {
-        if (g_device >= 0 && device != g_device) { (void)hipSetDevice(g_device); device = g_device; }
+        rmu_follow_device(device);
         if (!stream) {
             if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return RMU_E_HIP;
             for (auto& e : ev)
@@ -152,7 +118,7 @@ struct Tls {
     }
     // A server that spawns a thread per request (Flask's threaded dev server, server/server.py:394) creates one of
     // these per request: everything it owns goes back when the thread exits.  Only what has an order is done here -- the work in flight
-    // ends first; the workspaces free themselves (~Buf) once this body has run, i.e. behind the drained stream.
+    // ends first; the workspaces free themselves (~RmuDevBuf, ~RmuPinBuf) once this body has run, i.e. behind the drained stream.
     ~Tls() {
         if (g_runtime_down) return;
         RMU_ENTRY();
@@ -163,7 +129,6 @@ struct Tls {
             if (e) (void)hipEventDestroy(e);
         for (auto& e : lev) (void)hipEventDestroy(e);
         if (hflag) (void)hipHostFree(hflag);
-        if (hpin) (void)hipHostFree(hpin);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -501,7 +466,7 @@ static int wait_readers(rmu_index* idx, hipStream_t on = nullptr) {
     std::lock_guard<std::mutex> g(idx->readers_mu);
     for (auto& r : idx->readers) {
         const hipError_t e = on ? hipStreamWaitEvent(on, r.ev, 0) : hipEventSynchronize(r.ev);
-        if (e != hipSuccess) return fail(RMU_E_HIP, std::string("waiting for the scans in flight: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return rmu_fail(RMU_E_HIP, std::string("waiting for the scans in flight: ") + hipGetErrorString(e));
     }
     return RMU_OK;
 }
@@ -521,31 +486,31 @@ static int pad_dim_metric(int d, int metric) {
 
 extern "C" int rmu_index_create(rmu_index_t** out, int dim, int metric, int64_t capacity_hint) {
     RMU_ENTRY();
-    if (!out) return fail(RMU_E_INVALID, "rmu_index_create: out is null");
-    if (dim < 1 || dim > RMU_MAX_DIM_WIDE) return fail(RMU_E_INVALID, "rmu_index_create: dim must be in [1, 3072]");
+    if (!out) return rmu_fail(RMU_E_INVALID, "rmu_index_create: out is null");
+    if (dim < 1 || dim > RMU_MAX_DIM_WIDE) return rmu_fail(RMU_E_INVALID, "rmu_index_create: dim must be in [1, 3072]");
     if (metric != RMU_METRIC_IP && metric != RMU_METRIC_COSINE && metric != RMU_METRIC_L2SQ)
-        return fail(RMU_E_INVALID, "rmu_index_create: metric must be RMU_METRIC_IP, RMU_METRIC_COSINE or RMU_METRIC_L2SQ");
+        return rmu_fail(RMU_E_INVALID, "rmu_index_create: metric must be RMU_METRIC_IP, RMU_METRIC_COSINE or RMU_METRIC_L2SQ");
     if (pad_dim_metric(dim, metric) < 0)
-        return fail(RMU_E_INVALID, dim <= RMU_MAX_DIM ? "rmu_index_create: RMU_METRIC_L2SQ needs one spare column: dim must be <= 767"
+        return rmu_fail(RMU_E_INVALID, dim <= RMU_MAX_DIM ? "rmu_index_create: RMU_METRIC_L2SQ needs one spare column: dim must be <= 767"
                                                       : "rmu_index_create: a wide index (dim > 768) is RMU_METRIC_IP or RMU_METRIC_COSINE: RMU_METRIC_L2SQ (L2) "
                                                         "rows are at most 767 dimensions");
     int rc = g_tls.ensure_stream();
-    if (rc) return fail(rc, "rmu_index_create: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_create: stream");
     auto* idx = new (std::nothrow) rmu_index();
-    if (!idx) return fail(RMU_E_OOM, "rmu_index_create: host alloc");
+    if (!idx) return rmu_fail(RMU_E_OOM, "rmu_index_create: host alloc");
     idx->dim = dim;
     idx->dpad = pad_dim_metric(dim, metric);
     idx->metric = metric;
     int64_t cap = capacity_hint > 0 ? capacity_hint : 4096;
     hipError_t e = hipMalloc((void**)&idx->x, (size_t)(cap + kSlackRows) * idx->dpad * sizeof(float));
-    if (e != hipSuccess) { delete idx; return fail(RMU_E_OOM, "rmu_index_create: hipMalloc"); }
+    if (e != hipSuccess) { delete idx; return rmu_fail(RMU_E_OOM, "rmu_index_create: hipMalloc"); }
     // zero fill ON OUR STREAM and wait: a null-stream hipMemset is asynchronous to the host and is not ordered
     // with a hipStreamNonBlocking stream, so it could land after (and wipe) the first rows uploaded on it
     if (hipMemsetAsync(idx->x, 0, (size_t)(cap + kSlackRows) * idx->dpad * sizeof(float), g_tls.stream) != hipSuccess ||
         hipStreamSynchronize(g_tls.stream) != hipSuccess) {
         (void)hipFree(idx->x);
         delete idx;
-        return fail(RMU_E_HIP, "rmu_index_create: zero fill");
+        return rmu_fail(RMU_E_HIP, "rmu_index_create: zero fill");
     }
     idx->cap = cap;
     // screening image (+50% corpus memory): 384-wide rows only; RMU_SCREEN=0 disables
@@ -590,13 +555,13 @@ extern "C" int rmu_index_free(rmu_index_t* idx) {
 }
 
 extern "C" int rmu_index_size(rmu_index_t* idx, int64_t* n_rows) {
-    if (!idx || !n_rows) return fail(RMU_E_INVALID, "rmu_index_size: null");
+    if (!idx || !n_rows) return rmu_fail(RMU_E_INVALID, "rmu_index_size: null");
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     *n_rows = idx->n;
     return RMU_OK;
 }
 extern "C" int rmu_index_stat(rmu_index_t* idx, int what, double* out) {
-    if (!idx || !out) return fail(RMU_E_INVALID, "rmu_index_stat: null");
+    if (!idx || !out) return rmu_fail(RMU_E_INVALID, "rmu_index_stat: null");
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     switch (what) {
         case RMU_STAT_CAPACITY: *out = (double)idx->cap; break;
@@ -605,12 +570,12 @@ extern "C" int rmu_index_stat(rmu_index_t* idx, int what, double* out) {
         case RMU_STAT_LIVE_ROWS: *out = (double)idx->n_live; break;
         case RMU_STAT_COMPACT_COUNT: *out = (double)idx->compact_count; break;
         case RMU_STAT_COMPACT_MS: *out = idx->compact_ms; break;
-        default: return fail(RMU_E_INVALID, "rmu_index_stat: unknown statistic");
+        default: return rmu_fail(RMU_E_INVALID, "rmu_index_stat: unknown statistic");
     }
     return RMU_OK;
 }
 extern "C" int rmu_index_dim(rmu_index_t* idx, int* dim) {
-    if (!idx || !dim) return fail(RMU_E_INVALID, "rmu_index_dim: null");
+    if (!idx || !dim) return rmu_fail(RMU_E_INVALID, "rmu_index_dim: null");
     *dim = idx->dim;
     return RMU_OK;
 }
@@ -628,17 +593,17 @@ static int grow(rmu_index* idx, int64_t need) {
     if (hipMalloc((void**)&nx, (size_t)(cap + kSlackRows) * idx->dpad * sizeof(float)) != hipSuccess) {
         cap = need;  // retry with the exact size before giving up
         if (hipMalloc((void**)&nx, (size_t)(cap + kSlackRows) * idx->dpad * sizeof(float)) != hipSuccess)
-            return fail(RMU_E_OOM, "rmu_index_add: hipMalloc for growth");
+            return rmu_fail(RMU_E_OOM, "rmu_index_add: hipMalloc for growth");
     }
     // nobody may still be scanning the old matrix when it is freed below: searches on internal streams ended under the shared lock, the
     // ones left in flight on callers' streams are waited for one by one -- never the whole device (rmu_common.h: captures)
     int wrc = wait_readers(idx);
     if (wrc) { (void)rmu_free(nx); return wrc; }
     hipStream_t s = g_tls.stream;     // same stream as the uploads that follow (see rmu_index_create)
-    HIP_TRY(hipMemsetAsync(nx + idx->n * idx->dpad, 0, (size_t)(cap + kSlackRows - idx->n) * idx->dpad * sizeof(float), s));
+    RMU_HIP_TRY(hipMemsetAsync(nx + idx->n * idx->dpad, 0, (size_t)(cap + kSlackRows - idx->n) * idx->dpad * sizeof(float), s));
     if (idx->n)
-        HIP_TRY(hipMemcpyAsync(nx, idx->x, (size_t)idx->n * idx->dpad * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
+        RMU_HIP_TRY(hipMemcpyAsync(nx, idx->x, (size_t)idx->n * idx->dpad * sizeof(float), hipMemcpyDeviceToDevice, s));
+    RMU_HIP_TRY(hipStreamSynchronize(s));
     if (idx->split) {
         char* ns = nullptr;
         float* nn = nullptr;
@@ -649,13 +614,13 @@ static int grow(rmu_index* idx, int64_t need) {
             got = false;
         }
         if (got) {
-            HIP_TRY(hipMemsetAsync(ns + idx->n * rowb, 0, (size_t)(cap + kSlackRows - idx->n) * rowb, s));
-            if (idx->n) HIP_TRY(hipMemcpyAsync(ns, idx->split, (size_t)idx->n * rowb, hipMemcpyDeviceToDevice, s));
+            RMU_HIP_TRY(hipMemsetAsync(ns + idx->n * rowb, 0, (size_t)(cap + kSlackRows - idx->n) * rowb, s));
+            if (idx->n) RMU_HIP_TRY(hipMemcpyAsync(ns, idx->split, (size_t)idx->n * rowb, hipMemcpyDeviceToDevice, s));
             if (nn) {
-                HIP_TRY(hipMemsetAsync(nn + idx->n, 0xFF, (size_t)(cap + kSlackRows - idx->n) * sizeof(float), s));
-                if (idx->n) HIP_TRY(hipMemcpyAsync(nn, idx->nrm, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToDevice, s));
+                RMU_HIP_TRY(hipMemsetAsync(nn + idx->n, 0xFF, (size_t)(cap + kSlackRows - idx->n) * sizeof(float), s));
+                if (idx->n) RMU_HIP_TRY(hipMemcpyAsync(nn, idx->nrm, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToDevice, s));
             }
-            HIP_TRY(hipStreamSynchronize(s));
+            RMU_HIP_TRY(hipStreamSynchronize(s));
             (void)rmu_free(idx->split);
             if (idx->nrm) (void)rmu_free(idx->nrm);
             idx->split = ns;
@@ -676,10 +641,10 @@ static int grow(rmu_index* idx, int64_t need) {
 
 extern "C" int rmu_index_reserve(rmu_index_t* idx, int64_t rows) {
     RMU_ENTRY();
-    if (!idx || rows < 0) return fail(RMU_E_INVALID, "rmu_index_reserve: bad argument");
-    if (rows > 0xFFFFFFF0ll) return fail(RMU_E_INVALID, "rmu_index_reserve: row ids are 32-bit inside the scan");
+    if (!idx || rows < 0) return rmu_fail(RMU_E_INVALID, "rmu_index_reserve: bad argument");
+    if (rows > 0xFFFFFFF0ll) return rmu_fail(RMU_E_INVALID, "rmu_index_reserve: row ids are 32-bit inside the scan");
     int rc = g_tls.ensure_stream();
-    if (rc) return fail(rc, "rmu_index_reserve: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_reserve: stream");
     std::unique_lock<std::shared_mutex> lk(idx->mu);
     return grow(idx, rows);           // (rmu_index_add's geometric policy: a caller that reserves round by round does not re-allocate every round)
 }
@@ -689,10 +654,10 @@ extern "C" int rmu_index_reserve(rmu_index_t* idx, int64_t rows) {
 // stream synchronisation covers it, then fold_image_stats() folds the pair into the index -- one host round trip per
 // rmu_index_add instead of three (the reference inserts in 1000-document calls, server/RAGHelper.py:423-434).
 static int update_image_stats(rmu_index_t* idx, const float* dst, int64_t n, hipStream_t s, float* nrm_out = nullptr) {
-    Buf& nb = g_tls.nrm;
-    if (nb.ensure((size_t)n * sizeof(float) + 16)) return fail(RMU_E_OOM, "rmu_index_add: norm workspace");
+    RmuDevBuf& nb = g_tls.nrm;
+    if (nb.ensure((size_t)n * sizeof(float) + 16)) return rmu_fail(RMU_E_OOM, "rmu_index_add: norm workspace");
     unsigned* mx = (unsigned*)((char*)nb.p + (size_t)n * sizeof(float));
-    HIP_TRY(hipMemsetAsync(mx, 0, 2 * sizeof(unsigned), s));
+    RMU_HIP_TRY(hipMemsetAsync(mx, 0, 2 * sizeof(unsigned), s));
     if (idx->metric == RMU_METRIC_L2SQ) {      // |x|^2 is the augmented column (k_l2_aug_rows), not the norm of the augmented row
         hipLaunchKernelGGL(k_l2_nrm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dst, idx->dpad, idx->dim, n, nrm_out, (float*)nb.p);
         hipLaunchKernelGGL(k_max_norm2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)nb.p, n, mx);
@@ -701,10 +666,10 @@ static int update_image_stats(rmu_index_t* idx, const float* dst, int64_t n, hip
         hipLaunchKernelGGL(k_max_norm2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)nb.p, n, mx);
     }
     int rc = rmu_img_err_launch(dst, n, (float*)nb.p, s, idx->dpad);
-    if (rc) return fail(rc, "rmu_index_add: image error");
+    if (rc) return rmu_fail(rc, "rmu_index_add: image error");
     hipLaunchKernelGGL(k_max_norm2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)nb.p, n, mx + 1);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(idx->stat_host, mx, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipGetLastError());
+    RMU_HIP_TRY(hipMemcpyAsync(idx->stat_host, mx, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
     idx->stat_pending = true;
     return RMU_OK;
 }
@@ -714,7 +679,7 @@ static int build_image(rmu_index_t* idx, int64_t r0, int64_t n, hipStream_t s) {
     if (!idx->split) return RMU_OK;
     const float* rows = idx->x + r0 * (int64_t)idx->dpad;
     int rc = rmu_split_launch(rows, idx->split + (size_t)r0 * RMU_IMG_ROW_BYTES, n, s, idx->dpad, 64.0f);
-    if (rc) return fail(rc, "rmu_index_add: split image");
+    if (rc) return rmu_fail(rc, "rmu_index_add: split image");
     return update_image_stats(idx, rows, n, s, idx->nrm ? idx->nrm + r0 : nullptr);
 }
 
@@ -737,36 +702,36 @@ static void fold_image_stats(rmu_index_t* idx) {
 
 extern "C" int rmu_index_add(rmu_index_t* idx, const float* vecs, int64_t n, int is_device, int64_t* first_row) {
     RMU_ENTRY();
-    if (!idx || (!vecs && n > 0) || n < 0) return fail(RMU_E_INVALID, "rmu_index_add: bad argument");
+    if (!idx || (!vecs && n > 0) || n < 0) return rmu_fail(RMU_E_INVALID, "rmu_index_add: bad argument");
     int rc = g_tls.ensure_stream();
-    if (rc) return fail(rc, "rmu_index_add: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_add: stream");
     std::unique_lock<std::shared_mutex> lk(idx->mu);
     if (first_row) *first_row = idx->n;
     if (n == 0) return RMU_OK;
-    if (idx->n + n > 0xFFFFFFF0ll) return fail(RMU_E_INVALID, "rmu_index_add: row ids are 32-bit inside the scan");
+    if (idx->n + n > 0xFFFFFFF0ll) return rmu_fail(RMU_E_INVALID, "rmu_index_add: row ids are 32-bit inside the scan");
     rc = grow(idx, idx->n + n);
     if (rc) return rc;
     float* dst = idx->x + idx->n * (int64_t)idx->dpad;
     hipStream_t s = g_tls.stream;
     const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (idx->dpad == idx->dim)
-        HIP_TRY(hipMemcpyAsync(dst, vecs, (size_t)n * idx->dim * sizeof(float), kind, s));
+        RMU_HIP_TRY(hipMemcpyAsync(dst, vecs, (size_t)n * idx->dim * sizeof(float), kind, s));
     else
-        HIP_TRY(hipMemcpy2DAsync(dst, (size_t)idx->dpad * sizeof(float), vecs, (size_t)idx->dim * sizeof(float),
+        RMU_HIP_TRY(hipMemcpy2DAsync(dst, (size_t)idx->dpad * sizeof(float), vecs, (size_t)idx->dim * sizeof(float),
                                  (size_t)idx->dim * sizeof(float), (size_t)n, kind, s));
     if (idx->metric == RMU_METRIC_COSINE) {
         const int wpb = 4;
         hipLaunchKernelGGL(k_row_norm, dim3((unsigned)((n + wpb - 1) / wpb)), dim3(64 * wpb), 0, s, dst, idx->dpad, n, 1,
                            (float*)nullptr);
-        HIP_TRY(hipGetLastError());
+        RMU_HIP_TRY(hipGetLastError());
     }
     if (idx->metric == RMU_METRIC_L2SQ) {
         hipLaunchKernelGGL(k_l2_aug_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dst, idx->dpad, idx->dim, n);
-        HIP_TRY(hipGetLastError());
+        RMU_HIP_TRY(hipGetLastError());
     }
     rc = build_image(idx, idx->n, n, s);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
+    RMU_HIP_TRY(hipStreamSynchronize(s));
     fold_image_stats(idx);
     idx->alive.resize((size_t)(idx->n + n), 1);
     idx->n += n;
@@ -776,31 +741,31 @@ extern "C" int rmu_index_add(rmu_index_t* idx, const float* vecs, int64_t n, int
 
 extern "C" int rmu_index_remove_rows(rmu_index_t* idx, const int64_t* rows, int64_t n, int64_t* n_removed) {
     RMU_ENTRY();
-    if (!idx || (!rows && n > 0) || n < 0) return fail(RMU_E_INVALID, "rmu_index_remove_rows: bad argument");
+    if (!idx || (!rows && n > 0) || n < 0) return rmu_fail(RMU_E_INVALID, "rmu_index_remove_rows: bad argument");
     int rc = g_tls.ensure_stream();
-    if (rc) return fail(rc, "rmu_index_remove_rows: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_remove_rows: stream");
     std::unique_lock<std::shared_mutex> lk(idx->mu);
     std::vector<int64_t> todo;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t r = rows[i];
-        if (r < 0 || r >= idx->n) return fail(RMU_E_INVALID, "rmu_index_remove_rows: row out of range");
+        if (r < 0 || r >= idx->n) return rmu_fail(RMU_E_INVALID, "rmu_index_remove_rows: row out of range");
         if (idx->alive[(size_t)r]) { idx->alive[(size_t)r] = 0; todo.push_back(r); }
     }
     if (n_removed) *n_removed = (int64_t)todo.size();
     if (todo.empty()) return RMU_OK;
-    Buf& b = g_tls.in_r;
-    if (b.ensure(todo.size() * sizeof(int64_t))) return fail(RMU_E_OOM, "rmu_index_remove_rows: workspace");
+    RmuDevBuf& b = g_tls.in_r;
+    if (b.ensure(todo.size() * sizeof(int64_t))) return rmu_fail(RMU_E_OOM, "rmu_index_remove_rows: workspace");
     hipStream_t s = g_tls.stream;
     rc = wait_readers(idx, s);        // the poison kernels are ordered behind the scans still in flight on callers' streams
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(b.p, todo.data(), todo.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    RMU_HIP_TRY(hipMemcpyAsync(b.p, todo.data(), todo.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_poison_rows, dim3((unsigned)todo.size()), dim3(128), 0, s, idx->x, idx->dpad,
                        (const int64_t*)b.p, (int64_t)todo.size());
     if (idx->split)   // fp32 NaN pattern = one fp16 NaN per pair: every screening score of the row is NaN as well
         hipLaunchKernelGGL(k_poison_rows, dim3((unsigned)todo.size()), dim3(128), 0, s, (float*)idx->split, RMU_IMG_ROW_BYTES / 4,
                            (const int64_t*)b.p, (int64_t)todo.size());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));
+    RMU_HIP_TRY(hipGetLastError());
+    RMU_HIP_TRY(hipStreamSynchronize(s));
     idx->n_live -= (int64_t)todo.size();
     return RMU_OK;
 }
@@ -811,12 +776,12 @@ extern "C" int rmu_index_remove_rows(rmu_index_t* idx, const int64_t* rows, int6
 // allocation).  Afterwards the index is what a fresh index of the live rows would hold: rows past n_live zero (x, image) / NaN (norms).
 extern "C" int rmu_index_compact(rmu_index_t* idx, int64_t* old_to_new, int64_t map_len, int64_t* n_after) {
     RMU_ENTRY();
-    if (!idx || !n_after || (old_to_new && map_len < 0)) return fail(RMU_E_INVALID, "rmu_index_compact: bad argument");
+    if (!idx || !n_after || (old_to_new && map_len < 0)) return rmu_fail(RMU_E_INVALID, "rmu_index_compact: bad argument");
     int rc = g_tls.ensure_stream();
-    if (rc) return fail(rc, "rmu_index_compact: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_compact: stream");
     std::unique_lock<std::shared_mutex> lk(idx->mu);
     const int64_t n = idx->n, n_live = idx->n_live;
-    if (old_to_new && map_len < n) return fail(RMU_E_INVALID, "rmu_index_compact: map_len is smaller than the index's row count");
+    if (old_to_new && map_len < n) return rmu_fail(RMU_E_INVALID, "rmu_index_compact: map_len is smaller than the index's row count");
     const auto t0 = std::chrono::steady_clock::now();
     // the map, and the source row of every new row from the first dead row on (branch-free: tombstones fall anywhere)
     const uint8_t* alive = idx->alive.data();
@@ -846,10 +811,10 @@ extern "C" int rmu_index_compact(rmu_index_t* idx, int64_t* old_to_new, int64_t 
     rc = wait_readers(idx);
     if (rc) return rc;
     hipStream_t s = g_tls.stream;
-    Buf& bs = g_tls.in_r;
+    RmuDevBuf& bs = g_tls.in_r;
     if (!src.empty()) {
-        if (bs.ensure(src.size() * sizeof(u32))) return fail(RMU_E_OOM, "rmu_index_compact: source list workspace");
-        HIP_TRY(hipMemcpyAsync(bs.p, src.data(), src.size() * sizeof(u32), hipMemcpyHostToDevice, s));
+        if (bs.ensure(src.size() * sizeof(u32))) return rmu_fail(RMU_E_OOM, "rmu_index_compact: source list workspace");
+        RMU_HIP_TRY(hipMemcpyAsync(bs.p, src.data(), src.size() * sizeof(u32), hipMemcpyHostToDevice, s));
     }
     const u32* d_src = (const u32*)bs.p;
     const int64_t new_cap = std::max<int64_t>(4096, n_live + n_live / 8 + 1024);
@@ -864,7 +829,7 @@ extern "C" int rmu_index_compact(rmu_index_t* idx, int64_t* old_to_new, int64_t 
                    {(void**)&idx->split, RMU_IMG_ROW_BYTES, 0},
                    {(void**)&idx->nrm, (int64_t)sizeof(float), 0xFF}};   // NaN norms: never a candidate
     bool oop = !idx->compact_inplace && new_cap < idx->cap;
-    if (!oop && !get_staging()) return fail(RMU_E_OOM, "rmu_index_compact: staging buffer (the index is unchanged)");
+    if (!oop && !get_staging()) return rmu_fail(RMU_E_OOM, "rmu_index_compact: staging buffer (the index is unchanged)");
     hipError_t e = hipSuccess;
     for (int a = 0; a < 3 && e == hipSuccess; ++a) {
         if (!*arrs[a].base) continue;
@@ -875,7 +840,7 @@ extern "C" int rmu_index_compact(rmu_index_t* idx, int64_t* old_to_new, int64_t 
             e = hipSuccess;
             if (a == 0) {                                  // the matrix did not fit twice: the whole call goes in place
                 oop = false;
-                if (!get_staging()) return fail(RMU_E_OOM, "rmu_index_compact: staging buffer (the index is unchanged)");
+                if (!get_staging()) return rmu_fail(RMU_E_OOM, "rmu_index_compact: staging buffer (the index is unchanged)");
             } else if (!get_staging()) {                   // the matrix has moved; no room for the image either way: exact path only
                 (void)hipStreamSynchronize(s);             // (as grow() does when the image does not fit)
                 (void)rmu_free(idx->split);
@@ -890,7 +855,7 @@ extern "C" int rmu_index_compact(rmu_index_t* idx, int64_t* old_to_new, int64_t 
     const hipError_t es = hipStreamSynchronize(s);
     if (staging) (void)rmu_free(staging);
     if (e != hipSuccess || es != hipSuccess)
-        return fail(RMU_E_HIP, std::string("rmu_index_compact: ") + hipGetErrorString(e != hipSuccess ? e : es));
+        return rmu_fail(RMU_E_HIP, std::string("rmu_index_compact: ") + hipGetErrorString(e != hipSuccess ? e : es));
     if (oop) idx->cap = new_cap;
     idx->n = n_live;
     idx->alive.assign((size_t)n_live, 1);
@@ -901,24 +866,24 @@ extern "C" int rmu_index_compact(rmu_index_t* idx, int64_t* old_to_new, int64_t 
 extern "C" int rmu_index_get_rows(rmu_index_t* idx, const int64_t* rows, int64_t n, float* out_host) {
     RMU_ENTRY();
     if (!idx || (!rows && n > 0) || (!out_host && n > 0) || n < 0)
-        return fail(RMU_E_INVALID, "rmu_index_get_rows: bad argument");
+        return rmu_fail(RMU_E_INVALID, "rmu_index_get_rows: bad argument");
     if (n == 0) return RMU_OK;
     int rc = g_tls.ensure_stream();
-    if (rc) return fail(rc, "rmu_index_get_rows: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_get_rows: stream");
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     for (int64_t i = 0; i < n; ++i)
-        if (rows[i] < 0 || rows[i] >= idx->n) return fail(RMU_E_INVALID, "rmu_index_get_rows: row out of range");
-    Buf& br = g_tls.in_r;
-    Buf& bo = g_tls.out_s;
+        if (rows[i] < 0 || rows[i] >= idx->n) return rmu_fail(RMU_E_INVALID, "rmu_index_get_rows: row out of range");
+    RmuDevBuf& br = g_tls.in_r;
+    RmuDevBuf& bo = g_tls.out_s;
     if (br.ensure((size_t)n * sizeof(int64_t)) || bo.ensure((size_t)n * idx->dim * sizeof(float)))
-        return fail(RMU_E_OOM, "rmu_index_get_rows: workspace");
+        return rmu_fail(RMU_E_OOM, "rmu_index_get_rows: workspace");
     hipStream_t s = g_tls.stream;
-    HIP_TRY(hipMemcpyAsync(br.p, rows, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    RMU_HIP_TRY(hipMemcpyAsync(br.p, rows, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)n), dim3(128), 0, s, idx->x, idx->dpad, idx->dim,
                        (const int64_t*)br.p, n, (float*)bo.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_host, bo.p, (size_t)n * idx->dim * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    RMU_HIP_TRY(hipGetLastError());
+    RMU_HIP_TRY(hipMemcpyAsync(out_host, bo.p, (size_t)n * idx->dim * sizeof(float), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipStreamSynchronize(s));
     return RMU_OK;
 }
 
@@ -941,11 +906,11 @@ static void launch_mmr(const rmu_index* idx, const float* dq, const int64_t* dr,
 extern "C" int rmu_index_mmr(rmu_index_t* idx, const float* q, int64_t nq, const int64_t* rows, int fetch_k, int k,
                              double lambda_mult, unsigned flags, int32_t* out_pos) {
     RMU_ENTRY();
-    if (!idx || !q || !rows || !out_pos) return fail(RMU_E_INVALID, "rmu_index_mmr: null pointer");
-    if (nq < 1 || fetch_k < 1 || fetch_k > 64 || k < 1) return fail(RMU_E_INVALID, "rmu_index_mmr: nq >= 1, fetch_k in [1, 64], k >= 1");
+    if (!idx || !q || !rows || !out_pos) return rmu_fail(RMU_E_INVALID, "rmu_index_mmr: null pointer");
+    if (nq < 1 || fetch_k < 1 || fetch_k > 64 || k < 1) return rmu_fail(RMU_E_INVALID, "rmu_index_mmr: nq >= 1, fetch_k in [1, 64], k >= 1");
     Tls& t = g_tls;
     int rc = t.ensure_stream();
-    if (rc) return fail(rc, "rmu_index_mmr: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_mmr: stream");
     hipStream_t s = t.stream;
     const bool q_dev = flags & RMU_F_Q_DEVICE, io_dev = flags & RMU_F_OUT_DEVICE;
     std::shared_lock<std::shared_mutex> lk(idx->mu);
@@ -953,21 +918,21 @@ extern "C" int rmu_index_mmr(rmu_index_t* idx, const float* q, int64_t nq, const
     const int64_t* dr = rows;
     int* dout = (int*)out_pos;
     if (!q_dev) {
-        if (t.q.ensure((size_t)nq * idx->dim * sizeof(float))) return fail(RMU_E_OOM, "rmu_index_mmr: q workspace");
-        HIP_TRY(hipMemcpyAsync(t.q.p, q, (size_t)nq * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
+        if (t.q.ensure((size_t)nq * idx->dim * sizeof(float))) return rmu_fail(RMU_E_OOM, "rmu_index_mmr: q workspace");
+        RMU_HIP_TRY(hipMemcpyAsync(t.q.p, q, (size_t)nq * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
         dq = (const float*)t.q.p;
     }
     if (!io_dev) {
         if (t.in_r.ensure((size_t)nq * fetch_k * sizeof(int64_t)) || t.out_r.ensure((size_t)nq * k * sizeof(int)))
-            return fail(RMU_E_OOM, "rmu_index_mmr: workspace");
-        HIP_TRY(hipMemcpyAsync(t.in_r.p, rows, (size_t)nq * fetch_k * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            return rmu_fail(RMU_E_OOM, "rmu_index_mmr: workspace");
+        RMU_HIP_TRY(hipMemcpyAsync(t.in_r.p, rows, (size_t)nq * fetch_k * sizeof(int64_t), hipMemcpyHostToDevice, s));
         dr = (const int64_t*)t.in_r.p;
         dout = (int*)t.out_r.p;
     }
     launch_mmr(idx, dq, dr, nq, fetch_k, k, lambda_mult, dout, s);
-    HIP_TRY(hipGetLastError());
-    if (!io_dev) HIP_TRY(hipMemcpyAsync(out_pos, dout, (size_t)nq * k * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    RMU_HIP_TRY(hipGetLastError());
+    if (!io_dev) RMU_HIP_TRY(hipMemcpyAsync(out_pos, dout, (size_t)nq * k * sizeof(int), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipStreamSynchronize(s));
     return RMU_OK;
 }
 
@@ -984,14 +949,14 @@ static int search_mmr_enqueue(rmu_index_t* idx, const float* q, bool q_dev, int6
     // candidate scores / rows, the raw queries (the search normalises its own copy for COSINE), picks, and the results (rows | scores)
     if (t.mm_s.ensure(nf * sizeof(float)) || t.mm_r.ensure(nf * sizeof(int64_t)) || t.mm_q.ensure((size_t)nq * idx->dim * sizeof(float)) ||
         t.mm_p.ensure(nk * (sizeof(int) + sizeof(int64_t) + sizeof(float))))
-        return fail(RMU_E_OOM, std::string(who) + ": workspace");
+        return rmu_fail(RMU_E_OOM, std::string(who) + ": workspace");
     int64_t* d_rows = (int64_t*)t.mm_p.p;
     float* d_sc = (float*)(d_rows + nk);
     int* d_pos = (int*)(d_sc + nk);
     if (expect_rows >= 0) {
         std::shared_lock<std::shared_mutex> chk(idx->mu);
         if (idx->n != expect_rows)
-            return fail(RMU_E_INVALID, std::string(who) + ": the dense key table (" + std::to_string(expect_rows) + " keys) and the index (" +
+            return rmu_fail(RMU_E_INVALID, std::string(who) + ": the dense key table (" + std::to_string(expect_rows) + " keys) and the index (" +
                                            std::to_string(idx->n) + " rows) are out of step");
     }
     // (round 5: every stream operation of the one-query path is ~4.4 us of dependent-kernel boundary.)  No selection and fetch_k == k: the
@@ -1006,13 +971,13 @@ static int search_mmr_enqueue(rmu_index_t* idx, const float* q, bool q_dev, int6
     if (!direct) {
         const float* dq = q;
         if (!q_dev && lambda_mult >= 0.0) {
-            HIP_TRY(hipMemcpyAsync(t.mm_q.p, q, (size_t)nq * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
+            RMU_HIP_TRY(hipMemcpyAsync(t.mm_q.p, q, (size_t)nq * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
             dq = (const float*)t.mm_q.p;
         }
         if (lambda_mult >= 0.0) launch_mmr(idx, dq, (const int64_t*)t.mm_r.p, nq, fetch_k, k, lambda_mult, d_pos, s);
         hipLaunchKernelGGL(k_take_picks, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, lambda_mult >= 0.0 ? (const int*)d_pos : (const int*)nullptr,
                            (const int64_t*)t.mm_r.p, (const float*)t.mm_s.p, nq, fetch_k, k, row_base, d_rows, d_sc);
-        HIP_TRY(hipGetLastError());
+        RMU_HIP_TRY(hipGetLastError());
     }
     *d_rows_out = d_rows;
     return RMU_OK;
@@ -1023,17 +988,17 @@ static int search_mmr_on(rmu_index_t* idx, const float* q, bool q_dev, int64_t n
                          int64_t* out_rows, float* out_scores, hipStream_t s, const char* who) {
     Tls& t = g_tls;
     const size_t nk = (size_t)nq * k;
-    if (t.ensure_hpin(nk * (sizeof(int64_t) + sizeof(float)))) return fail(RMU_E_OOM, std::string(who) + ": pinned result buffer");
+    if (t.hpin.ensure(nk * (sizeof(int64_t) + sizeof(float)))) return rmu_fail(RMU_E_OOM, std::string(who) + ": pinned result buffer");
     std::shared_lock<std::shared_mutex> lk;
     int64_t* d_rows = nullptr;
     const int rc = search_mmr_enqueue(idx, q, q_dev, nq, fetch_k, k, lambda_mult, row_base, -1, s, who, lk, &d_rows);
     if (rc) return rc;
     // rows | scores are contiguous on the device: ONE copy into pinned memory (a copy into the caller's pageable arrays is staged by the
     // runtime, one staging round per call), split on the host behind the synchronisation
-    HIP_TRY(hipMemcpyAsync(t.hpin, d_rows, nk * (sizeof(int64_t) + sizeof(float)), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    memcpy(out_rows, t.hpin, nk * sizeof(int64_t));
-    if (out_scores) memcpy(out_scores, t.hpin + nk * sizeof(int64_t), nk * sizeof(float));
+    RMU_HIP_TRY(hipMemcpyAsync(t.hpin.p, d_rows, nk * (sizeof(int64_t) + sizeof(float)), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipStreamSynchronize(s));
+    memcpy(out_rows, t.hpin.p, nk * sizeof(int64_t));
+    if (out_scores) memcpy(out_scores, t.hpin.p + nk * sizeof(int64_t), nk * sizeof(float));
     t.finished(s, true);
     return RMU_OK;
 }
@@ -1042,7 +1007,7 @@ static int search_mmr_on(rmu_index_t* idx, const float* q, bool q_dev, int64_t n
 // the end-of-call bookkeeping of the thread's workspaces
 int rmu_thread_stream_(hipStream_t user, hipStream_t* s) {
     const int rc = g_tls.ensure_stream(user);
-    if (rc) return fail(rc, "cannot create the calling thread's stream");
+    if (rc) return rmu_fail(rc, "cannot create the calling thread's stream");
     *s = user ? user : g_tls.stream;
     return RMU_OK;
 }
@@ -1058,13 +1023,13 @@ int rmu_index_search_mmr_enqueue_(rmu_index_t* idx, const float* q, bool q_dev, 
 extern "C" int rmu_index_search_mmr(rmu_index_t* idx, const float* q, int64_t nq, int fetch_k, int k, double lambda_mult, int64_t row_base,
                                     int64_t* out_rows, float* out_scores) {
     RMU_ENTRY();
-    if (!idx || !q || !out_rows) return fail(RMU_E_INVALID, "rmu_index_search_mmr: null pointer");
+    if (!idx || !q || !out_rows) return rmu_fail(RMU_E_INVALID, "rmu_index_search_mmr: null pointer");
     if (nq < 1 || fetch_k < 1 || fetch_k > 64 || k < 1 || k > fetch_k)
-        return fail(RMU_E_INVALID, "rmu_index_search_mmr: nq >= 1, fetch_k in [1, 64], k in [1, fetch_k]");
-    if (lambda_mult < 0.0) return fail(RMU_E_INVALID, "rmu_index_search_mmr: lambda_mult must be >= 0");
+        return rmu_fail(RMU_E_INVALID, "rmu_index_search_mmr: nq >= 1, fetch_k in [1, 64], k in [1, fetch_k]");
+    if (lambda_mult < 0.0) return rmu_fail(RMU_E_INVALID, "rmu_index_search_mmr: lambda_mult must be >= 0");
     Tls& t = g_tls;
     int rc = t.ensure_stream();
-    if (rc) return fail(rc, "rmu_index_search_mmr: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_search_mmr: stream");
     return search_mmr_on(idx, q, false, nq, fetch_k, k, lambda_mult, row_base, out_rows, out_scores, t.stream, "rmu_index_search_mmr");
 }
 
@@ -1072,13 +1037,13 @@ extern "C" int rmu_index_search_mmr(rmu_index_t* idx, const float* q, int64_t nq
 extern "C" int rmu_index_search_mmr_dev_(rmu_index_t* idx, const float* q_dev, int64_t nq, int fetch_k, int k, double lambda_mult, int64_t row_base,
                                          int64_t* out_rows, float* out_scores, void* hip_stream) {
     RMU_ENTRY();
-    if (!idx || !q_dev || !out_rows || !hip_stream) return fail(RMU_E_INVALID, "rmu_bert_search_mmr: null pointer");
+    if (!idx || !q_dev || !out_rows || !hip_stream) return rmu_fail(RMU_E_INVALID, "rmu_bert_search_mmr: null pointer");
     if (nq < 1 || fetch_k < 1 || fetch_k > 64 || k < 1 || k > fetch_k)
-        return fail(RMU_E_INVALID, "rmu_bert_search_mmr: nq >= 1, fetch_k in [1, 64], k in [1, fetch_k]");
-    if (idx->dim != 384) return fail(RMU_E_INVALID, "rmu_bert_search_mmr: the index must hold 384-d rows (the encoder's width; a wide index never does)");
+        return rmu_fail(RMU_E_INVALID, "rmu_bert_search_mmr: nq >= 1, fetch_k in [1, 64], k in [1, fetch_k]");
+    if (idx->dim != 384) return rmu_fail(RMU_E_INVALID, "rmu_bert_search_mmr: the index must hold 384-d rows (the encoder's width; a wide index never does)");
     Tls& t = g_tls;
     int rc = t.ensure_stream((hipStream_t)hip_stream);
-    if (rc) return fail(rc, "rmu_bert_search_mmr: stream");
+    if (rc) return rmu_fail(rc, "rmu_bert_search_mmr: stream");
     return search_mmr_on(idx, q_dev, true, nq, fetch_k, k, lambda_mult, row_base, out_rows, out_scores, (hipStream_t)hip_stream, "rmu_bert_search_mmr");
 }
 
@@ -1096,12 +1061,12 @@ static_assert(sizeof(RmuFileHeader) == 64, "header");
 
 extern "C" int rmu_index_save(rmu_index_t* idx, const char* path) {
     RMU_ENTRY();
-    if (!idx || !path) return fail(RMU_E_INVALID, "rmu_index_save: null argument");
+    if (!idx || !path) return rmu_fail(RMU_E_INVALID, "rmu_index_save: null argument");
     int rc = g_tls.ensure_stream();
-    if (rc) return fail(rc, "rmu_index_save: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_save: stream");
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     FILE* f = fopen(path, "wb");
-    if (!f) return fail(RMU_E_INVALID, std::string("rmu_index_save: cannot open ") + path);
+    if (!f) return rmu_fail(RMU_E_INVALID, std::string("rmu_index_save: cannot open ") + path);
     RmuFileHeader h{};
     memcpy(h.magic, "RMUIDX01", 8);
     h.dim = idx->dim; h.dpad = idx->dpad; h.metric = idx->metric; h.n = idx->n; h.n_live = idx->n_live; h.xnorm_max = idx->xnorm_max;
@@ -1115,24 +1080,24 @@ extern "C" int rmu_index_save(rmu_index_t* idx, const char* path) {
         if (hipMemcpyAsync(host.data(), (const char*)idx->x + r0 * rowb, (size_t)nr * rowb, hipMemcpyDeviceToHost, g_tls.stream) != hipSuccess ||
             hipStreamSynchronize(g_tls.stream) != hipSuccess) {
             fclose(f);
-            return fail(RMU_E_HIP, "rmu_index_save: device read");
+            return rmu_fail(RMU_E_HIP, "rmu_index_save: device read");
         }
         ok = fwrite(host.data(), rowb, (size_t)nr, f) == (size_t)nr;
     }
     ok = (fclose(f) == 0) && ok;
-    return ok ? RMU_OK : fail(RMU_E_INVALID, std::string("rmu_index_save: write failed: ") + path);
+    return ok ? RMU_OK : rmu_fail(RMU_E_INVALID, std::string("rmu_index_save: write failed: ") + path);
 }
 
 extern "C" int rmu_index_load(rmu_index_t** out, const char* path) {
     RMU_ENTRY();
-    if (!out || !path) return fail(RMU_E_INVALID, "rmu_index_load: null argument");
+    if (!out || !path) return rmu_fail(RMU_E_INVALID, "rmu_index_load: null argument");
     FILE* f = fopen(path, "rb");
-    if (!f) return fail(RMU_E_INVALID, std::string("rmu_index_load: cannot open ") + path);
+    if (!f) return rmu_fail(RMU_E_INVALID, std::string("rmu_index_load: cannot open ") + path);
     RmuFileHeader h{};
     if (fread(&h, sizeof(h), 1, f) != 1 || memcmp(h.magic, "RMUIDX01", 8) != 0 || h.n < 0 || h.dim < 1 || h.dim > RMU_MAX_DIM_WIDE ||
         h.dpad != pad_dim_metric(h.dim, h.metric)) {
         fclose(f);
-        return fail(RMU_E_INVALID, std::string("rmu_index_load: not an RMUIDX01 file: ") + path);
+        return rmu_fail(RMU_E_INVALID, std::string("rmu_index_load: not an RMUIDX01 file: ") + path);
     }
     rmu_index_t* idx = nullptr;
     int rc = rmu_index_create(&idx, h.dim, h.metric, h.n > 0 ? h.n : 4096);
@@ -1152,7 +1117,7 @@ extern "C" int rmu_index_load(rmu_index_t** out, const char* path) {
         if (ok) fold_image_stats(idx);
     }
     fclose(f);
-    if (!ok) { rmu_index_free(idx); return fail(RMU_E_INVALID, std::string("rmu_index_load: truncated or unreadable: ") + path); }
+    if (!ok) { rmu_index_free(idx); return rmu_fail(RMU_E_INVALID, std::string("rmu_index_load: truncated or unreadable: ") + path); }
     idx->n = h.n; idx->n_live = h.n_live;
     if (h.xnorm_max > idx->xnorm_max) idx->xnorm_max = h.xnorm_max;
     *out = idx;
@@ -1286,14 +1251,14 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
         S.x = (const float*)idx->split; S.row0 = l ? bounds[(size_t)l - 1] : 0; S.n_rows = bounds[(size_t)l] - S.row0;
         S.dpad = 384; S.nq = (int)nb; S.k = kp;       // (the image's geometry; an L2 index keeps its fp32 rows 768 floats apart)
         S.nrm = idx->nrm;
-        if (rmu_screen_plan(&S) != RMU_OK) return fail(RMU_E_INVALID, "rmu_index_search: screening geometry");
+        if (rmu_screen_plan(&S) != RMU_OK) return rmu_fail(RMU_E_INVALID, "rmu_index_search: screening geometry");
         if (S.pace) pwords += (size_t)S.s_chunks * 4;
         gcand_bytes = std::max(gcand_bytes, (size_t)S.parts * (size_t)nb * (kp > RMU_KS_CAP - 8 ? RMU_KS_CAP_DEEP : RMU_KS_CAP) * sizeof(u64));
     }
     const size_t part_keys = (size_t)nb * kp;
     const size_t gwords = (size_t)((nb + 255) / 256 * 256 + 64);
     const size_t gbytes = (gwords + pwords) * sizeof(u32);    // one memset zeroes thresholds and progress words
-    if (gcand_bytes && t.gcand.ensure(gcand_bytes)) return fail(RMU_E_OOM, "rmu_index_search: screening candidate slots");
+    if (gcand_bytes && t.gcand.ensure(gcand_bytes)) return rmu_fail(RMU_E_OOM, "rmu_index_search: screening candidate slots");
     // Spill path (RMU_OPT_SCREEN_SPILL, scan_screen.hip "Spill path"): the SEEDED launches of the 8-wave kernels leave the accumulators of
     // passing lanes in per-wave lists and rmu_sift_launch takes the place of their merge.  The cold first launch, the 4-wave kernels and the
     // filter's debugging modes (RMU_NO_SHARED_THR, RMU_SCREEN_NOFILTER) go the old way; switched off, the ladder is enqueued as it always was.
@@ -1309,10 +1274,10 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
         for (int l = 1; l < nl; ++l)
             if (lv[(size_t)l].wq == 8) spill_lists = std::max(spill_lists, (size_t)lv[(size_t)l].s_chunks * (size_t)lv[(size_t)l].nqt * 8);
     if (spill_lists && (t.spill.ensure(spill_lists * (size_t)spill_cap * RMU_SPILL_REC) || t.spill_cnt.ensure(spill_lists * sizeof(u32))))
-        return fail(RMU_E_OOM, "rmu_index_search: screening spill lists");
+        return rmu_fail(RMU_E_OOM, "rmu_index_search: screening spill lists");
     if (t.partial.ensure((size_t)ladder_slots(lv) * part_keys * sizeof(u64)) || t.qsplit.ensure((size_t)nb * RMU_IMG_ROW_BYTES) ||
         t.gthr.ensure(gbytes) || t.ckeys.ensure(part_keys * sizeof(u64)) || t.eps.ensure((size_t)nb * sizeof(float)) || t.ensure_events(2 * nl))
-        return fail(RMU_E_OOM, "rmu_index_search: screening workspace");
+        return rmu_fail(RMU_E_OOM, "rmu_index_search: screening workspace");
     const int sflags = share | nofilter_env();
     // (an L2 index holds its queries as (2q, 1): the image is fp16(64 q) all the same)
     // (round 6) the conversion's first workgroup also zeroes the ladder's thresholds + pacing words and the caller's word: was two memsets
@@ -1325,7 +1290,7 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
     int rc = rmu_split_launch(qdev, t.qsplit.p, nb, s, idx->dpad, l2q ? 32.0f : 64.0f, (u32*)t.gthr.p,
                               (int)(gbytes / sizeof(u32)), zero_word, zero_word ? 1 : 0, band ? (float*)t.eps.p : nullptr, idx->xnorm_max, idx->dx_max,
                               l2q ? 1 : 0);
-    if (rc) return fail(rc, "rmu_index_search: query conversion");
+    if (rc) return rmu_fail(rc, "rmu_index_search: query conversion");
     int slot = 0;
     u32* prog_next = (u32*)t.gthr.p + gwords;
     for (int l = 0; l < nl; ++l) {
@@ -1344,17 +1309,17 @@ static int screen_enqueue(rmu_index* idx, Tls& t, const float* qdev, int64_t nb,
         const bool spill = spill_lists != 0 && l > 0 && S.wq == 8;
         if (spill) { S.spill = (char*)t.spill.p; S.spill_cnt = (u32*)t.spill_cnt.p; S.spill_cap = spill_cap; }
         if (spill && idx->screen_refresh) S.share_thr |= 8;     // RMU_OPT_SCREEN_REFRESH = 1: no wave of the launch drops its refresh (scan_screen.hip "Refresh")
-        if (timed) HIP_TRY(hipEventRecord(t.lev[(size_t)(2 * l)], s));
+        if (timed) RMU_HIP_TRY(hipEventRecord(t.lev[(size_t)(2 * l)], s));
         rc = rmu_screen_launch(&S, s);
-        if (rc) return fail(rc, "rmu_index_search: screening launch");
-        if (timed) HIP_TRY(hipEventRecord(t.lev[(size_t)(2 * l + 1)], s));
+        if (rc) return rmu_fail(rc, "rmu_index_search: screening launch");
+        if (timed) RMU_HIP_TRY(hipEventRecord(t.lev[(size_t)(2 * l + 1)], s));
         if (g_dbg) dbg_dump("screen range", S.n_rows, s);
         if (spill)       // the running top-K' (the head of the merge's run) + this launch's spill lists (+ the part lists of waves that fell back)
             rc = rmu_sift_launch(&S, lvl.merge_in, nb, kp, lvl.merged, seed, s, k, band ? (const float*)t.eps.p : nullptr);
         else
             rc = rmu_merge_to_keys_band_launch(lvl.merge_in, lvl.n_lists, nb, kp, lvl.merged, seed, s, raw ? 1 : 0, k,
                                                band ? (const float*)t.eps.p : nullptr);
-        if (rc) return fail(rc, "rmu_index_search: screening merge / threshold seeding");
+        if (rc) return rmu_fail(rc, "rmu_index_search: screening merge / threshold seeding");
     }
     *n_launches = nl;
     if (last_geom) *last_geom = lv.back();
@@ -1403,21 +1368,21 @@ static int prepare_queries(const rmu_index* idx, Tls& t, const float* qsrc, int6
     *qdev = qsrc;
     const bool need_copy = !q_dev || dpad != dim || idx->metric == RMU_METRIC_COSINE;
     if (!need_copy) return RMU_OK;
-    if (t.q.ensure((size_t)nb * dpad * sizeof(float))) return fail(RMU_E_OOM, std::string(who) + ": q workspace");
-    if (dpad != dim) HIP_TRY(hipMemsetAsync(t.q.p, 0, (size_t)nb * dpad * sizeof(float), s));
-    HIP_TRY(hipMemcpy2DAsync(t.q.p, (size_t)dpad * sizeof(float), qsrc, (size_t)dim * sizeof(float),
+    if (t.q.ensure((size_t)nb * dpad * sizeof(float))) return rmu_fail(RMU_E_OOM, std::string(who) + ": q workspace");
+    if (dpad != dim) RMU_HIP_TRY(hipMemsetAsync(t.q.p, 0, (size_t)nb * dpad * sizeof(float), s));
+    RMU_HIP_TRY(hipMemcpy2DAsync(t.q.p, (size_t)dpad * sizeof(float), qsrc, (size_t)dim * sizeof(float),
                              (size_t)dim * sizeof(float), (size_t)nb,
                              q_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     if (idx->metric == RMU_METRIC_COSINE) {
         hipLaunchKernelGGL(k_row_norm, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, dpad, nb, 1,
                            (float*)nullptr);
-        HIP_TRY(hipGetLastError());
+        RMU_HIP_TRY(hipGetLastError());
     }
     if (idx->metric == RMU_METRIC_L2SQ) {
-        if (t.qn.ensure((size_t)nb * sizeof(float))) return fail(RMU_E_OOM, std::string(who) + ": |q|^2 workspace");
+        if (t.qn.ensure((size_t)nb * sizeof(float))) return rmu_fail(RMU_E_OOM, std::string(who) + ": |q|^2 workspace");
         hipLaunchKernelGGL(k_l2_aug_queries, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, (float*)t.q.p, dpad, dim, nb,
                            (float*)t.qn.p);
-        HIP_TRY(hipGetLastError());
+        RMU_HIP_TRY(hipGetLastError());
     }
     *qdev = (const float*)t.q.p;
     return RMU_OK;
@@ -1427,7 +1392,7 @@ static int prepare_queries(const rmu_index* idx, Tls& t, const float* qsrc, int6
 static int stage_outputs(Tls& t, int64_t nb, int k, bool out_dev, float** d_s, int64_t** d_r, const char* who) {
     if (out_dev) return RMU_OK;
     if (t.out_s.ensure((size_t)nb * k * sizeof(float)) || t.out_r.ensure((size_t)nb * k * sizeof(int64_t)))
-        return fail(RMU_E_OOM, std::string(who) + ": output workspace");
+        return rmu_fail(RMU_E_OOM, std::string(who) + ": output workspace");
     *d_s = (float*)t.out_s.p;
     *d_r = (int64_t*)t.out_r.p;
     return RMU_OK;
@@ -1436,8 +1401,8 @@ static int stage_outputs(Tls& t, int64_t nb, int k, bool out_dev, float** d_s, i
 static int copy_outputs(float* out_scores, int64_t* out_rows, int64_t q0, int64_t nb, int k, bool out_dev, const float* d_s, const int64_t* d_r,
                         hipStream_t s) {
     if (out_dev) return RMU_OK;
-    HIP_TRY(hipMemcpyAsync(out_scores + q0 * k, d_s, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_rows + q0 * k, d_r, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipMemcpyAsync(out_scores + q0 * k, d_s, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipMemcpyAsync(out_rows + q0 * k, d_r, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     return RMU_OK;
 }
 
@@ -1460,12 +1425,12 @@ static int search_block_screened(SearchBlock& b), search_block_deep(SearchBlock&
 extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, int k, unsigned flags, int64_t row_base,
                                 float* out_scores, int64_t* out_rows, uint64_t hip_stream) {
     RMU_ENTRY();
-    if (!idx || !q || !out_scores || !out_rows) return fail(RMU_E_INVALID, "rmu_index_search: null pointer");
-    if (nq < 1) return fail(RMU_E_INVALID, "rmu_index_search: nq must be >= 1");
-    if (k < 1 || k > RMU_MAX_K) return fail(RMU_E_INVALID, "rmu_index_search: k must be in [1, 112]");
+    if (!idx || !q || !out_scores || !out_rows) return rmu_fail(RMU_E_INVALID, "rmu_index_search: null pointer");
+    if (nq < 1) return rmu_fail(RMU_E_INVALID, "rmu_index_search: nq must be >= 1");
+    if (k < 1 || k > RMU_MAX_K) return rmu_fail(RMU_E_INVALID, "rmu_index_search: k must be in [1, 112]");
     Tls& t = g_tls;
     int rc = t.ensure_stream((hipStream_t)hip_stream);
-    if (rc) return fail(rc, "rmu_index_search: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_search: stream");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : t.stream;
     const bool q_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE;
     const bool timed = t.timing && !hip_stream;
@@ -1477,8 +1442,8 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
     float scan_total = 0.f;
     bool any_screened = false;
     int rerun_total = 0;
-    if (timed) HIP_TRY(hipEventRecord(t.ev[0], s));
-    if (t.ensure_hflag()) return fail(RMU_E_OOM, "rmu_index_search: pinned flag");
+    if (timed) RMU_HIP_TRY(hipEventRecord(t.ev[0], s));
+    if (t.ensure_hflag()) return rmu_fail(RMU_E_OOM, "rmu_index_search: pinned flag");
 
     for (int64_t q0 = 0; q0 < nq; q0 += kMaxQueriesPerLaunch) {
         const int64_t nb = (nq - q0) < kMaxQueriesPerLaunch ? (nq - q0) : kMaxQueriesPerLaunch;
@@ -1497,7 +1462,7 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
         // workspace is reused by the next query block (and host outputs must land): drain per block.  With a caller stream,
         // device outputs and a single block nothing here waits: the work is merely ordered on that stream.
         const bool drained = !hip_stream || q0 + nb < nq || !out_dev;
-        if (drained) HIP_TRY(hipStreamSynchronize(s));
+        if (drained) RMU_HIP_TRY(hipStreamSynchronize(s));
         else mark_reader(idx, s);
         t.finished(s, drained);
         if (screened) {   // the count of re-run queries is unknown while a caller's stream still runs: reported as 0 then
@@ -1505,14 +1470,14 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
             if (drained) rerun_total += *t.hflag;
         }
         if (b.exact_timed) {
-            HIP_TRY(hipEventSynchronize(t.ev[3]));
+            RMU_HIP_TRY(hipEventSynchronize(t.ev[3]));
             scan_total += elapsed_ms(t.ev[2], t.ev[3]);
         }
     }
     t.screened = any_screened ? (rerun_total ? -rerun_total : 1) : 0;
     if (timed) {
-        HIP_TRY(hipEventRecord(t.ev[1], s));
-        HIP_TRY(hipEventSynchronize(t.ev[1]));
+        RMU_HIP_TRY(hipEventRecord(t.ev[1], s));
+        RMU_HIP_TRY(hipEventSynchronize(t.ev[1]));
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess) t.search_ms = ms;
         t.scan_ms = scan_total;
@@ -1521,7 +1486,7 @@ extern "C" int rmu_index_search(rmu_index_t* idx, const float* q, int64_t nq, in
 }
 
 // ---- the exact fp32 fused scan + merge of `nqq` device queries: plan first, then run.  ALL workspace of a block is sized before anything
-// that uses it is enqueued (a grow-only buffer must not be re-allocated under work already in flight), and no Buf::ensure may run between
+// that uses it is enqueued (a grow-only buffer must not be re-allocated under work already in flight), and no RmuDevBuf::ensure may run between
 // taking a buffer's pointer and the launch that uses it -- so a path plans every launch it may need, sizes t.partial / t.gthr for the largest
 // (exact_partial_bytes, gthr_bytes), and only then runs them; run_exact takes the pointers itself.  `cond` (optional) makes both launches
 // conditional on the device-side count of flagged queries; `scatter` redirects result row i to batch row scatter[i]. ---------------------
@@ -1531,7 +1496,7 @@ static int plan_exact(const SearchBlock& b, const float* qd, int64_t nqq, const 
     L->wide = b.idx->wide_scan ? 1 : 0;     // (a dpad above 768 is routed to the wide kernel by the planner itself)
     if (cond) L->cond = *cond;
     const int rc = rmu_scan_plan(L);
-    return rc ? fail(rc, "rmu_index_search: no scan geometry for this (dim, k)") : RMU_OK;
+    return rc ? rmu_fail(rc, "rmu_index_search: no scan geometry for this (dim, k)") : RMU_OK;
 }
 // bytes of a planned launch's partial lists (a launch that was never planned: 0)
 static size_t exact_partial_bytes(const ScanLaunch& L) { return (size_t)L.parts * L.nq * L.k * sizeof(u64); }
@@ -1544,20 +1509,20 @@ static int run_exact(SearchBlock& b, ScanLaunch& L, float* os, int64_t* orr, con
     L.partial = (u64*)t.partial.p;
     L.gthr = (u32*)t.gthr.p;
     L.share_thr = share_env();
-    if (zero_gthr_bytes) HIP_TRY(hipMemsetAsync(t.gthr.p, 0, zero_gthr_bytes, s));
+    if (zero_gthr_bytes) RMU_HIP_TRY(hipMemsetAsync(t.gthr.p, 0, zero_gthr_bytes, s));
     int rc;
     if (b.idx->n > 0) {
-        if (time_it) HIP_TRY(hipEventRecord(t.ev[2], s));
+        if (time_it) RMU_HIP_TRY(hipEventRecord(t.ev[2], s));
         rc = rmu_scan_launch(&L, s);
-        if (rc) return fail(rc, std::string("rmu_index_search: scan launch: ") + hipGetErrorString(hipGetLastError()));
-        if (time_it) { HIP_TRY(hipEventRecord(t.ev[3], s)); b.exact_timed = true; }
+        if (rc) return rmu_fail(rc, std::string("rmu_index_search: scan launch: ") + hipGetErrorString(hipGetLastError()));
+        if (time_it) { RMU_HIP_TRY(hipEventRecord(t.ev[3], s)); b.exact_timed = true; }
         if (!has_cond) t.note_geometry(L, 1);
     } else {
-        HIP_TRY(hipMemsetAsync(L.partial, 0, exact_partial_bytes(L), s));
+        RMU_HIP_TRY(hipMemsetAsync(L.partial, 0, exact_partial_bytes(L), s));
     }
     rc = rmu_merge_final_launch(L.partial, L.parts, L.nq, L.k, b.row_base, b.l2 ? 1 : 0, b.l2 ? (const float*)t.qn.p : nullptr, os, orr,
                                 scatter, has_cond ? &L.cond : nullptr, s);
-    if (rc) return fail(rc, "rmu_index_search: merge launch");
+    if (rc) return rmu_fail(rc, "rmu_index_search: merge launch");
     if (g_dbg && !has_cond) dbg_dump("exact", b.idx->n, s);
     return RMU_OK;
 }
@@ -1581,7 +1546,7 @@ static int search_block_screened(SearchBlock& b) {
     const int lim_small = one_class ? 0 : (mid_n > small_n ? small_n : mid_n);    // no mid launch: the small one covers 1..nb/8
     if (t.flag.ensure(2 * sizeof(int)) || t.fb_i.ensure((size_t)nb * sizeof(int64_t)) ||
         t.fbq.ensure((size_t)gather_n * dpad * sizeof(float)))
-        return fail(RMU_E_OOM, "rmu_index_search: re-run workspace");
+        return rmu_fail(RMU_E_OOM, "rmu_index_search: re-run workspace");
     const int* cnt = (const int*)t.flag.p;
     const RmuCond c1{cnt, 1, lim_small, 1}, c2{cnt, small_n + 1, mid_n, 1}, c3{cnt, (lim_small > 0 || mid_n > small_n ? mid_n : 0) + 1, 0x7fffffff, 0};
     ScanLaunch L1{}, L2{}, L3{};
@@ -1590,7 +1555,7 @@ static int search_block_screened(SearchBlock& b) {
     if ((rc = plan_exact(b, qdev, nb, &c3, &L3))) return rc;
     const size_t need_partial = std::max({exact_partial_bytes(L1), exact_partial_bytes(L2), exact_partial_bytes(L3)});
     const size_t need_gthr = gthr_bytes(nb);           // (L3's: the gathered launches are planned for fewer queries)
-    if (t.partial.ensure(need_partial) || t.gthr.ensure(need_gthr)) return fail(RMU_E_OOM, "rmu_index_search: re-run partials");
+    if (t.partial.ensure(need_partial) || t.gthr.ensure(need_gthr)) return rmu_fail(RMU_E_OOM, "rmu_index_search: re-run partials");
     int nl = 0;
     ScanLaunch lastg{};
     if ((rc = screen_enqueue(idx, t, qdev, nb, s, b.timed, &nl, &lastg, k, screen_kp(k), (u32*)t.flag.p))) return rc;    // (flag[0] = 0 by the query conversion)
@@ -1598,20 +1563,20 @@ static int search_block_screened(SearchBlock& b) {
     // sufficiency test are appended to the list fb_i (count in flag[0])
     rc = rmu_rescore_launch((const u64*)t.ckeys.p, screen_kp(k), idx->x, qdev, nb, k, idx->xnorm_max, idx->dx_max, b.row_base, d_s, d_r,
                             (int*)t.flag.p, (int64_t*)t.fb_i.p, nullptr, s, dpad, b.l2 ? (const float*)t.qn.p : nullptr);
-    if (rc) return fail(rc, "rmu_index_search: re-score launch");
+    if (rc) return rmu_fail(rc, "rmu_index_search: re-score launch");
     t.note_geometry(lastg, nl);
     // gather (batches above 32 queries) + the re-runs' threshold zeroing + the count to the host, one launch (see the kernel)
     const int g_n = (lim_small > 0 || mid_n > small_n) ? gather_n : 0;
     hipLaunchKernelGGL(k_gather_flagged, dim3((unsigned)(g_n > 0 ? g_n : 1)), dim3(128), 0, s, qdev, dpad, (const int64_t*)t.fb_i.p, cnt,
                        (float*)t.fbq.p, g_n, (u32*)t.gthr.p, (int)(need_gthr / sizeof(u32)), t.hflag_dev);
-    HIP_TRY(hipGetLastError());
+    RMU_HIP_TRY(hipGetLastError());
     // (zero_gthr_bytes = 0: the thresholds of the mutually exclusive re-run launches were zeroed by the launch above)
     if (lim_small > 0 && (rc = run_exact(b, L1, d_s, d_r, (const int64_t*)t.fb_i.p, false, 0))) return rc;
     if (mid_n > small_n && (rc = run_exact(b, L2, d_s, d_r, (const int64_t*)t.fb_i.p, false, 0))) return rc;
     if ((rc = run_exact(b, L3, d_s, d_r, nullptr, false, 0))) return rc;
     if (b.timed)
         for (int l = 0; l < nl; ++l) {
-            HIP_TRY(hipEventSynchronize(t.lev[(size_t)(2 * l + 1)]));
+            RMU_HIP_TRY(hipEventSynchronize(t.lev[(size_t)(2 * l + 1)]));
             b.scan_ms += elapsed_ms(t.lev[(size_t)(2 * l)], t.lev[(size_t)(2 * l + 1)]);
         }
     return RMU_OK;
@@ -1636,29 +1601,29 @@ static int search_block_deep(SearchBlock& b) {
         S.row0 = l ? bounds[(size_t)l - 1] : 0;
         S.x = idx->x + S.row0 * dpad; S.n_rows = bounds[(size_t)l] - S.row0; S.dpad = dpad; S.q = b.qdev; S.nq = (int)nb; S.k = k; S.dbg = g_dbg;
         S.wide = idx->wide_scan ? 1 : 0;
-        if ((rc = rmu_scan_plan(&S))) return fail(rc, "rmu_index_search: no scan geometry for this (dim, k)");
+        if ((rc = rmu_scan_plan(&S))) return rmu_fail(rc, "rmu_index_search: no scan geometry for this (dim, k)");
     }
     const size_t part_keys = (size_t)nb * k;
     const size_t gthr_need = gthr_bytes(nb);
     if (t.partial.ensure((size_t)ladder_slots(lv) * part_keys * sizeof(u64)) || t.gthr.ensure(gthr_need))
-        return fail(RMU_E_OOM, "rmu_index_search: ladder workspace");
-    HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_need, s));
+        return rmu_fail(RMU_E_OOM, "rmu_index_search: ladder workspace");
+    RMU_HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_need, s));
     int slot = 0;
-    if (b.timed) HIP_TRY(hipEventRecord(t.ev[2], s));
+    if (b.timed) RMU_HIP_TRY(hipEventRecord(t.ev[2], s));
     for (int l = 0; l < nl; ++l) {
         ScanLaunch& S = lv[(size_t)l];
         const LadderLevel lvl = ladder_level((u64*)t.partial.p, part_keys, &slot, l, nl, S.parts, nullptr /* the last merge writes results, not keys */);
         S.partial = lvl.parts; S.gthr = (u32*)t.gthr.p; S.share_thr = share_env();
         rc = rmu_scan_launch(&S, s);
-        if (rc) return fail(rc, std::string("rmu_index_search: scan launch: ") + hipGetErrorString(hipGetLastError()));
+        if (rc) return rmu_fail(rc, std::string("rmu_index_search: scan launch: ") + hipGetErrorString(hipGetLastError()));
         if (l + 1 < nl)
             rc = rmu_merge_to_keys_launch(lvl.merge_in, lvl.n_lists, nb, k, lvl.merged, (u32*)t.gthr.p, s);
         else
             rc = rmu_merge_final_launch(lvl.merge_in, lvl.n_lists, nb, k, b.row_base, b.l2 ? 1 : 0, b.l2 ? (const float*)t.qn.p : nullptr,
                                         b.d_s, b.d_r, nullptr, nullptr, s);
-        if (rc) return fail(rc, "rmu_index_search: ladder merge");
+        if (rc) return rmu_fail(rc, "rmu_index_search: ladder merge");
     }
-    if (b.timed) { HIP_TRY(hipEventRecord(t.ev[3], s)); b.exact_timed = true; }
+    if (b.timed) { RMU_HIP_TRY(hipEventRecord(t.ev[3], s)); b.exact_timed = true; }
     t.note_geometry(lv.back(), nl);
     return RMU_OK;
 }
@@ -1669,7 +1634,7 @@ static int search_block_exact(SearchBlock& b) {
     ScanLaunch L{};
     int rc;
     if ((rc = plan_exact(b, b.qdev, b.nb, nullptr, &L))) return rc;
-    if (t.partial.ensure(exact_partial_bytes(L)) || t.gthr.ensure(gthr_bytes(b.nb))) return fail(RMU_E_OOM, "rmu_index_search: partial workspace");
+    if (t.partial.ensure(exact_partial_bytes(L)) || t.gthr.ensure(gthr_bytes(b.nb))) return rmu_fail(RMU_E_OOM, "rmu_index_search: partial workspace");
     return run_exact(b, L, b.d_s, b.d_r, nullptr, b.timed, gthr_bytes(b.nb));
 }
 
@@ -1679,13 +1644,13 @@ static int search_block_exact(SearchBlock& b) {
 extern "C" int rmu_index_search_subset(rmu_index_t* idx, const float* q, int64_t nq, int k, unsigned flags, int64_t row_base,
                                        const int64_t* rows, int64_t n_sub, float* out_scores, int64_t* out_rows, uint64_t hip_stream) {
     RMU_ENTRY();
-    if (!idx || !q || !out_scores || !out_rows) return fail(RMU_E_INVALID, "rmu_index_search_subset: null pointer");
-    if (nq < 1) return fail(RMU_E_INVALID, "rmu_index_search_subset: nq must be >= 1");
-    if (k < 1 || k > RMU_MAX_K) return fail(RMU_E_INVALID, "rmu_index_search_subset: k must be in [1, 112]");
-    if (n_sub < 0 || (n_sub > 0 && !rows)) return fail(RMU_E_INVALID, "rmu_index_search_subset: rows / n_sub");
+    if (!idx || !q || !out_scores || !out_rows) return rmu_fail(RMU_E_INVALID, "rmu_index_search_subset: null pointer");
+    if (nq < 1) return rmu_fail(RMU_E_INVALID, "rmu_index_search_subset: nq must be >= 1");
+    if (k < 1 || k > RMU_MAX_K) return rmu_fail(RMU_E_INVALID, "rmu_index_search_subset: k must be in [1, 112]");
+    if (n_sub < 0 || (n_sub > 0 && !rows)) return rmu_fail(RMU_E_INVALID, "rmu_index_search_subset: rows / n_sub");
     Tls& t = g_tls;
     int rc = t.ensure_stream((hipStream_t)hip_stream);
-    if (rc) return fail(rc, "rmu_index_search_subset: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_search_subset: stream");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : t.stream;
     const bool q_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE, rows_dev = flags & RMU_F_ROWS_DEVICE;
 
@@ -1693,29 +1658,29 @@ extern "C" int rmu_index_search_subset(rmu_index_t* idx, const float* q, int64_t
     const int dpad = idx->dpad, dim = idx->dim;
     const bool l2 = idx->metric == RMU_METRIC_L2SQ;
     if (dpad > RMU_MAX_DIM)
-        return fail(RMU_E_INVALID, "rmu_index_search_subset: the index holds rows wider than 768 dimensions (RMU_MAX_DIM): the filtered search "
+        return rmu_fail(RMU_E_INVALID, "rmu_index_search_subset: the index holds rows wider than 768 dimensions (RMU_MAX_DIM): the filtered search "
                                    "does not serve a wide index yet");
     if (!rows_dev) {            // a host list is checked before anything is enqueued; a device list is the caller's contract
         int64_t prev = -1;
         for (int64_t i = 0; i < n_sub; ++i) {
             const int64_t r = rows[i];
             if (r <= prev || r >= idx->n)
-                return fail(RMU_E_INVALID, "rmu_index_search_subset: rows must be strictly ascending ids in [0, n): entry " + std::to_string(i));
+                return rmu_fail(RMU_E_INVALID, "rmu_index_search_subset: rows must be strictly ascending ids in [0, n): entry " + std::to_string(i));
             prev = r;
         }
     }
-    if (n_sub >= 0xFFFFFFFFll || idx->n >= 0xFFFFFFFFll) return fail(RMU_E_INVALID, "rmu_index_search_subset: row ids must fit 32 bits");
+    if (n_sub >= 0xFFFFFFFFll || idx->n >= 0xFFFFFFFFll) return rmu_fail(RMU_E_INVALID, "rmu_index_search_subset: row ids must fit 32 bits");
     const int64_t n_eff = idx->n > 0 ? n_sub : 0;       // (an empty index: every id of a device list is absent)
     t.scan_ms = -1.f; t.search_ms = -1.f; t.passes = 0; t.screened = 0;
     if (n_eff > 0) {
-        if (t.sub_ids.ensure((size_t)rmu_subset_ids_len(n_eff) * sizeof(u32))) return fail(RMU_E_OOM, "rmu_index_search_subset: id workspace");
+        if (t.sub_ids.ensure((size_t)rmu_subset_ids_len(n_eff) * sizeof(u32))) return rmu_fail(RMU_E_OOM, "rmu_index_search_subset: id workspace");
         const int64_t* drows = rows;
         if (!rows_dev) {
-            if (t.sub_rows.ensure((size_t)n_eff * sizeof(int64_t))) return fail(RMU_E_OOM, "rmu_index_search_subset: list workspace");
-            HIP_TRY(hipMemcpyAsync(t.sub_rows.p, rows, (size_t)n_eff * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            if (t.sub_rows.ensure((size_t)n_eff * sizeof(int64_t))) return rmu_fail(RMU_E_OOM, "rmu_index_search_subset: list workspace");
+            RMU_HIP_TRY(hipMemcpyAsync(t.sub_rows.p, rows, (size_t)n_eff * sizeof(int64_t), hipMemcpyHostToDevice, s));
             drows = (const int64_t*)t.sub_rows.p;
         }
-        if ((rc = rmu_subset_narrow_launch(drows, n_eff, idx->n, (u32*)t.sub_ids.p, s))) return fail(rc, "rmu_index_search_subset: list conversion");
+        if ((rc = rmu_subset_narrow_launch(drows, n_eff, idx->n, (u32*)t.sub_ids.p, s))) return rmu_fail(rc, "rmu_index_search_subset: list conversion");
     }
 
     for (int64_t q0 = 0; q0 < nq; q0 += kMaxQueriesPerLaunch) {
@@ -1728,30 +1693,30 @@ extern "C" int rmu_index_search_subset(rmu_index_t* idx, const float* q, int64_t
         if (n_eff > 0) {
             SubsetLaunch L{};
             L.x = idx->x; L.n_rows = idx->n; L.dpad = dpad; L.ids = (const u32*)t.sub_ids.p; L.n_sub = n_eff; L.q = qdev; L.nq = (int)nb; L.k = k;
-            if ((rc = rmu_subset_plan(&L))) return fail(rc, "rmu_index_search_subset: no scan geometry for this (dim, k)");
+            if ((rc = rmu_subset_plan(&L))) return rmu_fail(rc, "rmu_index_search_subset: no scan geometry for this (dim, k)");
             if (t.partial.ensure((size_t)L.parts * nb * k * sizeof(u64)) || t.gthr.ensure(gthr_bytes(nb)))
-                return fail(RMU_E_OOM, "rmu_index_search_subset: partial workspace");
+                return rmu_fail(RMU_E_OOM, "rmu_index_search_subset: partial workspace");
             L.partial = (u64*)t.partial.p;
             L.gthr = (u32*)t.gthr.p;
-            HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_bytes(nb), s));
+            RMU_HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_bytes(nb), s));
             rc = rmu_subset_launch(&L, s);
-            if (rc) return fail(rc, std::string("rmu_index_search_subset: scan launch: ") + hipGetErrorString(hipGetLastError()));
+            if (rc) return rmu_fail(rc, std::string("rmu_index_search_subset: scan launch: ") + hipGetErrorString(hipGetLastError()));
             t.note_geometry(L, 1);
             parts = L.parts;
         } else {               // nothing to scan: one all-empty partial, every slot comes out (-inf | +inf, -1)
-            if (t.partial.ensure((size_t)nb * k * sizeof(u64))) return fail(RMU_E_OOM, "rmu_index_search_subset: partial workspace");
-            HIP_TRY(hipMemsetAsync(t.partial.p, 0, (size_t)nb * k * sizeof(u64), s));
+            if (t.partial.ensure((size_t)nb * k * sizeof(u64))) return rmu_fail(RMU_E_OOM, "rmu_index_search_subset: partial workspace");
+            RMU_HIP_TRY(hipMemsetAsync(t.partial.p, 0, (size_t)nb * k * sizeof(u64), s));
         }
         rc = rmu_merge_final_launch((const u64*)t.partial.p, parts, nb, k, 0, l2 ? 1 : 0, l2 ? (const float*)t.qn.p : nullptr, d_s, d_r, nullptr,
                                     nullptr, s);
-        if (rc) return fail(rc, "rmu_index_search_subset: merge launch");
+        if (rc) return rmu_fail(rc, "rmu_index_search_subset: merge launch");
         if (n_eff > 0 && (rc = rmu_subset_map_launch(d_r, (const u32*)t.sub_ids.p, nb * k, row_base, s)))
-            return fail(rc, "rmu_index_search_subset: row id launch");
+            return rmu_fail(rc, "rmu_index_search_subset: row id launch");
         if ((rc = copy_outputs(out_scores, out_rows, q0, nb, k, out_dev, d_s, d_r, s))) return rc;
         // as rmu_index_search: drain per block unless this is the only block of a caller stream with device outputs.  A host list was
         // copied from pageable memory the caller may reuse: that call drains as well.
         const bool drained = !hip_stream || q0 + nb < nq || !out_dev || !rows_dev;
-        if (drained) HIP_TRY(hipStreamSynchronize(s));
+        if (drained) RMU_HIP_TRY(hipStreamSynchronize(s));
         else mark_reader(idx, s);
         t.finished(s, drained);
     }
@@ -1767,23 +1732,23 @@ extern "C" int rmu_index_search_groups(rmu_index_t* idx, const float* q, int64_t
                                        float* out_scores, int64_t* out_rows, uint64_t hip_stream) {
     RMU_ENTRY();
     // everything that needs neither the index nor the device comes first
-    if (nq < 1 || nq > kMaxQueriesPerLaunch) return fail(RMU_E_INVALID, "rmu_index_search_groups: nq must be in [1, 8192]");
-    if (k < 1 || k > RMU_MAX_K) return fail(RMU_E_INVALID, "rmu_index_search_groups: k must be in [1, 112]");
-    if (n_lists < 1) return fail(RMU_E_INVALID, "rmu_index_search_groups: n_lists must be >= 1");
-    if (!q || !out_scores || !out_rows || !list_ptr || !q_list) return fail(RMU_E_INVALID, "rmu_index_search_groups: null pointer");
-    if (list_ptr[0] != 0) return fail(RMU_E_INVALID, "rmu_index_search_groups: list_ptr[0] must be 0");
+    if (nq < 1 || nq > kMaxQueriesPerLaunch) return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: nq must be in [1, 8192]");
+    if (k < 1 || k > RMU_MAX_K) return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: k must be in [1, 112]");
+    if (n_lists < 1) return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: n_lists must be >= 1");
+    if (!q || !out_scores || !out_rows || !list_ptr || !q_list) return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: null pointer");
+    if (list_ptr[0] != 0) return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: list_ptr[0] must be 0");
     for (int g = 0; g < n_lists; ++g)
-        if (list_ptr[g + 1] < list_ptr[g]) return fail(RMU_E_INVALID, "rmu_index_search_groups: list_ptr must be non-decreasing: entry " + std::to_string(g + 1));
+        if (list_ptr[g + 1] < list_ptr[g]) return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: list_ptr must be non-decreasing: entry " + std::to_string(g + 1));
     const int64_t n_all = list_ptr[n_lists];
-    if (n_all >= 0xFFFFFFFFll) return fail(RMU_E_INVALID, "rmu_index_search_groups: the lists together must hold fewer than 2^32 rows");
-    if (n_all > 0 && !rows) return fail(RMU_E_INVALID, "rmu_index_search_groups: rows is null");
+    if (n_all >= 0xFFFFFFFFll) return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: the lists together must hold fewer than 2^32 rows");
+    if (n_all > 0 && !rows) return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: rows is null");
     for (int64_t i = 0; i < nq; ++i)
         if (q_list[i] < 0 || q_list[i] >= n_lists || (i > 0 && q_list[i] < q_list[i - 1]))
-            return fail(RMU_E_INVALID, "rmu_index_search_groups: q_list must be non-decreasing list numbers in [0, n_lists): entry " + std::to_string(i));
-    if (!idx) return fail(RMU_E_INVALID, "rmu_index_search_groups: null index");
+            return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: q_list must be non-decreasing list numbers in [0, n_lists): entry " + std::to_string(i));
+    if (!idx) return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: null index");
     Tls& t = g_tls;
     int rc = t.ensure_stream((hipStream_t)hip_stream);
-    if (rc) return fail(rc, "rmu_index_search_groups: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_search_groups: stream");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : t.stream;
     const bool q_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE, rows_dev = flags & RMU_F_ROWS_DEVICE;
 
@@ -1791,23 +1756,23 @@ extern "C" int rmu_index_search_groups(rmu_index_t* idx, const float* q, int64_t
     const int dpad = idx->dpad;
     const bool l2 = idx->metric == RMU_METRIC_L2SQ;
     if (dpad > RMU_MAX_DIM)
-        return fail(RMU_E_INVALID, "rmu_index_search_groups: the index holds rows wider than 768 dimensions (RMU_MAX_DIM): the filtered search "
+        return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: the index holds rows wider than 768 dimensions (RMU_MAX_DIM): the filtered search "
                                    "does not serve a wide index yet");
-    if (idx->n >= 0xFFFFFFFFll) return fail(RMU_E_INVALID, "rmu_index_search_groups: row ids must fit 32 bits");
+    if (idx->n >= 0xFFFFFFFFll) return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: row ids must fit 32 bits");
     if (!rows_dev) {            // host lists are checked before anything is enqueued; device lists are the caller's contract
         for (int g = 0; g < n_lists; ++g) {
             int64_t prev = -1;
             for (int64_t i = list_ptr[g]; i < list_ptr[g + 1]; ++i) {
                 const int64_t r = rows[i];
                 if (r <= prev || r >= idx->n)
-                    return fail(RMU_E_INVALID, "rmu_index_search_groups: every list must hold strictly ascending ids in [0, n): list " +
+                    return rmu_fail(RMU_E_INVALID, "rmu_index_search_groups: every list must hold strictly ascending ids in [0, n): list " +
                                                std::to_string(g) + ", entry " + std::to_string(i - list_ptr[g]));
                 prev = r;
             }
         }
     }
     GroupsPlan P;
-    if ((rc = rmu_groups_plan(dpad, k, (int)nq, list_ptr, q_list, &P))) return fail(rc, "rmu_index_search_groups: no scan geometry for this (dim, k)");
+    if ((rc = rmu_groups_plan(dpad, k, (int)nq, list_ptr, q_list, &P))) return rmu_fail(rc, "rmu_index_search_groups: no scan geometry for this (dim, k)");
     const bool scan = idx->n > 0 && !P.lists.empty();       // (an empty index: every id of a device list is absent)
     const int parts = scan ? P.parts : 1;
     t.scan_ms = -1.f; t.search_ms = -1.f; t.passes = 0; t.screened = 0;
@@ -1817,30 +1782,30 @@ extern "C" int rmu_index_search_groups(rmu_index_t* idx, const float* q, int64_t
     float* d_s = out_scores; int64_t* d_r = out_rows;
     if ((rc = stage_outputs(t, nq, k, out_dev, &d_s, &d_r, "rmu_index_search_groups"))) return rc;
     const size_t partial_bytes = (size_t)parts * nq * k * sizeof(u64), gthr_len = (size_t)(nq + 128) * sizeof(u32);
-    if (t.partial.ensure(partial_bytes) || t.gthr.ensure(gthr_len)) return fail(RMU_E_OOM, "rmu_index_search_groups: partial workspace");
-    HIP_TRY(hipMemsetAsync(t.partial.p, 0, partial_bytes, s));     // a group's missing parts, and the queries of empty lists: empty
+    if (t.partial.ensure(partial_bytes) || t.gthr.ensure(gthr_len)) return rmu_fail(RMU_E_OOM, "rmu_index_search_groups: partial workspace");
+    RMU_HIP_TRY(hipMemsetAsync(t.partial.p, 0, partial_bytes, s));     // a group's missing parts, and the queries of empty lists: empty
     if (scan) {
         // table: [descriptors of class 0][of class 1][used lists][per-query offsets], pinned -> device in one copy
         const size_t b_t0 = P.tab[0].size() * sizeof(GroupDesc), b_t1 = P.tab[1].size() * sizeof(GroupDesc);
         const size_t b_l = P.lists.size() * sizeof(GroupList), b_q = (size_t)nq * sizeof(u32), b_all = b_t0 + b_t1 + b_l + b_q;
-        if (t.ensure_hpin(b_all) || t.gtab.ensure(b_all) || t.sub_ids.ensure((size_t)P.ids_total * sizeof(u32)))
-            return fail(RMU_E_OOM, "rmu_index_search_groups: table / id workspace");
-        if (b_t0) memcpy(t.hpin, P.tab[0].data(), b_t0);
-        if (b_t1) memcpy(t.hpin + b_t0, P.tab[1].data(), b_t1);
-        memcpy(t.hpin + b_t0 + b_t1, P.lists.data(), b_l);
-        memcpy(t.hpin + b_t0 + b_t1 + b_l, P.q_off.data(), b_q);
-        HIP_TRY(hipMemcpyAsync(t.gtab.p, t.hpin, b_all, hipMemcpyHostToDevice, s));
+        if (t.hpin.ensure(b_all) || t.gtab.ensure(b_all) || t.sub_ids.ensure((size_t)P.ids_total * sizeof(u32)))
+            return rmu_fail(RMU_E_OOM, "rmu_index_search_groups: table / id workspace");
+        if (b_t0) memcpy(t.hpin.p, P.tab[0].data(), b_t0);
+        if (b_t1) memcpy(t.hpin.p + b_t0, P.tab[1].data(), b_t1);
+        memcpy(t.hpin.p + b_t0 + b_t1, P.lists.data(), b_l);
+        memcpy(t.hpin.p + b_t0 + b_t1 + b_l, P.q_off.data(), b_q);
+        RMU_HIP_TRY(hipMemcpyAsync(t.gtab.p, t.hpin.p, b_all, hipMemcpyHostToDevice, s));
         const char* tab = (const char*)t.gtab.p;
         const int64_t* drows = rows;
         if (!rows_dev) {
-            if (t.sub_rows.ensure((size_t)n_all * sizeof(int64_t))) return fail(RMU_E_OOM, "rmu_index_search_groups: list workspace");
-            HIP_TRY(hipMemcpyAsync(t.sub_rows.p, rows, (size_t)n_all * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            if (t.sub_rows.ensure((size_t)n_all * sizeof(int64_t))) return rmu_fail(RMU_E_OOM, "rmu_index_search_groups: list workspace");
+            RMU_HIP_TRY(hipMemcpyAsync(t.sub_rows.p, rows, (size_t)n_all * sizeof(int64_t), hipMemcpyHostToDevice, s));
             drows = (const int64_t*)t.sub_rows.p;
         }
         if ((rc = rmu_groups_narrow_launch(drows, (const GroupList*)(tab + b_t0 + b_t1), (int)P.lists.size(), idx->n, (u32*)t.sub_ids.p, P.ids_total, s)))
-            return fail(rc, "rmu_index_search_groups: list conversion");
-        HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_len, s));
-        if (t.timing) HIP_TRY(hipEventRecord(t.ev[2], s));         // rmu_set_timing: the scan launches between two events
+            return rmu_fail(rc, "rmu_index_search_groups: list conversion");
+        RMU_HIP_TRY(hipMemsetAsync(t.gthr.p, 0, gthr_len, s));
+        if (t.timing) RMU_HIP_TRY(hipEventRecord(t.ev[2], s));         // rmu_set_timing: the scan launches between two events
         for (int cls = 0; cls < 2; ++cls) {
             if (P.tab[cls].empty()) continue;
             GroupsLaunch L{};
@@ -1849,21 +1814,21 @@ extern "C" int rmu_index_search_groups(rmu_index_t* idx, const float* q, int64_t
             L.tab = (const GroupDesc*)(tab + (cls ? b_t0 : 0));
             L.wq = cls ? 4 : 1; L.kv = k <= 32 ? 0 : 1; L.grid = (int)P.tab[cls].size(); L.lds_bytes = P.lds_bytes[cls];
             rc = rmu_groups_launch(&L, s);
-            if (rc) return fail(rc, std::string("rmu_index_search_groups: scan launch: ") + hipGetErrorString(hipGetLastError()));
+            if (rc) return rmu_fail(rc, std::string("rmu_index_search_groups: scan launch: ") + hipGetErrorString(hipGetLastError()));
             t.note_geometry(L, 1);
         }
-        if (t.timing) HIP_TRY(hipEventRecord(t.ev[3], s));
+        if (t.timing) RMU_HIP_TRY(hipEventRecord(t.ev[3], s));
     }
     rc = rmu_merge_final_launch((const u64*)t.partial.p, parts, nq, k, 0, l2 ? 1 : 0, l2 ? (const float*)t.qn.p : nullptr, d_s, d_r, nullptr,
                                 nullptr, s);
-    if (rc) return fail(rc, "rmu_index_search_groups: merge launch");
+    if (rc) return rmu_fail(rc, "rmu_index_search_groups: merge launch");
     if (scan) {
         const size_t q_off_at = (P.tab[0].size() + P.tab[1].size()) * sizeof(GroupDesc) + P.lists.size() * sizeof(GroupList);
         if ((rc = rmu_groups_map_launch(d_r, (const u32*)t.sub_ids.p, (const u32*)((const char*)t.gtab.p + q_off_at), nq * k, k, row_base, s)))
-            return fail(rc, "rmu_index_search_groups: row id launch");
+            return rmu_fail(rc, "rmu_index_search_groups: row id launch");
     }
     if ((rc = copy_outputs(out_scores, out_rows, 0, nq, k, out_dev, d_s, d_r, s))) return rc;
-    HIP_TRY(hipStreamSynchronize(s));          // always: the table went through the thread's pinned buffer
+    RMU_HIP_TRY(hipStreamSynchronize(s));          // always: the table went through the thread's pinned buffer
     t.finished(s, true);
     if (t.timing && scan) t.scan_ms = elapsed_ms(t.ev[2], t.ev[3]);
     return RMU_OK;
@@ -1875,37 +1840,37 @@ extern "C" int rmu_index_search_groups(rmu_index_t* idx, const float* q, int64_t
 extern "C" int rmu_index_screen_candidates(rmu_index_t* idx, const float* q_host, int64_t nq, float* out_approx, int64_t* out_rows,
                                            float* out_exact, float* out_eps) {
     RMU_ENTRY();
-    if (!idx || !q_host || !out_approx || !out_rows || !out_exact || !out_eps) return fail(RMU_E_INVALID, "rmu_index_screen_candidates: null pointer");
-    if (nq < 1 || nq > kMaxQueriesPerLaunch) return fail(RMU_E_INVALID, "rmu_index_screen_candidates: 1 <= nq <= 8192");
+    if (!idx || !q_host || !out_approx || !out_rows || !out_exact || !out_eps) return rmu_fail(RMU_E_INVALID, "rmu_index_screen_candidates: null pointer");
+    if (nq < 1 || nq > kMaxQueriesPerLaunch) return rmu_fail(RMU_E_INVALID, "rmu_index_screen_candidates: 1 <= nq <= 8192");
     Tls& t = g_tls;
     int rc = t.ensure_stream();
-    if (rc) return fail(rc, "rmu_index_screen_candidates: stream");
+    if (rc) return rmu_fail(rc, "rmu_index_screen_candidates: stream");
     hipStream_t s = t.stream;
     std::shared_lock<std::shared_mutex> lk(idx->mu);
-    if (!idx->split || idx->dim != 384 || idx->n <= 0) return fail(RMU_E_INVALID, "rmu_index_screen_candidates: index has no screening image");
-    if (idx->metric == RMU_METRIC_L2SQ) return fail(RMU_E_INVALID, "rmu_index_screen_candidates: inner-product / cosine indexes only");
+    if (!idx->split || idx->dim != 384 || idx->n <= 0) return rmu_fail(RMU_E_INVALID, "rmu_index_screen_candidates: index has no screening image");
+    if (idx->metric == RMU_METRIC_L2SQ) return rmu_fail(RMU_E_INVALID, "rmu_index_screen_candidates: inner-product / cosine indexes only");
     const int kp = kScreenKp;
     if (t.flag.ensure((size_t)(nq + 1) * sizeof(int)) || t.fb_i.ensure((size_t)nq * sizeof(int64_t)) ||
         t.out_s.ensure((size_t)nq * kp * sizeof(float)) || t.out_r.ensure((size_t)nq * kp * sizeof(int64_t)) || t.nrm.ensure((size_t)nq * sizeof(float)))
-        return fail(RMU_E_OOM, "rmu_index_screen_candidates: workspace");
+        return rmu_fail(RMU_E_OOM, "rmu_index_screen_candidates: workspace");
     const float* qdev;
     if ((rc = prepare_queries(idx, t, q_host, nq, false, s, &qdev, "rmu_index_screen_candidates"))) return rc;
-    HIP_TRY(hipMemsetAsync(t.flag.p, 0, sizeof(int), s));
+    RMU_HIP_TRY(hipMemsetAsync(t.flag.p, 0, sizeof(int), s));
     int nl = 0;
     rc = screen_enqueue(idx, t, qdev, nq, s, false, &nl, nullptr, kp /* k = K': no band -- the true approximate top-K' */);
     if (rc) return rc;
     // k = K': the re-score kernel writes the exact fp32 score of EVERY candidate (rank order) and EPS(q)
     rc = rmu_rescore_launch((const u64*)t.ckeys.p, kp, idx->x, qdev, nq, kp, idx->xnorm_max, idx->dx_max, 0, (float*)t.out_s.p,
                             (int64_t*)t.out_r.p, (int*)t.flag.p, (int64_t*)t.fb_i.p, (float*)t.nrm.p, s);
-    if (rc) return fail(rc, "rmu_index_screen_candidates: re-score");
+    if (rc) return rmu_fail(rc, "rmu_index_screen_candidates: re-score");
     std::vector<u64> keys((size_t)nq * kp);
     std::vector<float> ex((size_t)nq * kp);
     std::vector<int64_t> er((size_t)nq * kp);
-    HIP_TRY(hipMemcpyAsync(keys.data(), t.ckeys.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ex.data(), t.out_s.p, ex.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(er.data(), t.out_r.p, er.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_eps, t.nrm.p, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    RMU_HIP_TRY(hipMemcpyAsync(keys.data(), t.ckeys.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipMemcpyAsync(ex.data(), t.out_s.p, ex.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipMemcpyAsync(er.data(), t.out_r.p, er.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipMemcpyAsync(out_eps, t.nrm.p, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipStreamSynchronize(s));
     for (int64_t i = 0; i < nq; ++i)
         for (int c = 0; c < kp; ++c) {
             const u64 key = keys[(size_t)(i * kp + c)];
@@ -1921,7 +1886,7 @@ extern "C" int rmu_index_screen_candidates(rmu_index_t* idx, const float* q_host
 }
 
 extern "C" int rmu_index_set_option(rmu_index_t* idx, int option, int64_t value) {
-    if (!idx) return fail(RMU_E_INVALID, "rmu_index_set_option: null index");
+    if (!idx) return rmu_fail(RMU_E_INVALID, "rmu_index_set_option: null index");
     std::unique_lock<std::shared_mutex> lk(idx->mu);
     switch (option) {
         case RMU_OPT_SCREEN: idx->screen_enabled = value != 0; return RMU_OK;
@@ -1934,15 +1899,15 @@ extern "C" int rmu_index_set_option(rmu_index_t* idx, int option, int64_t value)
         case RMU_OPT_SCREEN_REFRESH: idx->screen_refresh = value != 0; return RMU_OK;
         case RMU_OPT_COMPACT_INPLACE: idx->compact_inplace = value != 0; return RMU_OK;
         case RMU_OPT_WIDE_SCAN:
-            if (idx->metric == RMU_METRIC_L2SQ) return fail(RMU_E_INVALID, "rmu_index_set_option: RMU_OPT_WIDE_SCAN serves RMU_METRIC_IP / RMU_METRIC_COSINE indexes only");
-            if (value != 0 && value != 1) return fail(RMU_E_INVALID, "rmu_index_set_option: RMU_OPT_WIDE_SCAN takes 0 or 1");
+            if (idx->metric == RMU_METRIC_L2SQ) return rmu_fail(RMU_E_INVALID, "rmu_index_set_option: RMU_OPT_WIDE_SCAN serves RMU_METRIC_IP / RMU_METRIC_COSINE indexes only");
+            if (value != 0 && value != 1) return rmu_fail(RMU_E_INVALID, "rmu_index_set_option: RMU_OPT_WIDE_SCAN takes 0 or 1");
             idx->wide_scan = value == 1;
             return RMU_OK;
-        default: return fail(RMU_E_INVALID, "rmu_index_set_option: unknown option");
+        default: return rmu_fail(RMU_E_INVALID, "rmu_index_set_option: unknown option");
     }
 }
 extern "C" int rmu_index_metric(rmu_index_t* idx, int* metric) {
-    if (!idx || !metric) return fail(RMU_E_INVALID, "rmu_index_metric: null");
+    if (!idx || !metric) return rmu_fail(RMU_E_INVALID, "rmu_index_metric: null");
     *metric = idx->metric;
     return RMU_OK;
 }
@@ -1950,30 +1915,30 @@ extern "C" int rmu_index_metric(rmu_index_t* idx, int* metric) {
 extern "C" int rmu_topk_merge(const float* scores, const int64_t* rows, int parts, int64_t nq, int k, unsigned flags,
                               float* out_scores, int64_t* out_rows, uint64_t hip_stream) {
     RMU_ENTRY();
-    if (!scores || !rows || !out_scores || !out_rows) return fail(RMU_E_INVALID, "rmu_topk_merge: null pointer");
-    if (parts < 1 || nq < 1 || k < 1 || k > 128) return fail(RMU_E_INVALID, "rmu_topk_merge: parts/nq >= 1, k in [1,128]");
+    if (!scores || !rows || !out_scores || !out_rows) return rmu_fail(RMU_E_INVALID, "rmu_topk_merge: null pointer");
+    if (parts < 1 || nq < 1 || k < 1 || k > 128) return rmu_fail(RMU_E_INVALID, "rmu_topk_merge: parts/nq >= 1, k in [1,128]");
     Tls& t = g_tls;
     int rc = t.ensure_stream((hipStream_t)hip_stream);
-    if (rc) return fail(rc, "rmu_topk_merge: stream");
+    if (rc) return rmu_fail(rc, "rmu_topk_merge: stream");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : t.stream;
     const bool in_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE;
     const size_t cnt = (size_t)parts * nq * k;
     const float* ds = scores; const int64_t* dr = rows;
     if (!in_dev) {
         if (t.in_s.ensure(cnt * sizeof(float)) || t.in_r.ensure(cnt * sizeof(int64_t)))
-            return fail(RMU_E_OOM, "rmu_topk_merge: input workspace");
-        HIP_TRY(hipMemcpyAsync(t.in_s.p, scores, cnt * sizeof(float), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(t.in_r.p, rows, cnt * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            return rmu_fail(RMU_E_OOM, "rmu_topk_merge: input workspace");
+        RMU_HIP_TRY(hipMemcpyAsync(t.in_s.p, scores, cnt * sizeof(float), hipMemcpyHostToDevice, s));
+        RMU_HIP_TRY(hipMemcpyAsync(t.in_r.p, rows, cnt * sizeof(int64_t), hipMemcpyHostToDevice, s));
         ds = (const float*)t.in_s.p;
         dr = (const int64_t*)t.in_r.p;
     }
     float* os = out_scores; int64_t* orr = out_rows;
     if ((rc = stage_outputs(t, nq, k, out_dev, &os, &orr, "rmu_topk_merge"))) return rc;
     rc = rmu_merge_lists_launch(ds, dr, parts, nq * k, nq * k, nq, k, (flags & RMU_F_SMALLER_BETTER) ? 1 : 0, os, orr, s);
-    if (rc) return fail(rc, "rmu_topk_merge: launch");
+    if (rc) return rmu_fail(rc, "rmu_topk_merge: launch");
     if ((rc = copy_outputs(out_scores, out_rows, 0, nq, k, out_dev, os, orr, s))) return rc;
     const bool drained = !hip_stream || !out_dev || !in_dev;
-    if (drained) HIP_TRY(hipStreamSynchronize(s));
+    if (drained) RMU_HIP_TRY(hipStreamSynchronize(s));
     t.finished(s, drained);
     return RMU_OK;
 }

@@ -17,10 +17,8 @@
 #include <rccl/rccl.h>
 
 #include "rmu_common.h"
+#include "rmu_host.h"
 #include "../../include/rmu.h"
-
-extern "C" void rmu_set_error_(const char* msg);
-static int cfail(int code, const std::string& m) { rmu_set_error_(m.c_str()); return code; }
 
 namespace {
 
@@ -84,12 +82,12 @@ static_assert(RMU_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique-id size");
 
 extern "C" int rmu_comm_unique_id(void* id_out) {
     RMU_ENTRY();
-    if (!id_out) return cfail(RMU_E_INVALID, "rmu_comm_unique_id: null");
+    if (!id_out) return rmu_fail(RMU_E_INVALID, "rmu_comm_unique_id: null");
     const RcclApi& api = rccl();
-    if (!api.error.empty()) return cfail(RMU_E_RCCL, api.error);
+    if (!api.error.empty()) return rmu_fail(RMU_E_RCCL, api.error);
     ncclUniqueId id;
     const ncclResult_t r = api.GetUniqueId(&id);
-    if (r != ncclSuccess) return cfail(RMU_E_RCCL, std::string("ncclGetUniqueId: ") + api.GetErrorString(r));
+    if (r != ncclSuccess) return rmu_fail(RMU_E_RCCL, std::string("ncclGetUniqueId: ") + api.GetErrorString(r));
     memcpy(id_out, id.internal, NCCL_UNIQUE_ID_BYTES);
     return RMU_OK;
 }
@@ -120,17 +118,17 @@ extern "C" int rmu_comm_free(rmu_comm_t* c) {
 
 extern "C" int rmu_comm_init(rmu_comm_t** out, const void* id, int world, int rank) {
     RMU_ENTRY();
-    if (!out || !id) return cfail(RMU_E_INVALID, "rmu_comm_init: null argument");
-    if (world < 1 || rank < 0 || rank >= world) return cfail(RMU_E_INVALID, "rmu_comm_init: need 0 <= rank < world");
+    if (!out || !id) return rmu_fail(RMU_E_INVALID, "rmu_comm_init: null argument");
+    if (world < 1 || rank < 0 || rank >= world) return rmu_fail(RMU_E_INVALID, "rmu_comm_init: need 0 <= rank < world");
     const RcclApi& api = rccl();
-    if (!api.error.empty()) return cfail(RMU_E_RCCL, api.error);
+    if (!api.error.empty()) return rmu_fail(RMU_E_RCCL, api.error);
     auto* c = new (std::nothrow) rmu_comm();
-    if (!c) return cfail(RMU_E_OOM, "rmu_comm_init: host alloc");
+    if (!c) return rmu_fail(RMU_E_OOM, "rmu_comm_init: host alloc");
     c->world = world; c->rank = rank;
     if (hipGetDevice(&c->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         c->comm = nullptr;
         rmu_comm_free(c);                            // one cleanup path (a created stream goes back too)
-        return cfail(RMU_E_HIP, "rmu_comm_init: stream");
+        return rmu_fail(RMU_E_HIP, "rmu_comm_init: stream");
     }
     ncclUniqueId uid;
     memcpy(uid.internal, id, NCCL_UNIQUE_ID_BYTES);
@@ -138,7 +136,7 @@ extern "C" int rmu_comm_init(rmu_comm_t** out, const void* id, int world, int ra
     if (r != ncclSuccess) {
         c->comm = nullptr;
         rmu_comm_free(c);
-        return cfail(RMU_E_RCCL, std::string("ncclCommInitRank: ") + api.GetErrorString(r));
+        return rmu_fail(RMU_E_RCCL, std::string("ncclCommInitRank: ") + api.GetErrorString(r));
     }
     *out = c;
     return RMU_OK;
@@ -146,14 +144,14 @@ extern "C" int rmu_comm_init(rmu_comm_t** out, const void* id, int world, int ra
 
 extern "C" int rmu_comm_world(rmu_comm_t* c, int* world, int* rank) {
     RMU_ENTRY();
-    if (!c) return cfail(RMU_E_INVALID, "rmu_comm_world: null");
+    if (!c) return rmu_fail(RMU_E_INVALID, "rmu_comm_world: null");
     // what RCCL says the communicator is (ncclCommCount / ncclCommUserRank), not what rmu_comm_init was asked for
     int w = c->world, r = c->rank;
     const RcclApi& api = rccl();
     if (c->comm && api.CommCount && api.CommUserRank) {
         ncclResult_t e = api.CommCount(c->comm, &w);
         if (e == ncclSuccess) e = api.CommUserRank(c->comm, &r);
-        if (e != ncclSuccess) return cfail(RMU_E_RCCL, std::string("ncclCommCount/ncclCommUserRank: ") + api.GetErrorString(e));
+        if (e != ncclSuccess) return rmu_fail(RMU_E_RCCL, std::string("ncclCommCount/ncclCommUserRank: ") + api.GetErrorString(e));
     }
     if (world) *world = w;
     if (rank) *rank = r;
@@ -163,8 +161,8 @@ extern "C" int rmu_comm_world(rmu_comm_t* c, int* world, int* rank) {
 extern "C" int rmu_shard_allgather_topk(rmu_comm_t* c, const float* scores, const int64_t* rows, int64_t nq, int k, unsigned flags,
                                         float* out_scores, int64_t* out_rows, uint64_t hip_stream) {
     RMU_ENTRY();
-    if (!c || !scores || !rows || !out_scores || !out_rows) return cfail(RMU_E_INVALID, "rmu_shard_allgather_topk: null pointer");
-    if (nq < 1 || k < 1 || k > 128) return cfail(RMU_E_INVALID, "rmu_shard_allgather_topk: nq >= 1, k in [1,128]");
+    if (!c || !scores || !rows || !out_scores || !out_rows) return rmu_fail(RMU_E_INVALID, "rmu_shard_allgather_topk: null pointer");
+    if (nq < 1 || k < 1 || k > 128) return rmu_fail(RMU_E_INVALID, "rmu_shard_allgather_topk: nq >= 1, k in [1,128]");
     const RcclApi& api = rccl();
     std::lock_guard<std::mutex> lk(c->mu);
     CommDeviceScope dev(c->device);
@@ -173,55 +171,50 @@ extern "C" int rmu_shard_allgather_topk(rmu_comm_t* c, const float* scores, cons
     const int64_t n = nq * k;
     const size_t rows_off = ((size_t)n * sizeof(float) + 7) & ~(size_t)7;
     const size_t per_rank = rows_off + (size_t)n * sizeof(int64_t);
-#define C_TRY(expr)                                                                                                  \
-    do {                                                                                                             \
-        hipError_t e_ = (expr);                                                                                      \
-        if (e_ != hipSuccess) return cfail(e_ == hipErrorOutOfMemory ? RMU_E_OOM : RMU_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
     if (per_rank > c->cap_send) {
-        C_TRY(hipStreamSynchronize(s));
+        RMU_HIP_TRY(hipStreamSynchronize(s));
         if (c->send) (void)hipFree(c->send);
         if (c->recv) (void)hipFree(c->recv);
         c->send = c->recv = nullptr; c->cap_send = 0;
-        C_TRY(hipMalloc(&c->send, per_rank));
-        C_TRY(hipMalloc(&c->recv, per_rank * (size_t)c->world));
+        RMU_HIP_TRY(hipMalloc(&c->send, per_rank));
+        RMU_HIP_TRY(hipMalloc(&c->recv, per_rank * (size_t)c->world));
         c->cap_send = per_rank;
     }
     if ((!in_dev || !out_dev) && (size_t)n > c->cap_io) {
-        C_TRY(hipStreamSynchronize(s));
+        RMU_HIP_TRY(hipStreamSynchronize(s));
         for (void* p : {(void*)c->in_s, (void*)c->in_r, (void*)c->out_s, (void*)c->out_r})
             if (p) (void)hipFree(p);
         c->in_s = c->out_s = nullptr; c->in_r = c->out_r = nullptr; c->cap_io = 0;
-        C_TRY(hipMalloc((void**)&c->in_s, (size_t)n * sizeof(float)));
-        C_TRY(hipMalloc((void**)&c->in_r, (size_t)n * sizeof(int64_t)));
-        C_TRY(hipMalloc((void**)&c->out_s, (size_t)n * sizeof(float)));
-        C_TRY(hipMalloc((void**)&c->out_r, (size_t)n * sizeof(int64_t)));
+        RMU_HIP_TRY(hipMalloc((void**)&c->in_s, (size_t)n * sizeof(float)));
+        RMU_HIP_TRY(hipMalloc((void**)&c->in_r, (size_t)n * sizeof(int64_t)));
+        RMU_HIP_TRY(hipMalloc((void**)&c->out_s, (size_t)n * sizeof(float)));
+        RMU_HIP_TRY(hipMalloc((void**)&c->out_r, (size_t)n * sizeof(int64_t)));
         c->cap_io = (size_t)n;
     }
     const float* ds = scores;
     const int64_t* dr = rows;
     if (!in_dev) {
-        C_TRY(hipMemcpyAsync(c->in_s, scores, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-        C_TRY(hipMemcpyAsync(c->in_r, rows, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        RMU_HIP_TRY(hipMemcpyAsync(c->in_s, scores, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+        RMU_HIP_TRY(hipMemcpyAsync(c->in_r, rows, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
         ds = c->in_s; dr = c->in_r;
     }
     hipLaunchKernelGGL(k_pack_lists, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ds, dr, n, (int64_t)rows_off, (char*)c->send);
-    C_TRY(hipGetLastError());
+    RMU_HIP_TRY(hipGetLastError());
     // the single exchange of the path: every rank receives every rank's [scores | rows] block
     const ncclResult_t r = api.AllGather(c->send, c->recv, per_rank, ncclChar, c->comm, s);
-    if (r != ncclSuccess) return cfail(RMU_E_RCCL, std::string("ncclAllGather: ") + api.GetErrorString(r));
+    if (r != ncclSuccess) return rmu_fail(RMU_E_RCCL, std::string("ncclAllGather: ") + api.GetErrorString(r));
     float* os = out_dev ? out_scores : c->out_s;
     int64_t* orr = out_dev ? out_rows : c->out_r;
     // ranks hold ascending row ranges, so "lower part first on ties" is the (score, row) order of the single-GPU search
     const int rc = rmu_merge_lists_launch((const float*)c->recv, (const int64_t*)((const char*)c->recv + rows_off), c->world,
                                           (int64_t)(per_rank / sizeof(float)), (int64_t)(per_rank / sizeof(int64_t)), nq, k,
                                           (flags & RMU_F_SMALLER_BETTER) ? 1 : 0, os, orr, s);
-    if (rc) return cfail(rc, "rmu_shard_allgather_topk: merge launch");
+    if (rc) return rmu_fail(rc, "rmu_shard_allgather_topk: merge launch");
     if (!out_dev) {
-        C_TRY(hipMemcpyAsync(out_scores, os, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
-        C_TRY(hipMemcpyAsync(out_rows, orr, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        RMU_HIP_TRY(hipMemcpyAsync(out_scores, os, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+        RMU_HIP_TRY(hipMemcpyAsync(out_rows, orr, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     }
-    if (!hip_stream || !out_dev || !in_dev) C_TRY(hipStreamSynchronize(s));
+    if (!hip_stream || !out_dev || !in_dev) RMU_HIP_TRY(hipStreamSynchronize(s));
 #undef C_TRY
     return RMU_OK;
 }

@@ -29,16 +29,9 @@
 
 #include "../../include/rmu.h"
 #include "rmu_common.h"
+#include "rmu_host.h"
 #include "rmu_internal.h"      // rmu_hybrid_check_ / rmu_hybrid_search_dev_: the prototypes bert.hip calls them by
 
-extern "C" void rmu_set_error_(const char* msg);
-static int hfail(int code, const std::string& m) { rmu_set_error_(m.c_str()); return code; }
-#define RRF_TRY(expr)                                                                                               \
-    do {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                     \
-        if (e_ != hipSuccess)                                                                                       \
-            return hfail(e_ == hipErrorOutOfMemory ? RMU_E_OOM : RMU_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 
@@ -139,39 +132,13 @@ __global__ __launch_bounds__(kBlock) void rrf_fuse_kernel(RrfLaunch p) {
     }
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)rmu_free(p);
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return e; }
-        cap = want;
-        return hipSuccess;
-    }
-};
-bool g_rrf_down = false;       // static destructors have begun: thread-local destructors must leave HIP alone
-struct DownGuard { ~DownGuard() { g_rrf_down = true; } } g_down_guard;
 // per-thread workspaces.  rmu_rrf_fuse given a caller stream and device buffers leaves its work in flight on them: `ev` marks its end and the
 // thread's next call waits for it on the host before it touches them again (rare: every other form of the calls drains its stream)
 struct Ctx {
-    DevBuf keys, contrib, out;
-    char* pin = nullptr;       // the contribution table on its way in | the results on their way out
-    size_t pin_cap = 0;
+    RmuDevBuf keys, contrib, out;
+    RmuPinBuf pin{8192};       // the contribution table on its way in | the results on their way out
     hipEvent_t ev = nullptr;
     bool pending = false;
-    int ensure_pin(size_t bytes) {
-        if (bytes <= pin_cap) return RMU_OK;
-        if (pin) (void)hipHostFree(pin);
-        pin = nullptr; pin_cap = 0;
-        const size_t cap = bytes < 8192 ? 8192 : bytes * 2;
-        if (hipHostMalloc((void**)&pin, cap) != hipSuccess) { pin = nullptr; (void)hipGetLastError(); return RMU_E_OOM; }
-        pin_cap = cap;
-        return RMU_OK;
-    }
     int settle() {
         if (pending && hipEventSynchronize(ev) != hipSuccess) return RMU_E_HIP;
         pending = false;
@@ -182,14 +149,12 @@ struct Ctx {
         if ((ev || hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) && hipEventRecord(ev, s) == hipSuccess) pending = true;
         else { (void)hipGetLastError(); (void)hipStreamSynchronize(s); pending = false; }
     }
+    // only what has an order: the work in flight ends, the event goes; the buffers free themselves behind this body
     ~Ctx() {
-        if (g_rrf_down) return;
+        if (rmu_runtime_down() || !ev) return;
         RMU_ENTRY();
         if (pending) (void)hipEventSynchronize(ev);
-        if (ev) (void)hipEventDestroy(ev);
-        for (DevBuf* b : {&keys, &contrib, &out})
-            if (b->p) (void)rmu_free(b->p);
-        if (pin) (void)hipHostFree(pin);
+        (void)hipEventDestroy(ev);
     }
 };
 thread_local Ctx g_ctx;
@@ -210,7 +175,7 @@ size_t out_bytes_of(int64_t nq, int k_out) { return (size_t)nq * k_out * (sizeof
 // (the workspaces are sized, the table is in pinned memory) table to the device, the kernel, and -- host outputs -- the results to pinned memory
 int fuse_enqueue(Ctx& c, RrfLaunch& L, int64_t nq, bool out_host, hipStream_t s) {
     const size_t tab_bytes = (size_t)L.lists * L.depth * sizeof(double);
-    RRF_TRY(hipMemcpyAsync(c.contrib.p, c.pin, tab_bytes, hipMemcpyHostToDevice, s));
+    RMU_HIP_TRY(hipMemcpyAsync(c.contrib.p, c.pin.p, tab_bytes, hipMemcpyHostToDevice, s));
     L.contrib = (const double*)c.contrib.p;
     if (out_host) {
         const size_t nk = (size_t)nq * L.k_out;
@@ -219,13 +184,13 @@ int fuse_enqueue(Ctx& c, RrfLaunch& L, int64_t nq, bool out_host, hipStream_t s)
         L.out_src = (int32_t*)(L.out_keys + nk);
     }
     hipLaunchKernelGGL(rrf_fuse_kernel, dim3((unsigned)nq), dim3(kBlock), 0, s, L);
-    RRF_TRY(hipGetLastError());
-    if (out_host) RRF_TRY(hipMemcpyAsync(c.pin + kMaxEntries * sizeof(double), c.out.p, out_bytes_of(nq, L.k_out), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipGetLastError());
+    if (out_host) RMU_HIP_TRY(hipMemcpyAsync(c.pin.p + kMaxEntries * sizeof(double), c.out.p, out_bytes_of(nq, L.k_out), hipMemcpyDeviceToHost, s));
     return RMU_OK;
 }
 void take_results(const Ctx& c, int64_t nq, int k_out, double* out_scores, int64_t* out_keys, int32_t* out_src) {
     const size_t nk = (size_t)nq * k_out;
-    const char* src = c.pin + kMaxEntries * sizeof(double);
+    const char* src = c.pin.p + kMaxEntries * sizeof(double);
     memcpy(out_scores, src, nk * sizeof(double));
     memcpy(out_keys, src + nk * sizeof(double), nk * sizeof(int64_t));
     memcpy(out_src, src + nk * (sizeof(double) + sizeof(int64_t)), nk * sizeof(int32_t));
@@ -236,31 +201,31 @@ void take_results(const Ctx& c, int64_t nq, int k_out, double* out_scores, int64
 extern "C" int rmu_rrf_fuse(const int64_t* keys, int lists, int64_t nq, int depth, const double* weights, int c, int k_out, unsigned flags,
                             double* out_scores, int64_t* out_keys, int32_t* out_src, uint64_t hip_stream) {
     RMU_ENTRY();
-    if (!keys || !weights || !out_scores || !out_keys || !out_src) return hfail(RMU_E_INVALID, "rmu_rrf_fuse: null pointer");
-    if (lists < 1 || lists > RMU_RRF_MAX_LISTS) return hfail(RMU_E_INVALID, "rmu_rrf_fuse: 1 <= lists <= RMU_RRF_MAX_LISTS (4)");
-    if (depth < 1 || depth > RMU_MAX_K) return hfail(RMU_E_INVALID, "rmu_rrf_fuse: 1 <= depth <= RMU_MAX_K (112)");
-    if (k_out < 1 || k_out > lists * depth) return hfail(RMU_E_INVALID, "rmu_rrf_fuse: 1 <= k_out <= lists * depth");
-    if (nq < 1 || nq > 0x7FFFFFFFll) return hfail(RMU_E_INVALID, "rmu_rrf_fuse: 1 <= nq <= 2^31 - 1");
-    if (c < 0) return hfail(RMU_E_INVALID, "rmu_rrf_fuse: c must be >= 0");
-    if (!weights_ok(weights, lists)) return hfail(RMU_E_INVALID, "rmu_rrf_fuse: every weight must be finite and >= 0");
+    if (!keys || !weights || !out_scores || !out_keys || !out_src) return rmu_fail(RMU_E_INVALID, "rmu_rrf_fuse: null pointer");
+    if (lists < 1 || lists > RMU_RRF_MAX_LISTS) return rmu_fail(RMU_E_INVALID, "rmu_rrf_fuse: 1 <= lists <= RMU_RRF_MAX_LISTS (4)");
+    if (depth < 1 || depth > RMU_MAX_K) return rmu_fail(RMU_E_INVALID, "rmu_rrf_fuse: 1 <= depth <= RMU_MAX_K (112)");
+    if (k_out < 1 || k_out > lists * depth) return rmu_fail(RMU_E_INVALID, "rmu_rrf_fuse: 1 <= k_out <= lists * depth");
+    if (nq < 1 || nq > 0x7FFFFFFFll) return rmu_fail(RMU_E_INVALID, "rmu_rrf_fuse: 1 <= nq <= 2^31 - 1");
+    if (c < 0) return rmu_fail(RMU_E_INVALID, "rmu_rrf_fuse: c must be >= 0");
+    if (!weights_ok(weights, lists)) return rmu_fail(RMU_E_INVALID, "rmu_rrf_fuse: every weight must be finite and >= 0");
     const bool in_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE;
 
     Ctx& x = g_ctx;
-    if (x.settle() != RMU_OK) return hfail(RMU_E_HIP, "rmu_rrf_fuse: waiting for the thread's previous call");
+    if (x.settle() != RMU_OK) return rmu_fail(RMU_E_HIP, "rmu_rrf_fuse: waiting for the thread's previous call");
     hipStream_t s = nullptr;
     int rc = rmu_thread_stream_((hipStream_t)hip_stream, &s);
     if (rc) return rc;
     const size_t in_bytes = (size_t)lists * nq * depth * sizeof(int64_t);
-    if (x.ensure_pin(kMaxEntries * sizeof(double) + (out_dev ? 0 : out_bytes_of(nq, k_out))) != RMU_OK)
-        return hfail(RMU_E_OOM, "rmu_rrf_fuse: pinned staging buffer");
-    RRF_TRY(x.contrib.ensure(kMaxEntries * sizeof(double)));
-    if (!in_dev) RRF_TRY(x.keys.ensure(in_bytes));
-    if (!out_dev) RRF_TRY(x.out.ensure(out_bytes_of(nq, k_out)));
+    if (x.pin.ensure(kMaxEntries * sizeof(double) + (out_dev ? 0 : out_bytes_of(nq, k_out))) != RMU_OK)
+        return rmu_fail(RMU_E_OOM, "rmu_rrf_fuse: pinned staging buffer");
+    RMU_HIP_TRY(x.contrib.ensure(kMaxEntries * sizeof(double)));
+    if (!in_dev) RMU_HIP_TRY(x.keys.ensure(in_bytes));
+    if (!out_dev) RMU_HIP_TRY(x.out.ensure(out_bytes_of(nq, k_out)));
 
     RrfLaunch L{};
     const int64_t* dk = keys;
     if (!in_dev) {
-        RRF_TRY(hipMemcpyAsync(x.keys.p, keys, in_bytes, hipMemcpyHostToDevice, s));
+        RMU_HIP_TRY(hipMemcpyAsync(x.keys.p, keys, in_bytes, hipMemcpyHostToDevice, s));
         dk = (const int64_t*)x.keys.p;
     }
     int lens[RMU_RRF_MAX_LISTS] = {0, 0, 0, 0};
@@ -270,12 +235,12 @@ extern "C" int rmu_rrf_fuse(const int64_t* keys, int lists, int64_t nq, int dept
     }
     L.lists = lists; L.depth = depth; L.k_out = k_out; L.resolve = 0;
     L.out_scores = out_scores; L.out_keys = out_keys; L.out_src = out_src;
-    fill_contrib((double*)x.pin, weights, lens, lists, depth, c);
+    fill_contrib((double*)x.pin.p, weights, lens, lists, depth, c);
     rc = fuse_enqueue(x, L, nq, !out_dev, s);
     if (rc) { (void)hipStreamSynchronize(s); x.finished(s, true); rmu_thread_finished_(s, true); return rc; }
     const bool drained = !hip_stream || !out_dev || !in_dev;
     if (drained) {
-        RRF_TRY(hipStreamSynchronize(s));
+        RMU_HIP_TRY(hipStreamSynchronize(s));
         if (!out_dev) take_results(x, nq, k_out, out_scores, out_keys, out_src);
     }
     x.finished(s, drained);
@@ -298,10 +263,10 @@ struct rmu_hybrid {
 
 extern "C" int rmu_hybrid_create(rmu_hybrid_t** out, rmu_bm25_t* sparse, rmu_index_t* dense) {
     RMU_ENTRY();
-    if (!out) return hfail(RMU_E_INVALID, "rmu_hybrid_create: out is null");
-    if (!sparse && !dense) return hfail(RMU_E_INVALID, "rmu_hybrid_create: at least one member is needed");
+    if (!out) return rmu_fail(RMU_E_INVALID, "rmu_hybrid_create: out is null");
+    if (!sparse && !dense) return rmu_fail(RMU_E_INVALID, "rmu_hybrid_create: at least one member is needed");
     rmu_hybrid* h = new (std::nothrow) rmu_hybrid();
-    if (!h) return hfail(RMU_E_OOM, "rmu_hybrid_create: out of memory");
+    if (!h) return rmu_fail(RMU_E_OOM, "rmu_hybrid_create: out of memory");
     h->sparse = sparse;
     h->dense = dense;
     *out = h;
@@ -321,16 +286,16 @@ extern "C" int rmu_hybrid_free(rmu_hybrid_t* h) {
 }
 
 extern "C" int rmu_hybrid_set_keys(rmu_hybrid_t* h, int member, int64_t first, const int64_t* keys, int64_t n) {
-    if (!h || (member != 0 && member != 1) || n < 0 || (n > 0 && !keys)) return hfail(RMU_E_INVALID, "rmu_hybrid_set_keys: bad argument");
+    if (!h || (member != 0 && member != 1) || n < 0 || (n > 0 && !keys)) return rmu_fail(RMU_E_INVALID, "rmu_hybrid_set_keys: bad argument");
     std::unique_lock<std::shared_mutex> lk(h->mu);
     std::vector<int64_t>& tab = h->keys[member];
     if (first < 0 || (uint64_t)first > tab.size())
-        return hfail(RMU_E_INVALID, "rmu_hybrid_set_keys: first (" + std::to_string(first) + ") is beyond the table's length (" + std::to_string(tab.size()) + ")");
+        return rmu_fail(RMU_E_INVALID, "rmu_hybrid_set_keys: first (" + std::to_string(first) + ") is beyond the table's length (" + std::to_string(tab.size()) + ")");
     for (int64_t i = 0; i < n; ++i)
-        if (keys[i] < 0) return hfail(RMU_E_INVALID, "rmu_hybrid_set_keys: a key is negative");
+        if (keys[i] < 0) return rmu_fail(RMU_E_INVALID, "rmu_hybrid_set_keys: a key is negative");
     try {
         tab.resize((size_t)(first + n));
-    } catch (...) { return hfail(RMU_E_OOM, "rmu_hybrid_set_keys: out of memory"); }
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_hybrid_set_keys: out of memory"); }
     if (n) memcpy(tab.data() + first, keys, (size_t)n * sizeof(int64_t));
     if (h->d_len[member] > (size_t)first) h->d_len[member] = (size_t)first;
     return RMU_OK;
@@ -345,13 +310,13 @@ static int upload_tables(rmu_hybrid* h, hipStream_t s) {
             if (h->d_keys[m]) (void)rmu_free(h->d_keys[m]);
             h->d_keys[m] = nullptr; h->d_cap[m] = 0; h->d_len[m] = 0;
             const size_t cap = n + n / 4 + 1024;
-            RRF_TRY(hipMalloc((void**)&h->d_keys[m], cap * sizeof(int64_t)));
+            RMU_HIP_TRY(hipMalloc((void**)&h->d_keys[m], cap * sizeof(int64_t)));
             h->d_cap[m] = cap;
         }
         if (h->d_len[m] < n)
-            RRF_TRY(hipMemcpyAsync(h->d_keys[m] + h->d_len[m], h->keys[m].data() + h->d_len[m], (n - h->d_len[m]) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            RMU_HIP_TRY(hipMemcpyAsync(h->d_keys[m] + h->d_len[m], h->keys[m].data() + h->d_len[m], (n - h->d_len[m]) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     }
-    RRF_TRY(hipStreamSynchronize(s));          // (the host vectors are pageable)
+    RMU_HIP_TRY(hipStreamSynchronize(s));          // (the host vectors are pageable)
     for (int m = 0; m < 2; ++m) h->d_len[m] = h->keys[m].size();
     return RMU_OK;
 }
@@ -360,16 +325,16 @@ static int upload_tables(rmu_hybrid* h, hipStream_t s) {
 static int hybrid_check(const rmu_hybrid* h, const void* q, int64_t nq, const char* blob, int64_t bytes, int k_sparse, int fetch_k, int k_dense,
                         const double* weights, int c, int k_out, const void* o1, const void* o2, const void* o3, const char* who) {
     const std::string w(who);
-    if (!h || !q || !blob || !weights || !o1 || !o2 || !o3) return hfail(RMU_E_INVALID, w + ": null argument");
-    if (nq < 1 || nq > 65535 || bytes < nq) return hfail(RMU_E_INVALID, w + ": 1 <= nq <= 65535 queries, each NUL-terminated");
-    if (k_sparse < 1 || k_sparse > RMU_MAX_K) return hfail(RMU_E_INVALID, w + ": 1 <= k_sparse <= RMU_MAX_K");
-    if (fetch_k < 1 || fetch_k > 64 || k_dense < 1 || k_dense > fetch_k) return hfail(RMU_E_INVALID, w + ": fetch_k in [1, 64], k_dense in [1, fetch_k]");
-    if (k_out < 1 || k_out > k_sparse + k_dense) return hfail(RMU_E_INVALID, w + ": 1 <= k_out <= k_sparse + k_dense");
-    if (c < 0) return hfail(RMU_E_INVALID, w + ": c must be >= 0");
-    if (!weights_ok(weights, 2)) return hfail(RMU_E_INVALID, w + ": every weight must be finite and >= 0");
+    if (!h || !q || !blob || !weights || !o1 || !o2 || !o3) return rmu_fail(RMU_E_INVALID, w + ": null argument");
+    if (nq < 1 || nq > 65535 || bytes < nq) return rmu_fail(RMU_E_INVALID, w + ": 1 <= nq <= 65535 queries, each NUL-terminated");
+    if (k_sparse < 1 || k_sparse > RMU_MAX_K) return rmu_fail(RMU_E_INVALID, w + ": 1 <= k_sparse <= RMU_MAX_K");
+    if (fetch_k < 1 || fetch_k > 64 || k_dense < 1 || k_dense > fetch_k) return rmu_fail(RMU_E_INVALID, w + ": fetch_k in [1, 64], k_dense in [1, fetch_k]");
+    if (k_out < 1 || k_out > k_sparse + k_dense) return rmu_fail(RMU_E_INVALID, w + ": 1 <= k_out <= k_sparse + k_dense");
+    if (c < 0) return rmu_fail(RMU_E_INVALID, w + ": c must be >= 0");
+    if (!weights_ok(weights, 2)) return rmu_fail(RMU_E_INVALID, w + ": every weight must be finite and >= 0");
     int64_t strings = 0;
     for (int64_t i = 0; i < bytes; ++i) strings += blob[i] == '\0';
-    if (strings != nq || blob[bytes - 1] != '\0') return hfail(RMU_E_INVALID, w + ": the blob does not hold exactly nq NUL-terminated strings");
+    if (strings != nq || blob[bytes - 1] != '\0') return rmu_fail(RMU_E_INVALID, w + ": the blob does not hold exactly nq NUL-terminated strings");
     return RMU_OK;
 }
 
@@ -380,30 +345,30 @@ static int hybrid_search(rmu_hybrid* h, const float* q, bool q_dev, int64_t nq, 
     int rc = hybrid_check(h, q, nq, blob, bytes, k_sparse, fetch_k, k_dense, weights, c, k_out, out_scores, out_ids, out_member, who);
     if (rc) return rc;
     const std::string w(who);
-    if (std::isnan(lambda_mult)) return hfail(RMU_E_INVALID, w + ": lambda_mult is not a number");
+    if (std::isnan(lambda_mult)) return rmu_fail(RMU_E_INVALID, w + ": lambda_mult is not a number");
     Ctx& x = g_ctx;
     const int depth = k_sparse > k_dense ? k_sparse : k_dense;
     const int lens[RMU_RRF_MAX_LISTS] = {k_sparse, k_dense, 0, 0};
 
     std::shared_lock<std::shared_mutex> lk(h->mu);
     // the members' records against the tables, before anything is enqueued (the members check again under their own locks)
-    if (!h->sparse && !h->keys[0].empty()) return hfail(RMU_E_INVALID, w + ": a sparse key table without a sparse member: out of step");
-    if (!h->dense && !h->keys[1].empty()) return hfail(RMU_E_INVALID, w + ": a dense key table without a dense member: out of step");
+    if (!h->sparse && !h->keys[0].empty()) return rmu_fail(RMU_E_INVALID, w + ": a sparse key table without a sparse member: out of step");
+    if (!h->dense && !h->keys[1].empty()) return rmu_fail(RMU_E_INVALID, w + ": a dense key table without a dense member: out of step");
     if (h->sparse) {
         double docs = 0.0;
         if ((rc = rmu_bm25_stat(h->sparse, RMU_BM25_STAT_DOCS, &docs))) return rc;
         if ((int64_t)docs != (int64_t)h->keys[0].size())
-            return hfail(RMU_E_INVALID, w + ": the sparse key table (" + std::to_string(h->keys[0].size()) + " keys) and the BM25 index (" +
+            return rmu_fail(RMU_E_INVALID, w + ": the sparse key table (" + std::to_string(h->keys[0].size()) + " keys) and the BM25 index (" +
                                             std::to_string((int64_t)docs) + " documents) are out of step");
     }
     if (h->dense) {
         int64_t rows = 0;
         if ((rc = rmu_index_size(h->dense, &rows))) return rc;
         if (rows != (int64_t)h->keys[1].size())
-            return hfail(RMU_E_INVALID, w + ": the dense key table (" + std::to_string(h->keys[1].size()) + " keys) and the index (" + std::to_string(rows) +
+            return rmu_fail(RMU_E_INVALID, w + ": the dense key table (" + std::to_string(h->keys[1].size()) + " keys) and the index (" + std::to_string(rows) +
                                             " rows) are out of step");
     }
-    if (x.settle() != RMU_OK) return hfail(RMU_E_HIP, w + ": waiting for the thread's previous call");
+    if (x.settle() != RMU_OK) return rmu_fail(RMU_E_HIP, w + ": waiting for the thread's previous call");
     hipStream_t s = nullptr;
     if ((rc = rmu_thread_stream_(user, &s))) return rc;
     while (h->d_len[0] != h->keys[0].size() || h->d_len[1] != h->keys[1].size()) {
@@ -414,9 +379,9 @@ static int hybrid_search(rmu_hybrid* h, const float* q, bool q_dev, int64_t nq, 
         }
         lk.lock();
     }
-    if (x.ensure_pin(kMaxEntries * sizeof(double) + out_bytes_of(nq, k_out)) != RMU_OK) return hfail(RMU_E_OOM, w + ": pinned staging buffer");
-    RRF_TRY(x.contrib.ensure(kMaxEntries * sizeof(double)));
-    RRF_TRY(x.out.ensure(out_bytes_of(nq, k_out)));
+    if (x.pin.ensure(kMaxEntries * sizeof(double) + out_bytes_of(nq, k_out)) != RMU_OK) return rmu_fail(RMU_E_OOM, w + ": pinned staging buffer");
+    RMU_HIP_TRY(x.contrib.ensure(kMaxEntries * sizeof(double)));
+    RMU_HIP_TRY(x.out.ensure(out_bytes_of(nq, k_out)));
 
     // the two members, one behind the other on s; their shared locks stay held until s is drained
     std::shared_lock<std::shared_mutex> lk_sparse, lk_dense;
@@ -441,13 +406,13 @@ static int hybrid_search(rmu_hybrid* h, const float* q, bool q_dev, int64_t nq, 
         if (!L.table[m]) L.ids[m] = nullptr;                    // an empty table: the member has no records
     }
     L.lists = 2; L.depth = depth; L.k_out = k_out; L.resolve = 1;
-    fill_contrib((double*)x.pin, weights, lens, 2, depth, c);
+    fill_contrib((double*)x.pin.p, weights, lens, 2, depth, c);
     rc = fuse_enqueue(x, L, nq, true, s);
     const hipError_t es = hipStreamSynchronize(s);
     x.finished(s, true);
     rmu_thread_finished_(s, true);
     if (rc) return rc;
-    RRF_TRY(es);
+    RMU_HIP_TRY(es);
     take_results(x, nq, k_out, out_scores, out_ids, out_member);
     return RMU_OK;
 }
@@ -473,7 +438,7 @@ extern "C" int rmu_hybrid_search_dev_(rmu_hybrid_t* h, const float* q_dev, int64
                                       int k_dense, double lambda_mult, const double* weights, int c, int k_out, double* out_scores, int64_t* out_ids,
                                       int32_t* out_member, void* hip_stream) {
     RMU_ENTRY();
-    if (!hip_stream) return hfail(RMU_E_INVALID, "rmu_bert_search_hybrid: null stream");
+    if (!hip_stream) return rmu_fail(RMU_E_INVALID, "rmu_bert_search_hybrid: null stream");
     return hybrid_search(h, q_dev, true, nq, query_blob, bytes, k_sparse, fetch_k, k_dense, lambda_mult, weights, c, k_out, out_scores, out_ids,
                          out_member, (hipStream_t)hip_stream, "rmu_bert_search_hybrid");
 }

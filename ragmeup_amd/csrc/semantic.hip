@@ -101,15 +101,15 @@ thread_local CosCtx g_ctx;
 
 extern "C" int rmu_adjacent_cosine(const float* x, int64_t n, int dim, int64_t stride, unsigned flags, double* out, uint64_t hip_stream) {
     RMU_ENTRY();
-    if (!x || !out) return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: null pointer");
+    if (!x || !out) return rmu_fail(RMU_E_INVALID, "rmu_adjacent_cosine: null pointer");
     if (flags & ~(RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE))
-        return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: flags other than RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE");
-    if (dim < 1 || dim > RMU_MAX_DIM_WIDE) return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: 1 <= dim <= RMU_MAX_DIM_WIDE (3072)");
-    if (stride < dim) return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: stride must be >= dim");
-    if (n < 1) return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: n must be >= 1");
+        return rmu_fail(RMU_E_INVALID, "rmu_adjacent_cosine: flags other than RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE");
+    if (dim < 1 || dim > RMU_MAX_DIM_WIDE) return rmu_fail(RMU_E_INVALID, "rmu_adjacent_cosine: 1 <= dim <= RMU_MAX_DIM_WIDE (3072)");
+    if (stride < dim) return rmu_fail(RMU_E_INVALID, "rmu_adjacent_cosine: stride must be >= dim");
+    if (n < 1) return rmu_fail(RMU_E_INVALID, "rmu_adjacent_cosine: n must be >= 1");
     // the matrix in bytes and the grid (one workgroup per kBlockPairs pairs) must stay representable
     if (n > (int64_t)0x7FFFFFFFll * kBlockPairs || stride > INT64_MAX / 4 / n)
-        return cos_fail(RMU_E_INVALID, "rmu_adjacent_cosine: n * stride is too large");
+        return rmu_fail(RMU_E_INVALID, "rmu_adjacent_cosine: n * stride is too large");
     if (n == 1) return RMU_OK;                                  // no pair: nothing is written, nothing is launched
     const bool in_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE;
     const int64_t n_pairs = n - 1;
@@ -120,10 +120,10 @@ extern "C" int rmu_adjacent_cosine(const float* x, int64_t n, int dim, int64_t s
     if (rc) return rc;
     const size_t in_bytes = ((size_t)n_pairs * (size_t)stride + (size_t)dim) * sizeof(float);      // (the last row's pad columns are not touched)
     const size_t out_bytes = (size_t)n_pairs * sizeof(double);
-    if (!in_dev) COS_TRY(c.in.ensure(in_bytes));
+    if (!in_dev) RMU_HIP_TRY(c.in.ensure(in_bytes));
     if (!out_dev) {
-        COS_TRY(c.out.ensure(out_bytes));
-        if (c.ensure_pin(out_bytes) != RMU_OK) return cos_fail(RMU_E_OOM, "rmu_adjacent_cosine: pinned result buffer");
+        RMU_HIP_TRY(c.out.ensure(out_bytes));
+        if (c.pin.ensure(out_bytes) != RMU_OK) return rmu_fail(RMU_E_OOM, "rmu_adjacent_cosine: pinned result buffer");
     }
     const bool drained = !hip_stream || !out_dev || !in_dev;
     const float* dx = x;
@@ -138,17 +138,17 @@ extern "C" int rmu_adjacent_cosine(const float* x, int64_t n, int dim, int64_t s
         launch(dx, n_pairs, dim, stride, dout, s);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && !out_dev) e = hipMemcpyAsync(c.pin, dout, out_bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && !out_dev) e = hipMemcpyAsync(c.pin.p, dout, out_bytes, hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) {                                      // nothing of a failed call stays in flight on the thread's workspace
         (void)hipStreamSynchronize(s);
         rmu_thread_finished_(s, true);
-        return cos_fail(RMU_E_HIP, std::string("rmu_adjacent_cosine: ") + hipGetErrorString(e));
+        return rmu_fail(RMU_E_HIP, std::string("rmu_adjacent_cosine: ") + hipGetErrorString(e));
     }
     if (drained) {
         e = hipStreamSynchronize(s);
         rmu_thread_finished_(s, true);
-        if (e != hipSuccess) return cos_fail(RMU_E_HIP, std::string("rmu_adjacent_cosine: ") + hipGetErrorString(e));
-        if (!out_dev) memcpy(out, c.pin, out_bytes);
+        if (e != hipSuccess) return rmu_fail(RMU_E_HIP, std::string("rmu_adjacent_cosine: ") + hipGetErrorString(e));
+        if (!out_dev) memcpy(out, c.pin.p, out_bytes);
         return RMU_OK;
     }
     // left in flight on the caller's stream: it touched none of the thread's workspaces, so the thread's pending state stays as it was and

@@ -28,10 +28,9 @@
 
 #include "../../include/rmu.h"
 #include "rmu_common.h"
+#include "rmu_host.h"
 #include "pair_truncate.h"
 #include "wordpiece_tables.h"
-
-extern "C" void rmu_set_error_(const char* msg);
 
 // Open-addressing table over the vocabulary for the greedy longest-match loop: keyed by (bytes, length) with FNV-1a, whose state
 // after every byte is the hash of that PREFIX -- one pass over a word's remaining bytes yields the hashes of all its candidate

@@ -194,3 +194,71 @@ def test_no_kernel_of_the_product_library_spills_to_scratch(tmp_path):
     assert found > 40, found                                   # the metadata was really read
     hot = [s for s in spilled if re.search(r"k_ffn3|k_gemm3|k_attn3|k_gemm|scan_screen_lean3|scan_topk|k_qa|k_rescore|merge_select", s[0])]
     assert hot == [], hot
+
+
+def _csrc_sources():
+    """name -> text of every csrc/*.hip and *.h, `//` comments blanked (offsets keep their lines)."""
+    import glob
+    csrc = os.path.join(ROOT, "ragmeup_amd", "csrc")
+    out = {}
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))):
+        text = open(path, encoding="utf-8").read()
+        out[os.path.basename(path)] = re.sub(r"//[^\n]*", "", text)
+    return out
+
+
+def _block(text, open_brace):
+    """The text of the brace block that opens at text[open_brace]."""
+    depth = 0
+    for i in range(open_brace, len(text)):
+        depth += text[i] == "{"
+        depth -= text[i] == "}"
+        if depth == 0:
+            return text[open_brace:i + 1]
+    raise AssertionError("unbalanced braces")
+
+
+def _enclosing(text, pos, header):
+    """Name (group 1 of `header`, a regex that ends at an opening brace) of the innermost block that holds text[pos]."""
+    name = None
+    for m in re.finditer(header, text[:pos]):
+        if m.group(1) not in ("if", "for", "while", "switch", "catch") and m.end() - 1 + len(_block(text, m.end() - 1)) > pos:
+            name = m.group(1)
+    return name
+
+
+_FN = r"\b(\w+)\s*\([^;{}]*\)\s*(?:const\s*)?\{"
+_STRUCT = r"\bstruct\s+(\w+)[^;{}()]*\{"
+
+
+def test_host_plumbing_exists_once():
+    """One grow-only device buffer, one grow-only pinned buffer, one HIP error path, one runtime-down flag (csrc/rmu_host.h; the flag and the
+    thread's message live in rmu_api.hip): a unit that brings a copy of its own fails here."""
+    src = _csrc_sources()
+    dev, pin, macros, setters, decls, guards = [], [], [], [], [], []
+    for name, text in src.items():
+        for m in re.finditer(r"\bhipMalloc\(", text):
+            owner = _enclosing(text, m.start(), _STRUCT)      # (a member function: the encoder's free ensure_* functions grow a model's arrays)
+            if owner and (_enclosing(text, m.start(), _FN) or "").startswith("ensure"):
+                dev.append((name, owner))
+        for m in re.finditer(r"\bhipHostMalloc\(", text):
+            pin.append((name, _enclosing(text, m.start(), _STRUCT), _enclosing(text, m.start(), _FN)))
+        macros += [(name, m.group(1)) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+_TRY)\b", text, flags=re.M)]
+        for m in re.finditer(r"\brmu_set_error_\(\s*\w+\.c_str\(\)\s*\)", text):
+            setters.append((name, _enclosing(text, m.start(), _FN)))
+        decls += [name for m in re.finditer(r"\bvoid\s+rmu_set_error_\s*\([^)]*\)\s*;", text)]
+        for m in re.finditer(r"~(\w+)\s*\(\s*\)\s*\{", text):
+            if re.search(r"\w*down\w*\s*=\s*true", _block(text, m.end() - 1)):
+                guards.append((name, m.group(1)))
+    assert dev == [("rmu_host.h", "RmuDevBuf")], dev
+    # the two allowed other sites are no growable buffers: the index's single pinned word and the encoder's fixed staging
+    assert sorted(set(pin)) == [("bert.hip", None, "host_staging_locked"), ("rmu_api.hip", "Tls", "ensure_hflag"),
+                                ("rmu_host.h", "RmuPinBuf", "ensure")], pin
+    assert macros == [("rmu_host.h", "RMU_HIP_TRY")], macros
+    assert setters == [("rmu_host.h", "rmu_fail")], setters
+    assert decls == ["rmu_host.h"], decls
+    assert guards == [("rmu_api.hip", "RuntimeGuard")], guards
+    # no unit forwards to the one error path through a wrapper of its own
+    wrappers = [(name, m.group(1)) for name, text in src.items()
+                for m in re.finditer(r"\bint\s+(\w*fail)\s*\([^)]*\)\s*\{[^}]*\brmu_(?:fail|set_error_)\(", text) if m.group(1) != "rmu_fail"]
+    assert wrappers == [], wrappers
