@@ -433,6 +433,29 @@ int rmu_bm25_remove_docs(rmu_bm25_t* h, const int64_t* docs, int64_t n, int64_t*
  * of the list (every posting of a query term is still scored; only the selection is restricted). */
 int rmu_bm25_search_subset(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, const int64_t* docs,
                            int64_t n_sub, float* out_scores, int64_t* out_docs, uint64_t hip_stream);
+/* rmu_bm25_search_subset with ONE LIST PER GROUP OF QUERIES, in one call (rmu_index_search_groups' contract, transposed to documents): many
+ * concurrent requests, each filtered to its own upload, share one launch.  docs = n_lists HOST lists laid end to end, list g =
+ * docs[list_ptr[g] .. list_ptr[g + 1]) (list_ptr[0] = 0, list_ptr non-decreasing), each strictly ascending ids in [0, DOCS); lists may overlap,
+ * repeat each other, be empty or go unused.  q_list[i] in [0, n_lists) = the list of query i; it must be NON-DECREASING (the caller reorders
+ * its queries, the library does not).
+ * Result of query i: exactly what rmu_bm25_search_subset(h, query i, 1, k, doc_base, list q_list[i]) returns -- the same order (score, then
+ * lower id), the same (-inf, -1) padding, no removed document, every score bit for bit.  The bits cannot move: a document's score is the fp32
+ * sum over the query's terms in order with one posting per term, so it depends neither on the tile nor on the range a workgroup covers; the
+ * statistics (N, df, idf, avgdl) stay the whole live corpus's.
+ * Limits (RMU_E_INVALID with a message, before anything is enqueued; the lists are checked under the handle's shared lock, and again after the
+ * lock was given up for an image rebuild): those of rmu_bm25_search -- 1 <= nq <= 65535, at most 1024 tokens per query, 1 <= k <= RMU_MAX_K --
+ * and n_lists >= 1.  No device work at all when nothing is live or no used list holds a live document.  Outputs are HOST arrays; the stream
+ * has been drained when the call returns.
+ * Work: unlike the subset call, the time FOLLOWS THE LISTS.  The host keeps, per used list, only the tiles that hold a live candidate; runs
+ * of kept tiles become the document ranges of a work table, cut so that a long list still spreads over the CUs and joined across empty tiles
+ * so that no query has more than RMU_BM25_OPT_MAX_WGS parts; one workgroup scores one range for one query.  Only the mask words of kept
+ * ranges (allow AND live; the queries of a list share them) are built and uploaded, never n_lists x N / 8 bytes.  One scoring launch and one
+ * merge however many lists there are.  RMU_BM25_OPT_TILE_DOCS and RMU_BM25_OPT_MAX_WGS are honoured.
+ * Serves: the sparse member of the ensemble (RAGHelper.py:497-503) for a BATCH of requests whose filters differ -- every user asking about
+ * their own upload -- which the reference answers one retriever call per request. */
+int rmu_bm25_search_groups(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base,
+                           const int64_t* docs, const int64_t* list_ptr, int n_lists, const int32_t* q_list,
+                           float* out_scores, int64_t* out_docs, uint64_t hip_stream);
 /* Reclaim removed documents (the contract of rmu_index_compact): live documents keep their order and become 0 .. n_live-1.  old_to_new
  * [map_len] receives the new id of every old one, -1 for removed ids and for the entries [DOCS, map_len); map_len < DOCS gives RMU_E_INVALID
  * and changes nothing.  *n_after (may be NULL) = documents afterwards.  With no removed document nothing changes and the image stays clean.

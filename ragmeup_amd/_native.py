@@ -51,7 +51,7 @@ SYMBOLS = [
     "rmu_bert_create", "rmu_bert_free", "rmu_bert_encode", "rmu_bert_encode_host", "rmu_bert_search_mmr",
     "rmu_tok_create", "rmu_tok_free", "rmu_tok_vocab_size", "rmu_tok_encode", "rmu_tok_encode_blob",
     "rmu_bm25_create", "rmu_bm25_free", "rmu_bm25_add_texts", "rmu_bm25_stat", "rmu_bm25_df", "rmu_bm25_set_option", "rmu_bm25_search",
-    "rmu_bm25_remove_docs", "rmu_bm25_search_subset", "rmu_bm25_compact", "rmu_bm25_save", "rmu_bm25_load",
+    "rmu_bm25_remove_docs", "rmu_bm25_search_subset", "rmu_bm25_search_groups", "rmu_bm25_compact", "rmu_bm25_save", "rmu_bm25_load",
     "rmu_rrf_fuse", "rmu_hybrid_create", "rmu_hybrid_free", "rmu_hybrid_set_keys", "rmu_hybrid_search", "rmu_bert_search_hybrid",
     "rmu_adjacent_cosine", "rmu_attribution", "rmu_bert_attribute",
     "rmu_passages_create", "rmu_passages_free", "rmu_passages_size", "rmu_passages_set", "rmu_passages_pairs", "rmu_rerank_select", "rmu_bert_rerank",
@@ -119,6 +119,9 @@ def _declare(lib):
     lib.rmu_bm25_search.argtypes = [vp, c.c_char_p, i64, i64, i32, i64, vp, vp, u64]
     lib.rmu_bm25_remove_docs.argtypes = [vp, vp, i64, c.POINTER(i64)]
     lib.rmu_bm25_search_subset.argtypes = [vp, c.c_char_p, i64, i64, i32, i64, vp, i64, vp, vp, u64]
+    lib.rmu_bm25_search_groups.argtypes = [vp, c.c_char_p, i64, i64, i32, i64, vp, vp, i32, vp, vp, vp, u64]
+    # (test hook, not in rmu.h: the host plan of rmu_bm25_search_groups)
+    lib.rmu_bm25_groups_plan_.argtypes = [i64, vp, i32, i32, vp, vp, i32, vp, i64, vp, i64, vp, i64, vp]
     lib.rmu_bm25_compact.argtypes = [vp, vp, i64, c.POINTER(i64)]
     lib.rmu_bm25_save.argtypes = [vp, c.c_char_p]
     lib.rmu_bm25_load.argtypes = [c.POINTER(vp), c.c_char_p]

@@ -11,6 +11,8 @@ reference rebuilds the retriever over every remaining text), ``compact()`` / ``c
 ``search_kwargs={"filter": ..., "expr": ...}`` on every ``invoke`` -- so both members of one ensemble keep holding the same records.  After a
 removal every score is rank_bm25's over the LIVE documents (N, df, the vocabulary and avgdl are theirs); a filter restricts the candidates
 and leaves those statistics alone, as a Milvus or ParadeDB filter does.
+``batch_invoke(queries, exprs=[...])`` (or ``filters=[...]``) gives every request its own condition; the distinct lists share one
+``rmu_bm25_search_groups`` launch whose work follows the lists (profiles/bm25_groups.md).
 
 Scores are rank_bm25.BM25Okapi's.  Ties: score descending, then the LOWER document id -- rank_bm25's ``argsort()[::-1]`` puts the higher
 id first among equal scores and is not stable.  Not provided: upsert by id, the ParadeDB SQL retriever.
@@ -21,7 +23,7 @@ import ctypes
 import json
 import os
 import threading
-from typing import Any, Callable, Iterable, List, Optional
+from typing import Any, Callable, ClassVar, Iterable, List, Optional
 
 import numpy as np
 
@@ -155,6 +157,35 @@ class BM25Index:
                                                      scores.ctypes.data, out.ctypes.data, int(stream)), "rmu_bm25_search_subset")
         return scores, out
 
+    MAX_QUERIES_PER_CALL = 65535     # rmu_bm25_search's limit on nq
+
+    def search_groups(self, queries: list[str], k: int, lists, q_list, doc_base: int = 0, stream: int = 0):
+        """Top-k of every query among ITS OWN list of documents, all in one launch (rmu_bm25_search_groups): ``lists`` is a sequence of
+        strictly ascending int64 id arrays (they may overlap, repeat each other, be empty or go unused), ``q_list[i]`` the list of query
+        i, in any order.  numpy in -> numpy out: for query i exactly what ``search([queries[i]], k, docs=lists[q_list[i]])`` returns,
+        bit for bit.  The queries are sorted by list (stably), only the lists a call uses are sent, and the results are put back in the
+        caller's order."""
+        from .index import search_groups_blocks
+        texts = np.empty(len(queries), dtype=object)
+        texts[:] = list(queries)
+
+        def call(q_block, kk, docs, list_ptr, ql, base):
+            return self._groups_call(list(q_block), kk, docs, list_ptr, ql, base, int(stream))
+
+        return search_groups_blocks(call, texts, int(k), lists, q_list, int(doc_base), block=self.MAX_QUERIES_PER_CALL)
+
+    def _groups_call(self, queries: list[str], k: int, docs: np.ndarray, list_ptr: np.ndarray, q_list: np.ndarray, doc_base: int, stream: int):
+        """One rmu_bm25_search_groups call: docs = the lists end to end (int64), list_ptr int64 [n_lists + 1], q_list int32 [nq]
+        non-decreasing."""
+        nq = len(queries)
+        scores = np.empty((nq, k), np.float32)
+        out = np.empty((nq, k), np.int64)
+        blob = _blob(queries)
+        N.check(self._lib.rmu_bm25_search_groups(self._h, blob, len(blob), nq, k, doc_base, docs.ctypes.data, list_ptr.ctypes.data,
+                                                 int(list_ptr.shape[0]) - 1, q_list.ctypes.data, scores.ctypes.data, out.ctypes.data, stream),
+                "rmu_bm25_search_groups")
+        return scores, out
+
 
 def _joined(tokens) -> str:
     """Tokens of a caller's preprocess_func -> the text whose str.split() gives them back."""
@@ -185,7 +216,7 @@ class MI355XBM25Retriever(BaseRetriever):
     def _st(self) -> dict:
         st = self.__dict__.get("_bm25_state")
         if st is None:
-            st = {"alive": [], "ids": [], "rows": {}, "gen": 0, "lock": threading.RLock()}
+            st = {"alive": [], "ids": [], "rows": {}, "fmaps": {}, "fmap_builds": 0, "gen": 0, "lock": threading.RLock()}
             object.__setattr__(self, "_bm25_state", st)
         n = len(self.docs)
         if len(st["alive"]) < n:                          # documents handed to the constructor
@@ -235,7 +266,7 @@ class MI355XBM25Retriever(BaseRetriever):
                 self.docs.append(self._document(t, m, i))
             st["ids"] += ids
             st["alive"] += [True] * len(texts)
-            st["rows"] = {}
+            self._records_changed(st)
         return ids
 
     def add_documents(self, documents: Iterable[Document], ids: Optional[Iterable[str]] = None) -> list:
@@ -245,15 +276,57 @@ class MI355XBM25Retriever(BaseRetriever):
                               ids if ids is not None else [getattr(d, "id", None) for d in documents])
 
     # ---- conditions over the records: the store's language (MI355XVectorStore._conditions), evaluated over docs[i].metadata and the id ---
+    def _records_changed(self, st):
+        """(under st["lock"]) documents were added, removed or renumbered: the cached id lists and field maps no longer hold"""
+        st["rows"] = {}
+        st["fmaps"] = {}
+
+    def _field_map(self, field: str):
+        """value -> ascending int64 ids of the live documents whose ``field`` holds it (+ the few documents with unhashable values): the
+        store's ``_field_map``, built once per field until the records change, so a condition is a dictionary look-up, not a walk."""
+        st = self._st()
+        fm = st["fmaps"].get(field)
+        if fm is None:
+            with st["lock"]:
+                fm = st["fmaps"].get(field)
+                if fm is None:
+                    buckets: dict = {}
+                    odd: list = []
+                    for r, (d, alive, pk) in enumerate(zip(self.docs, st["alive"], st["ids"])):
+                        if not alive:
+                            continue
+                        v = pk if field == "pk" else d.metadata.get(field)      # (a document without the field holds None)
+                        try:
+                            buckets.setdefault(v, []).append(r)
+                        except TypeError:                                       # a list / dict as metadata value
+                            odd.append((r, v))
+                    fm = ({v: np.asarray(rs, dtype=np.int64) for v, rs in buckets.items()}, odd)
+                    st["fmaps"][field] = fm
+                    st["fmap_builds"] += 1
+        return fm
+
     def _matching(self, conds) -> np.ndarray:
         """Ascending int64 ids of the live documents that satisfy every condition; "pk" names the document's id."""
-        st = self._st()
-        out = []
-        for r, (d, alive, pk) in enumerate(zip(self.docs, st["alive"], st["ids"])):
-            if alive and all(any(v == x for x in vals) or v == vals
-                             for v, vals in ((pk if f == "pk" else d.metadata.get(f), vals) for f, vals in conds)):
-                out.append(r)
-        return np.asarray(out, dtype=np.int64)
+        rows = None
+        for field, vals in conds:
+            by_value, odd = self._field_map(field)
+            parts = []
+            for v in vals:
+                try:
+                    hit = by_value.get(v)
+                except TypeError:
+                    hit = None
+                if hit is not None:
+                    parts.append(hit)
+            if odd:
+                parts.append(np.asarray([r for r, v in odd if any(v == x for x in vals) or v == vals], dtype=np.int64))
+            if not parts:
+                return np.zeros(0, np.int64)
+            cur = parts[0] if len(parts) == 1 else np.unique(np.concatenate(parts))
+            rows = cur if rows is None else np.intersect1d(rows, cur, assume_unique=True)
+            if rows.size == 0:
+                break
+        return rows if rows is not None else np.flatnonzero(np.asarray(self._st()["alive"], dtype=bool)).astype(np.int64)
 
     def _candidates(self):
         """The document ids search_kwargs' "filter" / "expr" admit (None: no restriction), cached until the records change."""
@@ -294,7 +367,7 @@ class MI355XBM25Retriever(BaseRetriever):
                 assert n == len(rows)
                 for r in rows:
                     st["alive"][r] = False
-                st["rows"] = {}
+                self._records_changed(st)
                 thr = self.compact_threshold
                 if thr is not None and len(st["alive"]) - sum(st["alive"]) > float(thr) * len(st["alive"]):
                     self.compact()
@@ -314,8 +387,8 @@ class MI355XBM25Retriever(BaseRetriever):
                 self.docs = [docs[r] for r in keep]
                 st["ids"] = [pks[r] for r in keep]
                 st["alive"] = [True] * len(keep)
-                st["rows"] = {}
             finally:
+                self._records_changed(st)                 # compaction renumbers the documents
                 st["gen"] += 1
             return before - len(keep)
 
@@ -345,11 +418,63 @@ class MI355XBM25Retriever(BaseRetriever):
         st = self._st()
         st["ids"] = [r["id"] for r in recs]
         st["alive"] = [bool(r["alive"]) for r in recs]
+        self._records_changed(st)
         return self
 
-    def batch_invoke(self, queries: list[str]) -> list[list[Document]]:
-        """One rmu_bm25_search for the whole batch (rmu_bm25_search_subset under a filter); a removed document never comes back."""
+    # The grouped call (BM25Index.search_groups) answers two or more distinct lists in one launch.  profiles/bm25_groups.md measures it
+    # against the per-list subset calls it replaces (1M documents, k = 4, lists of contiguous and of random ids, 1 and 4 queries per list).
+    # Each row: (documents in the longest list at most, distinct lists at least, at most) -- exactly where the table has the grouped call
+    # ahead by more than the run-to-run spread in every run.  Not decided there, so the per-list loop stays: 2 lists of 10 000 documents
+    # (random ids: 0.88x and 1.04x), 2 and 128 lists of 100 000.  Not measured: more than 128 lists, lists beyond 100 000 documents.
+    GROUPS_RULE: ClassVar[tuple] = ((1_000, 2, 128), (10_000, 8, 128), (100_000, 8, 32))
+
+    @classmethod
+    def _use_groups(cls, index, lists: list) -> bool:
+        if len(lists) < 2 or not hasattr(index, "search_groups"):
+            return False
+        longest = max(int(l.size) for l in lists)
+        for docs_at_most, lists_at_least, lists_at_most in cls.GROUPS_RULE:
+            if longest <= docs_at_most:
+                return lists_at_least <= len(lists) <= lists_at_most
+        return False
+
+    def _search_each(self, texts: list[str], k: int, conds_each: list) -> np.ndarray:
+        """One condition per query (None = unfiltered), inside batch_invoke's retry loop: equal conditions share one list, the unfiltered
+        queries take the ordinary search, one distinct list takes the subset call, two or more take the grouped call where
+        profiles/bm25_groups.md has it ahead, an empty selection costs no launch.  -> ids [nq, k], padded with -1."""
+        nq = len(texts)
+        rows = np.full((nq, k), -1, np.int64)
+        plain = [i for i, c in enumerate(conds_each) if c is None]
+        if plain:
+            rows[plain] = self.vectorizer.search([texts[i] for i in plain], k)[1]
+        keys, lists, q_of = {}, [], []                      # condition -> list number; the lists; the queries of each list
+        for i, c in enumerate(conds_each):
+            if c is None:
+                continue
+            key = repr(c)
+            if key not in keys:
+                keys[key] = len(lists)
+                lists.append(self._matching(c))
+                q_of.append([])
+            q_of[keys[key]].append(i)
+        used = [g for g in range(len(lists)) if lists[g].size]      # (an empty selection: its queries keep the padding)
+        if self._use_groups(self.vectorizer, [lists[g] for g in used]):
+            qi = [i for g in used for i in q_of[g]]
+            ql = [n for n, g in enumerate(used) for _ in q_of[g]]
+            rows[qi] = self.vectorizer.search_groups([texts[i] for i in qi], k, [lists[g] for g in used], ql)[1]
+        else:
+            for g in used:
+                rows[q_of[g]] = self.vectorizer.search([texts[i] for i in q_of[g]], k, docs=lists[g])[1]
+        return rows
+
+    def batch_invoke(self, queries: list[str], filters: Optional[list] = None, exprs: Optional[list] = None) -> list[list[Document]]:
+        """One rmu_bm25_search for the whole batch (rmu_bm25_search_subset under a filter); a removed document never comes back.
+        ``filters`` / ``exprs``: one condition per query (None = unfiltered), e.g. every request asking about its own upload -- the
+        conditions are resolved through the cached field maps and the distinct lists share one rmu_bm25_search_groups call."""
+        from .vectorstore import MI355XVectorStore
         queries = list(queries)
+        kw = self.search_kwargs or {}
+        each = MI355XVectorStore._conditions_per_query(len(queries), kw.get("expr"), kw.get("filter"), exprs, filters)
         if not queries or not self.docs:
             return [[] for _ in queries]
         st = self._st()
@@ -362,7 +487,11 @@ class MI355XBM25Retriever(BaseRetriever):
                 continue
             docs = self.docs
             try:
-                _, rows = self.vectorizer.search(texts, min(int(self.k), N.MAX_K), docs=self._candidates())
+                k = min(int(self.k), N.MAX_K)
+                if each is None:
+                    _, rows = self.vectorizer.search(texts, k, docs=self._candidates())
+                else:                                     # (resolved here: a compaction cannot slip between the lists and the search)
+                    rows = self._search_each(texts, k, each)
                 out = [[docs[r] for r in row if r >= 0] for row in rows.tolist()]
             except Exception:
                 if st["gen"] != g:                        # e.g. an id that no longer exists

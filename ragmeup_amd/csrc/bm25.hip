@@ -39,6 +39,10 @@
 // bitonic helpers) and skips, with one ballot, every batch in which no key beats its current k-th; the waves combine through LDS at the end of
 // the range; the workgroup writes one sorted, zero-padded list [part, q, k], and rmu_merge_final_launch (topk_merge.hip) finishes.
 //
+// Kernel (bm25_groups_kernel, rmu_bm25_search_groups): the same body over a work table instead of a grid of equal ranges.  Every query has its
+// own list of candidate documents; the host keeps, per list, only the tiles that hold a live candidate and turns runs of them into ranges
+// (groups_plan), so the time follows the lists, not the postings of the terms over the whole corpus.  One workgroup per (query, range).
+//
 // Kernel (bm25_splice_kernel): a workgroup owns kSpliceSpan consecutive positions of the new image.  One binary search over the new post_ptr
 // finds the term that holds its first position; from there every lane walks the terms forward as its positions (lane, lane + 256, ...) pass
 // their ends.  Position j of term t is element j - new_ptr[t] of the term's list: the old image's while that is below the old length,
@@ -79,7 +83,8 @@ struct Bm25Launch {
     const u32* term_ptr;     // [nq + 1]: query q's descriptors are terms[term_ptr[q] .. term_ptr[q + 1])
     const TermDesc* terms;
     u64* partial;            // [parts, nq, k]
-    const u32* mask;         // bm25_masked_kernel only: bit d set = document d is a candidate; ceil(n_docs / 32) + 1 words
+    const u32* mask;         // bm25_masked_kernel: bit d set = document d is a candidate; ceil(n_docs / 32) + 1 words.  bm25_groups_kernel: the
+                             // mask words of all ranges, each range's at its GroupWork::mask_off
     u32 n_docs;
     int nq, k, tile, tiles_per_wg;
 };
@@ -100,21 +105,20 @@ __device__ __forceinline__ u64 kth_of(const u64 (&top)[NPL], int k) {
     return __shfl(v, (k - 1) & 63);
 }
 
-// The one body of both kernels.  MASKED: a document whose bit in p.mask is clear gets key 0, the padding key the final merge turns into
-// (-inf, -1); the score loop is the same, so a candidate's sum is the same ordered fp32 sum whatever is masked.
+// The one body of all three kernels: query q over the documents [d_lo, d_hi), d_lo a multiple of the tile; the workgroup's sorted list goes to
+// out[0, k).  MASKED: bit i of `mask` stands for document d_lo + i (2 * ceil((d_hi - d_lo) / 64) words are read); a document whose bit is clear
+// gets key 0, the padding key the final merge turns into (-inf, -1); the score loop is the same, so a candidate's sum is the same ordered fp32
+// sum whatever is masked and whatever the range.
 template <int NPL, bool MASKED>
-__device__ __forceinline__ void bm25_score_select(const Bm25Launch& p) {
+__device__ __forceinline__ void bm25_score_select(const Bm25Launch& p, const int q, const int64_t d_lo, const int64_t d_hi,
+                                                  const u32* __restrict__ mask, u64* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) float acc[kMaxTile];
     __shared__ u32 cur[kMaxTerms];
     __shared__ u32 wcnt[2][kWaves];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int q = blockIdx.y;
     const u32 tb = p.term_ptr[q];
     const int nt = (int)(p.term_ptr[q + 1] - tb);
     const TermDesc* __restrict__ terms = p.terms + tb;
-    const int64_t d_lo = (int64_t)blockIdx.x * p.tiles_per_wg * p.tile;
-    const int64_t d_end = d_lo + (int64_t)p.tiles_per_wg * p.tile;
-    const int64_t d_hi = d_end < (int64_t)p.n_docs ? d_end : (int64_t)p.n_docs;
 
     // the only search: first posting >= d_lo of every term, one lane per term
     for (int t = tid; t < nt; t += kBlock) {
@@ -143,7 +147,7 @@ __device__ __forceinline__ void bm25_score_select(const Bm25Launch& p) {
         if constexpr (MASKED) {
             const int jb = (w + kWaves * lane) * 64;
             if (jb < cnt) {
-                const u32* __restrict__ mp = p.mask + ((t0 + jb) >> 5);
+                const u32* __restrict__ mp = mask + ((t0 - d_lo + jb) >> 5);
                 m_lo = mp[0];
                 m_hi = mp[1];
             }
@@ -212,7 +216,6 @@ __device__ __forceinline__ void bm25_score_select(const Bm25Launch& p) {
         fold64<NPL>(top, key, lane);
         kth = kth_of<NPL>(top, p.k);
     }
-    u64* out = p.partial + ((int64_t)blockIdx.x * p.nq + q) * p.k;
 #pragma unroll
     for (int i = 0; i < NPL; ++i) {
         const int e = lane + 64 * i;
@@ -220,12 +223,34 @@ __device__ __forceinline__ void bm25_score_select(const Bm25Launch& p) {
     }
 }
 
+// grid = (workgroups over the document axis, queries): workgroup x owns tiles_per_wg tiles from its own offset, part list x of its query
+template <int NPL, bool MASKED>
+__device__ __forceinline__ void bm25_grid_range(const Bm25Launch& p) {
+    const int q = blockIdx.y;
+    const int64_t d_lo = (int64_t)blockIdx.x * p.tiles_per_wg * p.tile;
+    const int64_t d_end = d_lo + (int64_t)p.tiles_per_wg * p.tile;
+    const int64_t d_hi = d_end < (int64_t)p.n_docs ? d_end : (int64_t)p.n_docs;
+    bm25_score_select<NPL, MASKED>(p, q, d_lo, d_hi, MASKED ? p.mask + (d_lo >> 5) : nullptr, p.partial + ((int64_t)blockIdx.x * p.nq + q) * p.k);
+}
 // every document is a candidate: what an index without removed documents launches for an unfiltered search
 template <int NPL>
-__global__ __launch_bounds__(kBlock) void bm25_topk_kernel(Bm25Launch p) { bm25_score_select<NPL, false>(p); }
+__global__ __launch_bounds__(kBlock) void bm25_topk_kernel(Bm25Launch p) { bm25_grid_range<NPL, false>(p); }
 // candidates = the set bits of p.mask (the handle's liveness bitmap, or a call's allow AND live)
 template <int NPL>
-__global__ __launch_bounds__(kBlock) void bm25_masked_kernel(Bm25Launch p) { bm25_score_select<NPL, true>(p); }
+__global__ __launch_bounds__(kBlock) void bm25_masked_kernel(Bm25Launch p) { bm25_grid_range<NPL, true>(p); }
+
+// rmu_bm25_search_groups: one workgroup per entry of a work table the host planned from the lists (groups_plan below).  An entry names its
+// query, a document range that starts on a tile boundary and ends on one or at n_docs, the part list of the query it fills, and the first
+// mask word of the range (allow AND live of the query's list; the queries of one list read the same words)
+struct GroupWork {
+    u32 q, part, d_lo, d_hi, mask_off;
+};
+static_assert(sizeof(GroupWork) == 20, "work table layout");
+template <int NPL>
+__global__ __launch_bounds__(kBlock) void bm25_groups_kernel(Bm25Launch p, const GroupWork* __restrict__ work) {
+    const GroupWork g = work[blockIdx.x];
+    bm25_score_select<NPL, true>(p, (int)g.q, (int64_t)g.d_lo, (int64_t)g.d_hi, p.mask + g.mask_off, p.partial + ((int64_t)g.part * p.nq + g.q) * p.k);
+}
 
 // ---- splice: old image + delta -> new image --------------------------------------------------------------------------------------------
 constexpr int kSpliceItems = 8;                       // positions per lane
@@ -704,20 +729,15 @@ extern "C" int rmu_bm25_set_option(rmu_bm25_t* h, int option, int64_t value) {
     return RMU_OK;
 }
 
-// The first half of a search: everything up to and including the final merge is enqueued on *s_out (hip_stream, or the calling thread's own
-// stream) and the results are left on the device, *d_docs [nq, k] int64 (+ doc_base) and *d_scores [nq, k] fp32, in the thread's workspace.  `lk`
-// comes back holding the handle's shared lock, which the caller keeps until it has drained the stream (see the header: no reader is ever left in
-// flight behind the lock).  *empty: there is nothing to search (every slot is (-inf, -1)) and nothing was enqueued.  expect_docs >= 0 (the hybrid
-// call, rrf_fuse.hip): DOCS must equal it, checked under the lock before anything is enqueued.
-static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, bool subset, const int64_t* docs,
-                          int64_t n_sub, int64_t expect_docs, uint64_t hip_stream, std::shared_lock<std::shared_mutex>& lk, hipStream_t* s_out,
-                          int64_t** d_docs_out, float** d_scores_out, bool* empty) {
-    *empty = false;
-    if (!h || !query_blob) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: null argument");
+// ---- what rmu_bm25_search / _subset (search_enqueue) and rmu_bm25_search_groups (groups_impl) share: the queries' tokens, the image life
+// cycle under the handle's lock, the term descriptors and the final merge ----------------------------------------------------------------
+using QueryTokens = std::vector<std::vector<std::string>>;
+
+// the limits of every search, then the tokens of each query
+static int query_tokens(const char* query_blob, int64_t bytes, int64_t nq, int k, QueryTokens& toks) {
     if (nq < 1 || nq > 65535 || bytes < nq) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: 1 <= nq <= 65535 queries, each NUL-terminated");
     if (k < 1 || k > RMU_MAX_K) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: 1 <= k <= RMU_MAX_K");
     std::vector<std::pair<const char*, size_t>> qs;
-    std::vector<std::vector<std::string>> toks;
     try {
         if (!split_blob(query_blob, bytes, nq, qs)) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: the blob does not hold exactly nq NUL-terminated strings");
         toks.resize((size_t)nq);
@@ -726,26 +746,28 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
             if (toks[i].size() > (size_t)kMaxTerms) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: a query has more than 1024 tokens");
         }
     } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_search: out of memory while tokenising"); }
+    return RMU_OK;
+}
 
-    Ctx& c = g_ctx;
+// The image life cycle.  `lk` comes back holding the handle's shared lock over a clean image (not dirty, stale or grown) with *s_out the stream of
+// the call -- or with *empty set: there is nothing to search and nothing was enqueued, no stream was even created.  check(&nothing) runs under
+// the shared lock, the first time and AGAIN every time the lock was given up for a rebuild (documents may have been added meanwhile, never
+// renumbered unseen): it validates what the call says about the documents and may set `nothing`.
+template <class Check>
+static int lock_clean_image(rmu_bm25_t* h, Ctx& c, uint64_t hip_stream, std::shared_lock<std::shared_mutex>& lk, hipStream_t* s_out, bool* empty,
+                            Check check) {
     hipStream_t s = nullptr;
-    const auto nothing = [&]() {
-        *empty = true;
-        return RMU_OK;
-    };
+    *empty = false;
     lk = std::shared_lock<std::shared_mutex>(h->mu);
     for (;;) {
         if (h->broken) return rmu_fail(RMU_E_OOM, "rmu_bm25_search: an earlier add ran out of memory, the index is unusable");
-        if (expect_docs >= 0 && (int64_t)h->dl.size() != expect_docs)
-            return rmu_fail(RMU_E_INVALID, "rmu_hybrid_search: the sparse key table (" + std::to_string(expect_docs) + " keys) and the BM25 index (" +
-                                            std::to_string(h->dl.size()) + " documents) are out of step");
-        if (subset) {                            // (again after the lock was given up: documents may have been added, never renumbered unseen)
-            const int64_t n_docs = (int64_t)h->dl.size();
-            for (int64_t i = 0; i < n_sub; ++i)
-                if (docs[i] < 0 || docs[i] >= n_docs || (i > 0 && docs[i] <= docs[i - 1]))
-                    return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_subset: docs must be strictly ascending document ids in [0, DOCS)");
+        bool nothing = false;
+        const int rc = check(&nothing);
+        if (rc != RMU_OK) return rc;
+        if (h->n_live == 0 || nothing) {         // nothing to search: no device work at all
+            *empty = true;
+            return RMU_OK;
         }
-        if (h->n_live == 0 || (subset && n_sub == 0)) return nothing();     // nothing to search: no device work at all
         if (!s) {
             if (c.ensure_stream() != RMU_OK) return rmu_fail(RMU_E_HIP, "rmu_bm25_search: cannot create a stream");
             s = hip_stream ? (hipStream_t)hip_stream : c.stream;
@@ -755,27 +777,30 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
         {
             std::unique_lock<std::shared_mutex> wl(h->mu);
             if (!h->broken && h->n_live != 0 && (h->dirty || h->stale || h->grown)) {
-                const int rc = h->dirty ? build_image(h, s) : h->grown ? splice_image(h, s) : refresh_image(h, s);
-                if (rc != RMU_OK) { drop_image(h); return rc; }
+                const int rc2 = h->dirty ? build_image(h, s) : h->grown ? splice_image(h, s) : refresh_image(h, s);
+                if (rc2 != RMU_OK) { drop_image(h); return rc2; }
             }
         }
         lk.lock();
     }
-    const int64_t N = (int64_t)h->dl.size();
-    const bool masked = subset || h->n_live != (uint64_t)N;
+    *s_out = s;
+    return RMU_OK;
+}
 
-    // descriptors: term_ptr [nq + 1] | TermDesc [...], one pinned staging buffer, one copy
+// (shared lock held, image clean) term_ptr [nq + 1] | TermDesc [...] at the start of the thread's pinned buffer, which is made large enough
+// for tail_bytes more behind them.  *ptr_bytes: where the descriptors start; *desc_bytes: where they end (a multiple of 16)
+static int stage_terms(const rmu_bm25_t* h, Ctx& c, const QueryTokens& toks, size_t tail_bytes, size_t* ptr_bytes_out, size_t* desc_bytes_out) {
+    const size_t nq = toks.size();
     size_t n_terms = 0;
     for (const auto& t : toks) n_terms += t.size();
-    const size_t ptr_bytes = ((size_t)(nq + 1) * sizeof(u32) + 15) & ~(size_t)15;
-    const size_t mask_bytes = subset ? (((size_t)N + 31) / 32 + 1) * sizeof(u32) : 0;      // allow AND live, behind the descriptors
-    if (c.pin.ensure(ptr_bytes + (n_terms ? n_terms : 1) * sizeof(TermDesc) + mask_bytes) != RMU_OK)
+    const size_t ptr_bytes = ((nq + 1) * sizeof(u32) + 15) & ~(size_t)15;
+    if (c.pin.ensure(ptr_bytes + (n_terms ? n_terms : 1) * sizeof(TermDesc) + tail_bytes) != RMU_OK)
         return rmu_fail(RMU_E_OOM, "rmu_bm25_search: pinned staging buffer");
     u32* tp = (u32*)c.pin.p;
     TermDesc* td = (TermDesc*)(c.pin.p + ptr_bytes);
     u32 nd = 0;
     try {
-        for (int64_t i = 0; i < nq; ++i) {
+        for (size_t i = 0; i < nq; ++i) {
             tp[i] = nd;
             for (const auto& tok : toks[i]) {
                 const auto it = h->ids.find(tok);
@@ -787,23 +812,97 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
         }
     } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_search: out of memory"); }
     tp[nq] = nd;
-    const size_t desc_bytes = ptr_bytes + (size_t)nd * sizeof(TermDesc);       // (a multiple of 16: the bitmap's word pairs are aligned)
+    *ptr_bytes_out = ptr_bytes;
+    *desc_bytes_out = ptr_bytes + (size_t)nd * sizeof(TermDesc);
+    return RMU_OK;
+}
+
+// the launch parameters every kernel of the family reads, over the image and the staged descriptors
+static Bm25Launch launch_params(const rmu_bm25_t* h, const Ctx& c, size_t ptr_bytes, int64_t nq, int k, int tile) {
+    Bm25Launch L{};
+    L.post_doc = h->post_doc; L.post_tf = h->post_tf; L.doc_norm = h->doc_norm;
+    L.term_ptr = (const u32*)c.stage.p;
+    L.terms = (const TermDesc*)((const char*)c.stage.p + ptr_bytes);
+    L.partial = (u64*)c.partial.p;
+    L.n_docs = (u32)h->dl.size(); L.nq = (int)nq; L.k = k; L.tile = tile;
+    return L;
+}
+
+// behind the scoring launch: the part lists of c.partial -> *d_docs [nq, k] int64 (+ doc_base) and *d_scores [nq, k] fp32 in c.out
+static int merge_parts(Ctx& c, int parts, int64_t nq, int k, int64_t doc_base, hipStream_t s, int64_t** d_docs_out, float** d_scores_out) {
+    RMU_HIP_TRY(hipGetLastError());
+    int64_t* d_docs = (int64_t*)c.out.p;
+    float* d_scores = (float*)((char*)c.out.p + (size_t)nq * k * sizeof(int64_t));
+    const int rc = rmu_merge_final_launch((const u64*)c.partial.p, parts, nq, k, doc_base, 0, nullptr, d_scores, d_docs, nullptr, nullptr, s);
+    if (rc != RMU_OK) { (void)hipStreamSynchronize(s); return rmu_fail(rc, "rmu_bm25_search: merge launch failed"); }
+    *d_docs_out = d_docs;
+    *d_scores_out = d_scores;
+    return RMU_OK;
+}
+
+// the default tile: the largest, halved while the launch would have fewer than 1024 workgroups (`tiles_at(tile)` of them)
+template <class TilesAt>
+static int pick_tile(const rmu_bm25_t* h, TilesAt tiles_at) {
+    int tile = (int)h->opt_tile;
+    if (!tile) {
+        tile = kMaxTile;
+        while (tile > 1024 && tiles_at(tile) < 1024) tile >>= 1;
+    }
+    return tile;
+}
+static int64_t pick_max_wgs(const rmu_bm25_t* h, int64_t nq) {
+    return h->opt_max_wgs ? h->opt_max_wgs : std::min<int64_t>(kMaxParts, std::max<int64_t>(8, 4096 / nq));
+}
+
+// The first half of a search: everything up to and including the final merge is enqueued on *s_out (hip_stream, or the calling thread's own
+// stream) and the results are left on the device, *d_docs [nq, k] int64 (+ doc_base) and *d_scores [nq, k] fp32, in the thread's workspace.  `lk`
+// comes back holding the handle's shared lock, which the caller keeps until it has drained the stream (see the header: no reader is ever left in
+// flight behind the lock).  *empty: there is nothing to search (every slot is (-inf, -1)) and nothing was enqueued.  expect_docs >= 0 (the hybrid
+// call, rrf_fuse.hip): DOCS must equal it, checked under the lock before anything is enqueued.
+static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, bool subset, const int64_t* docs,
+                          int64_t n_sub, int64_t expect_docs, uint64_t hip_stream, std::shared_lock<std::shared_mutex>& lk, hipStream_t* s_out,
+                          int64_t** d_docs_out, float** d_scores_out, bool* empty) {
+    *empty = false;
+    if (!h || !query_blob) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: null argument");
+    QueryTokens toks;
+    int rc = query_tokens(query_blob, bytes, nq, k, toks);
+    if (rc != RMU_OK) return rc;
+
+    Ctx& c = g_ctx;
+    hipStream_t s = nullptr;
+    rc = lock_clean_image(h, c, hip_stream, lk, &s, empty, [&](bool* nothing) {
+        if (expect_docs >= 0 && (int64_t)h->dl.size() != expect_docs)
+            return rmu_fail(RMU_E_INVALID, "rmu_hybrid_search: the sparse key table (" + std::to_string(expect_docs) + " keys) and the BM25 index (" +
+                                            std::to_string(h->dl.size()) + " documents) are out of step");
+        if (subset) {
+            const int64_t n_docs = (int64_t)h->dl.size();
+            for (int64_t i = 0; i < n_sub; ++i)
+                if (docs[i] < 0 || docs[i] >= n_docs || (i > 0 && docs[i] <= docs[i - 1]))
+                    return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_subset: docs must be strictly ascending document ids in [0, DOCS)");
+            *nothing = n_sub == 0;
+        }
+        return (int)RMU_OK;
+    });
+    if (rc != RMU_OK || *empty) return rc;
+    const int64_t N = (int64_t)h->dl.size();
+    const bool masked = subset || h->n_live != (uint64_t)N;
+
+    // descriptors: term_ptr [nq + 1] | TermDesc [...], one pinned staging buffer, one copy
+    const size_t mask_bytes = subset ? (((size_t)N + 31) / 32 + 1) * sizeof(u32) : 0;      // allow AND live, behind the descriptors
+    size_t ptr_bytes = 0, desc_bytes = 0;                                                   // (desc_bytes: a multiple of 16, the bitmap's word pairs are aligned)
+    rc = stage_terms(h, c, toks, mask_bytes, &ptr_bytes, &desc_bytes);
+    if (rc != RMU_OK) return rc;
     if (subset) {
         int64_t n_cand = 0;
         live_bitmap(h, (u32*)(c.pin.p + desc_bytes), docs, n_sub, &n_cand);
-        if (n_cand == 0) return nothing();
+        if (n_cand == 0) { *empty = true; return RMU_OK; }
     }
     const size_t stage_bytes = desc_bytes + mask_bytes;
 
     // geometry.  Neither the tile nor the grid changes a bit of the result: both only spread the work
-    int tile = (int)h->opt_tile;
-    if (!tile) {
-        tile = kMaxTile;
-        while (tile > 1024 && ((N + tile - 1) / tile) * nq < 1024) tile >>= 1;
-    }
+    const int tile = pick_tile(h, [&](int t) { return ((N + t - 1) / t) * nq; });
     const int64_t tiles_total = (N + tile - 1) / tile;
-    int64_t max_wgs = h->opt_max_wgs;
-    if (!max_wgs) max_wgs = std::min<int64_t>(kMaxParts, std::max<int64_t>(8, 4096 / nq));
+    const int64_t max_wgs = pick_max_wgs(h, nq);
     const int64_t tiles_per_wg = (tiles_total + max_wgs - 1) / max_wgs;
     const int parts = (int)((tiles_total + tiles_per_wg - 1) / tiles_per_wg);
     if (tiles_per_wg * tile > 0x7FFFFFFFll) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search: document range of one workgroup too large");
@@ -813,12 +912,8 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
     RMU_HIP_TRY(c.partial.ensure((size_t)parts * nq * k * sizeof(u64)));
     RMU_HIP_TRY(c.out.ensure(out_bytes));
     RMU_HIP_TRY(hipMemcpyAsync(c.stage.p, c.pin.p, stage_bytes, hipMemcpyHostToDevice, s));
-    Bm25Launch L{};
-    L.post_doc = h->post_doc; L.post_tf = h->post_tf; L.doc_norm = h->doc_norm;
-    L.term_ptr = (const u32*)c.stage.p;
-    L.terms = (const TermDesc*)((const char*)c.stage.p + ptr_bytes);
-    L.partial = (u64*)c.partial.p;
-    L.n_docs = (u32)N; L.nq = (int)nq; L.k = k; L.tile = tile; L.tiles_per_wg = (int)tiles_per_wg;
+    Bm25Launch L = launch_params(h, c, ptr_bytes, nq, k, tile);
+    L.tiles_per_wg = (int)tiles_per_wg;
     L.mask = !masked ? nullptr : subset ? (const u32*)((const char*)c.stage.p + desc_bytes) : h->live_bits;
     const dim3 grid((unsigned)parts, (unsigned)nq), block(kBlock);
     if (!masked) {
@@ -828,14 +923,198 @@ static int search_enqueue(rmu_bm25_t* h, const char* query_blob, int64_t bytes, 
         if (k <= 64) hipLaunchKernelGGL(bm25_masked_kernel<1>, grid, block, 0, s, L);
         else hipLaunchKernelGGL(bm25_masked_kernel<2>, grid, block, 0, s, L);
     }
-    RMU_HIP_TRY(hipGetLastError());
-    int64_t* d_docs = (int64_t*)c.out.p;
-    float* d_scores = (float*)((char*)c.out.p + (size_t)nq * k * sizeof(int64_t));
-    const int rc = rmu_merge_final_launch((const u64*)c.partial.p, parts, nq, k, doc_base, 0, nullptr, d_scores, d_docs, nullptr, nullptr, s);
-    if (rc != RMU_OK) { (void)hipStreamSynchronize(s); return rmu_fail(rc, "rmu_bm25_search: merge launch failed"); }
     *s_out = s;
-    *d_docs_out = d_docs;
-    *d_scores_out = d_scores;
+    return merge_parts(c, parts, nq, k, doc_base, s, d_docs_out, d_scores_out);
+}
+
+// ---- rmu_bm25_search_groups: the plan ------------------------------------------------------------------------------------------------------
+// A pure host function of its arguments (exported for the tests as rmu_bm25_groups_plan_).  Per list that a query uses: the tiles that hold a
+// live candidate; runs of consecutive kept tiles, cut into pieces of at most ceil(kept / cap) tiles so that a long list still spreads over the
+// CUs; and, if that leaves more than `cap` pieces, every ceil(pieces / cap) neighbours joined into one range across the empty tiles between
+// them (their mask words are zero).  A range is [first tile * tile, min(end of last tile, n_docs)) and owns 2 * ceil(length / 64) mask words:
+// one bit per document plus what the kernel's word-pair load reads past the end.  The same pass checks every list, used or not: strictly
+// ascending ids in [0, n_docs), RMU_E_INVALID otherwise.
+namespace {
+struct DocGroupsPlan {
+    std::vector<u32> lo, hi, mask_off;      // the ranges of all lists, list after list
+    std::vector<u32> first;                 // [n_lists + 1]: list g owns ranges first[g] .. first[g + 1] (none: unused, or no live candidate)
+    int64_t n_work = 0, mask_words = 0, kept_tiles = 0;
+    int max_parts = 0;
+};
+}  // namespace
+
+static int groups_plan(int64_t n_docs, const uint8_t* live, int tile, int cap, const int64_t* docs, const int64_t* list_ptr, int n_lists,
+                       const int32_t* q_list, int64_t nq, DocGroupsPlan& P) {
+    try {
+        std::vector<int64_t> users((size_t)n_lists, 0);
+        for (int64_t i = 0; i < nq; ++i) ++users[(size_t)q_list[i]];
+        P.first.assign((size_t)n_lists + 1, 0);
+        std::vector<u32> kept, plo, phi;        // of one list: kept tiles; pieces [plo, phi) in tiles
+        const int shift = __builtin_ctz((unsigned)tile);      // (the tile is a power of two)
+        for (int g = 0; g < n_lists; ++g) {
+            P.first[(size_t)g] = (u32)P.lo.size();
+            kept.clear(); plo.clear(); phi.clear();
+            const bool used = users[(size_t)g] != 0;
+            int64_t prev = -1;
+            for (int64_t i = list_ptr[g]; i < list_ptr[g + 1]; ++i) {
+                const int64_t d = docs[i];
+                if (d <= prev || d >= n_docs)               // (unused lists are checked all the same)
+                    return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_groups: every list must hold strictly ascending document ids in [0, DOCS)");
+                prev = d;
+                if (!used || !live[d]) continue;
+                const u32 t = (u32)(d >> shift);
+                if (kept.empty() || kept.back() != t) kept.push_back(t);
+            }
+            if (kept.empty()) continue;
+            P.kept_tiles += (int64_t)kept.size();
+            const size_t per = (kept.size() + (size_t)cap - 1) / (size_t)cap;
+            for (const u32 t : kept) {
+                if (!plo.empty() && phi.back() == t && phi.back() - plo.back() < per) ++phi.back();
+                else { plo.push_back(t); phi.push_back(t + 1); }
+            }
+            const size_t join = (plo.size() + (size_t)cap - 1) / (size_t)cap;
+            for (size_t a = 0; a < plo.size(); a += join) {
+                const size_t b = std::min(plo.size(), a + join) - 1;
+                const int64_t d_lo = (int64_t)plo[a] * tile, d_hi = std::min<int64_t>((int64_t)phi[b] * tile, n_docs);
+                if (P.mask_words > 0x7FFFFFFFll) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_groups: the lists' tiles need more than 2^31 mask words");
+                P.lo.push_back((u32)d_lo);
+                P.hi.push_back((u32)d_hi);
+                P.mask_off.push_back((u32)P.mask_words);
+                P.mask_words += 2 * ((d_hi - d_lo + 63) / 64);
+            }
+            const int parts = (int)(P.lo.size() - P.first[(size_t)g]);
+            P.max_parts = std::max(P.max_parts, parts);
+            P.n_work += (int64_t)parts * users[(size_t)g];
+        }
+        P.first[(size_t)n_lists] = (u32)P.lo.size();
+    } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_search_groups: out of memory while planning"); }
+    return RMU_OK;
+}
+// the plan written out: work [P.n_work] in query order, part by part; mask [P.mask_words] = allow AND live of every range
+static void groups_fill(const DocGroupsPlan& P, const uint8_t* live, const int64_t* docs, const int64_t* list_ptr, int n_lists, const int32_t* q_list,
+                        int64_t nq, GroupWork* work, u32* mask) {
+    memset(mask, 0, (size_t)P.mask_words * sizeof(u32));
+    for (int g = 0; g < n_lists; ++g) {
+        u32 r = P.first[(size_t)g];
+        const u32 r_end = P.first[(size_t)g + 1];
+        if (r == r_end) continue;
+        for (int64_t i = list_ptr[g]; i < list_ptr[g + 1]; ++i) {
+            const int64_t d = docs[i];
+            if (!live[d]) continue;
+            while ((int64_t)P.hi[r] <= d) ++r;          // (every live candidate lies in a range of its list: r stays below r_end)
+            mask[P.mask_off[r] + (u32)((d - (int64_t)P.lo[r]) >> 5)] |= 1u << (d & 31);       // (lo is a multiple of 64)
+        }
+    }
+    int64_t n = 0;
+    for (int64_t i = 0; i < nq; ++i) {
+        const size_t g = (size_t)q_list[i];
+        for (u32 r = P.first[g]; r < P.first[g + 1]; ++r) work[n++] = GroupWork{(u32)i, r - P.first[g], P.lo[r], P.hi[r], P.mask_off[r]};
+    }
+}
+// what does not depend on the index: the shape of list_ptr and q_list
+static int groups_check_shape(const int64_t* list_ptr, int n_lists, const int32_t* q_list, int64_t nq) {
+    if (n_lists < 1) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_groups: n_lists >= 1");
+    if (list_ptr[0] != 0) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_groups: list_ptr[0] must be 0");
+    for (int g = 0; g < n_lists; ++g)
+        if (list_ptr[g + 1] < list_ptr[g]) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_groups: list_ptr must be non-decreasing");
+    for (int64_t i = 0; i < nq; ++i)
+        if (q_list[i] < 0 || q_list[i] >= n_lists || (i > 0 && q_list[i] < q_list[i - 1]))
+            return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_groups: q_list must be non-decreasing list numbers in [0, n_lists)");
+    return RMU_OK;
+}
+
+// Test hook (not in rmu.h): the plan for an index of n_docs documents with liveness bytes `live`.  out_work [work_cap, 5] int32 = (query, part,
+// d_lo, d_hi, first mask word) per entry, out_mask [mask_cap] the mask words; counts[4] = entries, mask words, kept tiles, most parts of a
+// query.  The lists are checked as the call checks them.  Entries or words beyond a capacity are not written (the counts still say how many).
+extern "C" int rmu_bm25_groups_plan_(int64_t n_docs, const uint8_t* live, int tile, int cap, const int64_t* docs, const int64_t* list_ptr,
+                                     int n_lists, const int32_t* q_list, int64_t nq, int32_t* out_work, int64_t work_cap, uint32_t* out_mask,
+                                     int64_t mask_cap, int64_t* counts) {
+    RMU_ENTRY();
+    if (n_docs < 0 || n_docs > 0x7FFFFFFFll || (n_docs > 0 && !live) || !list_ptr || !q_list || !counts || nq < 1 || work_cap < 0 || mask_cap < 0 ||
+        (work_cap > 0 && !out_work) || (mask_cap > 0 && !out_mask))
+        return rmu_fail(RMU_E_INVALID, "rmu_bm25_groups_plan_: bad argument");
+    if (tile < 64 || tile > kMaxTile || (tile & (tile - 1)) || cap < 1 || cap > kMaxParts)
+        return rmu_fail(RMU_E_INVALID, "rmu_bm25_groups_plan_: tile is a power of two in [64, 8192], 1 <= cap <= 1024");
+    int rc = groups_check_shape(list_ptr, n_lists, q_list, nq);
+    if (rc != RMU_OK) return rc;
+    if (list_ptr[n_lists] > 0 && !docs) return rmu_fail(RMU_E_INVALID, "rmu_bm25_groups_plan_: bad argument");
+    DocGroupsPlan P;
+    rc = groups_plan(n_docs, live, tile, cap, docs, list_ptr, n_lists, q_list, nq, P);
+    if (rc != RMU_OK) return rc;
+    counts[0] = P.n_work; counts[1] = P.mask_words; counts[2] = P.kept_tiles; counts[3] = P.max_parts;
+    if (P.n_work <= work_cap && P.mask_words <= mask_cap) {
+        try {
+            std::vector<GroupWork> work((size_t)P.n_work + 1);
+            std::vector<u32> mask((size_t)P.mask_words + 1);
+            groups_fill(P, live, docs, list_ptr, n_lists, q_list, nq, work.data(), mask.data());
+            static_assert(sizeof(GroupWork) == 5 * sizeof(int32_t), "one entry = five int32");
+            if (P.n_work) memcpy(out_work, work.data(), (size_t)P.n_work * sizeof(GroupWork));
+            if (P.mask_words) memcpy(out_mask, mask.data(), (size_t)P.mask_words * sizeof(u32));
+        } catch (...) { return rmu_fail(RMU_E_OOM, "rmu_bm25_groups_plan_: out of memory"); }
+    }
+    return RMU_OK;
+}
+
+// rmu_bm25_search_groups: the shared first half (tokens, life cycle, term descriptors), the plan, one launch over its work table, the merge
+static int groups_impl(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, const int64_t* docs,
+                       const int64_t* list_ptr, int n_lists, const int32_t* q_list, float* out_scores, int64_t* out_docs, uint64_t hip_stream) {
+    if (!h || !query_blob || !list_ptr || !q_list || !out_scores || !out_docs) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_groups: null argument");
+    QueryTokens toks;
+    int rc = query_tokens(query_blob, bytes, nq, k, toks);
+    if (rc != RMU_OK) return rc;
+    rc = groups_check_shape(list_ptr, n_lists, q_list, nq);
+    if (rc != RMU_OK) return rc;
+    if (list_ptr[n_lists] > 0 && !docs) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_groups: null argument");
+
+    Ctx& c = g_ctx;
+    hipStream_t s = nullptr;
+    bool empty = false;
+    std::shared_lock<std::shared_mutex> lk;
+    // the lists are checked and the plan is made in one pass over them, under the shared lock.  Geometry: the work follows the lists, so the
+    // tile is sized by the tiles the queries' lists cover at least
+    int64_t ids_of_queries = 0;
+    for (int64_t i = 0; i < nq; ++i) ids_of_queries += list_ptr[q_list[i] + 1] - list_ptr[q_list[i]];
+    DocGroupsPlan P;
+    int tile = 0;
+    rc = lock_clean_image(h, c, hip_stream, lk, &s, &empty, [&](bool* nothing) {
+        P = DocGroupsPlan{};
+        tile = pick_tile(h, [&](int t) { return ids_of_queries / t + nq; });
+        const int prc = groups_plan((int64_t)h->dl.size(), h->live.data(), tile, (int)pick_max_wgs(h, nq), docs, list_ptr, n_lists, q_list, nq, P);
+        *nothing = P.n_work == 0;                // no used list holds a live document
+        return prc;
+    });
+    if (rc != RMU_OK) return rc;
+    if (empty) {
+        for (int64_t i = 0; i < nq * k; ++i) { out_scores[i] = -INFINITY; out_docs[i] = -1; }
+        return RMU_OK;
+    }
+    if (P.n_work > 0x7FFFFFFFll) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_groups: more than 2^31 - 1 workgroups; send fewer queries per call");
+
+    // one pinned staging buffer, one copy: term_ptr | TermDesc [...] | mask words | work table
+    const size_t mask_bytes = ((size_t)P.mask_words * sizeof(u32) + 15) & ~(size_t)15, work_bytes = (size_t)P.n_work * sizeof(GroupWork);
+    size_t ptr_bytes = 0, desc_bytes = 0;
+    rc = stage_terms(h, c, toks, mask_bytes + work_bytes, &ptr_bytes, &desc_bytes);
+    if (rc != RMU_OK) return rc;
+    groups_fill(P, h->live.data(), docs, list_ptr, n_lists, q_list, nq, (GroupWork*)(c.pin.p + desc_bytes + mask_bytes), (u32*)(c.pin.p + desc_bytes));
+    const size_t stage_bytes = desc_bytes + mask_bytes + work_bytes, part_bytes = (size_t)P.max_parts * nq * k * sizeof(u64);
+    RMU_HIP_TRY(c.stage.ensure(stage_bytes));
+    RMU_HIP_TRY(c.partial.ensure(part_bytes));
+    RMU_HIP_TRY(c.out.ensure((size_t)nq * k * (sizeof(int64_t) + sizeof(float))));
+    RMU_HIP_TRY(hipMemcpyAsync(c.stage.p, c.pin.p, stage_bytes, hipMemcpyHostToDevice, s));
+    RMU_HIP_TRY(hipMemsetAsync(c.partial.p, 0, part_bytes, s));          // key 0: a query with fewer ranges than the longest pads its part lists
+    Bm25Launch L = launch_params(h, c, ptr_bytes, nq, k, tile);
+    L.mask = (const u32*)((const char*)c.stage.p + desc_bytes);
+    const GroupWork* work = (const GroupWork*)((const char*)c.stage.p + desc_bytes + mask_bytes);
+    const dim3 grid((unsigned)P.n_work), block(kBlock);
+    if (k <= 64) hipLaunchKernelGGL(bm25_groups_kernel<1>, grid, block, 0, s, L, work);
+    else hipLaunchKernelGGL(bm25_groups_kernel<2>, grid, block, 0, s, L, work);
+    int64_t* d_docs = nullptr;
+    float* d_scores = nullptr;
+    rc = merge_parts(c, P.max_parts, nq, k, doc_base, s, &d_docs, &d_scores);
+    if (rc != RMU_OK) return rc;
+    RMU_HIP_TRY(hipMemcpyAsync(out_docs, d_docs, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipMemcpyAsync(out_scores, d_scores, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s));
+    RMU_HIP_TRY(hipStreamSynchronize(s));
     return RMU_OK;
 }
 
@@ -883,6 +1162,13 @@ extern "C" int rmu_bm25_search_subset(rmu_bm25_t* h, const char* query_blob, int
     RMU_ENTRY();
     if (n_sub < 0 || (n_sub > 0 && !docs)) return rmu_fail(RMU_E_INVALID, "rmu_bm25_search_subset: bad document list");
     return search_impl(h, query_blob, bytes, nq, k, doc_base, true, docs, n_sub, out_scores, out_docs, hip_stream);
+}
+
+extern "C" int rmu_bm25_search_groups(rmu_bm25_t* h, const char* query_blob, int64_t bytes, int64_t nq, int k, int64_t doc_base, const int64_t* docs,
+                                      const int64_t* list_ptr, int n_lists, const int32_t* q_list, float* out_scores, int64_t* out_docs,
+                                      uint64_t hip_stream) {
+    RMU_ENTRY();
+    return groups_impl(h, query_blob, bytes, nq, k, doc_base, docs, list_ptr, n_lists, q_list, out_scores, out_docs, hip_stream);
 }
 
 // ---- removal, compaction, persistence: host only -----------------------------------------------------------------------------------------

@@ -5,7 +5,8 @@ code so the hybrid retriever works with our dense retriever when langchain is no
 reference's own EnsembleRetriever accepts our retriever unchanged (it only calls ``invoke``)."""
 from __future__ import annotations
 
-from typing import Any, List, Sequence
+import inspect
+from typing import Any, List, Optional, Sequence
 
 from ._lc import BaseRetriever, Document
 
@@ -42,7 +43,26 @@ class MI355XEnsembleRetriever(BaseRetriever):
         lists = [r.invoke(query) if hasattr(r, "invoke") else r.get_relevant_documents(query) for r in self.retrievers]
         return weighted_reciprocal_rank(lists, self._weights(), self.c)
 
-    def batch_invoke(self, queries: list[str]) -> list[list[Document]]:
-        per = [r.batch_invoke(queries) if hasattr(r, "batch_invoke") else [r.invoke(q) for q in queries]
+    def batch_invoke(self, queries: list[str], filters: Optional[list] = None, exprs: Optional[list] = None) -> list[list[Document]]:
+        """`filters` / `exprs`: one condition per query (None = unfiltered), handed to every member's `batch_invoke`; a member that does
+        not take them is a ValueError (a silently unfiltered member would be wrong)."""
+        each = per_query_conditions(self.retrievers, filters, exprs)
+        per = [r.batch_invoke(queries, **each) if hasattr(r, "batch_invoke") else [r.invoke(q) for q in queries]
                for r in self.retrievers]
         return [weighted_reciprocal_rank([m[i] for m in per], self._weights(), self.c) for i in range(len(queries))]
+
+
+def per_query_conditions(retrievers: Sequence[Any], filters, exprs) -> dict:
+    """The keyword arguments that carry `filters=` / `exprs=` to every member's `batch_invoke` ({} when neither is given); ValueError
+    when a member has no `batch_invoke` that takes them."""
+    each = {name: v for name, v in (("filters", filters), ("exprs", exprs)) if v is not None}
+    for r in retrievers if each else ():
+        try:
+            params = inspect.signature(r.batch_invoke).parameters
+        except (AttributeError, TypeError, ValueError):
+            params = {}
+        takes_any = any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
+        if not takes_any and any(name not in params for name in each):
+            raise ValueError(f"{type(r).__name__}.batch_invoke does not take {' / '.join(f'{n}=' for n in each)}: per-request filters need "
+                             "every member of the ensemble to apply them")
+    return each

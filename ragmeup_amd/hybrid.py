@@ -11,7 +11,7 @@ the library fuses those numbers.  The retriever keeps one key per BM25 document 
 that member's records changed behind its back (an upload, a delete + compact, a rebuilt BM25 retriever): detection, not ownership of the add
 path, because the reference's server changes the members directly.
 
-Whatever the one call cannot serve -- a ``filter`` / ``expr`` on either member, ``fetch_k`` > 64, a dense ``search_type`` other than
+Whatever the one call cannot serve -- a ``filter`` / ``expr`` on either member, per-request ``filters=`` / ``exprs=`` of ``batch_invoke``, ``fetch_k`` > 64, a dense ``search_type`` other than
 ``similarity`` / ``mmr``, a caller ``preprocess_func``, a pending pipelined insert -- takes the two member calls and
 ``weighted_reciprocal_rank``: the same result by definition.
 """
@@ -26,7 +26,7 @@ import numpy as np
 from . import _native as N
 from ._lc import BaseRetriever, Document
 from .bm25 import BM25Index, MI355XBM25Retriever, _blob
-from .ensemble import weighted_reciprocal_rank
+from .ensemble import per_query_conditions, weighted_reciprocal_rank
 from .vectorstore import MI355XRetriever, MI355XVectorStore
 
 
@@ -244,13 +244,16 @@ class MI355XHybridRetriever(BaseRetriever):
             if sst["gen"] == gs and store._gen == gd:
                 return out
 
-    def batch_invoke(self, queries: list[str]) -> list[list[Document]]:
+    def batch_invoke(self, queries: list[str], filters: Optional[list] = None, exprs: Optional[list] = None) -> list[list[Document]]:
+        """`filters` / `exprs`: one condition per query (None = unfiltered).  The one call takes no lists, so a per-request form takes
+        the two member batch calls (each one grouped call) and the host fusion: the route a `search_kwargs` filter takes."""
         queries = list(queries)
+        each = per_query_conditions([self.sparse, self.dense], filters, exprs)
         if not queries:
             return []
-        plan = self._plan()
+        plan = None if each else self._plan()
         if plan is None:
-            per = [self.sparse.batch_invoke(queries), self.dense.batch_invoke(queries)]
+            per = [self.sparse.batch_invoke(queries, **each), self.dense.batch_invoke(queries, **each)]
             return [weighted_reciprocal_rank([m[i] for m in per], self._weights(), self.c) for i in range(len(queries))]
         return self._one_call(queries, plan, single=False)
 
