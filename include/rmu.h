@@ -162,6 +162,9 @@ int rmu_index_get_rows(rmu_index_t* idx, const int64_t* rows, int64_t n, float* 
  * fetch_k candidate rows rows[i, :] (index-local ids as rmu_index_search returned them, -1 = absent): first the candidate
  * most similar to the query, then repeatedly argmax lambda*cos(q,x) - (1-lambda)*max cos(x, picked), lowest position on
  * ties.  out_pos [nq, k] int32 = positions in the candidate list (-1 past the number of candidates).
+ * An id that is not a row of the index (>= its size) and the id of a REMOVED row (a stale list: search, remove_rows, then mmr) are absent
+ * as well: never picked, not counted as candidates, and the output is padded with -1 accordingly.  (Both kernels decide this by the
+ * row's norm -- a removed row is NaN -- so a live row that holds a NaN is absent too.)
  * flags: RMU_F_Q_DEVICE (q), RMU_F_OUT_DEVICE (rows and out_pos).  fetch_k <= 64.
  * Serves: VectorStoreRetriever(search_type="mmr") -> maximal_marginal_relevance (RAGHelper.py:497-499) without the
  * per-query "fetch 20 vectors by pk" round trip. */

@@ -249,8 +249,8 @@ __global__ void k_gather_flagged(const float* __restrict__ q, int dpad, const in
 // server/RAGHelper.py:497-499): one wave per query, lane i = candidate i (fetch_k <= 64), fp64 like the numpy original.
 //   first pick = argmax_i cos(q, x_i); then repeatedly argmax_i  lambda*cos(q, x_i) - (1-lambda)*max_{s picked} cos(x_i, x_s),
 //   strict '>' so the lowest index wins ties; cos = dot / (|a||b|), NaN/inf -> 0.
-// rows: [nq, fetch_k] index-local row ids (-1 = absent, as rmu_index_search pads them); out_pos: [nq, k] positions in the
-// candidate list, -1 past the number of candidates.
+// rows: [nq, fetch_k] index-local row ids (-1 = absent, as rmu_index_search pads them; so is an id >= n_rows and a REMOVED row, whose
+// norm is NaN: never picked, not counted); out_pos: [nq, k] positions in the candidate list, -1 past the number of candidates.
 __global__ __launch_bounds__(256) void k_mmr(const float* __restrict__ x, int dpad, int dim, int64_t n_rows,
                                              const float* __restrict__ q, const int64_t* __restrict__ rows, int64_t nq,
                                              int fetch_k, int k, double lambda, int* __restrict__ out_pos) {
@@ -258,8 +258,8 @@ __global__ __launch_bounds__(256) void k_mmr(const float* __restrict__ x, int dp
     const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (qi >= nq) return;
     const int64_t row = lane < fetch_k ? rows[qi * fetch_k + lane] : -1;
-    const bool valid = row >= 0 && row < n_rows;
-    const float* xr = x + (valid ? row : 0) * (int64_t)dpad;
+    const bool in_index = row >= 0 && row < n_rows;
+    const float* xr = x + (in_index ? row : 0) * (int64_t)dpad;
     const float* qv = q + qi * dim;
     double dq = 0.0, nx = 0.0, nqq = 0.0;
     for (int c = 0; c < dim; ++c) {
@@ -269,6 +269,7 @@ __global__ __launch_bounds__(256) void k_mmr(const float* __restrict__ x, int dp
         nqq = fma(b, b, nqq);
     }
     nx = sqrt(nx); nqq = sqrt(nqq);
+    const bool valid = in_index && nx == nx;          // a removed row is NaN-poisoned: its norm is NaN and the candidate is ABSENT, like a -1
     double sim_q = dq / (nx * nqq);
     if (!(sim_q == sim_q) || isinf(sim_q)) sim_q = 0.0;
     const int n_valid = __builtin_popcountll(__ballot(valid));
@@ -358,9 +359,9 @@ __global__ __launch_bounds__(256) void k_mmr_lds(const float* __restrict__ x, in
     if (threadIdx.x >= 64) return;
     const int lane = threadIdx.x;
     const int64_t row = lane < fetch_k ? rows[qi * fetch_k + lane] : -1;
-    const bool valid = row >= 0 && row < n_rows;
     const int li = lane < fetch_k ? lane : 0;
     const double nx = sqrt(G[li * 64 + li]), nqq = sqrt(G[65 * 64]);
+    const bool valid = row >= 0 && row < n_rows && nx == nx;          // as in k_mmr: a removed (NaN) row is absent
     double sim_q = G[64 * 64 + li] / (nx * nqq);
     if (!(sim_q == sim_q) || isinf(sim_q)) sim_q = 0.0;
     const int n_valid = __builtin_popcountll(__ballot(valid));
@@ -890,7 +891,7 @@ extern "C" int rmu_index_get_rows(rmu_index_t* idx, const int64_t* rows, int64_t
 static void launch_mmr(const rmu_index* idx, const float* dq, const int64_t* dr, int64_t nq, int fetch_k, int k, double lambda_mult, int* dout,
                        hipStream_t s) {
     static const bool lds_off = rmu_env("RMU_MMR_LDS") && atoi(rmu_env("RMU_MMR_LDS")) == 0;
-    if (idx->dim <= 384 && nq <= 65535 && !lds_off) {          // one workgroup per query, candidates staged in LDS (bit-identical picks)
+    if (idx->dim <= 384 && nq <= 65535 && !lds_off) {          // one workgroup per query, candidates staged in LDS (bit-identical picks: tests/test_mmr_regimes_gpu.py)
         // rows [64][dim + 1] + q [dim] at the head of a (64 * 385 + 384)-float area, then the fp64 Gram block [65][64] + 1
         const size_t lds = (size_t)(64 * 385 + 384) * sizeof(float) + (size_t)(65 * 64 + 1) * sizeof(double);
         static const hipError_t attr_rc = hipFuncSetAttribute((const void*)k_mmr_lds, hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -185,7 +185,8 @@ class FlatIndex:
 
     def mmr(self, q, rows, k: int, lambda_mult: float = 0.5) -> np.ndarray:
         """Batched greedy MMR on the device: q [nq, dim] fp32, rows [nq, fetch_k] int64 candidate row ids (-1 = absent, as
-        `search` pads them; without a row_base) -> positions [nq, k] int32 into each candidate list (-1 = none)."""
+        `search` pads them; without a row_base) -> positions [nq, k] int32 into each candidate list (-1 = none).  An id past the last row and
+        the id of a removed row (a list from before a `remove_rows`) are absent as well."""
         qq = np.ascontiguousarray(q, dtype=np.float32)
         if qq.ndim == 1:
             qq = qq[None]
