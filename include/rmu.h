@@ -623,6 +623,64 @@ int rmu_bert_rerank(rmu_bert_t* m, rmu_passages_t* p, const int32_t* q_tokens, c
                     const int64_t* keys, int m_cand, int batch_pad, int max_len, int top_n,
                     int32_t* out_pos, float* out_scores, float* out_logits /* [nq, m_cand], may be NULL */);
 
+/* ---- metadata columns in HBM: the row lists of a filtered search built on the device (columns.hip) -------------------------------------
+ * Serves: the step IN FRONT of rmu_index_search_subset / rmu_index_search_groups -- which rows does expr='source == "a.pdf"' name
+ * (RAGHelper.py:497-499 with search_kwargs) -- which a host otherwise answers by walking its records after every upload or delete
+ * (server.py:150-183, 353-385; RAGHelper.py:518-538) and ships as 8 bytes per selected row on every call.
+ *
+ * The columns hold one int32 code per row and field, 1..8 fields.  The HOST numbers the values of each field; the library sees only codes
+ * >= 0.  A host master copy lives behind the handle: create, append, size, compact, set_option and free never touch the GPU.  The device
+ * image is field-major (one contiguous int32 array per field) and follows at the next selection: only the tail is uploaded, and the image is
+ * re-allocated only when the rows no longer fit.  Rows are the index's rows: append where the index appends, compact with the map
+ * rmu_index_compact returned.  A removed (tombstoned) row keeps its codes: selections may name it, the scan never returns it.
+ * Thread-safe: selections on one handle run concurrently (shared lock, scratch belongs to the calling thread); append, compact and
+ * set_option are exclusive. */
+typedef struct rmu_columns rmu_columns_t;
+int rmu_columns_create(rmu_columns_t** out, int n_fields, int64_t capacity_hint);
+int rmu_columns_free(rmu_columns_t* c);
+int rmu_columns_size(rmu_columns_t* c, int64_t* n_rows, int* n_fields);      /* either output may be NULL */
+/* codes [n, n_fields] row-major HOST int32, every code >= 0; *first_row (may be NULL) = row of codes[0].  RMU_E_INVALID changes nothing. */
+int rmu_columns_append(rmu_columns_t* c, const int32_t* codes, int64_t n, int64_t* first_row);
+/* Apply the old_to_new map rmu_index_compact returned (map_len >= rows, otherwise RMU_E_INVALID and nothing changes; -1 = dropped; the kept
+ * rows must map to 0, 1, 2, ... in order); *n_after (may be NULL) = rows afterwards. */
+int rmu_columns_compact(rmu_columns_t* c, const int64_t* old_to_new, int64_t map_len, int64_t* n_after);
+#define RMU_COLUMNS_OPT_TILE_ROWS 1   /* testing switch: rows per workgroup tile of the selection kernels, a power of two in [64, 16384]; 0 = default
+                                       * (4096 = 256 lanes x 16 rows).  Small corpora cross tile boundaries, wave boundaries and the width of
+                                       * the scan's block through it.  Results are identical for every value. */
+int rmu_columns_set_option(rmu_columns_t* c, int option, int64_t value);
+
+/* A SELECTION is a conjunction of 1..4 terms; a term is (field, accepted codes): the row's code in that field is one of them.  The accepted
+ * codes of a term are strictly ascending (an empty set matches no row), and a selection carries at most 1024 codes in all.  The selections
+ * of a call are passed flattened: terms [n_terms], codes [], sel_ptr [n_sel + 1] into terms (sel_ptr[0] = 0, sel_ptr[n_sel] = n_terms);
+ * selection g = terms[sel_ptr[g] .. sel_ptr[g + 1]), term t accepts codes[codes_begin .. codes_end).  All three are HOST arrays, checked
+ * before anything is enqueued: a field outside [0, n_fields), unsorted, repeated or negative codes, more than 4 terms, no term, more than
+ * 1024 codes, or n_sel outside [1, 8192] gives RMU_E_INVALID with a message that names the selection. */
+typedef struct rmu_col_term {
+    int32_t field;
+    int32_t codes_begin;
+    int32_t codes_end;
+} rmu_col_term;
+
+/* The rows in [0, rows) whose codes satisfy selection g, ascending, the lists laid end to end: list g = out_rows[list_ptr[g] .. list_ptr[g + 1]).
+ * list_ptr [n_sel + 1]: HOST, always written (the stream is drained).  out_rows: int64, HOST or (RMU_F_OUT_DEVICE, the only flag) DEVICE, room
+ * for out_cap entries; NULL = count only.  out_cap < list_ptr[n_sel]: RMU_E_INVALID, list_ptr still holds the offsets, nothing else is written.
+ * Work: one pass over the named columns per selection to count (one count per tile), an exclusive scan per selection and one over the
+ * totals -- list_ptr is all the host reads, one synchronisation --, one pass to write; the lists come out ascending by construction. */
+int rmu_columns_select(rmu_columns_t* c, const rmu_col_term* terms, int n_terms, const int32_t* codes, const int32_t* sel_ptr, int n_sel,
+                       unsigned flags, int64_t* out_rows, int64_t out_cap, int64_t* list_ptr, uint64_t hip_stream);
+
+/* Selection + rmu_index_search_groups in one call: query i is searched over the rows of selection q_sel[i] (HOST int32 [nq], NON-DECREASING,
+ * as q_list there).  The lists never leave the device.  Result of query i: exactly -- bit for bit, order, padding -- what
+ * rmu_index_search_subset returns for the HOST list of those rows.  Tombstoned rows never appear (the scan's own rule).
+ * Selections that no query names are not evaluated; a selection without rows costs its queries no scan work (they get the (-inf | +inf, -1)
+ * padding); when every named selection is empty no scan is launched.
+ * The columns and the index must hold the same number of rows: otherwise RMU_E_INVALID, the message contains "out of step", nothing is
+ * enqueued.  Limits and flags (RMU_F_Q_DEVICE, RMU_F_OUT_DEVICE, row_base, k, nq <= 8192, rows of at most RMU_MAX_DIM dimensions) are
+ * rmu_index_search_groups', checked before anything is enqueued; the call always drains its stream. */
+int rmu_index_search_where(rmu_index_t* idx, rmu_columns_t* c, const float* q, int64_t nq, int k, unsigned flags, int64_t row_base,
+                           const rmu_col_term* terms, int n_terms, const int32_t* codes, const int32_t* sel_ptr, int n_sel,
+                           const int32_t* q_sel, float* out_scores, int64_t* out_rows, uint64_t hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

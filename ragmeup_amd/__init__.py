@@ -3,7 +3,7 @@
 Python host code over hand-written gfx950 HIP kernels behind a C-ABI (include/rmu.h).
 """
 from . import _native  # noqa: F401
-from .index import FlatIndex, topk_merge  # noqa: F401
+from .index import Columns, FlatIndex, topk_merge  # noqa: F401
 from .documents import Document  # noqa: F401
 from .reranker import ScoredCrossEncoderReranker  # noqa: F401
 from .vectorstore import MI355XVectorStore  # noqa: F401
@@ -16,7 +16,7 @@ from .rerank import MI355XRerankRetriever, PassageTable  # noqa: F401
 from .vectorstore import MI355XRetriever  # noqa: F401
 from . import factory  # noqa: F401
 
-__all__ = ["FlatIndex", "topk_merge", "Document", "ScoredCrossEncoderReranker", "MI355XVectorStore", "MI355XRetriever",
+__all__ = ["FlatIndex", "Columns", "topk_merge", "Document", "ScoredCrossEncoderReranker", "MI355XVectorStore", "MI355XRetriever",
            "BM25Index", "MI355XBM25Retriever", "HybridIndex", "MI355XHybridRetriever", "MI355XSemanticChunker", "DocumentSimilarityAttribution", "MI355XSimilarityAttribution", "MI355XRerankRetriever", "PassageTable", "BertEncoder", "MI355XEmbeddings", "MI355XCrossEncoder", "factory"]
 
 

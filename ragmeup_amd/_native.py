@@ -13,6 +13,7 @@ if os.environ.get("RMU_TUNING") == "1" and os.environ.get("RMU_LIB"):
     SO_PATH = os.path.abspath(os.environ["RMU_LIB"])
 
 RMU_OK = 0
+RMU_E_INVALID = -1
 METRIC_IP, METRIC_COSINE, METRIC_L2SQ = 0, 1, 2
 F_Q_DEVICE, F_OUT_DEVICE, F_SMALLER_BETTER = 1, 2, 4
 F_ROWS_DEVICE = 8
@@ -36,6 +37,8 @@ BM25_OPT_TILE_DOCS, BM25_OPT_MAX_WGS, BM25_OPT_REPACK_ON_REMOVE = 1, 2, 4
 BM25_OPT_REPACK_ON_ADD = 8
 BM25_STAT_IMAGE_PACKS, BM25_STAT_IMAGE_SPLICES, BM25_STAT_IMAGE_UPLOAD_BYTES = 16, 17, 18
 RRF_MAX_LISTS = 4
+COLUMNS_OPT_TILE_ROWS = 1
+COLUMNS_MAX_FIELDS, COLUMNS_MAX_TERMS, COLUMNS_MAX_CODES, COLUMNS_MAX_SELECTIONS = 8, 4, 1024, 8192
 RERANK_MAX_M = 256
 # launch geometry of rmu_adjacent_cosine (semantic.hip: kWavePairs, kBlockPairs).  Results do not depend on it; the tests put their sizes on
 # both sides of these run boundaries
@@ -55,6 +58,8 @@ SYMBOLS = [
     "rmu_rrf_fuse", "rmu_hybrid_create", "rmu_hybrid_free", "rmu_hybrid_set_keys", "rmu_hybrid_search", "rmu_bert_search_hybrid",
     "rmu_adjacent_cosine", "rmu_attribution", "rmu_bert_attribute",
     "rmu_passages_create", "rmu_passages_free", "rmu_passages_size", "rmu_passages_set", "rmu_passages_pairs", "rmu_rerank_select", "rmu_bert_rerank",
+    "rmu_columns_create", "rmu_columns_free", "rmu_columns_size", "rmu_columns_append", "rmu_columns_compact", "rmu_columns_set_option",
+    "rmu_columns_select", "rmu_index_search_where",
 ]
 
 
@@ -139,6 +144,17 @@ def _declare(lib):
     lib.rmu_passages_set.argtypes = [vp, i64, vp, vp, i64]
     lib.rmu_passages_pairs.argtypes = [vp, vp, vp, i64, i32, vp, i32, i32, vp, vp, vp]
     lib.rmu_rerank_select.argtypes = [vp, vp, i64, i32, i32, u32, vp, vp, u64]
+    lib.rmu_columns_create.argtypes = [c.POINTER(vp), i32, i64]
+    lib.rmu_columns_free.argtypes = [vp]
+    lib.rmu_columns_size.argtypes = [vp, c.POINTER(i64), c.POINTER(i32)]
+    lib.rmu_columns_append.argtypes = [vp, vp, i64, c.POINTER(i64)]
+    lib.rmu_columns_compact.argtypes = [vp, vp, i64, c.POINTER(i64)]
+    lib.rmu_columns_set_option.argtypes = [vp, i32, i64]
+    lib.rmu_columns_select.argtypes = [vp, vp, i32, vp, vp, i32, u32, vp, i64, vp, u64]
+    lib.rmu_index_search_where.argtypes = [vp, vp, vp, i64, i32, u32, i64, vp, i32, vp, vp, i32, vp, vp, vp, u64]
+    # (probe hook, not in rmu.h: kernel times of the thread's last selection under RMU_TUNING=1 RMU_COLUMNS_TIMING=1)
+    if hasattr(lib, "rmu_columns_last_ms_"):
+        lib.rmu_columns_last_ms_.argtypes = [c.POINTER(f32), c.POINTER(f32)]
     if hasattr(lib, "rmu_bert_create"):
         lib.rmu_bert_create.argtypes = [c.POINTER(vp), vp, c.POINTER(vp), i32]
         lib.rmu_bert_free.argtypes = [vp]

@@ -59,6 +59,98 @@ def search_groups_blocks(call, q: np.ndarray, k: int, lists, q_list, row_base: i
     return out_s, out_r
 
 
+def flatten_selections(selections):
+    """[[(field_no, [codes...]), ...], ...] -> (terms int32 [n_terms, 3] = field, codes_begin, codes_end; codes int32; sel_ptr int32
+    [n_sel + 1]): the flattened form rmu_columns_select takes.  The codes of a term are deduplicated and sorted here; everything else
+    (field numbers, term and code counts) is the library's to check."""
+    terms, codes, sel_ptr = [], [], [0]
+    for sel in selections:
+        for field, cs in sel:
+            cs = np.unique(np.asarray(list(cs), dtype=np.int64))
+            if cs.size and (cs[0] < 0 or cs[-1] > 0x7FFFFFFF):
+                raise ValueError("codes must be in [0, 2^31)")
+            terms.append((int(field), len(codes), len(codes) + int(cs.size)))
+            codes.extend(cs.tolist())
+        sel_ptr.append(len(terms))
+    return (np.asarray(terms, dtype=np.int32).reshape(-1, 3), np.asarray(codes, dtype=np.int32), np.asarray(sel_ptr, dtype=np.int32))
+
+
+class Columns:
+    """Metadata columns of a FlatIndex (rmu_columns_*): one int32 code per row and field, numbered by the caller.  The master copy is on the
+    host (append, compact and len never touch the GPU); the device image follows at the next selection."""
+
+    def __init__(self, n_fields: int, capacity_hint: int = 0):
+        self._lib = N.lib()
+        self.n_fields = int(n_fields)
+        h = ctypes.c_void_p()
+        N.check(self._lib.rmu_columns_create(ctypes.byref(h), self.n_fields, int(capacity_hint)), "rmu_columns_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.rmu_columns_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        n = ctypes.c_int64()
+        N.check(self._lib.rmu_columns_size(self._h, ctypes.byref(n), None), "rmu_columns_size")
+        return int(n.value)
+
+    def append(self, codes) -> int:
+        """codes [n, n_fields] (or [n] for one field), every code >= 0; returns the row of codes[0]."""
+        c = np.ascontiguousarray(codes, dtype=np.int32)
+        if c.ndim == 1 and self.n_fields == 1:
+            c = c[:, None]
+        if c.ndim != 2 or c.shape[1] != self.n_fields:
+            raise ValueError(f"expected [n, {self.n_fields}] got {c.shape}")
+        first = ctypes.c_int64()
+        N.check(self._lib.rmu_columns_append(self._h, c.ctypes.data, c.shape[0], ctypes.byref(first)), "rmu_columns_append")
+        return int(first.value)
+
+    def compact(self, old_to_new) -> int:
+        """Apply the map FlatIndex.compact() returned; returns the rows afterwards."""
+        m = np.ascontiguousarray(old_to_new, dtype=np.int64).reshape(-1)
+        after = ctypes.c_int64()
+        N.check(self._lib.rmu_columns_compact(self._h, m.ctypes.data, m.shape[0], ctypes.byref(after)), "rmu_columns_compact")
+        return int(after.value)
+
+    def set_tile_rows(self, rows: int = 0):
+        """RMU_COLUMNS_OPT_TILE_ROWS (testing switch): a power of two in [64, 16384], 0 = default; results are identical for every value."""
+        N.check(self._lib.rmu_columns_set_option(self._h, N.COLUMNS_OPT_TILE_ROWS, int(rows)), "rmu_columns_set_option")
+
+    def select(self, selections, count_only: bool = False, device: bool = False):
+        """selections: [[(field_no, [codes...]), ...], ...] -> one ascending int64 row array per selection (numpy; `device`: views of one
+        torch CUDA tensor).  count_only: the int64 list_ptr [n_sel + 1] instead.  A convenience for tests and tools, not a hot path: it
+        calls the library twice -- once to count, so that the output can be allocated, once for the lists -- and so runs the count pass
+        twice; FlatIndex.search_where is the one-call form."""
+        terms, codes, sel_ptr = flatten_selections(selections)
+        n_sel = len(sel_ptr) - 1
+        lp = np.zeros(n_sel + 1, dtype=np.int64)
+
+        def call(flags, out_ptr, cap):
+            return self._lib.rmu_columns_select(self._h, terms.ctypes.data, terms.shape[0], codes.ctypes.data, sel_ptr.ctypes.data, n_sel,
+                                                flags, out_ptr, cap, lp.ctypes.data, 0)
+        N.check(call(0, None, 0), "rmu_columns_select")
+        if count_only:
+            return lp
+        total = int(lp[-1])
+        if device:
+            import torch
+            out = torch.empty(max(total, 1), dtype=torch.int64, device="cuda")
+            torch.cuda.current_stream().synchronize()
+            N.check(call(N.F_OUT_DEVICE, out.data_ptr(), total), "rmu_columns_select")
+        else:
+            out = np.empty(max(total, 1), dtype=np.int64)
+            N.check(call(0, out.ctypes.data, total), "rmu_columns_select")
+        return [out[int(lp[g]):int(lp[g + 1])] for g in range(n_sel)]
+
+
 class FlatIndex:
     def __init__(self, dim: int, metric: int = N.METRIC_IP, capacity_hint: int = 0, device: int | None = None):
         """dim <= 3072 (N.MAX_DIM_WIDE) for METRIC_IP / METRIC_COSINE, <= 767 for METRIC_L2SQ; RmuError otherwise."""
@@ -337,6 +429,45 @@ class FlatIndex:
         N.check(self._lib.rmu_index_search_groups(self._h, qq.ctypes.data, nq, k, flags, row_base, rows_ptr, list_ptr.ctypes.data,
                                                   int(list_ptr.shape[0]) - 1, q_list.ctypes.data, out_s.ctypes.data, out_r.ctypes.data, 0),
                 "rmu_index_search_groups")
+        return out_s, out_r
+
+    def search_where(self, q, k: int, columns: "Columns", selections, q_sel, row_base: int = 0):
+        """Exact top-k of every query against the rows ITS SELECTION names, the lists built on the device (rmu_index_search_where):
+        `selections` is a sequence of [(field_no, [codes...]), ...] conjunctions over `columns`, `q_sel[i]` the selection of query i, in
+        any order.  numpy in -> numpy out: for query i exactly what `search(q[i], k, rows=<the rows of its selection>)` returns.  The
+        queries are sorted by selection (stably), sent in blocks of at most N.MAX_QUERIES_PER_CALL -- each with only the selections it names --
+        and put back in the caller's order.  The codes of a term are deduplicated and sorted here."""
+        if self.dim > N.MAX_DIM:
+            raise ValueError(f"search_where serves rows of at most {N.MAX_DIM} dimensions; this index holds {self.dim}-d rows "
+                             "(the filtered search of a wide index does not exist yet)")
+        qq = np.ascontiguousarray(q, dtype=np.float32)
+        if qq.ndim == 1:
+            qq = qq[None]
+        if qq.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] got {qq.shape}")
+        k = int(k)
+        selections = list(selections)
+        nq, n_sel = qq.shape[0], len(selections)
+        qs = np.asarray(q_sel, dtype=np.int64).reshape(-1)
+        if qs.shape[0] != nq:
+            raise ValueError(f"q_sel names the selection of each query: expected {nq} entries, got {qs.shape[0]}")
+        if nq and (n_sel == 0 or qs.min() < 0 or qs.max() >= n_sel):
+            raise ValueError(f"q_sel entries must be in [0, {n_sel})")
+        order = np.argsort(qs, kind="stable")
+        out_s = np.empty((nq, k), dtype=np.float32)
+        out_r = np.empty((nq, k), dtype=np.int64)
+        for b0 in range(0, nq, N.MAX_QUERIES_PER_CALL):
+            pick = order[b0:b0 + N.MAX_QUERIES_PER_CALL]
+            named, ql = np.unique(qs[pick], return_inverse=True)  # only the selections this block names, renumbered (the queries are sorted)
+            terms, codes, sel_ptr = flatten_selections([selections[int(g)] for g in named])
+            qb = np.ascontiguousarray(qq[pick])
+            ql = ql.astype(np.int32)
+            s = np.empty((len(pick), k), dtype=np.float32)
+            r = np.empty((len(pick), k), dtype=np.int64)
+            N.check(self._lib.rmu_index_search_where(self._h, columns._h, qb.ctypes.data, len(pick), k, 0, int(row_base), terms.ctypes.data,
+                                                     terms.shape[0], codes.ctypes.data, sel_ptr.ctypes.data, len(named), ql.ctypes.data,
+                                                     s.ctypes.data, r.ctypes.data, 0), "rmu_index_search_where")
+            out_s[pick], out_r[pick] = s, r
         return out_s, out_r
 
     def set_screening(self, on: bool = True):
