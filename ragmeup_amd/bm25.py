@@ -29,6 +29,8 @@ import numpy as np
 
 from . import _native as N
 from ._lc import BaseRetriever, Document
+from .records import (DeleteResult, FieldMaps, Seqlock, conditions, conditions_per_query, consistent, flatten_groups, group_conditions,
+                      json_default)
 
 
 def _blob(texts: list[str]) -> bytes:
@@ -196,6 +198,12 @@ def _joined(tokens) -> str:
     return " ".join(toks)
 
 
+def _records_changed(st: dict):
+    """(under the retriever's lock) documents were added, removed or renumbered: the cached id list and the field maps no longer hold"""
+    st["rows"] = {}
+    st["fields"].changed()
+
+
 class MI355XBM25Retriever(BaseRetriever):
     """``BM25Retriever`` (langchain-community) over ``BM25Index``: fields ``vectorizer`` (the index), ``docs``, ``k`` and
     ``preprocess_func`` (None = str.split(), langchain's default, done inside the library).  Beside langchain's surface, what
@@ -212,11 +220,16 @@ class MI355XBM25Retriever(BaseRetriever):
     class Config:
         arbitrary_types_allowed = True
 
-    # ---- private records beside `docs`: liveness, the ids given at add time, the cached filter results -----------------------------
+    # ---- private records beside `docs`: liveness, the ids given at add time, the cached filter result, the field maps over all three
+    # ("fields"; _matching hands them the three sequences) and the seqlock of compact() ("seq", whose
+    # lock is the writer lock) -----------------------------------------------------------------------------------------------------------
     def _st(self) -> dict:
         st = self.__dict__.get("_bm25_state")
         if st is None:
-            st = {"alive": [], "ids": [], "rows": {}, "fmaps": {}, "fmap_builds": 0, "gen": 0, "lock": threading.RLock()}
+            lock = threading.RLock()
+            st = {"alive": [], "ids": [], "rows": {}}
+            st["fields"] = FieldMaps(lock)
+            st["seq"] = Seqlock(lock, lambda: _records_changed(st))
             object.__setattr__(self, "_bm25_state", st)
         n = len(self.docs)
         if len(st["alive"]) < n:                          # documents handed to the constructor
@@ -259,14 +272,14 @@ class MI355XBM25Retriever(BaseRetriever):
             raise ValueError("texts, metadatas and ids differ in length")
         prepared = [self._text(t) for t in texts]
         st = self._st()
-        with st["lock"]:
+        with st["seq"].lock:
             first = self.vectorizer.add_texts(prepared)
             assert first == len(self.docs)
             for t, m, i in zip(texts, metadatas, ids):
                 self.docs.append(self._document(t, m, i))
             st["ids"] += ids
             st["alive"] += [True] * len(texts)
-            self._records_changed(st)
+            _records_changed(st)
         return ids
 
     def add_documents(self, documents: Iterable[Document], ids: Optional[Iterable[str]] = None) -> list:
@@ -275,62 +288,14 @@ class MI355XBM25Retriever(BaseRetriever):
         return self.add_texts([d.page_content for d in documents], [d.metadata for d in documents],
                               ids if ids is not None else [getattr(d, "id", None) for d in documents])
 
-    # ---- conditions over the records: the store's language (MI355XVectorStore._conditions), evaluated over docs[i].metadata and the id ---
-    def _records_changed(self, st):
-        """(under st["lock"]) documents were added, removed or renumbered: the cached id lists and field maps no longer hold"""
-        st["rows"] = {}
-        st["fmaps"] = {}
-
-    def _field_map(self, field: str):
-        """value -> ascending int64 ids of the live documents whose ``field`` holds it (+ the few documents with unhashable values): the
-        store's ``_field_map``, built once per field until the records change, so a condition is a dictionary look-up, not a walk."""
-        st = self._st()
-        fm = st["fmaps"].get(field)
-        if fm is None:
-            with st["lock"]:
-                fm = st["fmaps"].get(field)
-                if fm is None:
-                    buckets: dict = {}
-                    odd: list = []
-                    for r, (d, alive, pk) in enumerate(zip(self.docs, st["alive"], st["ids"])):
-                        if not alive:
-                            continue
-                        v = pk if field == "pk" else d.metadata.get(field)      # (a document without the field holds None)
-                        try:
-                            buckets.setdefault(v, []).append(r)
-                        except TypeError:                                       # a list / dict as metadata value
-                            odd.append((r, v))
-                    fm = ({v: np.asarray(rs, dtype=np.int64) for v, rs in buckets.items()}, odd)
-                    st["fmaps"][field] = fm
-                    st["fmap_builds"] += 1
-        return fm
-
+    # ---- conditions over the records: the store's language (records.conditions), evaluated over docs[i].metadata and the id ------------
     def _matching(self, conds) -> np.ndarray:
         """Ascending int64 ids of the live documents that satisfy every condition; "pk" names the document's id."""
-        rows = None
-        for field, vals in conds:
-            by_value, odd = self._field_map(field)
-            parts = []
-            for v in vals:
-                try:
-                    hit = by_value.get(v)
-                except TypeError:
-                    hit = None
-                if hit is not None:
-                    parts.append(hit)
-            if odd:
-                parts.append(np.asarray([r for r, v in odd if any(v == x for x in vals) or v == vals], dtype=np.int64))
-            if not parts:
-                return np.zeros(0, np.int64)
-            cur = parts[0] if len(parts) == 1 else np.unique(np.concatenate(parts))
-            rows = cur if rows is None else np.intersect1d(rows, cur, assume_unique=True)
-            if rows.size == 0:
-                break
-        return rows if rows is not None else np.flatnonzero(np.asarray(self._st()["alive"], dtype=bool)).astype(np.int64)
+        st = self._st()
+        return st["fields"].matching(conds, lambda: (st["alive"], st["ids"], [d.metadata for d in self.docs]))
 
     def _candidates(self):
         """The document ids search_kwargs' "filter" / "expr" admit (None: no restriction), cached until the records change."""
-        from .vectorstore import MI355XVectorStore
         kw = self.search_kwargs or {}
         expr, flt = kw.get("expr"), kw.get("filter")
         if expr is None and flt is None:
@@ -339,10 +304,10 @@ class MI355XBM25Retriever(BaseRetriever):
         key = repr((expr, flt))
         rows = st["rows"].get(key)
         if rows is None:
-            conds = MI355XVectorStore._conditions(expr, flt)
+            conds = conditions(expr, flt)
             if conds is None:
                 return None
-            with st["lock"]:
+            with st["seq"].lock:
                 rows = self._matching(conds)
                 st["rows"] = {key: rows}
         return rows
@@ -351,14 +316,13 @@ class MI355XBM25Retriever(BaseRetriever):
         """Delete by document id list, by a Milvus-style expression or by a metadata dict: the three selectors of
         ``MI355XVectorStore.delete``, parsed by the store's own code.  Where the reference's /delete handler (server.py:353-385) calls
         ``loadData()`` to rebuild BM25 without the file, call this.  Returns the store's result type (``delete_count``)."""
-        from .vectorstore import MI355XVectorStore, _DeleteResult
         st = self._st()
-        with st["lock"]:
+        with st["seq"].lock:
             rows: list[int] = []
             if ids:
                 want = set(ids)
                 rows += [r for r, pk in enumerate(st["ids"]) if pk is not None and pk in want]
-            conds = MI355XVectorStore._conditions(expr or None, filter or None)
+            conds = conditions(expr or None, filter or None)
             if conds:
                 rows += self._matching(conds).tolist()
             rows = sorted({r for r in rows if st["alive"][r]})
@@ -367,42 +331,37 @@ class MI355XBM25Retriever(BaseRetriever):
                 assert n == len(rows)
                 for r in rows:
                     st["alive"][r] = False
-                self._records_changed(st)
+                _records_changed(st)
                 thr = self.compact_threshold
                 if thr is not None and len(st["alive"]) - sum(st["alive"]) > float(thr) * len(st["alive"]):
                     self.compact()
-        return _DeleteResult(len(rows))
+        return DeleteResult(len(rows))
 
     def compact(self) -> int:
         """Reclaim the removed documents in the index and renumber ``docs`` with its map; returns how many were reclaimed."""
         st = self._st()
-        with st["lock"]:
+        with st["seq"].lock:
             if all(st["alive"]):
                 return 0
             before = len(self.docs)
-            st["gen"] += 1                                # odd: a search that overlaps this section repeats
-            try:
+            with st["seq"].write():                       # (a search that overlaps this section repeats; the caches are dropped on the way out)
                 keep = np.flatnonzero(self.vectorizer.compact() >= 0).tolist()
                 docs, pks = self.docs, st["ids"]
                 self.docs = [docs[r] for r in keep]
                 st["ids"] = [pks[r] for r in keep]
                 st["alive"] = [True] * len(keep)
-            finally:
-                self._records_changed(st)                 # compaction renumbers the documents
-                st["gen"] += 1
             return before - len(keep)
 
     # ---- persistence: the index file + one JSON record per document ---------------------------------------------------------------------
     def persist(self, path: str):
         """Write ``path + ".bm25"`` (rmu_bm25_save) and ``path + ".docs.jsonl"`` (text, metadata, id, alive per line)."""
-        from .vectorstore import _json_default
         st = self._st()
-        with st["lock"]:
+        with st["seq"].lock:
             self.vectorizer.save(path + ".bm25")
             with open(path + ".docs.jsonl", "w", encoding="utf-8") as f:
                 for d, alive, pk in zip(self.docs, st["alive"], st["ids"]):
                     f.write(json.dumps({"text": d.page_content, "metadata": d.metadata, "id": pk, "alive": 1 if alive else 0},
-                                       default=_json_default) + "\n")
+                                       default=json_default) + "\n")
 
     @classmethod
     def load(cls, path: str, preprocess_func: Optional[Callable[[str], List[str]]] = None, **kwargs: Any):
@@ -418,7 +377,7 @@ class MI355XBM25Retriever(BaseRetriever):
         st = self._st()
         st["ids"] = [r["id"] for r in recs]
         st["alive"] = [bool(r["alive"]) for r in recs]
-        self._records_changed(st)
+        _records_changed(st)
         return self
 
     # The grouped call (BM25Index.search_groups) answers two or more distinct lists in one launch.  profiles/bm25_groups.md measures it
@@ -439,28 +398,18 @@ class MI355XBM25Retriever(BaseRetriever):
         return False
 
     def _search_each(self, texts: list[str], k: int, conds_each: list) -> np.ndarray:
-        """One condition per query (None = unfiltered), inside batch_invoke's retry loop: equal conditions share one list, the unfiltered
+        """One condition per query (None = unfiltered), inside batch_invoke's consistent read: equal conditions share one list, the unfiltered
         queries take the ordinary search, one distinct list takes the subset call, two or more take the grouped call where
         profiles/bm25_groups.md has it ahead, an empty selection costs no launch.  -> ids [nq, k], padded with -1."""
         nq = len(texts)
         rows = np.full((nq, k), -1, np.int64)
-        plain = [i for i, c in enumerate(conds_each) if c is None]
+        plain, conds, q_of = group_conditions(conds_each)
         if plain:
             rows[plain] = self.vectorizer.search([texts[i] for i in plain], k)[1]
-        keys, lists, q_of = {}, [], []                      # condition -> list number; the lists; the queries of each list
-        for i, c in enumerate(conds_each):
-            if c is None:
-                continue
-            key = repr(c)
-            if key not in keys:
-                keys[key] = len(lists)
-                lists.append(self._matching(c))
-                q_of.append([])
-            q_of[keys[key]].append(i)
+        lists = [self._matching(c) for c in conds]
         used = [g for g in range(len(lists)) if lists[g].size]      # (an empty selection: its queries keep the padding)
         if self._use_groups(self.vectorizer, [lists[g] for g in used]):
-            qi = [i for g in used for i in q_of[g]]
-            ql = [n for n, g in enumerate(used) for _ in q_of[g]]
+            qi, ql = flatten_groups([q_of[g] for g in used])
             rows[qi] = self.vectorizer.search_groups([texts[i] for i in qi], k, [lists[g] for g in used], ql)[1]
         else:
             for g in used:
@@ -471,34 +420,22 @@ class MI355XBM25Retriever(BaseRetriever):
         """One rmu_bm25_search for the whole batch (rmu_bm25_search_subset under a filter); a removed document never comes back.
         ``filters`` / ``exprs``: one condition per query (None = unfiltered), e.g. every request asking about its own upload -- the
         conditions are resolved through the cached field maps and the distinct lists share one rmu_bm25_search_groups call."""
-        from .vectorstore import MI355XVectorStore
         queries = list(queries)
         kw = self.search_kwargs or {}
-        each = MI355XVectorStore._conditions_per_query(len(queries), kw.get("expr"), kw.get("filter"), exprs, filters)
+        each = conditions_per_query(len(queries), kw.get("expr"), kw.get("filter"), exprs, filters)
         if not queries or not self.docs:
             return [[] for _ in queries]
-        st = self._st()
         texts = [self._text(q) for q in queries]
-        while True:
-            g = st["gen"]
-            if g & 1:                                     # a compaction is renumbering: it holds the lock until it is done
-                with st["lock"]:
-                    pass
-                continue
+
+        def read():
             docs = self.docs
-            try:
-                k = min(int(self.k), N.MAX_K)
-                if each is None:
-                    _, rows = self.vectorizer.search(texts, k, docs=self._candidates())
-                else:                                     # (resolved here: a compaction cannot slip between the lists and the search)
-                    rows = self._search_each(texts, k, each)
-                out = [[docs[r] for r in row if r >= 0] for row in rows.tolist()]
-            except Exception:
-                if st["gen"] != g:                        # e.g. an id that no longer exists
-                    continue
-                raise
-            if st["gen"] == g:
-                return out
+            k = min(int(self.k), N.MAX_K)
+            if each is None:
+                _, rows = self.vectorizer.search(texts, k, docs=self._candidates())
+            else:                                         # (resolved here: a compaction cannot slip between the lists and the search)
+                rows = self._search_each(texts, k, each)
+            return [[docs[r] for r in row if r >= 0] for row in rows.tolist()]
+        return consistent(read, self._st()["seq"])
 
     def _get_relevant_documents(self, query: str, *, run_manager: Any = None, **kw) -> list[Document]:
         return self.batch_invoke([query])[0]

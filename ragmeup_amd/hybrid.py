@@ -27,6 +27,7 @@ from . import _native as N
 from ._lc import BaseRetriever, Document
 from .bm25 import BM25Index, MI355XBM25Retriever, _blob
 from .ensemble import per_query_conditions, weighted_reciprocal_rank
+from .records import consistent
 from .vectorstore import MI355XRetriever, MI355XVectorStore
 
 
@@ -189,7 +190,7 @@ class MI355XHybridRetriever(BaseRetriever):
             st["handle"], st["members"], st["stamp"] = HybridIndex(*members), members, [None, None]
         h = st["handle"]
         docs, texts = sp.docs, store._texts
-        stamps = ((id(sp), len(docs), sp._st()["gen"]), (id(store), len(texts), store._gen))
+        stamps = ((id(sp), len(docs), sp._st()["seq"].value), (id(store), len(texts), store._seq.value))
         for m, (records, stamp) in enumerate(zip((docs, texts), stamps)):
             old = st["stamp"][m]
             if old == stamp:
@@ -205,7 +206,6 @@ class MI355XHybridRetriever(BaseRetriever):
         sp, store = self.sparse, self.dense.vectorstore
         k_sparse, fetch_k, k_dense, lam = plan
         st = self._st()
-        sst = sp._st()
         emb = store._embeddings
         # the query vectors, as the dense member's own invoke / batch_invoke makes them
         tokens = vecs = None
@@ -213,36 +213,27 @@ class MI355XHybridRetriever(BaseRetriever):
             tokens = emb.query_ids(queries[0])
         if tokens is None:
             vecs = store._embed_query(queries[0])[None] if single else store._embed_docs(queries)
-        tries = 0
-        while True:
-            gs, gd = sst["gen"], store._gen
-            if gs & 1:                                        # a compaction is renumbering: it holds the member's lock until it is done
-                with sst["lock"]:
-                    pass
-                continue
-            if gd & 1:
-                with store._lock:
-                    pass
-                continue
-            try:
-                with st["lock"]:
-                    h, docs = self._sync(st)
-                if tokens is not None:
-                    _, ids, member = h.search_tokens(emb.encoder, tokens[0], tokens[1], emb._mode, queries, k_sparse, fetch_k, k_dense, lam,
-                                                     self._weights(), self.c)
-                else:
-                    _, ids, member = h.search(vecs, queries, k_sparse, fetch_k, k_dense, lam, self._weights(), self.c)
-                out = [[docs[i] if m == 0 else store._doc(i) for i, m in zip(row_i, row_m) if i >= 0]
-                       for row_i, row_m in zip(ids.tolist(), member.tolist())]
-            except Exception as e:
-                if sst["gen"] != gs or store._gen != gd:      # e.g. an id that no longer exists
-                    continue
-                if isinstance(e, N.RmuError) and "out of step" in str(e) and tries < self._MAX_OUT_OF_STEP:
-                    tries += 1                                # records were added between the refresh and the search
-                    continue
-                raise
-            if sst["gen"] == gs and store._gen == gd:
-                return out
+
+        def search():
+            with st["lock"]:
+                h, docs = self._sync(st)
+            if tokens is not None:
+                _, ids, member = h.search_tokens(emb.encoder, tokens[0], tokens[1], emb._mode, queries, k_sparse, fetch_k, k_dense, lam,
+                                                 self._weights(), self.c)
+            else:
+                _, ids, member = h.search(vecs, queries, k_sparse, fetch_k, k_dense, lam, self._weights(), self.c)
+            return [[docs[i] if m == 0 else store._doc(i) for i, m in zip(row_i, row_m) if i >= 0]
+                    for row_i, row_m in zip(ids.tolist(), member.tolist())]
+
+        def read():
+            for tries in range(self._MAX_OUT_OF_STEP + 1):
+                try:
+                    return search()
+                except N.RmuError as e:                       # records were added between the refresh and the search: refresh again
+                    if "out of step" not in str(e) or tries == self._MAX_OUT_OF_STEP:
+                        raise
+        # (a compaction of either member renumbers what the tables name: the read is repeated)
+        return consistent(read, sp._st()["seq"], store._seq)
 
     def batch_invoke(self, queries: list[str], filters: Optional[list] = None, exprs: Optional[list] = None) -> list[list[Document]]:
         """`filters` / `exprs`: one condition per query (None = unfiltered).  The one call takes no lists, so a per-request form takes

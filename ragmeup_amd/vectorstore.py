@@ -28,8 +28,6 @@ from __future__ import annotations
 import atexit
 import json
 import os
-import re
-import sys
 import threading
 import time
 import weakref
@@ -41,6 +39,8 @@ from . import _log
 from . import _native as N
 from ._lc import Document, VectorStore, VectorStoreRetriever
 from .index import Columns, FlatIndex
+from .records import (DeleteResult, FieldMaps, Seqlock, conditions, conditions_per_query, consistent, flatten_groups, group_conditions,
+                      json_default)
 
 
 def _cosine_similarity(x: np.ndarray, y: np.ndarray) -> np.ndarray:
@@ -115,20 +115,6 @@ class MI355XRetriever(VectorStoreRetriever):
 _METRICS = {"ip": N.METRIC_IP, "cosine": N.METRIC_COSINE, "l2": N.METRIC_L2SQ}
 
 
-def _json_default(o):
-    """Metadata values loaders produce that JSON does not know (numpy scalars, datetimes, bytes, Paths): stored as plain
-    numbers where they are numbers, else as their string form -- persist() must not fail on them."""
-    if isinstance(o, np.integer):
-        return int(o)
-    if isinstance(o, np.floating):
-        return float(o)
-    if isinstance(o, np.ndarray):
-        return o.tolist()
-    if isinstance(o, (bytes, bytearray)):
-        return o.decode("utf-8", "replace")
-    return str(o)
-
-
 class MI355XVectorStore(VectorStore):
     # drop_old=False re-attaches to a live collection; weak values: the registry does not keep a 15 GB index alive
     _collections: "weakref.WeakValueDictionary[str, MI355XVectorStore]" = weakref.WeakValueDictionary()
@@ -178,10 +164,9 @@ class MI355XVectorStore(VectorStore):
         self._pks: list[str] = []
         self._alive: list[bool] = []
         self._pk_to_row: dict[str, int] = {}
-        # filtered search: field -> (value -> ascending int64 rows of the live records holding it), built on the first filtered query that
-        # names the field and dropped whenever records change (_records_changed); _field_map_builds counts the builds
-        self._field_maps: dict[str, tuple] = {}
-        self._field_map_builds = 0
+        # filtered search: the field maps over the records above, dropped whenever records change (_records_changed); _filter_rows hands
+        # them the lists
+        self._fields = FieldMaps(self._lock)
         # device fields: field -> position in the code rows; one dictionary value -> code per field (a record without the field holds None,
         # which gets a code like any value); the code rows themselves (created with the first row); the fields that received an unhashable
         # value and take the host route from then on
@@ -192,9 +177,9 @@ class MI355XVectorStore(VectorStore):
         self._dev_codes: list[dict] = [{} for _ in fields]
         self._dev_demoted: set[str] = set()
         self._columns = None
-        # compact() renumbers the rows while searches run without self._lock: a seqlock.  _gen is odd while the index and the records
-        # are being renumbered; a read that started under another value (or an odd one) is repeated (see _consistent)
-        self._gen = 0
+        # compact() renumbers the rows while searches run without self._lock: a seqlock, odd while the index and the records are being
+        # renumbered; a read that started under another value (or an odd one) is repeated (records.consistent)
+        self._seq = Seqlock(self._lock, self._fields.changed)
         # None: rows of deleted / replaced records stay in the index (tombstones) until compact(); a fraction: compact() once dead rows
         # exceed it of all rows -- checked at the end of delete() and of an insert (or flush()) that leaves no deferred half in flight
         if compact_threshold is not None and not 0.0 <= float(compact_threshold) < 1.0:
@@ -296,7 +281,7 @@ class MI355XVectorStore(VectorStore):
             with open(paths[1] + ".tmp", "w", encoding="utf-8") as f:
                 json.dump({"format": 1, "n": len(self._texts), "dim": self._dim, "metric": self.metric,
                            "score_mode": self.score_mode, "texts": self._texts, "metas": self._metas, "pks": self._pks,
-                           "alive": [1 if a else 0 for a in self._alive]}, f, default=_json_default)
+                           "alive": [1 if a else 0 for a in self._alive]}, f, default=json_default)
             os.replace(paths[0] + ".tmp", paths[0])
             os.replace(paths[1] + ".tmp", paths[1])
             self._dirty = False
@@ -921,139 +906,20 @@ class MI355XVectorStore(VectorStore):
         return self._add([d.page_content for d in documents], lambda: [d.metadata for d in documents], ids)
 
     # ---- delete (server.py:373-377) -----------------------------------------------------------------------
-    # ---- conditions on records: one language for delete(expr=, filter=) and for every search entry point ------------------------
-    # expr (Milvus style): `field == "v"`, `field in ["a", 'b']`, joined by `and` / `&&`; values are quoted strings or plain numbers.
-    # filter (PGVector style): {field: value} or {field: [values]} = any of them.  Every condition must hold; "pk" names the primary key.
-    _EXPR = re.compile(r"""^\s*(\w+)\s*==\s*(['"])(.*)\2\s*$""")        # the whole expression as ONE equality: the value may hold anything
-    _TOKEN = re.compile(r"""\s*(?:(?P<str>"[^"]*"|'[^']*')|(?P<num>-?\d+(?:\.\d+)?(?![\w.]))|(?P<op>==|&&|\[|\]|,)|(?P<word>\w+))""")
-
-    @classmethod
-    def _parse_expr(cls, expr: str) -> list[tuple[str, list]]:
-        """-> [(field, [accepted values])]; ValueError for anything the grammar above does not cover (an expression is never ignored)"""
-        toks, pos = [], 0
-        text = expr.rstrip()
-        while pos < len(text):
-            m = cls._TOKEN.match(text, pos)
-            if not m:
-                toks = None
-                break
-            kind = m.lastgroup
-            raw = m.group(kind)
-            toks.append((kind, raw[1:-1] if kind == "str" else (float(raw) if "." in raw else int(raw)) if kind == "num" else raw))
-            pos = m.end()
-        conds: list[tuple[str, list]] = []
-
-        def value(i):
-            if i < len(toks) and toks[i][0] in ("str", "num"):
-                return toks[i][1], i + 1
-            raise ValueError
-
-        try:
-            if not toks:
-                raise ValueError
-            i = 0
-            while True:
-                if toks[i][0] != "word" or toks[i][1] in ("and", "in"):
-                    raise ValueError
-                field = toks[i][1]
-                if toks[i + 1] == ("op", "=="):
-                    v, i = value(i + 2)
-                    conds.append((field, [v]))
-                elif toks[i + 1] == ("word", "in") and toks[i + 2] == ("op", "["):
-                    vals, i = [], i + 3
-                    while True:
-                        v, i = value(i)
-                        vals.append(v)
-                        if toks[i] == ("op", "]"):
-                            i += 1
-                            break
-                        if toks[i] != ("op", ","):
-                            raise ValueError
-                        i += 1
-                    conds.append((field, vals))
-                else:
-                    raise ValueError
-                if i == len(toks):
-                    return conds
-                if toks[i] not in (("word", "and"), ("op", "&&")):
-                    raise ValueError
-                i += 1
-        except (ValueError, IndexError):
-            # what delete() always took: one equality whose value may itself hold quotes -- but not a second condition this grammar
-            # does not know (`or`, `>`...): that is an error, not a strange value
-            m = cls._EXPR.match(expr)
-            if m and not re.search(r"==|\bin\s*\[", m.group(3)):
-                return [(m.group(1), [m.group(3)])]
-            raise ValueError(f"unsupported filter expression: {expr!r}") from None
-
-    @classmethod
-    def _conditions(cls, expr, filter) -> list[tuple[str, list]] | None:
-        """The conditions `expr=` and `filter=` state together, or None when neither is given."""
-        if expr is None and filter is None:
-            return None
-        if filter is not None and not isinstance(filter, dict):
-            raise ValueError(f"filter must be a dict of field -> value or list of values, got {type(filter).__name__}")
-        if expr is not None and not isinstance(expr, str):
-            raise ValueError(f"expr must be a string, got {type(expr).__name__}")
-        conds = [(str(f), list(v) if isinstance(v, (list, tuple, set, frozenset)) else [v]) for f, v in (filter or {}).items()]
-        if expr is not None and expr.strip():
-            conds += cls._parse_expr(expr)
-        elif expr is not None and not conds:
-            raise ValueError("unsupported filter expression: ''")
-        return conds or None                             # (filter={} states nothing)
-
+    # (the conditions of delete(expr=, filter=) and of every search entry point: records.conditions, resolved by _filter_rows)
     def _records_changed(self):
-        self._field_maps = {}
+        self._fields.changed()
 
-    def _field_map(self, field: str):
-        """value -> ascending int64 rows of the live records whose `field` holds it (+ the few records with unhashable values), built once
-        per field until the records change.  Built under the writer lock: no insert or delete can slip between the walk and the store."""
-        fm = self._field_maps.get(field)
-        if fm is None:
-            with self._lock:
-                fm = self._field_maps.get(field)
-                if fm is None:
-                    buckets: dict = {}
-                    odd: list[tuple[int, Any]] = []
-                    alive, pks, metas = self._alive, self._pks, self._metas
-                    for r in range(len(alive)):
-                        if not alive[r]:
-                            continue
-                        if field == "pk":
-                            v = pks[r]
-                        else:
-                            v = metas[r].get(field)      # (a record without the field holds None, as delete always compared)
-                        try:
-                            buckets.setdefault(v, []).append(r)
-                        except TypeError:                # a list / dict as metadata value
-                            odd.append((r, v))
-                    fm = ({v: np.asarray(rs, dtype=np.int64) for v, rs in buckets.items()}, odd)
-                    self._field_maps[field] = fm
-                    self._field_map_builds += 1
-        return fm
+    def _records(self):
+        return self._alive, self._pks, self._metas
 
-    def _filter_rows(self, conds: list[tuple[str, list]]) -> np.ndarray:
-        """Ascending int64 rows of the live records that satisfy every condition."""
-        rows = None
-        for field, vals in conds:
-            by_value, odd = self._field_map(field)
-            parts = []
-            for v in vals:
-                try:
-                    hit = by_value.get(v)
-                except TypeError:
-                    hit = None
-                if hit is not None:
-                    parts.append(hit)
-            if odd:
-                parts.append(np.asarray([r for r, v in odd if v in vals or v == vals], dtype=np.int64))
-            if not parts:
-                return np.zeros(0, np.int64)
-            cur = parts[0] if len(parts) == 1 else np.unique(np.concatenate(parts))
-            rows = cur if rows is None else np.intersect1d(rows, cur, assume_unique=True)
-            if rows.size == 0:
-                break
-        return rows if rows is not None else np.flatnonzero(np.asarray(self._alive, dtype=bool)).astype(np.int64)
+    def _filter_rows(self, conds) -> np.ndarray:
+        return self._fields.matching(conds, self._records)
+
+    @property
+    def _field_map_builds(self) -> int:
+        """walks over the records so far (read by tools/where_probe.py and the tests: the device route must not cause any)"""
+        return self._fields.builds
 
     def delete(self, ids: Optional[list[str]] = None, expr: Optional[str] = None, filter: Optional[dict] = None, **kw):
         """Delete by pk list, by a Milvus-style expression (`field == "value"`, and the forms the searches take), or by a metadata dict.
@@ -1063,7 +929,7 @@ class MI355XVectorStore(VectorStore):
             rows: list[int] = []
             if ids:
                 rows += [self._pk_to_row[i] for i in ids if i in self._pk_to_row]
-            conds = self._conditions(expr or None, filter or None)
+            conds = conditions(expr or None, filter or None)
             if conds:
                 rows += self._filter_rows(conds).tolist()
             rows = sorted({r for r in rows if self._alive[r]})
@@ -1077,7 +943,7 @@ class MI355XVectorStore(VectorStore):
                 self._maybe_compact()
                 if self.auto_persist is True:
                     self.persist()
-        return _DeleteResult(len(rows))
+        return DeleteResult(len(rows))
 
     # ---- compaction (rmu_index_compact) ---------------------------------------------------------------------
     def compact(self) -> int:
@@ -1097,8 +963,7 @@ class MI355XVectorStore(VectorStore):
         before = len(self._alive)
         if len(self._index) != before:
             raise RuntimeError(f"index rows ({len(self._index)}) and host records ({before}) out of step: not compacting")
-        self._gen += 1                                   # odd: readers that overlap this section repeat their read
-        try:
+        with self._seq.write():                          # (the field maps are dropped on the way out: compaction renumbers the rows)
             m = np.asarray(self._index.compact())
             if self._columns is not None:
                 self._columns.compact(m)
@@ -1109,9 +974,6 @@ class MI355XVectorStore(VectorStore):
             self._pks = [pks[r] for r in keep]
             self._alive = [True] * len(keep)
             self._pk_to_row = {pk: j for j, pk in enumerate(self._pks)}
-        finally:
-            self._records_changed()                      # compaction renumbers the rows
-            self._gen += 1
         self._dirty = True
         return before - len(self._alive)
 
@@ -1125,27 +987,9 @@ class MI355XVectorStore(VectorStore):
             return False
         return self._compact_locked() > 0
 
-    def _consistent(self, read):
-        """Run `read` (index call + row numbers -> Documents) until no compaction overlapped it: the seqlock's read side.  Searches
-        still run in parallel with each other; only a read that overlapped a compaction is repeated."""
-        while True:
-            g = self._gen
-            if g & 1:                                    # a compaction is in progress: it holds the writer lock until it is done
-                with self._lock:
-                    pass
-                continue
-            try:
-                out = read()
-            except Exception:
-                if self._gen != g:                       # e.g. a row number that no longer exists
-                    continue
-                raise
-            if self._gen == g:
-                return out
-
     # ---- search ---------------------------------------------------------------------------------------------
     def _search_vecs(self, qvecs: np.ndarray, k: int, conds=None):
-        """conds (a filtered query): the conditions are resolved to rows HERE, inside the caller's _consistent read, and the index searches
+        """conds (a filtered query): the conditions are resolved to rows HERE, inside the caller's consistent read, and the index searches
         those rows only (FlatIndex.search(rows=...): the gathered scan); without conditions the index is called as it always was."""
         if self._pending:
             self.flush()
@@ -1171,19 +1015,6 @@ class MI355XVectorStore(VectorStore):
         return self._index.search(qvecs, kk, rows=rows)
 
     # ---- one condition per query (filters= / exprs= of the batch entry points) ---------------------------------------------------
-    @classmethod
-    def _conditions_per_query(cls, nq: int, expr, filter, exprs, filters):
-        """-> None (no plural form given: the singular expr= / filter= hold for the whole batch, as ever) or a list with one entry per query:
-        its conditions, or None for an unfiltered query.  ValueError when a singular and a plural form are given together."""
-        if exprs is None and filters is None:
-            return None
-        if expr is not None or filter is not None:
-            raise ValueError("give either expr= / filter= (one condition for the whole batch) or exprs= / filters= (one per query), not both")
-        for name, v in (("exprs", exprs), ("filters", filters)):
-            if v is not None and (not isinstance(v, (list, tuple)) or len(v) != nq):
-                raise ValueError(f"{name} must be a list with one entry per query ({nq}); None = unfiltered")
-        return [cls._conditions(exprs[i] if exprs is not None else None, filters[i] if filters is not None else None) for i in range(nq)]
-
     # the grouped call (FlatIndex.search_groups) answers two or more distinct lists in one scan.  profiles/groups_search.md measures it
     # against the per-list calls it replaces (1M x 384, k = 10, host lists): faster by more than the run-to-run spread for 2 .. 128 lists
     # of 1 000 .. 100 000 rows (0.03x .. 0.79x the time) as long as the lists together hold at most 3.2M rows; at 128 lists x 100 000
@@ -1196,7 +1027,7 @@ class MI355XVectorStore(VectorStore):
         return len(lists) >= 2 and hasattr(index, "search_groups") and sum(int(l.size) for l in lists) <= cls.GROUPS_MAX_LIST_ROWS
 
     def _search_vecs_each(self, qvecs: np.ndarray, k: int, conds_each: list):
-        """_search_vecs with one condition per query, inside the caller's _consistent read: equal conditions share one list, the unfiltered
+        """_search_vecs with one condition per query, inside the caller's consistent read: equal conditions share one list, the unfiltered
         queries take the ordinary search, an empty selection costs no launch.  -> (scores, rows) [nq, kk], padded with (-inf, -1)."""
         if self._pending:
             self.flush()
@@ -1206,7 +1037,7 @@ class MI355XVectorStore(VectorStore):
         kk = max(1, min(int(k), N.MAX_K))
         s = np.full((nq, kk), -np.inf, np.float32)
         r = np.full((nq, kk), -1, np.int64)
-        plain = [i for i, c in enumerate(conds_each) if c is None]
+        plain, conds, q_of = group_conditions(conds_each)
         if plain:
             s[plain], r[plain] = self._index.search(qvecs[plain], kk)
         if len(plain) == nq:
@@ -1214,43 +1045,20 @@ class MI355XVectorStore(VectorStore):
         if getattr(self._index, "dim", 0) > N.MAX_DIM:
             raise ValueError(f"filtered search (exprs= / filters=) serves embeddings of at most {N.MAX_DIM} dimensions; this store holds "
                              f"{self._index.dim}-d vectors")
-        keys, hconds, q_of = {}, [], []                     # condition -> list number; the host route's conditions; the queries of each
-        dkeys, sels, dconds, dq_of = {}, [], [], []         # the same for the conditions over device fields: selections instead of lists
-        for i, c in enumerate(conds_each):
-            if c is None:
-                continue
-            key = repr(c)
-            if key in dkeys:
-                dq_of[dkeys[key]].append(i)
-                continue
-            sel = self._device_selection(c) if key not in keys else None
-            if sel is not None:
-                dkeys[key] = len(sels)
-                sels.append(sel)
-                dconds.append(c)
-                dq_of.append([i])
-                continue
-            if key not in keys:
-                keys[key] = len(hconds)
-                hconds.append(c)
-                q_of.append([])
-            q_of[keys[key]].append(i)
-        dused = [g for g in range(len(sels)) if sels[g]]            # (a term without a known value: its queries keep the padding)
+        sels = [self._device_selection(c) for c in conds]           # a selection over device fields, or None: the host route's
+        host = [g for g, sel in enumerate(sels) if sel is None]
+        dused = [g for g, sel in enumerate(sels) if sel]            # (a term without a known value: its queries keep the padding)
         if dused:
-            qi = [i for g in dused for i in dq_of[g]]
-            ql = [n for n, g in enumerate(dused) for _ in dq_of[g]]
+            qi, ql = flatten_groups([q_of[g] for g in dused])
             got = self._where(qvecs[qi], kk, [sels[g] for g in dused], ql)
             if got is not None:
                 s[qi], r[qi] = got
             else:                                                   # an insert slipped in: these conditions are the host route's this time
-                for g in dused:
-                    hconds.append(dconds[g])
-                    q_of.append(dq_of[g])
-        lists = [self._filter_rows(c) for c in hconds]
-        used = [g for g in range(len(lists)) if lists[g].size]      # (an empty selection: its queries keep the padding)
+                host += dused
+        lists = {g: self._filter_rows(conds[g]) for g in host}
+        used = [g for g in host if lists[g].size]                   # (an empty selection: its queries keep the padding)
         if self._use_groups(self._index, [lists[g] for g in used]):
-            qi = [i for g in used for i in q_of[g]]
-            ql = [n for n, g in enumerate(used) for _ in q_of[g]]
+            qi, ql = flatten_groups([q_of[g] for g in used])
             s[qi], r[qi] = self._index.search_groups(qvecs[qi], kk, [lists[g] for g in used], ql)
         else:
             for g in used:
@@ -1260,12 +1068,12 @@ class MI355XVectorStore(VectorStore):
     def similarity_search_with_score_by_vector(self, embedding, k: int = 4, filter: Optional[dict] = None, expr: Optional[str] = None,
                                                **kw) -> list[tuple[Document, float]]:
         q = np.asarray(embedding, dtype=np.float32)[None]
-        conds = self._conditions(expr, filter)
+        conds = conditions(expr, filter)
 
         def read():
             s, r = self._search_vecs(q, k, conds)
             return [(self._doc(int(row)), self._convert(float(sc))) for sc, row in zip(s[0], r[0]) if row >= 0]
-        return self._consistent(read)
+        return consistent(read, self._seq)
 
     def _fused_query(self, query: str, fetch_k: int, k: int, lambda_mult):
         """One query through `rmu_bert_search_mmr` (token ids in, rows out: forward, dense top-fetch_k and the selection in ONE library
@@ -1290,7 +1098,7 @@ class MI355XVectorStore(VectorStore):
                 return None
             return [(self._doc(int(row)), self._convert(float(sc))) for row, sc in zip(*hit) if row >= 0]
         # a filtered query does not take the fused call (rmu_bert_search_mmr has no subset form): embed, subset search
-        out = self._consistent(read) if self._conditions(expr, filter) is None else None
+        out = consistent(read, self._seq) if conditions(expr, filter) is None else None
         if out is not None:
             return out
         return self.similarity_search_with_score_by_vector(self._embed_query(query), k, filter=filter, expr=expr, **kw)
@@ -1300,13 +1108,13 @@ class MI355XVectorStore(VectorStore):
 
     def similarity_search_with_relevance_scores(self, query: str, k: int = 4, filter: Optional[dict] = None, expr: Optional[str] = None,
                                                 **kw) -> list[tuple[Document, float]]:
-        conds = self._conditions(expr, filter)
+        conds = conditions(expr, filter)
         q = self._embed_query(query)[None]
 
         def read():
             s, r = self._search_vecs(q, k, conds)
             return [(self._doc(int(row)), float(sc)) for sc, row in zip(s[0], r[0]) if row >= 0]
-        return self._consistent(read)
+        return consistent(read, self._seq)
 
     def similarity_search_with_score_batch(self, queries: list[str], k: int = 4, filter: Optional[dict] = None,
                                            expr: Optional[str] = None, filters: Optional[list] = None, exprs: Optional[list] = None,
@@ -1314,22 +1122,22 @@ class MI355XVectorStore(VectorStore):
         """`filter=` / `expr=`: one condition for the whole batch.  `filters=` / `exprs=`: a list with one entry per query (None =
         unfiltered); queries with different conditions still share one scan (FlatIndex.search_groups)."""
         queries = list(queries)
-        each = self._conditions_per_query(len(queries), expr, filter, exprs, filters)
-        conds = self._conditions(expr, filter)
+        each = conditions_per_query(len(queries), expr, filter, exprs, filters)
+        conds = conditions(expr, filter)
         qv = self._embed_docs(queries)
 
         def read():
             s, r = self._search_vecs(qv, k, conds) if each is None else self._search_vecs_each(qv, k, each)
             return [[(self._doc(int(row)), self._convert(float(sc))) for sc, row in zip(ss, rr) if row >= 0]
                     for ss, rr in zip(s, r)]
-        return self._consistent(read)
+        return consistent(read, self._seq)
 
     def max_marginal_relevance_search_by_vector(self, embedding, k: int = 4, fetch_k: int = 20,
                                                 lambda_mult: float = 0.5, filter: Optional[dict] = None, expr: Optional[str] = None,
                                                 **kw) -> list[Document]:
         q = np.asarray(embedding, dtype=np.float32)
-        conds = self._conditions(expr, filter)
-        return self._consistent(lambda: self._mmr_by_vector(q, k, fetch_k, lambda_mult, conds))
+        conds = conditions(expr, filter)
+        return consistent(lambda: self._mmr_by_vector(q, k, fetch_k, lambda_mult, conds), self._seq)
 
     def _mmr_by_vector(self, q: np.ndarray, k: int, fetch_k: int, lambda_mult: float, conds=None) -> list[Document]:
         if self._pending:
@@ -1358,7 +1166,7 @@ class MI355XVectorStore(VectorStore):
         def read():
             hit = self._fused_query(query, int(fetch_k), int(k), float(lambda_mult))     # the reference's per-request call (RAGHelper.py:497-499)
             return None if hit is None else [self._doc(int(x)) for x in hit[0] if x >= 0]
-        out = self._consistent(read) if self._conditions(expr, filter) is None else None     # filtered: embed, subset search, device MMR
+        out = consistent(read, self._seq) if conditions(expr, filter) is None else None     # filtered: embed, subset search, device MMR
         if out is not None:
             return out
         return self.max_marginal_relevance_search_by_vector(self._embed_query(query), k, fetch_k, lambda_mult, filter=filter, expr=expr)
@@ -1370,10 +1178,10 @@ class MI355XVectorStore(VectorStore):
         tie order as the single-query path; no per-query vector re-fetch).  fetch_k > 64 falls back to the host loop.
         `filters=` / `exprs=`: one condition per query (None = unfiltered), as similarity_search_with_score_batch takes them."""
         queries = list(queries)
-        each = self._conditions_per_query(len(queries), expr, filter, exprs, filters)
-        conds = self._conditions(expr, filter)
+        each = conditions_per_query(len(queries), expr, filter, exprs, filters)
+        conds = conditions(expr, filter)
         qv = self._embed_docs(queries)
-        return self._consistent(lambda: self._mmr_batch(qv, k, fetch_k, lambda_mult, conds, each))
+        return consistent(lambda: self._mmr_batch(qv, k, fetch_k, lambda_mult, conds, each), self._seq)
 
     def _mmr_batch(self, qv: np.ndarray, k: int, fetch_k: int, lambda_mult: float, conds=None, each=None) -> list[list[Document]]:
         s, r = self._search_vecs(qv, fetch_k, conds) if each is None else self._search_vecs_each(qv, fetch_k, each)
@@ -1411,12 +1219,3 @@ class _DeferredFailure:
 
     def __init__(self, items, error):
         self.items, self.error = items, error
-
-
-class _DeleteResult(int):
-    """int subclass carrying ``delete_count`` (pymilvus MutationResult field read at server.py:385)."""
-
-    def __new__(cls, n: int):
-        obj = super().__new__(cls, n)
-        obj.delete_count = n
-        return obj

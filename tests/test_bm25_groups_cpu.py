@@ -317,14 +317,14 @@ def test_the_field_map_is_built_once_per_field_and_rebuilt_when_the_records_chan
     st = r._st()
     exprs = [f'source == "f{i % 4}.pdf"' for i in range(32)]
     r.batch_invoke(["q"] * 32, exprs=exprs)
-    assert st["fmap_builds"] == 1                                           # 32 conditions: one walk, 32 look-ups
+    assert st["fields"].builds == 1                                           # 32 conditions: one walk, 32 look-ups
     r.batch_invoke(["q"] * 2, exprs=['page == 0', 'source == "f1.pdf" and page == 1'])
-    assert st["fmap_builds"] == 2
-    assert r._matching([("source", ["f1.pdf"])]).tolist() == [1, 5, 9] and st["fmap_builds"] == 2
+    assert st["fields"].builds == 2
+    assert r._matching([("source", ["f1.pdf"])]).tolist() == [1, 5, 9] and st["fields"].builds == 2
     r.add_texts(["more"], [{"source": "f1.pdf"}])
-    assert r._matching([("source", ["f1.pdf"])]).tolist() == [1, 5, 9, 12] and st["fmap_builds"] == 3
-    assert r.delete(expr='pk == "id-5"').delete_count == 1 and st["fmap_builds"] == 4          # (the pk map; the delete drops both)
-    assert r._matching([("source", ["f1.pdf"])]).tolist() == [1, 9, 12] and st["fmap_builds"] == 5
+    assert r._matching([("source", ["f1.pdf"])]).tolist() == [1, 5, 9, 12] and st["fields"].builds == 3
+    assert r.delete(expr='pk == "id-5"').delete_count == 1 and st["fields"].builds == 4          # (the pk map; the delete drops both)
+    assert r._matching([("source", ["f1.pdf"])]).tolist() == [1, 9, 12] and st["fields"].builds == 5
     # values that cannot be dictionary keys still match, as the walk matched them
     r.add_texts(["odd"], [{"tags": ["x", "y"]}])
     assert r._matching([("tags", ["x", "y"])]).tolist() == [13]
@@ -344,7 +344,7 @@ def test_compact_and_load_drop_the_field_maps(librmu, tmp_path):
         r.persist(str(tmp_path / "p"))
         back = MI355XBM25Retriever.load(str(tmp_path / "p"))
         try:
-            assert back._matching([("s", [1])]).tolist() == [1, 3] and back._st()["fmap_builds"] == 1
+            assert back._matching([("s", [1])]).tolist() == [1, 3] and back._st()["fields"].builds == 1
         finally:
             back.vectorizer.close()
     finally:

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from ragmeup_amd import records
 from ragmeup_amd.vectorstore import MI355XVectorStore
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,7 +48,7 @@ def test_flatindex_search_takes_rows():
 
 # ---- the expression parser -----------------------------------------------------------------------------------------------------
 def test_expression_parser_accepted_forms():
-    P = MI355XVectorStore._parse_expr
+    P = records.parse_expr
     assert P('source == "a.pdf"') == [("source", ["a.pdf"])]
     assert P("  source=='a.pdf'  ") == [("source", ["a.pdf"])]
     assert P('source in ["a.pdf", \'b.pdf\']') == [("source", ["a.pdf", "b.pdf"])]
@@ -59,7 +60,7 @@ def test_expression_parser_accepted_forms():
     assert P('source == "/data/it\'s here.pdf"') == [("source", ["/data/it's here.pdf"])]
     assert P('source == "the "quoted" name.pdf"') == [("source", ['the "quoted" name.pdf'])]
     assert P('source == "rock and roll.pdf"') == [("source", ["rock and roll.pdf"])]
-    C = MI355XVectorStore._conditions
+    C = records.conditions
     assert C(None, None) is None
     assert C(None, {"source": "a", "lang": ["en", "nl"]}) == [("source", ["a"]), ("lang", ["en", "nl"])]
     assert C('page == 1', {"source": "a"}) == [("source", ["a"]), ("page", [1])]
@@ -70,14 +71,14 @@ def test_expression_parser_accepted_forms():
                                  'source != "a"', 'source like "a%"'])
 def test_expression_parser_rejects_what_it_does_not_understand(bad):
     with pytest.raises(ValueError):
-        MI355XVectorStore._conditions(bad, None)
+        records.conditions(bad, None)
 
 
 def test_filter_must_be_a_dict():
     with pytest.raises(ValueError):
-        MI355XVectorStore._conditions(None, "source == 'a'")
+        records.conditions(None, "source == 'a'")
     with pytest.raises(ValueError):
-        MI355XVectorStore._conditions(["source"], None)
+        records.conditions(["source"], None)
 
 
 # ---- a small exact index of this file's own -------------------------------------------------------------------------------------
