@@ -281,7 +281,8 @@ int rmu_wide_plan(ScanLaunch* p) {
     rmu_plan_chunks(p->nqt, (p->n_rows + rt - 1) / rt, &p->s_chunks, &p->tiles_per_chunk);
     p->grid = p->s_chunks * p->nqt;
     p->parts = p->s_chunks * (4 / p->wq);
-    p->nt = (p->nqt == 1 && p->kv == 0 && p->wq <= 2) ? 1 : 0;
+    static const int nt_env = rmu_env("RMU_NT") ? atoi(rmu_env("RMU_NT")) : 1;
+    p->nt = (nt_env && p->nqt == 1 && p->kv == 0 && p->wq <= 2) ? 1 : 0;
     p->lds_bytes = with_wcfg(p->wq, p->kv, 0, [](auto c) { return (int)decltype(c)::LDS_BYTES; });
     return p->lds_bytes > 0 ? RMU_OK : RMU_E_INVALID;
 }

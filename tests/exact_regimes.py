@@ -246,25 +246,26 @@ def _unit(v):
     return np.ascontiguousarray(v / np.linalg.norm(v.astype(np.float64), axis=1, keepdims=True).astype(np.float32), dtype=np.float32)
 
 
-def flood_layout() -> list:
+def flood_layout(sizes: tuple = FLOOD_SIZES) -> list:
     """[(m, placement, rows)]: query i of every batch is aimed at cluster i.  "spread": a few copies (fewer than any k > 7) at the END of
     one unit -- the last rows its workgroup scans -- and the rest over the next two units: the k lowest ids come from several
     workgroups, and the one that holds the lowest meets a shared bound EQUAL to their score.  "boundary": a contiguous run centred on
-    row 128 of a unit, a tile boundary inside a chunk for every RT.  "run": a contiguous run from the start of a tile."""
+    row 128 of a unit, a tile boundary inside a chunk for every RT.  "run": a contiguous run from the start of a tile.
+    `sizes`: the cluster sizes (tests/wide_regimes.py has its own, for the slot depths of the wide scan)."""
     out, c = [], 1
-    for m in FLOOD_SIZES:
+    for m in sizes:
         a = max(1, min(7, m // 3))
         b = (m - a + 1) // 2
         rows = np.concatenate([UNIT * (c + 1) - a + np.arange(a), UNIT * (c + 1) + 17 + np.arange(b), UNIT * (c + 2) + 1 + 2 * np.arange(m - a - b)])
         out.append((m, "spread", rows.astype(np.int64)))
         c += 3
-    for m in FLOOD_SIZES:
+    for m in sizes:
         if m // 2 > 128:
             c += 1
         out.append((m, "boundary", (UNIT * c + 128 - m // 2 + np.arange(m)).astype(np.int64)))
         c += 2 if m > 256 else 1
     second = False
-    for m in FLOOD_SIZES:                        # (two to a unit where they fit: at row 0, and at row 256 -- the start of a tile for every RT)
+    for m in sizes:                        # (two to a unit where they fit: at row 0, and at row 256 -- the start of a tile for every RT)
         if second and m > UNIT - 256:
             c, second = c + 1, False
         out.append((m, "run", (UNIT * c + (256 if second else 0) + np.arange(m)).astype(np.int64)))
@@ -279,21 +280,20 @@ FLOOD_END = 16_000               # every cluster lies below this row: present at
 
 
 @lru_cache(maxsize=2)
-def corpus(kind: str, dim: int, n: int = 0) -> tuple:
+def corpus(kind: str, dim: int, n: int = 0, sizes: tuple = FLOOD_SIZES) -> tuple:
     """(x [n, dim], q [NQ_MAX, dim]) fp32, seeded; n = 0: rows_max of the width.  The rows of a smaller n are the first rows of a larger one
-    (`falling` excepted) and the queries do not depend on n.
+    (`falling` excepted) and the queries do not depend on n.  `sizes`: the flood clusters, as in flood_layout; any dim with an explicit n.
     random   unit rows with the flood clusters written over them; queries 0..23 aimed at the clusters (unit(v + 0.3 unit noise)), query 24
              all zero, the rest next to rows below 4000 (present at every row count of CASES)
     rising   rows c_r u, c_r = 1 + r / 65536, queries unit(u + 0.5 unit noise): u.q > 0 and every row beats all lower rows
     falling  the same rows in reverse order
     scaled   `random` with rows of norm 0.25 .. 4 and queries of norm 0.5 .. 2 (COSINE and L2 cases: the image kernels have work to do)"""
-    dpad = DIMS.get(dim) or L2_DIMS[dim]
-    n = n or rows_max(dpad)
+    n = n or rows_max(DIMS.get(dim) or L2_DIMS[dim])
     rng_x, rng, rng_s = (np.random.default_rng(zlib.crc32(f"exact-{kind}-{dim}-{what}".encode())) for what in ("rows", "queries", "scales"))
     if kind in ("random", "scaled"):
         x = _unit(rng_x.standard_normal((n, dim), dtype=np.float32))
         q = np.empty((NQ_MAX, dim), np.float32)
-        lay = flood_layout()
+        lay = flood_layout(sizes)
         for i, (m, _, rows) in enumerate(lay):
             v = _unit(rng.standard_normal((1, dim), dtype=np.float32))
             x[rows[rows < n]] = v

@@ -1,7 +1,11 @@
 """GPU tests of the wide flat index (rows of 769..3072 dimensions, scan_wide.hip) against the fp64 oracle, and of scan_wide_kernel against
-scan_topk_kernel, bit for bit, at the widths both serve (RMU_OPT_WIDE_SCAN).
+scan_topk_kernel, bit for bit, at the widths both serve (RMU_OPT_WIDE_SCAN): the index's life cycle, its limits and the store on top.
 
-Bar: tests.helpers.assert_topk_parity with its default tolerances against oracle.flat_search run 4 deeper than k, and at most 1% of the
+The bit-level bar of the kernel itself lives in tests/test_wide_regimes_gpu.py (cases: tests/wide_regimes.py): every configuration,
+tile class, block-map branch and query-tile count against the fmaf chain, with no tolerance and no tie rule, on corpora that fill the
+candidate slots.  The ladder test below is held to the same chain.
+
+Bar here: tests.helpers.assert_topk_parity with its default tolerances against oracle.flat_search run 4 deeper than k, and at most 1% of the
 returned positions forgiven as near-ties (neighbouring fp64 scores closer than 1e-6 are 0.4-0.9% of the top 116 of 5000 unit-norm
 Gaussian rows at widths 769..3072; a plain fp32 product is within 1.1e-7 of fp64).
 """
@@ -185,6 +189,8 @@ def test_exact_ladder_over_a_large_corpus(rmu, tmp_path):
     launches = idx.last_geometry()["launches"]
     assert launches > 1
     print("forgiven / positions:", _check(s, r, q, x, 40, IP, block=32768))
+    from tests import exact_regimes as E
+    assert not E.mismatch(s, r, *E.expected_topk(E.chain(q, x, 1024), None, 40))      # ... and to the fmaf chain, bit for bit
     for ratio, first in ((8, 256), (3, 16384)):              # accepted, no effect
         idx.set_ladder(ratio, first)
         s2, r2 = idx.search(q, 40)
