@@ -681,6 +681,24 @@ int rmu_index_search_where(rmu_index_t* idx, rmu_columns_t* c, const float* q, i
                            const rmu_col_term* terms, int n_terms, const int32_t* codes, const int32_t* sel_ptr, int n_sel,
                            const int32_t* q_sel, float* out_scores, int64_t* out_rows, uint64_t hip_stream);
 
+/* GROUPED search: the best row of each of the k best groups (Milvus group_by_field; "one chunk per document").  `field` names one column
+ * of `c`, whose codes are the groups; the columns must be in step with the index.  For each query, take all live rows in the order
+ * rmu_index_search returns them -- score descending, then lower row id (RMU_METRIC_L2SQ: distance ascending, then lower row id) -- walk
+ * that order and keep a row if and only if no kept row has the same code in `field`; the first k kept rows are the answer, in that order.
+ * So every group is represented by its best row (the lowest id among bit-equal best scores) and the k best groups come out ordered by
+ * their representatives.  Every returned score has exactly the bits rmu_index_search gives that row.  Tombstoned rows never appear and
+ * never represent a group; a group whose rows are all removed is absent; with fewer than k live groups the remaining slots hold
+ * (-inf | +inf for L2SQ, -1).  Exact: a selection that knows the groups (scan_distinct.hip), not an over-fetch -- one group may own
+ * any number of the best rows.  An empty index, or one without a live row, gives all padding and launches no scan.
+ * flags: RMU_F_Q_DEVICE, RMU_F_OUT_DEVICE; row_base is added to the returned ids; all three metrics; any nq >= 1 (more than 8192 queries
+ * are sent in blocks).  RMU_E_INVALID with a message, before anything is enqueued: a null pointer, nq < 1, k outside
+ * [1, RMU_MAX_K_DISTINCT], `field` outside [0, n_fields), an unknown flag, an index of rows wider than RMU_MAX_DIM (a wide index is not
+ * served), columns and index holding different row counts (the message contains "out of step").  Lock order: the columns' lock, then the
+ * index's; the call always drains its stream.  Not built: k > 32, a filter beside the grouping, wide rows, more than one row per group. */
+#define RMU_MAX_K_DISTINCT 32
+int rmu_index_search_distinct(rmu_index_t* idx, rmu_columns_t* c, int field, const float* q, int64_t nq, int k, unsigned flags,
+                              int64_t row_base, float* out_scores, int64_t* out_rows, uint64_t hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

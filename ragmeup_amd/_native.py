@@ -29,6 +29,7 @@ STAT_CAPACITY, STAT_GROW_COUNT, STAT_GROW_MS, STAT_LIVE_ROWS = 1, 2, 3, 4
 STAT_COMPACT_COUNT, STAT_COMPACT_MS = 5, 6
 COMM_ID_BYTES = 128
 MAX_K = 112
+MAX_K_DISTINCT = 32      # largest k of the grouped search (rmu_index_search_distinct)
 MAX_QUERIES_PER_CALL = 8192   # rmu_index_search_groups takes one block of queries per call
 MAX_DIM = 768            # widest row of the register-resident scans
 MAX_DIM_WIDE = 3072      # widest row of an index (ip / cosine)
@@ -59,7 +60,7 @@ SYMBOLS = [
     "rmu_adjacent_cosine", "rmu_attribution", "rmu_bert_attribute",
     "rmu_passages_create", "rmu_passages_free", "rmu_passages_size", "rmu_passages_set", "rmu_passages_pairs", "rmu_rerank_select", "rmu_bert_rerank",
     "rmu_columns_create", "rmu_columns_free", "rmu_columns_size", "rmu_columns_append", "rmu_columns_compact", "rmu_columns_set_option",
-    "rmu_columns_select", "rmu_index_search_where",
+    "rmu_columns_select", "rmu_index_search_where", "rmu_index_search_distinct",
 ]
 
 
@@ -152,6 +153,10 @@ def _declare(lib):
     lib.rmu_columns_set_option.argtypes = [vp, i32, i64]
     lib.rmu_columns_select.argtypes = [vp, vp, i32, vp, vp, i32, u32, vp, i64, vp, u64]
     lib.rmu_index_search_where.argtypes = [vp, vp, vp, i64, i32, u32, i64, vp, i32, vp, vp, i32, vp, vp, vp, u64]
+    lib.rmu_index_search_distinct.argtypes = [vp, vp, i32, vp, i64, i32, u32, i64, vp, vp, u64]
+    # (probe hook, not in rmu.h: the fold's kernel time and part count of the thread's last grouped search under rmu_set_timing)
+    if hasattr(lib, "rmu_last_distinct_"):
+        lib.rmu_last_distinct_.argtypes = [c.POINTER(f32), c.POINTER(i32)]
     # (probe hook, not in rmu.h: kernel times of the thread's last selection under RMU_TUNING=1 RMU_COLUMNS_TIMING=1)
     if hasattr(lib, "rmu_columns_last_ms_"):
         lib.rmu_columns_last_ms_.argtypes = [c.POINTER(f32), c.POINTER(f32)]

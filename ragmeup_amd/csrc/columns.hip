@@ -589,3 +589,36 @@ extern "C" int rmu_index_search_where(rmu_index_t* idx, rmu_columns_t* c, const 
     if (rc) return drained(s, rc);
     return RMU_OK;
 }
+
+// Grouped search (include/rmu.h): the codes of `field` name each row's group.  Here: every limit that needs no device, the columns' shared
+// lock (held until the scan has drained: it reads the image), the image brought up to date; the scan, the fold and the finishing are
+// rmu_api.hip's (rmu_index_search_distinct_on_), under the index's shared lock -- the lock order above.
+extern "C" int rmu_index_search_distinct(rmu_index_t* idx, rmu_columns_t* c, int field, const float* q, int64_t nq, int k, unsigned flags,
+                                         int64_t row_base, float* out_scores, int64_t* out_rows, uint64_t hip_stream) {
+    RMU_ENTRY();
+    const std::string w("rmu_index_search_distinct");
+    if (!idx || !c || !q || !out_scores || !out_rows) return rmu_fail(RMU_E_INVALID, w + ": null pointer (idx, c, q, out_scores, out_rows)");
+    if (nq < 1) return rmu_fail(RMU_E_INVALID, w + ": nq must be >= 1");
+    if (k < 1 || k > RMU_MAX_K_DISTINCT) return rmu_fail(RMU_E_INVALID, w + ": k must be in [1, 32]");
+    if (flags & ~(RMU_F_Q_DEVICE | RMU_F_OUT_DEVICE)) return rmu_fail(RMU_E_INVALID, w + ": the flags are RMU_F_Q_DEVICE and RMU_F_OUT_DEVICE");
+    if (field < 0 || field >= c->n_fields)
+        return rmu_fail(RMU_E_INVALID, w + ": field " + std::to_string(field) + " is outside [0, " + std::to_string(c->n_fields) + ")");
+    int rc, dim = 0;
+    if ((rc = rmu_index_dim(idx, &dim))) return rc;
+    if (dim > RMU_MAX_DIM)
+        return rmu_fail(RMU_E_INVALID, w + ": the index holds rows wider than 768 dimensions (RMU_MAX_DIM): the grouped search does not serve a wide index");
+    hipStream_t s = nullptr;
+    if ((rc = rmu_thread_stream_((hipStream_t)hip_stream, &s))) return rc;
+    std::shared_lock<std::shared_mutex> lk(c->mu);
+    int64_t idx_rows = 0;
+    if ((rc = rmu_index_size(idx, &idx_rows))) return rc;
+    if (idx_rows != c->n)
+        return rmu_fail(RMU_E_INVALID, w + ": the columns (" + std::to_string(c->n) + " rows) and the index (" + std::to_string(idx_rows) + " rows) are out of step");
+    if ((rc = settle_image(c, lk, s))) return drained(s, rc);
+    if (idx_rows != c->n)          // (an append while the lock was given up for the upload)
+        return drained(s, rmu_fail(RMU_E_INVALID, w + ": the columns (" + std::to_string(c->n) + " rows) and the index (" + std::to_string(idx_rows) + " rows) are out of step"));
+    const int32_t* codes = c->n > 0 ? (const int32_t*)c->img.p + (int64_t)field * c->cap_rows : nullptr;
+    rc = rmu_index_search_distinct_on_(idx, codes, c->n, q, nq, k, flags, row_base, out_scores, out_rows, (hipStream_t)hip_stream);
+    if (rc) return drained(s, rc);
+    return RMU_OK;
+}

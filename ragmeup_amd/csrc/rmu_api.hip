@@ -84,6 +84,8 @@ struct Tls {
     }
     bool timing = false;
     float scan_ms = -1.f, search_ms = -1.f;
+    float fold_ms = -1.f;          // rmu_index_search_distinct under rmu_set_timing: k_distinct_fold's time, and the part lists it folded
+    int fold_parts = 0;
     int grid = 0, block = 0, lds = 0, passes = 0, screened = 0;
     // what rmu_last_scan_geometry reports: the geometry of the last scan enqueued, the launches of the whole call
     template <class Launch>          // (ScanLaunch, SubsetLaunch)
@@ -1832,6 +1834,79 @@ extern "C" int rmu_index_search_groups(rmu_index_t* idx, const float* q, int64_t
     RMU_HIP_TRY(hipStreamSynchronize(s));          // always: the table went through the thread's pinned buffer
     t.finished(s, true);
     if (t.timing && scan) t.scan_ms = elapsed_ms(t.ev[2], t.ev[3]);
+    return RMU_OK;
+}
+
+// Grouped top-k behind rmu_index_search_distinct (columns.hip; prototype in rmu_common.h): per block of queries the distinct scan
+// (scan_distinct.hip) fills [parts, nb, k] part lists, k_distinct_fold folds them into [nb, k] distinct keys behind them in the same
+// workspace, and rmu_index_search's own finishing (rmu_merge_final_launch over ONE list) writes scores, row ids + row_base, the L2
+// conversion and the padding.  The query preparation is rmu_index_search's (same padded, normalised, augmented queries: the scores have
+// the same bits).  The caller holds the columns' shared lock for the codes: every block is drained before this returns.
+int rmu_index_search_distinct_on_(rmu_index* idx, const int32_t* codes_dev, int64_t expect_rows, const float* q, int64_t nq, int k, unsigned flags,
+                                  int64_t row_base, float* out_scores, int64_t* out_rows, hipStream_t user_stream) {
+    const char* who = "rmu_index_search_distinct";
+    Tls& t = g_tls;
+    int rc = t.ensure_stream(user_stream);
+    if (rc) return rmu_fail(rc, std::string(who) + ": stream");
+    hipStream_t s = user_stream ? user_stream : t.stream;
+    const bool q_dev = flags & RMU_F_Q_DEVICE, out_dev = flags & RMU_F_OUT_DEVICE;
+
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    const int dpad = idx->dpad, dim = idx->dim;
+    const bool l2 = idx->metric == RMU_METRIC_L2SQ;
+    if (dpad > RMU_MAX_DIM)
+        return rmu_fail(RMU_E_INVALID, std::string(who) + ": the index holds rows wider than 768 dimensions (RMU_MAX_DIM): the grouped search does "
+                                                          "not serve a wide index");
+    if (idx->n != expect_rows)
+        return rmu_fail(RMU_E_INVALID, std::string(who) + ": the columns (" + std::to_string(expect_rows) + " rows) and the index (" +
+                                           std::to_string(idx->n) + " rows) are out of step");
+    if (idx->n >= 0xFFFFFFFFll) return rmu_fail(RMU_E_INVALID, std::string(who) + ": row ids must fit 32 bits");
+    const bool scan = idx->n > 0 && idx->n_live > 0 && codes_dev != nullptr;
+    t.scan_ms = -1.f; t.search_ms = -1.f; t.passes = 0; t.screened = 0; t.fold_ms = -1.f; t.fold_parts = 0;
+
+    for (int64_t q0 = 0; q0 < nq; q0 += kMaxQueriesPerLaunch) {
+        const int64_t nb = (nq - q0) < kMaxQueriesPerLaunch ? (nq - q0) : kMaxQueriesPerLaunch;
+        const float* qdev;
+        if ((rc = prepare_queries(idx, t, q + q0 * dim, nb, q_dev, s, &qdev, who))) return rc;
+        float* d_s = out_scores + q0 * k; int64_t* d_r = out_rows + q0 * k;
+        if ((rc = stage_outputs(t, nb, k, out_dev, &d_s, &d_r, who))) return rc;
+        const size_t list_keys = (size_t)nb * k;
+        const u64* folded;
+        if (scan) {
+            DistinctLaunch L{};
+            L.x = idx->x; L.n_rows = idx->n; L.dpad = dpad; L.codes = codes_dev; L.q = qdev; L.nq = (int)nb; L.k = k;
+            if ((rc = rmu_distinct_plan(&L))) return rmu_fail(rc, std::string(who) + ": no scan geometry for this (dim, k)");
+            if (t.partial.ensure(((size_t)L.parts + 1) * list_keys * sizeof(u64))) return rmu_fail(RMU_E_OOM, std::string(who) + ": partial workspace");
+            L.partial = (u64*)t.partial.p;
+            u64* out_keys = L.partial + (size_t)L.parts * list_keys;
+            if (t.timing) RMU_HIP_TRY(hipEventRecord(t.ev[2], s));        // rmu_set_timing: the scan between two events, the fold between two more
+            rc = rmu_distinct_launch(&L, s);
+            if (rc) return rmu_fail(rc, std::string(who) + ": scan launch: " + hipGetErrorString(hipGetLastError()));
+            if (t.timing) { RMU_HIP_TRY(hipEventRecord(t.ev[3], s)); RMU_HIP_TRY(hipEventRecord(t.ev[4], s)); }
+            if ((rc = rmu_distinct_fold_launch(L.partial, L.parts, nb, k, codes_dev, out_keys, s))) return rmu_fail(rc, std::string(who) + ": fold launch");
+            if (t.timing) RMU_HIP_TRY(hipEventRecord(t.ev[5], s));
+            t.note_geometry(L, 1);
+            t.fold_parts = L.parts;
+            folded = out_keys;
+        } else {               // nothing to scan: one all-empty list, every slot comes out (-inf | +inf, -1)
+            if (t.partial.ensure(list_keys * sizeof(u64))) return rmu_fail(RMU_E_OOM, std::string(who) + ": partial workspace");
+            RMU_HIP_TRY(hipMemsetAsync(t.partial.p, 0, list_keys * sizeof(u64), s));
+            folded = (const u64*)t.partial.p;
+        }
+        rc = rmu_merge_final_launch(folded, 1, nb, k, row_base, l2 ? 1 : 0, l2 ? (const float*)t.qn.p : nullptr, d_s, d_r, nullptr, nullptr, s);
+        if (rc) return rmu_fail(rc, std::string(who) + ": merge launch");
+        if ((rc = copy_outputs(out_scores, out_rows, q0, nb, k, out_dev, d_s, d_r, s))) return rc;
+        RMU_HIP_TRY(hipStreamSynchronize(s));          // always: the caller's lock on the codes ends with this call
+        t.finished(s, true);
+        if (t.timing && scan) { t.scan_ms = elapsed_ms(t.ev[2], t.ev[3]); t.fold_ms = elapsed_ms(t.ev[4], t.ev[5]); }
+    }
+    return RMU_OK;
+}
+// (probe hook, not in rmu.h; tools/distinct_probe.py) the calling thread's last grouped search under rmu_set_timing: the fold's kernel time
+// (< 0 = not taken) and the part lists it folded -- of the last block of queries
+extern "C" int rmu_last_distinct_(float* fold_ms, int* parts) {
+    if (fold_ms) *fold_ms = g_tls.fold_ms;
+    if (parts) *parts = g_tls.fold_parts;
     return RMU_OK;
 }
 

@@ -335,6 +335,28 @@ int rmu_groups_narrow_launch(const int64_t* rows, const GroupList* lists, int n_
 // position in the query's own list -> row id + row_base; q_off [nq]: where that list starts in ids
 int rmu_groups_map_launch(int64_t* out_rows, const u32* ids, const u32* q_off, int64_t total, int k, int64_t row_base, hipStream_t s);
 
+// ---- grouped top-k (rmu_index_search_distinct; scan_distinct.hip): the best row of each of the k best groups, contiguous rows ----------
+struct DistinctLaunch {
+    const float* x;        // [n_rows, dpad] fp32 row-major: the index's matrix
+    int64_t n_rows;
+    int dpad;
+    const int32_t* codes;  // [n_rows] device: the group of every row (one field of the columns' image)
+    const float* q;        // [nq, dpad] fp32 device, prepared like rmu_index_search's
+    int nq;
+    int k;                 // <= RMU_MAX_K_DISTINCT
+    u64* partial;          // [parts, nq, k] keys: every part list sorted, distinct inside, zeros last
+    // filled by rmu_distinct_plan
+    int wq, s_chunks, nqt, tiles_per_chunk, grid, parts, lds_bytes;
+};
+int rmu_distinct_plan(DistinctLaunch* p);
+int rmu_distinct_launch(const DistinctLaunch* p, hipStream_t s);
+// part lists [parts <= 1024, nq, k] -> out_keys [nq, k]: one distinct list per query, sorted, zero-padded (rmu_merge_final_launch with parts = 1 finishes it)
+int rmu_distinct_fold_launch(const u64* partial, int parts, int64_t nq, int k, const int32_t* codes, u64* out_keys, hipStream_t s);
+// rmu_api.hip, behind rmu_index_search_distinct (columns.hip, which holds the columns' shared lock and has settled their image): the scan, the
+// fold and rmu_index_search's finishing; RMU_E_INVALID ("out of step") unless the index holds expect_rows rows; always drains its stream
+int rmu_index_search_distinct_on_(rmu_index* idx, const int32_t* codes_dev, int64_t expect_rows, const float* q, int64_t nq, int k, unsigned flags,
+                                  int64_t row_base, float* out_scores, int64_t* out_rows, hipStream_t user_stream);
+
 // row moves of rmu_index_compact (rmu_compact.hip), one array of the index at a time: rows of row_bytes (a multiple of 256, or 4 for the
 // L2 norms); new row j in [first, n_live) comes from old row src_rows[j - first] (device list, strictly increasing, src_rows[i] >= first + i);
 // rows [0, first) stay where they are.

@@ -470,6 +470,42 @@ class FlatIndex:
             out_s[pick], out_r[pick] = s, r
         return out_s, out_r
 
+    def search_distinct(self, q, k: int, columns: "Columns", field: int, row_base: int = 0):
+        """Grouped exact top-k (rmu_index_search_distinct): the best row of each of the k best groups, a group being the rows that share
+        one code in column `field` of `columns` (which must hold as many rows as the index).  -> (scores, rows) [nq, k]: the rows `search`
+        would return, in its order, with every row dropped whose group an earlier row already represents; each score has the bits
+        `search` gives that row; fewer than k live groups: (-inf | +inf, -1) padding.  numpy in -> numpy out; torch CUDA in -> torch
+        CUDA out.  k <= N.MAX_K_DISTINCT.  ValueError on an index of more than 768 dimensions (N.MAX_DIM): a wide index is not served."""
+        if self.dim > N.MAX_DIM:
+            raise ValueError(f"search_distinct serves rows of at most {N.MAX_DIM} dimensions; this index holds {self.dim}-d rows "
+                             "(the grouped search of a wide index does not exist)")
+        k = int(k)
+        if _is_torch_cuda(q):
+            import torch
+            qq = q.detach().to(torch.float32).contiguous()
+            if qq.ndim == 1:
+                qq = qq[None]
+            if qq.shape[1] != self.dim:
+                raise ValueError(f"expected [nq, {self.dim}] got {tuple(qq.shape)}")
+            nq = qq.shape[0]
+            out_s = torch.empty((nq, k), dtype=torch.float32, device=qq.device)
+            out_r = torch.empty((nq, k), dtype=torch.int64, device=qq.device)
+            torch.cuda.current_stream().synchronize()
+            N.check(self._lib.rmu_index_search_distinct(self._h, columns._h, int(field), qq.data_ptr(), nq, k, N.F_Q_DEVICE | N.F_OUT_DEVICE,
+                                                        int(row_base), out_s.data_ptr(), out_r.data_ptr(), 0), "rmu_index_search_distinct")
+            return out_s, out_r
+        qq = np.ascontiguousarray(q, dtype=np.float32)
+        if qq.ndim == 1:
+            qq = qq[None]
+        if qq.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] got {qq.shape}")
+        nq = qq.shape[0]
+        out_s = np.empty((nq, k), dtype=np.float32)
+        out_r = np.empty((nq, k), dtype=np.int64)
+        N.check(self._lib.rmu_index_search_distinct(self._h, columns._h, int(field), qq.ctypes.data, nq, k, 0, int(row_base),
+                                                    out_s.ctypes.data, out_r.ctypes.data, 0), "rmu_index_search_distinct")
+        return out_s, out_r
+
     def set_screening(self, on: bool = True):
         """RMU_OPT_SCREEN: allow (default) or forbid the fp16 screening path; results are identical either way."""
         N.check(self._lib.rmu_index_set_option(self._h, N.OPT_SCREEN, 1 if on else 0), "rmu_index_set_option")

@@ -108,7 +108,7 @@ class MI355XRetriever(VectorStoreRetriever):
         each = {name: v for name, v in (("filters", filters), ("exprs", exprs)) if v is not None}
         if self.search_type == "mmr":
             return self.vectorstore.max_marginal_relevance_search_batch(queries, **self.search_kwargs, **each)
-        flt = {name: self.search_kwargs[name] for name in ("filter", "expr") if name in self.search_kwargs}
+        flt = {name: self.search_kwargs[name] for name in ("filter", "expr", "group_by") if name in self.search_kwargs}
         return [[d for d, _ in row] for row in self.vectorstore.similarity_search_with_score_batch(queries, k=k, **flt, **each)]
 
 
@@ -1014,6 +1014,43 @@ class MI355XVectorStore(VectorStore):
             return none
         return self._index.search(qvecs, kk, rows=rows)
 
+    # ---- group_by="<field>": one document per value of a device field (FlatIndex.search_distinct) --------------------------------------
+    _MAX_OUT_OF_STEP = 8      # an insert ran beside the search: follow it and search again, this often at most
+
+    def _check_group_by(self, group_by, k, *others):
+        """The limits of group_by= that need no search: ValueError with the reason."""
+        if any(o is not None for o in others):
+            raise ValueError("group_by= cannot be combined with expr= / filter= / exprs= / filters=: the grouped search over a subset of "
+                             "the rows (a gathered distinct scan) is not built")
+        if group_by not in self._device_fields or group_by in self._dev_demoted:
+            raise ValueError(f"group_by={group_by!r} must name one of the store's device fields that holds hashable values only: create "
+                             f"the store with device_fields=({group_by!r}, ...) (this store: device_fields={tuple(self._device_fields)})")
+        if int(k) > N.MAX_K_DISTINCT:
+            raise ValueError(f"group_by= serves k <= {N.MAX_K_DISTINCT}, got k={int(k)}")
+        if self._index is not None and getattr(self._index, "dim", 0) > N.MAX_DIM:
+            raise ValueError(f"group_by= serves embeddings of at most {N.MAX_DIM} dimensions; this store holds {self._index.dim}-d vectors")
+
+    def _search_grouped(self, qvecs: np.ndarray, k: int, group_by: str):
+        """_search_vecs for group_by=: the best row of each of the k best values of the field, inside the caller's consistent read.  Exact
+        on the device or an error: there is no host fallback.  Searches run without the writer lock and an insert appends to the index
+        before it appends the code rows, so the library may find the two out of step: the code rows are brought up (under the writer
+        lock, i.e. behind that insert) and the search is repeated, a bounded number of times."""
+        if self._pending:
+            self.flush()
+        self._check_group_by(group_by, k)
+        if self._index is None or len(self._index) == 0:
+            return np.full((qvecs.shape[0], 0), -np.inf, np.float32), np.full((qvecs.shape[0], 0), -1, np.int64)
+        kk = max(1, int(k))
+        for tries in range(self._MAX_OUT_OF_STEP + 1):
+            if self._columns is None or len(self._columns) != len(self._index):
+                with self._lock:
+                    self._columns_follow()
+            try:
+                return self._index.search_distinct(qvecs, kk, self._columns, self._device_fields[group_by])
+            except N.RmuError as e:
+                if e.code != N.RMU_E_INVALID or "out of step" not in str(e) or tries == self._MAX_OUT_OF_STEP:
+                    raise
+
     # ---- one condition per query (filters= / exprs= of the batch entry points) ---------------------------------------------------
     # the grouped call (FlatIndex.search_groups) answers two or more distinct lists in one scan.  profiles/groups_search.md measures it
     # against the per-list calls it replaces (1M x 384, k = 10, host lists): faster by more than the run-to-run spread for 2 .. 128 lists
@@ -1066,12 +1103,16 @@ class MI355XVectorStore(VectorStore):
         return s, r
 
     def similarity_search_with_score_by_vector(self, embedding, k: int = 4, filter: Optional[dict] = None, expr: Optional[str] = None,
-                                               **kw) -> list[tuple[Document, float]]:
+                                               group_by: Optional[str] = None, **kw) -> list[tuple[Document, float]]:
+        """group_by="<field>" (one of device_fields): at most one document per value of the field -- the best chunk of each of the k best
+        documents with group_by="source" -- in the order and with the scores the ungrouped search gives them (k <= 32)."""
         q = np.asarray(embedding, dtype=np.float32)[None]
         conds = conditions(expr, filter)
+        if group_by is not None:
+            self._check_group_by(group_by, k, expr, filter)
 
         def read():
-            s, r = self._search_vecs(q, k, conds)
+            s, r = self._search_vecs(q, k, conds) if group_by is None else self._search_grouped(q, k, group_by)
             return [(self._doc(int(row)), self._convert(float(sc))) for sc, row in zip(s[0], r[0]) if row >= 0]
         return consistent(read, self._seq)
 
@@ -1091,7 +1132,10 @@ class MI355XVectorStore(VectorStore):
         return rows[0], scores[0]
 
     def similarity_search_with_score(self, query: str, k: int = 4, filter: Optional[dict] = None, expr: Optional[str] = None,
-                                     **kw) -> list[tuple[Document, float]]:
+                                     group_by: Optional[str] = None, **kw) -> list[tuple[Document, float]]:
+        if group_by is not None:                     # (the fused call has no grouped form: embed, grouped search)
+            self._check_group_by(group_by, k, expr, filter)
+            return self.similarity_search_with_score_by_vector(self._embed_query(query), k, group_by=group_by, **kw)
         def read():
             hit = self._fused_query(query, int(k), int(k), None)
             if hit is None:
@@ -1107,21 +1151,33 @@ class MI355XVectorStore(VectorStore):
         return [d for d, _ in self.similarity_search_with_score(query, k, **kw)]
 
     def similarity_search_with_relevance_scores(self, query: str, k: int = 4, filter: Optional[dict] = None, expr: Optional[str] = None,
-                                                **kw) -> list[tuple[Document, float]]:
+                                                group_by: Optional[str] = None, **kw) -> list[tuple[Document, float]]:
         conds = conditions(expr, filter)
+        if group_by is not None:
+            self._check_group_by(group_by, k, expr, filter)
         q = self._embed_query(query)[None]
 
         def read():
-            s, r = self._search_vecs(q, k, conds)
+            s, r = self._search_vecs(q, k, conds) if group_by is None else self._search_grouped(q, k, group_by)
             return [(self._doc(int(row)), float(sc)) for sc, row in zip(s[0], r[0]) if row >= 0]
         return consistent(read, self._seq)
 
     def similarity_search_with_score_batch(self, queries: list[str], k: int = 4, filter: Optional[dict] = None,
                                            expr: Optional[str] = None, filters: Optional[list] = None, exprs: Optional[list] = None,
-                                           **kw) -> list[list[tuple[Document, float]]]:
+                                           group_by: Optional[str] = None, **kw) -> list[list[tuple[Document, float]]]:
         """`filter=` / `expr=`: one condition for the whole batch.  `filters=` / `exprs=`: a list with one entry per query (None =
-        unfiltered); queries with different conditions still share one scan (FlatIndex.search_groups)."""
+        unfiltered); queries with different conditions still share one scan (FlatIndex.search_groups).  `group_by=`: one document per
+        value of a device field for every query, one grouped scan for the batch (not together with a condition)."""
         queries = list(queries)
+        if group_by is not None:
+            self._check_group_by(group_by, k, expr, filter, exprs, filters)
+            qg = self._embed_docs(queries)
+
+            def read_grouped():
+                s, r = self._search_grouped(qg, k, group_by)
+                return [[(self._doc(int(row)), self._convert(float(sc))) for sc, row in zip(ss, rr) if row >= 0]
+                        for ss, rr in zip(s, r)]
+            return consistent(read_grouped, self._seq)
         each = conditions_per_query(len(queries), expr, filter, exprs, filters)
         conds = conditions(expr, filter)
         qv = self._embed_docs(queries)
@@ -1135,9 +1191,16 @@ class MI355XVectorStore(VectorStore):
     def max_marginal_relevance_search_by_vector(self, embedding, k: int = 4, fetch_k: int = 20,
                                                 lambda_mult: float = 0.5, filter: Optional[dict] = None, expr: Optional[str] = None,
                                                 **kw) -> list[Document]:
+        self._no_group_by(kw)
         q = np.asarray(embedding, dtype=np.float32)
         conds = conditions(expr, filter)
         return consistent(lambda: self._mmr_by_vector(q, k, fetch_k, lambda_mult, conds), self._seq)
+
+    @staticmethod
+    def _no_group_by(kw: dict):
+        if kw.get("group_by") is not None:
+            raise ValueError("group_by= is served by the similarity searches only: MMR picks among the fetch_k best ROWS, a grouped "
+                             "candidate pool is not built")
 
     def _mmr_by_vector(self, q: np.ndarray, k: int, fetch_k: int, lambda_mult: float, conds=None) -> list[Document]:
         if self._pending:
@@ -1163,6 +1226,8 @@ class MI355XVectorStore(VectorStore):
 
     def max_marginal_relevance_search(self, query: str, k: int = 4, fetch_k: int = 20, lambda_mult: float = 0.5,
                                       filter: Optional[dict] = None, expr: Optional[str] = None, **kw) -> list[Document]:
+        self._no_group_by(kw)
+
         def read():
             hit = self._fused_query(query, int(fetch_k), int(k), float(lambda_mult))     # the reference's per-request call (RAGHelper.py:497-499)
             return None if hit is None else [self._doc(int(x)) for x in hit[0] if x >= 0]
@@ -1177,6 +1242,7 @@ class MI355XVectorStore(VectorStore):
         """One dense search + ONE device-side MMR selection for the whole batch (`rmu_index_mmr`: fp64, same greedy rule and
         tie order as the single-query path; no per-query vector re-fetch).  fetch_k > 64 falls back to the host loop.
         `filters=` / `exprs=`: one condition per query (None = unfiltered), as similarity_search_with_score_batch takes them."""
+        self._no_group_by(kw)
         queries = list(queries)
         each = conditions_per_query(len(queries), expr, filter, exprs, filters)
         conds = conditions(expr, filter)
