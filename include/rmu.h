@@ -283,16 +283,23 @@ int rmu_set_timing(int on);
  * launches on a stream of its own and returns the mean of the last half of them.  Thread-safe; allocates and frees its own buffers. */
 int rmu_probe_mfma_rate(int dtype, int variant, int millis, double* tflops_out);
 
-/* ---- BERT-6x384 encoder (bi-encoder and cross-encoder forwards) -------------------------------
+/* ---- BERT encoder (bi-encoder and cross-encoder forwards) -------------------------------------
  * Serves: HuggingFaceEmbeddings.embed_documents / embed_query (RAGHelper_local.py:107-117 via
  * RAGHelper.py:423-434) and HuggingFaceCrossEncoder.score (RAGHelper.py:483-486 ->
- * ScoredCrossEncoderReranker.py:42). */
+ * ScoredCrossEncoderReranker.py:42).
+ * Two geometries are built (post-LayerNorm BERT, GELU(erf), absolute positions, 1 <= layers <= 48, max_pos <= 512):
+ *   TUNED    hidden 384, 12 heads of 32, ffn 1536 (the MiniLM / bge-small family): its own kernels, every entry point below;
+ *   GENERAL  64-wide heads: hidden = 64 * heads with 2 <= heads <= 16 (128 .. 1024: bert-tiny .. bert-base / bge-base 768/12/3072 ..
+ *            bert-large / bge-large 1024/16/4096), ffn a multiple of 64 in [64, 4096] (csrc/bert_any.hip).  Served by rmu_bert_encode
+ *            in all four modes; rmu_bert_encode_host, rmu_bert_search_mmr, rmu_bert_search_hybrid, rmu_bert_attribute and
+ *            rmu_bert_rerank need the tuned geometry and return RMU_E_INVALID for such a model (before any device work).
+ * Anything else -- another head width, hidden above 1024, ffn above 4096 -- is refused by rmu_bert_create. */
 typedef struct rmu_bert_cfg {
     int vocab_size;   /* 30522 */
-    int hidden;       /* 384 (must be 384 in this build) */
-    int layers;       /* 6 */
-    int heads;        /* 12 (head_dim 32) */
-    int ffn;          /* 1536 */
+    int hidden;       /* 384, or 64 * heads (128 .. 1024) */
+    int layers;       /* 6 (1 .. 48) */
+    int heads;        /* 12 at hidden 384 (head_dim 32); 2 .. 16 otherwise (head_dim 64) */
+    int ffn;          /* 1536 at hidden 384; a multiple of 64 up to 4096 otherwise */
     int max_pos;      /* 512 */
     int type_vocab;   /* 2 */
     float ln_eps;     /* 1e-12 */
@@ -321,6 +328,9 @@ int rmu_bert_free(rmu_bert_t* m);
  * max_len <= 256: the small-batch GEMMs; <= 16384: the GEMM pair; above: the fused FFN kernel) -- a sequence's result is bit-identical across
  * calls that take the same kernels and equal up to bf16 rounding noise (|d| < 2e-3 on unit vectors, cosine > 0.9999)
  * otherwise: a query embedded alone reproduces the vector its text got at indexing time to that noise, not bit for bit.
+ * A GENERAL model has ONE set of kernels for every call size: a sequence's result is bit-identical whatever else is in the call.  Its
+ * workspace is that of one group of whole sequences of at most 16384 packed tokens (a call is walked group by group), whatever the call size.
+ * out_stride >= hidden.
  * hip_stream != 0: the forward is left in flight on that stream (inputs and out_dev must stay valid until it has run); the model's next
  * call on any OTHER stream -- stream 0 and the host-path entry points included -- is ordered behind it on the device (one workspace per
  * model), so a caller may queue the next block's forward while this one runs. */
@@ -333,7 +343,8 @@ int rmu_bert_encode(rmu_bert_t* m, const int32_t* ids, const int32_t* type_ids, 
  * /chat call, RAGHelper.py:497-499; ScoredCrossEncoderReranker.py:42).  The library replays one captured hipGraph per input shape
  * (H2D, ~45 launches, D2H: one graph launch, one synchronisation) and keeps the 64 most recently used shapes: callers should bucket
  * batch and max_len (a padded sequence has lens = 0 and costs nothing).
- * ids / type_ids (may be NULL) [batch, max_len], lens [batch]: host int32; out_host as out_dev above, on the host. */
+ * ids / type_ids (may be NULL) [batch, max_len], lens [batch]: host int32; out_host as out_dev above, on the host.
+ * Tuned geometry only (a general model: RMU_E_INVALID, use rmu_bert_encode). */
 int rmu_bert_encode_host(rmu_bert_t* m, const int32_t* ids, const int32_t* type_ids, const int32_t* lens,
                          int batch, int max_len, int mode, float* out_host, int64_t out_stride);
 
@@ -343,7 +354,8 @@ int rmu_bert_encode_host(rmu_bert_t* m, const int32_t* ids, const int32_t* type_
  * + row_base in pick order, -1 past the number of candidates) and out_scores [batch, k] fp32 (the search score of each pick; may be
  * NULL) out.  The pooled query vectors stay on the device between the forward and the search (out_vecs, if not NULL, receives
  * them: [batch, 384] fp32).  lambda_mult < 0: no selection -- the top-k in score order (k <= fetch_k), i.e. rmu_index_search.
- * fetch_k <= 64, k <= fetch_k; the index must hold 384-d rows.  Results equal rmu_bert_encode_host + rmu_index_search_mmr. */
+ * fetch_k <= 64, k <= fetch_k; the index must hold 384-d rows.  Results equal rmu_bert_encode_host + rmu_index_search_mmr.
+ * Tuned geometry only (a general model: RMU_E_INVALID, use rmu_bert_encode + rmu_index_search_mmr). */
 int rmu_bert_search_mmr(rmu_bert_t* m, rmu_index_t* idx, const int32_t* ids, const int32_t* type_ids, const int32_t* lens, int batch,
                         int max_len, int mode, int fetch_k, int k, double lambda_mult, int64_t row_base, int64_t* out_rows,
                         float* out_scores, float* out_vecs);

@@ -1,4 +1,9 @@
-"""BertEncoder -- Python handle on the hand-written BERT-6x384 forward in librmu.so (rmu_bert_*).
+"""BertEncoder -- Python handle on the hand-written BERT forwards in librmu.so (rmu_bert_*).
+
+Two sets of kernels sit behind one handle.  hidden/heads/ffn = 384/12/1536 (the MiniLM / bge-small family) runs the tuned encoder and
+every one-call route built on it (`fused` is True).  Every other BERT with 64-wide heads -- hidden = 64 * heads, 2 <= heads <= 16
+(bert-tiny ... bert-base 768/12 ... bert-large 1024/16), ffn a multiple of 64 up to 4096 -- runs the general forward: `encode_ids` in all
+four modes, nothing else (`fused` is False, `host_shape` answers None, the callers take their unfused routes).
 
 Serves the two transformer forwards on the reference's hot path:
   * sentence-transformers bi-encoder: BertModel -> Pooling (masked mean | CLS token) -> [Normalize]   (MODE_MEAN / MODE_CLS)
@@ -60,7 +65,8 @@ def _strip(state: Mapping) -> dict:
 class BertEncoder:
     """weights: mapping HF-name -> array/tensor (fp32).  Use `from_pretrained_dir` for a checkpoint directory."""
 
-    HIDDEN = 384
+    HIDDEN = 384                # the tuned geometry's width; an instance carries its own (`self.HIDDEN = self.hidden`)
+    TUNED = (384, 12, 1536)     # hidden / heads / ffn of the tuned kernels and of every fused one-call route
 
     def __init__(self, weights: Mapping, layers: int = 6, heads: int = 12, ffn: int = 1536, ln_eps: float = 1e-12,
                  has_head: bool | None = None, device: int = 0):
@@ -82,6 +88,8 @@ class BertEncoder:
         tens = [torch.as_tensor(np.asarray(w[n], dtype=np.float32) if not torch.is_tensor(w[n]) else w[n])
                 .to(self.device, torch.float32).contiguous() for n in names]
         hid = tens[0].shape[1]
+        self.hidden = self.HIDDEN = int(hid)
+        self.heads, self.ffn, self.layers = int(heads), int(ffn), int(layers)
         cfg = BertCfg(int(tens[0].shape[0]), int(hid), int(layers), int(heads), int(ffn), int(tens[1].shape[0]),
                       int(tens[2].shape[0]), float(ln_eps), int(self.has_head))
         ptrs = (ctypes.c_void_p * len(tens))(*[t.data_ptr() for t in tens])
@@ -140,10 +148,19 @@ class BertEncoder:
                 return v
         return n
 
+    @property
+    def fused(self) -> bool:
+        """True for the tuned 384/12/1536 geometry: the host entry points (encode_host, search_host, attribute_host, rmu_bert_rerank,
+        the hybrid call) exist for it alone; every other geometry is served by `encode_ids`."""
+        return (self.hidden, self.heads, self.ffn) == self.TUNED
+
     def host_shape(self, batch: int, max_len: int, mode: int) -> tuple[int, int] | None:
         """The bucketed (batch, max_len) a host call of this shape runs at -- the library keeps one captured graph per SHAPE, so
         shapes are rounded up to a few sizes (a padded sequence has length 0: the packed-token kernels spend nothing on it, the
-        results are those of the unpadded call bit for bit) -- or None when the call does not fit the host entry points."""
+        results are those of the unpadded call bit for bit) -- or None when the call does not fit the host entry points, or the model
+        is not the fused geometry (no host entry point serves it)."""
+        if not getattr(self, "fused", True):
+            return None
         kind = mode & 0xff
         lb = min(-(-max(int(max_len), 1) // 32) * 32, self.max_pos) if max_len > 16 else 16
         if kind == MODE_TOKENS:                            # packed token states: the row count is the token count, no padding rows
@@ -194,7 +211,10 @@ class BertEncoder:
                     want_vectors: bool = False):
         """rmu_bert_search_mmr: the query's token ids in, result rows out -- forward (graph replay), dense top-fetch_k and the greedy
         MMR selection (lambda_mult None: no selection, the top-k in score order) in ONE library call with ONE synchronisation; the
-        query vector never visits the host.  -> rows [B, k] int64, scores [B, k] fp32 (, vectors [B, 384] fp32)."""
+        query vector never visits the host.  -> rows [B, k] int64, scores [B, k] fp32 (, vectors [B, 384] fp32).  Fused geometry only."""
+        if not self.fused:
+            raise ValueError(f"search_host needs the fused 384/12/1536 encoder; this model is {self.hidden}/{self.heads}/{self.ffn}: "
+                             "embed with encode_ids and search the index")
         pi, pl, pt, B, bb, lb = self._host_arrays(ids, lens, None, mode)
         rows = np.empty((bb, int(k)), dtype=np.int64)
         scores = np.empty((bb, int(k)), dtype=np.float32)
@@ -208,7 +228,10 @@ class BertEncoder:
         """rmu_bert_attribute: the token ids of the answers, queries and contexts of one or more requests in, the similarity provenance of
         every context out -- forward (graph replay) and the attribution kernel behind it in ONE library call with ONE synchronisation.
         groups [g, 4] int32 (answer_row, query_row or -1, first_doc_row, n_docs) names rows of `ids`.
-        -> scores [sum n_docs] fp64, sims [sum n_docs, 2] fp64 (, vectors [B, 384] fp32)."""
+        -> scores [sum n_docs] fp64, sims [sum n_docs, 2] fp64 (, vectors [B, 384] fp32).  Fused geometry only."""
+        if not self.fused:
+            raise ValueError(f"attribute_host needs the fused 384/12/1536 encoder; this model is {self.hidden}/{self.heads}/{self.ffn}: "
+                             "embed with encode_ids and attribute the vectors")
         pi, pl, pt, B, bb, lb = self._host_arrays(ids, lens, None, mode)
         g = np.ascontiguousarray(np.asarray(groups, dtype=np.int32)).reshape(-1, 4)
         if len(g) and (int(g[:, (0, 2)].max()) >= B or int(g[:, 1].max()) >= B or int((g[:, 2] + np.maximum(g[:, 3], 0)).max()) > B):
@@ -223,8 +246,8 @@ class BertEncoder:
         return (scores, sims, vecs[:B]) if want_vectors else (scores, sims)
 
     def encode_ids(self, ids, lens, type_ids=None, mode: int = 0, out=None, stream=None):
-        """ids [B, L] int (numpy or torch, padded), lens [B].  mode = MODE_MEAN / MODE_CLS (| NO_NORMALIZE) -> [B, 384] fp32
-        (torch CUDA); MODE_CE -> [B] fp32 logits; MODE_TOKENS -> [sum(min(lens, L)), 384] fp32, sequences packed in batch order.
+        """ids [B, L] int (numpy or torch, padded), lens [B].  mode = MODE_MEAN / MODE_CLS (| NO_NORMALIZE) -> [B, hidden] fp32
+        (torch CUDA); MODE_CE -> [B] fp32 logits; MODE_TOKENS -> [sum(min(lens, L)), hidden] fp32, sequences packed in batch order.
         `out` may be a pre-allocated CUDA tensor (e.g. a slice of a corpus matrix).
         `stream` (a torch.cuda.Stream; inputs must be int32 CUDA tensors that are complete, `out` given): the forward is ENQUEUED on that
         stream and the call returns with it in flight -- the caller synchronises (or records an event) before reading `out` or reusing the

@@ -12,6 +12,11 @@ The reference names its models by hub id and lets the third-party loaders interp
 Here the same files of a LOCAL directory decide the same things; anything this build cannot run raises instead of
 being embedded silently wrong (e.g. the reference's template default `avsolatorio/GIST-small-Embedding-v0`,
 server/.env.template:3, is a 12-layer CLS-pooling model: CLS pooling is served, mean is not assumed).
+
+Geometries that are built (`read_arch`): hidden/heads/ffn = 384/12/1536 (the tuned encoder with its one-call routes), and every BERT
+with 64-wide heads -- hidden = 64 * heads, 2 <= heads <= 16, ffn a multiple of 64 up to 4096: bert-tiny ... bert-base / bge-base / e5-base
+768/12/3072 ... bert-large / bge-large / e5-large 1024/16/4096 (the general forward).  A directory whose config.json and stored tensors
+disagree about the geometry is refused as inconsistent (`_check_shapes`).
 """
 from __future__ import annotations
 
@@ -63,6 +68,45 @@ class CheckpointSpec:
     config: dict = field(default_factory=dict, repr=False)   # the raw config.json (head-specific readers look things up in it)
 
 
+def general_geometry(hidden: int, heads: int, ffn: int) -> bool:
+    """What the general forward (csrc/bert_any.hip) runs: heads of width 64, hidden 128..1024, ffn a multiple of 64 up to 4096."""
+    return 2 <= heads <= 16 and hidden == 64 * heads and 64 <= ffn <= 4096 and ffn % 64 == 0
+
+
+_SHAPE_KEYS = ("embeddings.word_embeddings.weight", "encoder.layer.0.intermediate.dense.weight")
+
+
+def _stored_geometry(shapes: dict) -> Optional[tuple]:
+    """(hidden, ffn) of the stored tensors, from a name -> shape mapping (any of the usual prefixes), or None when the two tensors that
+    tell are not there (the loader then reports what is missing)."""
+    found = {}
+    for name, shape in shapes.items():
+        for key in _SHAPE_KEYS:
+            if name == key or name.endswith("." + key):
+                found[key] = tuple(int(v) for v in shape)
+    if len(found) != 2 or any(len(v) != 2 for v in found.values()):
+        return None
+    return found[_SHAPE_KEYS[0]][1], found[_SHAPE_KEYS[1]][0]
+
+
+def _check_shapes(arch: BertArch, shapes: dict) -> None:
+    """config.json against the stored tensors: a directory that declares one geometry and holds another is inconsistent."""
+    got = _stored_geometry(shapes)
+    if got is not None and got != (arch.hidden, arch.ffn):
+        raise UnsupportedCheckpoint(f"config.json declares hidden/heads/ffn = {arch.hidden}/{arch.heads}/{arch.ffn} but the stored tensors are "
+                                    f"those of {got[0]}/{arch.heads}/{got[1]}")
+
+
+def _safetensors_shapes(path: str) -> dict:
+    """name -> shape from a .safetensors header (8-byte little-endian length + JSON): no tensor data is read."""
+    with open(path, "rb") as f:
+        n = int.from_bytes(f.read(8), "little")
+        if not 0 < n <= 100 << 20:
+            return {}
+        head = json.loads(f.read(n).decode("utf-8"))
+    return {k: v["shape"] for k, v in head.items() if k != "__metadata__" and isinstance(v, dict) and "shape" in v}
+
+
 def read_arch(cfg: dict) -> BertArch:
     mt = cfg.get("model_type", "bert")
     if mt != "bert":
@@ -77,8 +121,11 @@ def read_arch(cfg: dict) -> BertArch:
                  ffn=int(cfg["intermediate_size"]), max_pos=int(cfg.get("max_position_embeddings", 512)),
                  type_vocab=int(cfg.get("type_vocab_size", 2)), vocab_size=int(cfg["vocab_size"]),
                  ln_eps=float(cfg.get("layer_norm_eps", 1e-12)))
-    if (a.hidden, a.heads, a.ffn) != (384, 12, 1536):
-        raise UnsupportedCheckpoint(f"hidden/heads/ffn = {a.hidden}/{a.heads}/{a.ffn}: this build's kernels are specialised for 384/12/1536")
+    if (a.hidden, a.heads, a.ffn) != (384, 12, 1536) and not general_geometry(a.hidden, a.heads, a.ffn):
+        raise UnsupportedCheckpoint(f"hidden/heads/ffn = {a.hidden}/{a.heads}/{a.ffn}: this build has tuned kernels for 384/12/1536 and a general "
+                                    "forward for 64-wide heads (hidden = 64 * heads, 2 <= heads <= 16, ffn a multiple of 64 up to 4096)")
+    if not 1 <= a.layers <= 48:
+        raise UnsupportedCheckpoint(f"num_hidden_layers={a.layers}: must be in [1, 48]")
     if not 1 <= a.max_pos <= 512:
         raise UnsupportedCheckpoint(f"max_position_embeddings={a.max_pos}: must be in [1, 512]")
     if "id2label" in cfg:
@@ -101,6 +148,8 @@ def _common(path: str) -> CheckpointSpec:
             break
     if spec.weights_file is None:
         raise FileNotFoundError(f"{path}: neither model.safetensors nor pytorch_model.bin")
+    if spec.weights_file.endswith(".safetensors"):       # (a .bin is checked once it is loaded: load_state)
+        _check_shapes(spec.arch, _safetensors_shapes(spec.weights_file))
     vocab = os.path.join(path, "vocab.txt")
     spec.vocab_file = vocab if os.path.exists(vocab) else None
     tcfg = _load(os.path.join(path, "tokenizer_config.json")) or {}
@@ -181,4 +230,6 @@ def load_state(spec: CheckpointSpec) -> dict:
         return load_file(spec.weights_file)
     import torch
     # weights_only: a checkpoint directory is data, never code (torch < 2.6 unpickles arbitrary objects otherwise)
-    return torch.load(spec.weights_file, map_location="cpu", weights_only=True)
+    state = torch.load(spec.weights_file, map_location="cpu", weights_only=True)
+    _check_shapes(spec.arch, {k: tuple(v.shape) for k, v in state.items() if hasattr(v, "shape")})
+    return state

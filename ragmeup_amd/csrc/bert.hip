@@ -36,6 +36,7 @@
 #include "../../include/rmu.h"
 #include "bert_plan.h"
 #include "rmu_internal.h"
+#include "bert_any.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -2924,6 +2925,9 @@ struct rmu_bert {
     hipEvent_t tail_ev = nullptr;
     hipStream_t tail_stream = nullptr;
     bool tail_set = false;
+    // a geometry other than 384/12/1536 (head width 64: bert_any.hip): the general forward's context.  Such a model holds none of the tuned
+    // path's weights or workspaces and is served by rmu_bert_encode only.
+    rmu_any_bert* any = nullptr;
 };
 static constexpr size_t MAX_CLONES = 3;
 // the host path's staging (HOST_TOKENS, HOST_ROWS: bert_plan.h): ids | type ids | lens; results: HOST_ROWS rows of 384 floats or one logit per sequence
@@ -2980,6 +2984,7 @@ extern "C" int rmu_bert_free(rmu_bert_t* m) {
     if (m->d_out) (void)hipFree(m->d_out);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     if (m->tail_ev) (void)hipEventDestroy(m->tail_ev);
+    rmu_any_free_(m->any);
     delete m;
     return RMU_OK;
 }
@@ -3008,8 +3013,10 @@ static int mark_tail(rmu_bert* m, hipStream_t s) {
 extern "C" int rmu_bert_create(rmu_bert_t** out, const rmu_bert_cfg* cfg, const void* const* wptr, int n_weights) {
     RMU_ENTRY();
     if (!out || !cfg || !wptr) return rmu_fail(RMU_E_INVALID, "rmu_bert_create: null argument");
-    if (cfg->hidden != H || cfg->heads != NH || cfg->ffn != FF || cfg->layers < 1 || cfg->layers > 48)
-        return rmu_fail(RMU_E_INVALID, "rmu_bert_create: this build supports hidden 384, 12 heads, ffn 1536");
+    const bool tuned = cfg->hidden == H && cfg->heads == NH && cfg->ffn == FF;
+    if ((!tuned && !rmu_any_geometry_(cfg)) || cfg->layers < 1 || cfg->layers > 48)
+        return rmu_fail(RMU_E_INVALID, "rmu_bert_create: this build supports hidden 384, 12 heads, ffn 1536 (the tuned kernels) and 64-wide heads: "
+                                       "hidden = 64 * heads with 2 <= heads <= 16, ffn a multiple of 64 up to 4096; 1 <= layers <= 48");
     if (cfg->max_pos < 1 || cfg->max_pos > 512 || cfg->vocab_size < 1 || cfg->type_vocab < 1)
         return rmu_fail(RMU_E_INVALID, "rmu_bert_create: max_pos must be in [1, 512]");
     const int need = 5 + 16 * cfg->layers + (cfg->has_head ? 4 : 0);
@@ -3023,6 +3030,15 @@ extern "C" int rmu_bert_create(rmu_bert_t** out, const rmu_bert_cfg* cfg, const 
     hipStream_t s = m->stream;
     int rc = RMU_OK;
     int wi = 0;
+    if (!tuned) {                                // the general forward converts and keeps its own operands (bert_any.hip)
+        rc = rmu_any_create_(&m->any, cfg, wptr, s);
+        if (rc || hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+            rmu_bert_free(m);
+            return rmu_fail(rc ? rc : RMU_E_HIP, "rmu_bert_create: weight upload failed");
+        }
+        *out = m;
+        return RMU_OK;
+    }
     rc |= copy_f32(m, &m->wemb, wptr[wi++], (size_t)cfg->vocab_size * H, 1.f, s);
     rc |= copy_f32(m, &m->pemb, wptr[wi++], (size_t)cfg->max_pos * H, 1.f, s);
     rc |= copy_f32(m, &m->temb, wptr[wi++], (size_t)cfg->type_vocab * H, 1.f, s);
@@ -3345,6 +3361,14 @@ static void launch_qkv_attn_small(hipStream_t s, int batch, const bf16* A, const
     hipLaunchKernelGGL((k_qkv_attn_small<KT, LNA>), dim3((unsigned)(batch * NH)), dim3(256), C::LDS_BYTES, s, A, W, bias, cu, batch, lng, lnb, eps, stats_out, ctx);
 }
 
+// The host-path and one-call entry points stage and copy in terms of the tuned width: a general model (rmu_bert::any) is refused there -- behind
+// the argument checks that do not look at the handle, before any HIP call -- and pointed at the entry point that serves it.
+static int tuned_only(const rmu_bert_t* m, const char* who) {
+    if (!m || !m->any) return RMU_OK;
+    return rmu_fail(RMU_E_INVALID, std::string(who) + ": this model's geometry is served by rmu_bert_encode only (the host-path and one-call forms need the "
+                                   "384/12/1536 encoder)");
+}
+
 static int check_encode_args(rmu_bert_t* m, const void* ids, const void* lens, const void* out, int batch, int max_len, int mode, int64_t out_stride) {
     if (!m || !ids || !lens || !out) return rmu_fail(RMU_E_INVALID, "rmu_bert_encode: null argument");
     if (batch < 1 || batch > 65535 || max_len < 1 || max_len > m->cfg.max_pos)
@@ -3353,7 +3377,7 @@ static int check_encode_args(rmu_bert_t* m, const void* ids, const void* lens, c
     if ((mode & ~(0xff | RMU_BERT_NO_NORMALIZE)) || kind > RMU_BERT_TOKENS)
         return rmu_fail(RMU_E_INVALID, "rmu_bert_encode: mode must be RMU_BERT_POOL_MEAN / CE_LOGIT / POOL_CLS / TOKENS (| RMU_BERT_NO_NORMALIZE)");
     if (kind == RMU_BERT_CE_LOGIT && !m->cfg.has_head) return rmu_fail(RMU_E_INVALID, "rmu_bert_encode: model has no classification head");
-    if (kind != RMU_BERT_CE_LOGIT && out_stride < H) return rmu_fail(RMU_E_INVALID, "rmu_bert_encode: out_stride < hidden");
+    if (kind != RMU_BERT_CE_LOGIT && out_stride < m->cfg.hidden) return rmu_fail(RMU_E_INVALID, "rmu_bert_encode: out_stride < hidden");
     return RMU_OK;
 }
 
@@ -3514,11 +3538,17 @@ extern "C" int rmu_bert_encode(rmu_bert_t* m, const int32_t* ids, const int32_t*
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(m->mu);
     (void)hipGetLastError();                     // (an error some earlier call of this thread left behind -- the caller's framework polls events -- is not this call's)
-    rc = ensure_ws(m, (int64_t)batch * max_len, batch);
+    if (m->any) {
+        if (rmu_any_ws_grows_(m->any, batch, max_len)) quiesce(m);       // (the forward a caller's stream still runs owns the buffers about to go)
+        rc = rmu_any_ensure_ws_(m->any, batch, max_len);
+    } else {
+        rc = ensure_ws(m, (int64_t)batch * max_len, batch);
+    }
     if (rc) return rmu_fail(rc, "rmu_bert_encode: workspace");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m->stream;
     if ((rc = order_behind_tail(m, s))) return rmu_fail(rc, "rmu_bert_encode: ordering behind the forward in flight");
-    enqueue_forward(m, ids, type_ids, lens, batch, max_len, mode, out_dev, out_stride, s);
+    if (m->any) rmu_any_enqueue_forward_(m->any, ids, type_ids, lens, batch, max_len, mode, out_dev, out_stride, s);
+    else enqueue_forward(m, ids, type_ids, lens, batch, max_len, mode, out_dev, out_stride, s);
     RMU_HIP_TRY(hipGetLastError());
     if (!hip_stream) {
         RMU_HIP_TRY(hipStreamSynchronize(s));
@@ -3662,6 +3692,7 @@ extern "C" int rmu_bert_encode_host(rmu_bert_t* m, const int32_t* ids, const int
     RMU_ENTRY();
     int rc = check_encode_args(m, ids, lens, out_host, batch, max_len, mode, out_stride);
     if (rc) return rc;
+    if (tuned_only(m, "rmu_bert_encode_host")) return RMU_E_INVALID;
     const int kind = mode & 0xff;
     std::unique_lock<std::mutex> lk;
     m = acquire_ctx(m, lk);
@@ -3690,6 +3721,7 @@ extern "C" int rmu_bert_search_mmr(rmu_bert_t* m, rmu_index_t* idx, const int32_
     if (!idx || !out_rows) return rmu_fail(RMU_E_INVALID, "rmu_bert_search_mmr: null argument");
     int rc = check_encode_args(m, ids, lens, out_rows, batch, max_len, mode, H);
     if (rc) return rc;
+    if (tuned_only(m, "rmu_bert_search_mmr")) return RMU_E_INVALID;
     const int kind = mode & 0xff;
     if (kind != RMU_BERT_POOL_MEAN && kind != RMU_BERT_POOL_CLS) return rmu_fail(RMU_E_INVALID, "rmu_bert_search_mmr: mode must be a pooling mode");
     std::unique_lock<std::mutex> lk;
@@ -3718,6 +3750,7 @@ extern "C" int rmu_bert_attribute(rmu_bert_t* m, const int32_t* ids, const int32
     int rc = rmu_attribution_check_("rmu_bert_attribute", batch, H, groups, n_groups, out_scores, &total);
     if (rc) return rc;
     if (!m) return rmu_fail(RMU_E_INVALID, "rmu_bert_attribute: null argument");
+    if (tuned_only(m, "rmu_bert_attribute")) return RMU_E_INVALID;
     rc = check_encode_args(m, ids, lens, out_scores, batch, max_len, mode, H);
     if (rc) return rc;
     std::unique_lock<std::mutex> lk;
@@ -3746,6 +3779,7 @@ extern "C" int rmu_bert_search_hybrid(rmu_bert_t* m, rmu_hybrid_t* h, const int3
     if (!h || !out_scores) return rmu_fail(RMU_E_INVALID, "rmu_bert_search_hybrid: null argument");
     int rc = check_encode_args(m, ids, lens, out_scores, batch, max_len, mode, H);
     if (rc) return rc;
+    if (tuned_only(m, "rmu_bert_search_hybrid")) return RMU_E_INVALID;
     const int kind = mode & 0xff;
     if (kind != RMU_BERT_POOL_MEAN && kind != RMU_BERT_POOL_CLS) return rmu_fail(RMU_E_INVALID, "rmu_bert_search_hybrid: mode must be a pooling mode");
     rmu_index_t* idx = nullptr;
@@ -3781,6 +3815,7 @@ extern "C" int rmu_bert_rerank(rmu_bert_t* m, rmu_passages_t* p, const int32_t* 
     int rc = rmu_rerank_check_(p, q_tokens, q_lens, nq, q_stride, keys, m_cand, batch_pad, max_len, top_n, out_pos, out_scores, nullptr);
     if (rc) return rc;
     if (!m) return rmu_fail(RMU_E_INVALID, "rmu_bert_rerank: null pointer");
+    if (tuned_only(m, "rmu_bert_rerank")) return RMU_E_INVALID;
     if (!m->cfg.has_head) return rmu_fail(RMU_E_INVALID, "rmu_bert_rerank: model has no classification head");
     if (max_len > m->cfg.max_pos) return rmu_fail(RMU_E_INVALID, "rmu_bert_rerank: max_len > max_pos");
     const int64_t cap = (int64_t)batch_pad * max_len;

@@ -107,6 +107,16 @@ class _EncoderBase:
 
     _wants_head: bool | None = None
 
+    @property
+    def hidden(self) -> int:
+        """Width of the encoder's vectors (384 for the MiniLM family, 768 / 1024 for BERT-base / -large checkpoints)."""
+        return int(getattr(self.encoder, "HIDDEN", 384))
+
+    @property
+    def _fused(self) -> bool:
+        """Whether the encoder has the library's host entry points (BertEncoder.fused; any other encoder object decides by its own gates)."""
+        return bool(getattr(self.encoder, "fused", True))
+
     def _read_spec(self, model_dir):      # overridden
         raise NotImplementedError
 
@@ -143,11 +153,11 @@ class _EncoderBase:
             i += n
 
     def _run_arrays(self, ids: np.ndarray, types: np.ndarray | None, lens: np.ndarray, mode: int, out=None):
-        """Padded id arrays -> torch CUDA [n, 384] (pooling modes) | [n] (cross-encoder), rows in input order."""
+        """Padded id arrays -> torch CUDA [n, hidden] (pooling modes) | [n] (cross-encoder), rows in input order."""
         import torch
         n = ids.shape[0]
         if out is None:
-            out = torch.empty((n, 384) if (mode & 0xff) != B.MODE_CE else (n,), dtype=torch.float32, device=self.encoder.device)
+            out = torch.empty((n, self.hidden) if (mode & 0xff) != B.MODE_CE else (n,), dtype=torch.float32, device=self.encoder.device)
         if n == 0:
             return out
         lens = np.minimum(np.asarray(lens, dtype=np.int32), min(ids.shape[1], self.max_seq_length))
@@ -207,15 +217,15 @@ class MI355XEmbeddings(_EncoderBase, Embeddings):
         return ids, lens
 
     def embed_ids(self, seqs: Sequence[Sequence[int]]):
-        """Pre-tokenised sequences (already carrying [CLS]/[SEP]) -> torch CUDA [n, 384] fp32."""
+        """Pre-tokenised sequences (already carrying [CLS]/[SEP]) -> torch CUDA [n, hidden] fp32."""
         return self._run(seqs, None, mode=self._mode)
 
     def embed_id_arrays(self, ids: np.ndarray, lens: np.ndarray, out=None):
-        """Padded [n, L] id array + lengths -> torch CUDA [n, 384] fp32 (rows in input order)."""
+        """Padded [n, L] id array + lengths -> torch CUDA [n, hidden] fp32 (rows in input order)."""
         return self._run_arrays(np.asarray(ids), None, np.asarray(lens), self._mode, out=out)
 
     def embed_documents_device(self, texts: list[str], out=None):
-        """texts -> torch CUDA [n, 384] fp32, rows in text order.  The vector store appends this tensor to
+        """texts -> torch CUDA [n, hidden] fp32, rows in text order.  The vector store appends this tensor to
         the HBM-resident corpus device-to-device (`rmu_index_add(is_device=1)`): embeddings never visit the host."""
         import torch
         texts = list(texts)
@@ -225,7 +235,7 @@ class MI355XEmbeddings(_EncoderBase, Embeddings):
         # two-stage pipeline over blocks of texts: a worker thread tokenises the next block while this thread encodes
         from concurrent.futures import ThreadPoolExecutor
         if out is None:
-            out = torch.empty((len(texts), 384), dtype=torch.float32, device=self.encoder.device)
+            out = torch.empty((len(texts), self.hidden), dtype=torch.float32, device=self.encoder.device)
         # blocks: a short first one (its tokenisation has nothing to hide behind), then `blk` texts each
         first = min(blk, max(1024, blk // 4))
         starts = [0] + list(range(first, len(texts), blk))
@@ -299,7 +309,7 @@ class MI355XEmbeddings(_EncoderBase, Embeddings):
 
     def enqueue_token_arrays(self, parts: list, round_no: int):
         """The GPU half, left IN FLIGHT: `parts` = the (ids, lens) pairs of `tokenize_for_index` of one or more calls, in row order ->
-        (torch CUDA [n, 384] fp32, event that marks its end), or None when these rows have to take `embed_token_arrays_device` (no native
+        (torch CUDA [n, hidden] fp32, event that marks its end), or None when these rows have to take `embed_token_arrays_device` (no native
         encoder, more tokens than one forward).  The ids are written part by part into the pinned staging slot `add<round_no & 1>` (no
         concatenated host copy in between): a caller keeps at most two rounds going and waits for round r before it starts round r + 2."""
         import torch
@@ -315,7 +325,7 @@ class MI355XEmbeddings(_EncoderBase, Embeddings):
         if fwd is None:
             fwd = enc._fwd_stream = torch.cuda.Stream(enc.device)
         ids_d, lens_d = enc.upload_rows([a for a, _ in parts], cut, Lmax, slot=f"add{round_no & 1}", min_cap=self.token_budget)
-        out = torch.empty((n, 384), dtype=torch.float32, device=enc.device)
+        out = torch.empty((n, self.hidden), dtype=torch.float32, device=enc.device)
         fwd.wait_stream(torch.cuda.current_stream(enc.device))      # `out` may be a recycled block still read on the allocating stream
         enc.encode_ids(ids_d, lens_d, None, mode=self._mode, out=out, stream=fwd)
         done = torch.cuda.Event()
@@ -323,7 +333,7 @@ class MI355XEmbeddings(_EncoderBase, Embeddings):
         return out, done
 
     def embed_token_arrays_device(self, ids: np.ndarray, lens: np.ndarray):
-        """The GPU half: token arrays of `tokenize_for_index` -> torch CUDA [n, 384] fp32 (what `embed_documents_device` returns)."""
+        """The GPU half: token arrays of `tokenize_for_index` -> torch CUDA [n, hidden] fp32 (what `embed_documents_device` returns)."""
         return self.embed_id_arrays(ids, lens)
 
     def embed_documents_array(self, texts: list[str]) -> np.ndarray:
@@ -334,9 +344,9 @@ class MI355XEmbeddings(_EncoderBase, Embeddings):
 
     def query_ids(self, text: str):
         """(ids [1, L] int32, lens [1]) of one query when it can go through the library's host entry points (native encoder +
-        tokenizer, <= 256 tokens), else None.  What MI355XVectorStore hands to `BertEncoder.search_host`."""
+        tokenizer, the fused geometry, <= 256 tokens), else None.  What MI355XVectorStore hands to `BertEncoder.search_host`."""
         enc = getattr(self, "encoder", None)
-        if not isinstance(enc, BertEncoder) or getattr(self, "tokenizer", None) is None:
+        if not isinstance(enc, BertEncoder) or getattr(self, "tokenizer", None) is None or not enc.fused:
             return None
         ids, lens = self._tokenize([text])
         return (ids, lens) if ids.shape[1] <= enc.SMALL_TOKENS else None
@@ -349,7 +359,7 @@ class MI355XEmbeddings(_EncoderBase, Embeddings):
         if not isinstance(enc, BertEncoder) or getattr(self, "tokenizer", None) is None:
             return None
         ids, lens = self._tokenize([text])
-        if ids.shape[1] > enc.SMALL_TOKENS:
+        if ids.shape[1] > enc.SMALL_TOKENS or not enc.fused:        # (a general geometry has no host entry point: the device forward)
             return self.embed_id_arrays(ids, lens).cpu().numpy()[0]
         return enc.encode_host(ids, lens, None, self._mode)[0]
 
@@ -363,7 +373,7 @@ class MI355XEmbeddings(_EncoderBase, Embeddings):
 
     def token_embeddings_ids(self, ids: np.ndarray, lens: np.ndarray):
         """Final hidden state of every token (sentence-transformers output_value="token_embeddings"): one batch, packed
-        [sum(lens), 384] fp32 torch CUDA in input order."""
+        [sum(lens), hidden] fp32 torch CUDA in input order."""
         return self.encoder.encode_ids(np.asarray(ids), np.asarray(lens), None, mode=B.MODE_TOKENS)
 
 
@@ -417,8 +427,11 @@ class MI355XCrossEncoder(_EncoderBase, *CROSS_ENCODER_BASES):
 
     @property
     def passages(self):
-        """The model's PassageTable (ragmeup_amd.rerank), created on first use; None unless the tokenizer is the native WordPieceTokenizer."""
+        """The model's PassageTable (ragmeup_amd.rerank), created on first use; None unless the tokenizer is the native WordPieceTokenizer
+        and the encoder the fused geometry (rmu_bert_rerank is its only reader)."""
         from .tokenizer import WordPieceTokenizer
+        if not self._fused:
+            return None
         if self._passages is None and isinstance(self.tokenizer, WordPieceTokenizer) and 8 <= self.max_seq_length <= 512:
             from .rerank import PassageTable
             with MI355XCrossEncoder._passages_lock:
@@ -430,7 +443,7 @@ class MI355XCrossEncoder(_EncoderBase, *CROSS_ENCODER_BASES):
     def rerank(self, query: str, texts: Sequence[str], top_n: int):
         """-> (positions, scores): what ``sorted(zip(range(len(texts)), self.score([(query, t) for t in texts])), key=itemgetter(1),
         reverse=True)[:top_n]`` gives, position for position and float for float, in ONE library call with one synchronisation -- or None
-        when that call does not serve the request (the caller then takes ``score``): another encoder or tokenizer, a sigmoid activation (the
+        when that call does not serve the request (the caller then takes ``score``): another encoder, geometry or tokenizer, a sigmoid activation (the
         activated scores can tie where the logits do not), no text or more than 256, a query longer than the pair budget (which side gets
         the odd token of the budget then depends on the passages' lengths before their cut, which the table does not keep)."""
         from .tokenizer import WordPieceTokenizer
@@ -440,6 +453,12 @@ class MI355XCrossEncoder(_EncoderBase, *CROSS_ENCODER_BASES):
         if (not isinstance(enc, BertEncoder) or not isinstance(tok, WordPieceTokenizer) or self.activation != "identity"
                 or not 1 <= m <= N.RERANK_MAX_M or int(top_n) < 1):
             return None
+        if not enc.fused:
+            # a general geometry has no one-call form: the pairs go through `score` (encode_ids, MODE_CE, in batches) and the stable sort the
+            # docstring names is done here; no passages table is built
+            scores = self.score([(query, t) for t in texts])
+            order = sorted(range(m), key=lambda i: scores[i], reverse=True)[:min(int(top_n), m)]
+            return order, [scores[i] for i in order]
         table = self.passages
         if table is None:
             return None
